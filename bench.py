@@ -15,6 +15,10 @@ dynamics, Euler step, stage cost over the whole horizon) then K2 (adjoint march 
 N > 1, the one exchange the path has: an RCCL all-gather of the per-rollout costs.  Each rank works on its
 own 65536 rollouts (weak scaling; rollouts are independent).  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the outputs of the last
+timed step if --dump-outputs DIR is given, the line.  --full adds the measurements that take runs of their own:
+cpu_baseline / cpu_baseline_torch, other_modes and (N > 1) strong_scaling.
+
 Extra objects on the line:
   roofline      for the dominant kernel (K2, k_rollout_grad): algorithmic FLOPs per launch (SURVEY.md 8d:
                 74.2 kFLOP per rollout-step of VJP work) / average launch duration measured live with events on
@@ -24,8 +28,8 @@ Extra objects on the line:
                 not have done it).  traffic = measured HBM bytes per K2 launch (separate --pmc passes), mostly
                 the K1->K2 activation stash; hbm_* fields compare algorithmic and measured bytes with the 8 TB/s
                 roof, as north_star asks.
-  cpu_baseline  the CPU oracle (plain-C port of the reference algorithm, float32, OpenMP over rollouts) timed
-                on this box's host cores on a bounded sample of the same workload.
+  cpu_baseline  (--full) the CPU oracle (plain-C port of the reference algorithm, float32, OpenMP over rollouts)
+                timed on the host's CPU cores on a bounded sample of the same workload.
 """
 import argparse
 import json
@@ -46,6 +50,7 @@ PEAK_16BIT_MFMA = 2.5e15   # dense bf16 / f16 MFMA peak
 PEAK_HBM = 8.0e12
 # matrix instructions issued per f32-equivalent product in each matmul mode
 SPLIT_PRODUCTS = {"f32": 1, "bf16x3": 6, "f16x2": 3}
+DUMP_BYTES = 60_000_000  # --dump-outputs stays below 64 MB in all (npy headers included)
 
 
 def parse():
@@ -63,13 +68,13 @@ def parse():
     ap.add_argument("--model", default="phnn_cartpole",
                     choices=["phnn_cartpole", "canonical_cartpole", "phnn_pendulum", "odefunc_pendulum"])
     ap.add_argument("--integrator", default="euler", choices=["euler", "rk4"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline / cpu_baseline_torch")
     ap.add_argument("--no-stash", action="store_true", help="K2 recomputes the forward tape instead of reading K1's")
     ap.add_argument("--cpu-sample", type=int, default=4096, help="rollouts timed on the host for cpu_baseline")
     ap.add_argument("--matmul", default=None, choices=["default", "f32", "bf16x3", "f16x2"],
                     help="how the hidden x hidden products are evaluated (default: PHNN_MATMUL or the library default)")
     ap.add_argument("--no-other-modes", action="store_true",
-                    help="skip the short timed loops of the other matmul modes (other_modes on the JSON line)")
+                    help="with --full: skip the short timed loops of the other matmul modes (other_modes on the JSON line)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch rollouts per GPU (default); strong: --global-batch rollouts split over the GPUs")
     ap.add_argument("--global-batch", type=int, default=65536, help="total rollouts with --scaling strong")
@@ -80,7 +85,19 @@ def parse():
     ap.add_argument("--config", default=None, choices=["headline", "config4"],
                     help="named workloads: headline = H=50, 65536 rollouts per GPU; config4 = BASELINE config 4, "
                          "2^20 rollouts over 8 GPUs = 131072 per GPU")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baselines (cpu_baseline, "
+                         "cpu_baseline_torch), the short timed loops of the other matmul modes (other_modes) and, for N > 1, "
+                         "the strong-scaling figure (strong_scaling).  Off by default: a plain run sets up, warms up, times "
+                         "--steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's share) as DIR/<name>.npy, "
+                         "float32: cost (B,), grad_u (B, H, 1), traj (B, H+1, n); above DUMP_BYTES a fixed seeded sample of "
+                         "rollouts, the same rows in every array, named by DIR/rollout_index.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.preheat < 0:
+        ap.error("--steps must be >= 1, --warmup and --preheat >= 0")
+    return args
 
 
 def synthetic_inputs(n, B, H, rank, u_amp):
@@ -255,6 +272,10 @@ def main():
             assert torch.isfinite(c_last).all(), "non-finite cost in the bench workload"
             return el, k1, k2
 
+        def outputs(self):
+            """What the last step handed its caller: per-rollout cost, d cost / d u, the trajectory."""
+            return {"cost": self.cost, "grad_u": self.gu, "traj": self.traj}
+
     class RehearsalWorkload(Workload):
         """The same flow -- K1, all-gather of the costs, K2, barriers, max over ranks -- on a CPU stand-in engine
         (engine protocol: rollout_cost_grad(..., after_forward=)).  Host clocks; not a measurement."""
@@ -274,11 +295,15 @@ def main():
                 if world > 1:
                     dist.all_gather_into_tensor(self.gathered, self.c_pad)
 
-            c, _ = self.eng.rollout_cost_grad(x0[: self.B], U[: self.B], cost, args.integrator, dt, after_forward=gather)
+            c, g = self.eng.rollout_cost_grad(x0[: self.B], U[: self.B], cost, args.integrator, dt, after_forward=gather)
             self.mark[2] = time.perf_counter()
             if ev is not None:
                 ev.extend(self.mark)
+            self.last = {"cost": c, "grad_u": g}
             return c
+
+        def outputs(self):
+            return self.last
 
         def timed(self, steps, warmup):
             for _ in range(warmup):
@@ -303,10 +328,12 @@ def main():
     main_wl = WL(eng, B, B_pad, stash=not args.no_stash)
     ws_stash = main_wl.stash
     elapsed, k1_ms, k2_ms = main_wl.timed(args.steps, args.preheat + args.warmup)
+    if args.dump_outputs and rank == 0:  # before anything else runs: the buffers still hold the last timed step
+        dump_outputs(args.dump_outputs, main_wl.outputs())
 
-    # strong-scaling figure next to the weak one (N > 1): the SAME global batch of 65536 split over the ranks
+    # --full: strong-scaling figure next to the weak one (N > 1): the SAME global batch of 65536 split over the ranks
     strong = None
-    if world > 1 and args.scaling == "weak":
+    if args.full and world > 1 and args.scaling == "weak":
         lo, hi = shard_bounds(args.global_batch, world, rank)
         Bs, Bs_pad = hi - lo, -(-args.global_batch // world)
         if Bs <= B:
@@ -317,9 +344,10 @@ def main():
             strong = {"global_batch": args.global_batch, "batch_per_gpu": Bs_pad, "steps": ks,
                       "value": round(args.global_batch * ks / el_s, 1), "ms_per_step": round(1e3 * el_s / ks, 4),
                       "k1_launch_ms": round(k1s, 4), "k2_launch_ms": round(k2s, 4)}
-    # the 24-bit-exact product modes, short timed loops in the same run (single GPU only)
+    # --full: the 24-bit-exact product modes, short timed loops in the same run (single GPU only)
     other_modes = None
-    if world == 1 and not rehearsal and not args.no_other_modes and args.model in ("phnn_cartpole", "canonical_cartpole"):
+    if (args.full and world == 1 and not rehearsal and not args.no_other_modes
+            and args.model in ("phnn_cartpole", "canonical_cartpole")):
         other_modes = {}
         for mode in ("bf16x3", "f32"):
             if mode == eng.matmul_mode:
@@ -377,7 +405,7 @@ def main():
             "k1_hbm_traffic_frac": None if traffic_k1 is None else round(traffic_k1 / (k1_ms * 1e-3) / PEAK_HBM, 4),
         }
         cpu = cpu_torch = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(w, cost, x0_h, U_h, args.integrator, dt, args.cpu_sample)
             if args.model == "phnn_cartpole" and args.integrator == "euler":
                 cpu_torch = cpu_baseline_torch(w, x0_h, U_h, dt, umax)
@@ -421,6 +449,24 @@ def main():
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: arrays (name -> tensor with the rollout as its first axis) as out_dir/<name>.npy in float32.
+    When all of them together exceed DUMP_BYTES, the same fixed sample of rollouts (numpy seed 0, sorted) is kept from
+    every array; out_dir/rollout_index.npy (float64) names the rows either way."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: torch.as_tensor(t) for name, t in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(4 * t[0].numel() for t in arrays.values()) + 8  # + 8: the float64 index
+    keep = min(B, DUMP_BYTES // row_bytes)
+    idx = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+    np.save(os.path.join(out_dir, "rollout_index.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        if keep < B:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def host_cpu():

@@ -428,7 +428,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal(torch):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "8192", "--steps", "5", "--warmup", "2",
-                        "--global-batch", "9001", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--global-batch", "9001", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 16384 and line["config"]["collective_backend"] == "gloo"

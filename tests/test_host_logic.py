@@ -199,12 +199,12 @@ def test_backward_through_H_without_wgrad_kernels_raises():
     assert x.grad is not None
 
 
-def test_unsupported_model_options_raise():
+def test_unsupported_model_options_raise(tmp_path):
     cfg = yaml.safe_load(open(CFG))
     cfg["model"]["H_mlp"]["activation"] = "nn.ReLU"
-    p = os.path.join(ROOT, "gpurun_out", "_tmp_relu.yaml")
-    os.makedirs(os.path.dirname(p), exist_ok=True)
-    yaml.safe_dump(cfg, open(p, "w"))
+    p = str(tmp_path / "relu.yaml")
+    with open(p, "w") as f:
+        yaml.safe_dump(cfg, f)
     m = pHNN(p)
     with pytest.raises(NotImplementedError):
         m.engine

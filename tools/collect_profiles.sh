@@ -18,7 +18,7 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -- python3 "$
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_wgrad" -- python3 "$ROOT/tools/wgrad_probe.py" > "$OUT/wgrad_probe.txt" 2> "$OUT/trace_wgrad.log"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_rk4" -- python3 "$ROOT/tools/rk4_probe.py" > "$OUT/rk4_probe.txt" 2> "$OUT/trace_rk4.log"
 cd "$ROOT"
-python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 python3 bench.py --config config4 --no-cpu-baseline --no-other-modes > "$OUT/bench_config4.json" 2> "$OUT/bench_config4.err"
 python3 tools/bench_configs.py > "$OUT/other_configs.jsonl" 2> "$OUT/other_configs.err"
 python3 tools/latency_probe.py > "$OUT/latency_probe.txt" 2> "$OUT/latency_probe.err"
