@@ -130,6 +130,24 @@ typedef struct {
   float barrier_weight; /* reference constant: 1000 */
 } phnn_cost;
 
+/* Reference trajectories (the *_ref entry points): problem b tracks its own, possibly time-varying, target,
+ *   cost_b = sum_{t=0..H} (x_t - r_{b,row(t)})^T Q (x_t - r_{b,row(t)}) + sum_{t<H} u_t^T R u_t + barrier,
+ *   r_{b,row} = x_ref[b * batch_stride + row * time_stride + 0 .. n-1],   row(t) = min(offset + t, rows - 1)
+ * (past its end a reference holds its last row).  Everything else is phnn_cost's: Q, R (shared by the batch), the
+ * u clamp, the barrier, the gradient w.r.t. the unclamped u; x_target is not read.  The difference x - r is formed
+ * as x - x_target is, so a reference equal to x_target everywhere gives the non-tracking results bit for bit.
+ * offset: *offset_dev when offset_dev != NULL -- read by each launch, so a captured HIP graph walks along the
+ * reference when it is the counter phnn_plant_step / phnn_shift_controls advance -- else offset_host (>= 0).
+ * A device offset outside [0, rows - 1] is clamped to it.  x_ref must hold every row it addresses for the B problems. */
+typedef struct {
+  const float* x_ref;        /* device */
+  int64_t batch_stride;      /* floats between problems; 0 = shared by all */
+  int64_t time_stride;       /* floats between rows;     0 = constant setpoint */
+  int32_t rows;              /* >= 1 */
+  const int32_t* offset_dev; /* device step counter added to the row index (graph replay), or NULL */
+  int32_t offset_host;       /* used when offset_dev == NULL */
+} phnn_reference;
+
 typedef struct phnn_handle phnn_handle;
 
 /* Build a handle: validates the description, packs the weights into the MFMA fragment order the
@@ -203,6 +221,18 @@ int phnn_rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, in
                      const phnn_cost* cost, int32_t integrator, float dt, const float* traj_dev,
                      const void* workspace_dev, const float* traj_bar_dev, const float* cost_bar_dev,
                      float* grad_u_dev, float* grad_x0_dev, void* stream);
+
+/* K1 / K2 tracking a reference (phnn_reference above): the same as phnn_rollout_fwd / phnn_rollout_grad with the
+ * stage cost of problem b taken about its reference rows instead of cost->x_target (same workspace and stash
+ * format; the workspace a phnn_rollout_fwd_ref filled serves the phnn_rollout_grad_ref of the same reference).
+ * PHNN_ERR_INVALID_ARG for ref == NULL, x_ref == NULL (B > 0), rows < 1, negative strides or offset_host < 0. */
+int phnn_rollout_fwd_ref(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                         const phnn_cost* cost, const phnn_reference* ref, int32_t integrator, float dt, float* cost_dev,
+                         float* traj_dev, void* workspace_dev, void* stream);
+int phnn_rollout_grad_ref(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                          const phnn_cost* cost, const phnn_reference* ref, int32_t integrator, float dt,
+                          const float* traj_dev, const void* workspace_dev, float* grad_u_dev, float* grad_x0_dev,
+                          void* stream);
 
 /* ---- training side: rollouts with gradients w.r.t. the MODEL PARAMETERS ----------------------
  * What loss.backward() does in the reference's training loops (scripts/train_cartpole_phnn.py:112-178,
@@ -295,6 +325,12 @@ int phnn_solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int
                int32_t integrator, float dt, const phnn_solve_options* opt, float* exp_avg_dev, float* exp_avg_sq_dev,
                float* grad_dev, float* cost_dev, float* traj_dev, void* workspace_dev, float* costs_dev,
                float* best_cost_dev, float* best_u_dev, void* stream);
+/* phnn_solve with every K1 / K2 of the solve tracking `ref` (phnn_rollout_fwd_ref / phnn_rollout_grad_ref); with
+ * ref->offset_dev the offset is read by every launch, so a captured closed-loop step advances along the reference. */
+int phnn_solve_ref(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                   const phnn_reference* ref, int32_t integrator, float dt, const phnn_solve_options* opt,
+                   float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_dev, float* cost_dev, float* traj_dev,
+                   void* workspace_dev, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream);
 
 /* ---- the plant on the other side of the path ------------------------------------------
  * Ground-truth cart-pole of src/cartpole_simulator.py:63-112: float64, explicit Euler, the standard cart-pole

@@ -31,7 +31,7 @@ EXPORTED = [
     "phnn_model_vjp", "phnn_rollout_fwd", "phnn_workspace_bytes", "phnn_rollout_grad", "phnn_rollout_vjp",
     "phnn_rollout_trajectory", "phnn_rollout_trajectory_ws", "phnn_wgrad_workspace_bytes", "phnn_wgrad_record_info", "phnn_rollout_wgrad", "phnn_model_wgrad",
     "phnn_adam_step", "phnn_solve", "phnn_plant_step", "phnn_shift_controls", "phnn_kernel_info", "phnn_variant_name",
-    "phnn_version",
+    "phnn_version", "phnn_rollout_fwd_ref", "phnn_rollout_grad_ref", "phnn_solve_ref",
 ]
 
 
@@ -82,6 +82,12 @@ class Cost(C.Structure):
                 ("x_target", C.c_float * PHNN_MAX_N), ("u_min", C.c_float), ("u_max", C.c_float),
                 ("has_u_bounds", C.c_int32), ("x_min", C.c_float * PHNN_MAX_N), ("x_max", C.c_float * PHNN_MAX_N),
                 ("has_x_min", C.c_int32), ("has_x_max", C.c_int32), ("barrier_weight", C.c_float)]
+
+
+class Reference(C.Structure):
+    """phnn_reference: problem b tracks x_ref[b * batch_stride + min(offset + t, rows - 1) * time_stride + i]."""
+    _fields_ = [("x_ref", C.c_void_p), ("batch_stride", C.c_int64), ("time_stride", C.c_int64), ("rows", C.c_int32),
+                ("offset_dev", C.c_void_p), ("offset_host", C.c_int32)]
 
 
 def make_cost(n, m, Q, R, x_target=None, u_min=None, u_max=None, x_min=None, x_max=None, barrier_weight=1000.0):
@@ -197,6 +203,15 @@ def load_library():
     lib.phnn_solve.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), i32, C.c_float, C.POINTER(SolveOptions), f32p, f32p,
                                f32p, f32p, f32p, vp, f32p, f32p, f32p, vp]
     lib.phnn_solve.restype = C.c_int
+    lib.phnn_rollout_fwd_ref.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
+                                         f32p, f32p, vp, vp]
+    lib.phnn_rollout_fwd_ref.restype = C.c_int
+    lib.phnn_rollout_grad_ref.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
+                                          f32p, vp, f32p, f32p, vp]
+    lib.phnn_rollout_grad_ref.restype = C.c_int
+    lib.phnn_solve_ref.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
+                                   C.POINTER(SolveOptions), f32p, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, vp]
+    lib.phnn_solve_ref.restype = C.c_int
     lib.phnn_plant_step.argtypes = [vp, C.POINTER(Plant), vp, f32p, i64, i64, i32, C.c_float, C.c_float, f32p, vp, vp, i32,
                                     vp, f32p, vp]
     lib.phnn_plant_step.restype = C.c_int

@@ -9,6 +9,9 @@
   run_mpc_batch_device   the same loop with NOTHING on the host: the plant (k_plant_step, float64), the warm-start shift,
                          the logs and the done mask are device kernels, one control step = solve + plant step is
                          captured as a HIP graph and replayed num_steps times; the host synchronises once, at the end.
+  x_ref                  (all three drivers) per-plant reference trajectories broadcastable to (B, rows, 4): control
+                         step s solves with the window starting at row s (past its end a reference holds its last
+                         row) -- the loop index on the host, the device step counter in the device loop.
   stability_report       the "stability achieved" criterion of scripts/run_cartpole_mpc.py:117-159 with the
                          tolerances of the `stability` config section, per plant.
 """
@@ -45,19 +48,23 @@ class BatchedCartPole:
         return self.state.copy()
 
 
-def run_mpc_batch(simulator, controller, initial_states, num_steps):
-    """-> dict(states (T+1,B,4), controls (T,B,1), done_step (B,) first step a plant terminated at, or -1)."""
+def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None):
+    """-> dict(states (T+1,B,4), controls (T,B,1), done_step (B,) first step a plant terminated at, or -1).
+    x_ref: reference trajectories broadcastable to (B, rows, 4); control step s tracks them from row s."""
     x = simulator.reset(initial_states)
     B = x.shape[0]
     states, controls = [x.copy()], []
     done_step = np.full(B, -1, dtype=np.int64)
     canonical = hasattr(controller, "control_batch")
     u_prev = None
+    rkw = {}
     for step in range(num_steps):
+        if x_ref is not None:
+            rkw = {"x_ref": x_ref, "ref_offset": step}
         if canonical:
-            u, u_prev, _ = controller.control_batch(x.astype(np.float32), u_prev)
+            u, u_prev, _ = controller.control_batch(x.astype(np.float32), u_prev, **rkw)
         else:
-            u = controller.compute_control_batch(x.astype(np.float32))
+            u = controller.compute_control_batch(x.astype(np.float32), **rkw)
         x, done = simulator.step(u)
         newly = done & (done_step < 0)
         done_step[newly] = step
@@ -73,9 +80,15 @@ class DeviceClosedLoop:
     best clamped iterate).  One control step enqueues: iters x (K1, K2, K3), k_plant_step, k_shift_controls; with
     use_graph the step is captured once and replayed.  Per-plant arithmetic is identical to run_mpc_batch (same
     kernels, same order); the plant differs from the numpy one only by the device's double-precision sin/cos.
+
+    x_ref: reference trajectories broadcastable to (B, rows, 4) (engine.reference_view); every solve tracks them from
+    row step_dev, the device counter the plant step logs with and the shift advances, so each replay of the captured
+    step moves one row along.  The graph reads the reference through a pointer taken here: a float32 tensor on the
+    engine's device with a contiguous last dimension is read in place (keep it alive and in place -- the loop holds a
+    view of it; values changed in place between runs are seen), anything else is copied once, here.
     """
 
-    def __init__(self, controller, initial_states, num_steps, use_graph=True, dt=None):
+    def __init__(self, controller, initial_states, num_steps, use_graph=True, dt=None, x_ref=None):
         import torch
         from . import _capi
         self.torch, self.ctl = torch, controller
@@ -100,6 +113,10 @@ class DeviceClosedLoop:
         self.best_u = torch.empty_like(self.u) if self.canonical else None
         self.ws = {}
         self.cost = controller._cost()
+        self.x_ref = None
+        if x_ref is not None:
+            from .engine import reference_view
+            self.x_ref = reference_view(x_ref, B, 4, dev)[0]
         self.iters = controller.optimizer_steps if self.canonical else controller.max_iterations
         self.lr = controller.learning_rate if self.canonical else controller.lr
         if not self.canonical and controller.optimizer_type != "Adam":
@@ -115,8 +132,9 @@ class DeviceClosedLoop:
         if self.canonical:
             self.best_cost.fill_(float("inf"))
             self.best_u.zero_()
+        rkw = {} if self.x_ref is None else {"x_ref": self.x_ref, "ref_offset": self.step_dev}
         for k in range(self.iters):
-            cost, g = eng.rollout_cost_grad(self.x32, self.u, self.cost, c.integrator, c.dt, workspace=self.ws)
+            cost, g = eng.rollout_cost_grad(self.x32, self.u, self.cost, c.integrator, c.dt, workspace=self.ws, **rkw)
             eng.adam_step(self.u, g, self.exp_avg, self.exp_avg_sq, self.lr, k + 1,
                           cost=cost if self.canonical else None, best_cost=self.best_cost, best_u=self.best_u,
                           u_min=c.u_min, u_max=c.u_max)
@@ -157,9 +175,9 @@ class DeviceClosedLoop:
                 "done_step": self.done_step.cpu().numpy().astype(np.int64)}
 
 
-def run_mpc_batch_device(controller, initial_states, num_steps, use_graph=True):
+def run_mpc_batch_device(controller, initial_states, num_steps, use_graph=True, x_ref=None):
     """Device-resident version of run_mpc_batch: same return dict, one host synchronisation at the end."""
-    return DeviceClosedLoop(controller, initial_states, num_steps, use_graph=use_graph).run()
+    return DeviceClosedLoop(controller, initial_states, num_steps, use_graph=use_graph, x_ref=x_ref).run()
 
 
 def stability_report(states, target, tolerance, min_duration, dt):

@@ -2511,11 +2511,13 @@ struct OdeModel {
 // The empty asm has side effects as far as the compiler knows, so the block cannot be speculated.
 DEV void no_speculation() { asm volatile("" ::: "memory"); }
 
-template <int N>
-DEV float state_cost(const phnn_cost& c, f32x4 x) {
+// tgt: the cost's x_target (float[PHNN_MAX_N]) or, in the tracking kernels, the reference row of the step (f32x4); the
+// difference x - tgt is formed in the same order either way, so a reference equal to x_target gives the same bits.
+template <int N, class Tgt>
+DEV float state_cost(const phnn_cost& c, f32x4 x, const Tgt& tgt) {
   float e[N], cost = 0.f;
 #pragma unroll
-  for (int i = 0; i < N; ++i) e[i] = x[i] - c.x_target[i];
+  for (int i = 0; i < N; ++i) e[i] = x[i] - tgt[i];
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     float s = 0.f;
@@ -2547,12 +2549,12 @@ DEV float state_cost(const phnn_cost& c, f32x4 x) {
 }
 
 // Qs = Q + Q^T from the host (RollParams::Qs; the same float32 sum the kernel used to form per step)
-template <int N>
-DEV f32x4 state_cost_grad(const phnn_cost& c, const float (&Qs)[16], f32x4 x) {
+template <int N, class Tgt>
+DEV f32x4 state_cost_grad(const phnn_cost& c, const float (&Qs)[16], f32x4 x, const Tgt& tgt) {
   float e[N];
   f32x4 g = splat4(0.f);
 #pragma unroll
-  for (int i = 0; i < N; ++i) e[i] = x[i] - c.x_target[i];
+  for (int i = 0; i < N; ++i) e[i] = x[i] - tgt[i];
 #pragma unroll
   for (int i = 0; i < N; ++i) {
     float s = 0.f;
@@ -2597,6 +2599,13 @@ struct RollParams {
   float dt, half_dt, sixth_dt;
   phnn_cost c;
   float Qs[16];        // Q + Q^T (row-major n x n), formed on the host in float32: the adjoint used to rebuild it every step
+  // reference tracking (marches built with REF; phnn_reference): the target of step t of rollout b is
+  // x_ref + b * ref_bs + min(off + t, ref_rows - 1) * ref_ts, off = *ref_off_dev if set, else ref_off_host
+  const float* x_ref;
+  long long ref_bs, ref_ts;
+  int ref_rows;
+  const int* ref_off_dev;
+  int ref_off_host;
 };
 
 struct PointParams {
@@ -2710,8 +2719,35 @@ DEV bool tile_ctx(TileCtx& c, float* lds, long long B) {  // false: no tile for 
   return true;
 }
 
-// K1: forward march of one tile.
-template <class M, int INTEG, bool STASH>
+// Reference rows of one rollout (tracking marches).  The start row is read once per launch (a device counter lets a
+// captured graph walk along the reference) and clamped to the rows that exist, so no offset reads outside them.  The
+// row pointer is only float aligned (the strides are the caller's), hence element loads: the compiler merges the four
+// into one global_load_dwordx4, which needs dword alignment only.  The row index is wave-uniform (scalar arithmetic).
+template <int N>
+struct RefRows {
+  const float* base;
+  long long ts;
+  int off, last;
+  DEV void init(const RollParams& p, long long b) {
+    base = p.x_ref + b * p.ref_bs;
+    ts = p.ref_ts;
+    last = p.ref_rows - 1;
+    const int o = p.ref_off_dev ? *p.ref_off_dev : p.ref_off_host;
+    off = o < 0 ? 0 : (o > last ? last : o);
+  }
+  DEV f32x4 row(int t) const {  // row min(off + t, rows - 1)
+    const int r = t < last - off ? off + t : last;
+    const float* q = base + r * ts;
+    f32x4 v = splat4(0.f);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = q[i];
+    return v;
+  }
+};
+
+// K1: forward march of one tile.  REF: the target of every stage cost is the rollout's reference row of that step
+// (loaded at the top of the step, used after the dynamics) instead of p.c.x_target.
+template <class M, int INTEG, bool STASH, bool REF = false>
 DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
   constexpr int N = M::N;
   const Lane ln = tc.ln;
@@ -2720,11 +2756,20 @@ DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
   const bool writer = tc.writer;
   f32x4 x = load_state<N>(p.x0 + b * N);
   if (p.traj && writer) store_state<N>(p.traj + (b * (p.H + 1)) * N, x);
-  float cost = state_cost<N>(p.c, x);
+  RefRows<N> rr;
+  float cost;
+  if constexpr (REF) {
+    rr.init(p, b);
+    cost = state_cost<N>(p.c, x, rr.row(0));
+  } else {
+    cost = state_cost<N>(p.c, x, p.c.x_target);
+  }
   constexpr int MI = M::MI;
   const float* up = p.u + b * p.H * MI;
   float Hd;
   for (int t = 0; t < p.H; ++t) {
+    f32x4 tgt;
+    if constexpr (REF) tgt = rr.row(t + 1);
     f32x4 u = clamp_u4<MI>(p.c, load_u<MI>(up, t));
     if (MI == 1) cost = __builtin_fmaf(u[0] * p.c.R[0], u[0], cost);
     else cost += control_cost<MI>(p.c, u);
@@ -2748,24 +2793,28 @@ DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
       }
       x = x + p.sixth_dt * acc;
     }
-    cost += state_cost<N>(p.c, x);
+    if constexpr (REF) cost += state_cost<N>(p.c, x, tgt);
+    else cost += state_cost<N>(p.c, x, p.c.x_target);
     if (p.traj && writer) store_state<N>(p.traj + (b * (p.H + 1) + t + 1) * N, x);
   }
   if (writer && p.cost) p.cost[b] = cost;
 }
 
-template <class M, int INTEG, bool STASH>
+template <class M, int INTEG, bool STASH, bool REF = false>
 __global__ __launch_bounds__(64 * kMaxWaves) void k_rollout_fwd(RollParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   stage_image<M::IMG>(lds, p.img);
   TileCtx tc;
   if (!tile_ctx<M>(tc, lds, p.B)) return;
-  fwd_march<M, INTEG, STASH>(p, lds, tc);
+  fwd_march<M, INTEG, STASH, REF>(p, lds, tc);
 }
 
 // K2: adjoint march over the states K1 stored.  WG: every dynamics VJP also emits its weight-gradient record
 // (training side: k_wgrad_reduce sums them into d loss / d theta).
-template <class M, int INTEG, bool STASH, bool WG = false>
+// REF: the stage-cost gradient of step t is taken about the rollout's reference row of that step, used after the
+// dynamics VJP.  Euler loads the row alongside x_t at the top of the step (its latency hides under the VJP); RK4 loads it
+// where x_t is re-read after the four stage VJPs, so that it does not ride through them (registers are full there).
+template <class M, int INTEG, bool STASH, bool WG = false, bool REF = false>
 DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
   constexpr int N = M::N;
   const Lane ln = tc.ln;
@@ -2780,13 +2829,22 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
   const float* db = p.dx_bar ? p.dx_bar + (b * p.H) * N : nullptr;
   // a padding lane (rollout index beyond the batch) must not contribute to the weight gradient: its cotangents are zeroed
   const float live = valid ? 1.0f : 0.0f;
-  f32x4 lam = cb * state_cost_grad<N>(p.c, p.Qs, load_state<N>(tr + (long long)p.H * N));
+  RefRows<N> rr;
+  f32x4 lam;
+  if constexpr (REF) {
+    rr.init(p, b);
+    lam = cb * state_cost_grad<N>(p.c, p.Qs, load_state<N>(tr + (long long)p.H * N), rr.row(p.H));
+  } else {
+    lam = cb * state_cost_grad<N>(p.c, p.Qs, load_state<N>(tr + (long long)p.H * N), p.c.x_target);
+  }
   if (tb) lam = lam + load_state<N>(tb + (long long)p.H * N);
   if (WG) lam = lam * live;
   constexpr int STAGES = INTEG == PHNN_INTEG_EULER ? 1 : 4;
   float Hd;
   for (int t = p.H - 1; t >= 0; --t) {
     f32x4 x = load_state<N>(tr + (long long)t * N);
+    f32x4 tgt;
+    if constexpr (REF && INTEG == PHNN_INTEG_EULER) tgt = rr.row(t);
     f32x4 uraw = load_u<MI>(up, t);
     f32x4 u = p.no_cost ? uraw : clamp_u4<MI>(p.c, uraw);
     f32x4 dxb = splat4(0.f);
@@ -2845,10 +2903,12 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
       }
       lam = lam + ysum;
       x = load_state<N>(tr + (long long)t * N);
+      if constexpr (REF) tgt = rr.row(t);
       uraw = load_u<MI>(up, t);
       u = p.no_cost ? uraw : clamp_u4<MI>(p.c, uraw);
     }
-    lam = lam + cb * state_cost_grad<N>(p.c, p.Qs, x);
+    if constexpr (REF) lam = lam + cb * state_cost_grad<N>(p.c, p.Qs, x, tgt);
+    else lam = lam + cb * state_cost_grad<N>(p.c, p.Qs, x, p.c.x_target);
     if (tb) lam = lam + load_state<N>(tb + (long long)t * N) * (WG ? live : 1.0f);
 #pragma unroll
     for (int k = 0; k < MI; ++k) {
@@ -2868,13 +2928,13 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
   if (p.grad_x0 && writer) store_state<N>(p.grad_x0 + b * N, lam);
 }
 
-template <class M, int INTEG, bool STASH, bool WG = false>
+template <class M, int INTEG, bool STASH, bool WG = false, bool REF = false>
 __global__ __launch_bounds__(64 * kMaxWaves) void k_rollout_grad(RollParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   stage_image<M::IMG>(lds, p.img);
   TileCtx tc;
   if (!tile_ctx<M>(tc, lds, p.B)) return;
-  grad_march<M, INTEG, STASH, WG>(p, lds, tc);
+  grad_march<M, INTEG, STASH, WG, REF>(p, lds, tc);
 }
 
 // (Measured, round 3, and removed: a fused solve kernel -- `iters` x (forward march, adjoint march, Adam step) for one

@@ -26,6 +26,10 @@ struct KernelSet {
   void (*grad[2])(RollParams);
   void (*fwd_stash[2])(RollParams);   // Euler, RK4: K1 keeps the tape(s) for K2
   void (*grad_stash[2])(RollParams);  // K2 reads the tape(s) instead of recomputing them
+  void (*fwd_ref[2])(RollParams);     // the four pairs above with reference tracking (phnn_reference)
+  void (*grad_ref[2])(RollParams);
+  void (*fwd_stash_ref[2])(RollParams);
+  void (*grad_stash_ref[2])(RollParams);
   int stash_floats[2];                // per wave (16 rollouts) per step
   int scr_floats;                  // per-wave LDS scratch
   void (*mfwd)(PointParams);
@@ -41,6 +45,10 @@ KernelSet make_set(const char* name) {
   k.fwd[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false>;
   k.fwd_stash[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true>;
   k.fwd_stash[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true>;
+  k.fwd_ref[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false, true>;
+  k.fwd_ref[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false, true>;
+  k.fwd_stash_ref[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true, true>;
+  k.fwd_stash_ref[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true, true>;
   k.stash_floats[0] = StashStep<M, PHNN_INTEG_EULER>::FLOATS;
   k.stash_floats[1] = StashStep<M, PHNN_INTEG_RK4>::FLOATS;
   k.scr_floats = M::SCR;
@@ -64,6 +72,10 @@ bool kernel_set(int v, KernelSet* k) {
   k->grad[1] = g.grad[1];
   k->grad_stash[0] = g.grad_stash[0];
   k->grad_stash[1] = g.grad_stash[1];
+  for (int i = 0; i < 2; ++i) {
+    k->grad_ref[i] = g.grad_ref[i];
+    k->grad_stash_ref[i] = g.grad_stash_ref[i];
+  }
   k->mvjp = g.mvjp;
   return true;
 }
@@ -537,7 +549,7 @@ int check_cost(phnn_handle* h, const phnn_cost* c) {
 
 extern "C" {
 
-int phnn_version(void) { return 220; }
+int phnn_version(void) { return 230; }
 
 const char* phnn_variant_name(const phnn_handle* h) { return h ? h->ks.name : ""; }
 
@@ -627,6 +639,12 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
   if (e == hipSuccess) e = allow_big_lds(h->ks.grad[1]);
   if (e == hipSuccess) e = allow_big_lds(h->ks.grad_stash[0]);
   if (e == hipSuccess) e = allow_big_lds(h->ks.grad_stash[1]);
+  for (int i = 0; i < 2; ++i) {
+    if (e == hipSuccess) e = allow_big_lds(h->ks.fwd_ref[i]);
+    if (e == hipSuccess) e = allow_big_lds(h->ks.fwd_stash_ref[i]);
+    if (e == hipSuccess) e = allow_big_lds(h->ks.grad_ref[i]);
+    if (e == hipSuccess) e = allow_big_lds(h->ks.grad_stash_ref[i]);
+  }
   if (e == hipSuccess) e = allow_big_lds(h->ks.mfwd);
   if (e == hipSuccess) e = allow_big_lds(h->ks.mvjp);
   if (h->has_wgrad) {
@@ -647,6 +665,12 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
     if (e == hipSuccess) e = allow_big_lds(h->sp.grad[1]);
     if (e == hipSuccess) e = allow_big_lds(h->sp.grad_stash[0]);
     if (e == hipSuccess) e = allow_big_lds(h->sp.grad_stash[1]);
+    for (int i = 0; i < 2; ++i) {
+      if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_ref[i]);
+      if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_stash_ref[i]);
+      if (e == hipSuccess) e = allow_big_lds(h->sp.grad_ref[i]);
+      if (e == hipSuccess) e = allow_big_lds(h->sp.grad_stash_ref[i]);
+    }
     if ((size_t)h->sp.lds_floats * sizeof(float) > 160 * 1024) h->has_split = false;
   }
   if (e != hipSuccess) {
@@ -809,12 +833,30 @@ size_t phnn_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t 
   return tiles * (size_t)H * (size_t)h->ks.stash_floats[integrator] * sizeof(float);
 }
 
-int phnn_rollout_fwd(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
-                     const phnn_cost* cost, int32_t integrator, float dt, float* cost_dev, float* traj_dev,
-                     void* workspace_dev, void* stream) {
+// phnn_reference -> RollParams (the *_ref entry points); ref == NULL leaves the tracking fields zero
+static int fill_ref(phnn_handle* h, RollParams* p, const phnn_reference* ref, int64_t B) {
+  if (!ref) return PHNN_OK;
+  if (ref->rows < 1) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference: rows < 1");
+  if (ref->batch_stride < 0 || ref->time_stride < 0)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference: negative batch_stride / time_stride");
+  if (!ref->offset_dev && ref->offset_host < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference: offset_host < 0");
+  if (B > 0 && !ref->x_ref) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference: x_ref is NULL");
+  p->x_ref = ref->x_ref;
+  p->ref_bs = ref->batch_stride;
+  p->ref_ts = ref->time_stride;
+  p->ref_rows = ref->rows;
+  p->ref_off_dev = ref->offset_dev;
+  p->ref_off_host = ref->offset_host;
+  return PHNN_OK;
+}
+
+static int rollout_fwd(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                       const phnn_cost* cost, int32_t integrator, float dt, float* cost_dev, float* traj_dev,
+                       void* workspace_dev, const phnn_reference* ref, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
   RollParams p;
   if (int rc = fill_roll(h, &p, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
+  if (int rc = fill_ref(h, &p, ref, B)) return rc;
   if (B == 0) return PHNN_OK;
   if (!cost_dev) return fail(h, PHNN_ERR_INVALID_ARG, "cost_dev is NULL");
   PHNN_ON_DEVICE(h);
@@ -824,24 +866,36 @@ int phnn_rollout_fwd(phnn_handle* h, const float* x0_dev, const float* u_dev, in
   const bool split = use_split(h, tiles);
   const bool stash = workspace_dev != nullptr;
   p.stash = (float*)workspace_dev;
+  if (ref) {
+    if (split) return launch_split(h, stash ? h->sp.fwd_stash_ref[integrator] : h->sp.fwd_ref[integrator], p, tiles, (hipStream_t)stream);
+    return launch(h, stash ? h->ks.fwd_stash_ref[integrator] : h->ks.fwd_ref[integrator], p, tiles, false, (hipStream_t)stream);
+  }
   if (split) return launch_split(h, stash ? h->sp.fwd_stash[integrator] : h->sp.fwd[integrator], p, tiles, (hipStream_t)stream);
   return launch(h, stash ? h->ks.fwd_stash[integrator] : h->ks.fwd[integrator], p, tiles, false, (hipStream_t)stream);
 }
 
-int phnn_rollout_grad(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
-                      const phnn_cost* cost, int32_t integrator, float dt, const float* traj_dev,
-                      const void* workspace_dev, float* grad_u_dev, float* grad_x0_dev, void* stream) {
-  return phnn_rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, nullptr, nullptr,
-                          grad_u_dev, grad_x0_dev, stream);
+int phnn_rollout_fwd(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                     const phnn_cost* cost, int32_t integrator, float dt, float* cost_dev, float* traj_dev,
+                     void* workspace_dev, void* stream) {
+  return rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, cost_dev, traj_dev, workspace_dev, nullptr, stream);
 }
 
-int phnn_rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
-                     const phnn_cost* cost, int32_t integrator, float dt, const float* traj_dev,
-                     const void* workspace_dev, const float* traj_bar_dev, const float* cost_bar_dev,
-                     float* grad_u_dev, float* grad_x0_dev, void* stream) {
+int phnn_rollout_fwd_ref(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                         const phnn_cost* cost, const phnn_reference* ref, int32_t integrator, float dt, float* cost_dev,
+                         float* traj_dev, void* workspace_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (!ref) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference is NULL");
+  return rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, cost_dev, traj_dev, workspace_dev, ref, stream);
+}
+
+static int rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                       const phnn_cost* cost, int32_t integrator, float dt, const float* traj_dev,
+                       const void* workspace_dev, const float* traj_bar_dev, const float* cost_bar_dev,
+                       float* grad_u_dev, float* grad_x0_dev, const phnn_reference* ref, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
   RollParams p;
   if (int rc = fill_roll(h, &p, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
+  if (int rc = fill_ref(h, &p, ref, B)) return rc;
   if (B == 0) return PHNN_OK;
   if (!traj_dev || !grad_u_dev) return fail(h, PHNN_ERR_INVALID_ARG, "traj_dev / grad_u_dev is NULL");
   PHNN_ON_DEVICE(h);
@@ -854,8 +908,37 @@ int phnn_rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, in
   const bool split = use_split(h, tiles);
   const bool stash = workspace_dev != nullptr;
   p.stash = (float*)workspace_dev;
+  if (ref) {
+    if (split) return launch_split(h, stash ? h->sp.grad_stash_ref[integrator] : h->sp.grad_ref[integrator], p, tiles, (hipStream_t)stream);
+    return launch(h, stash ? h->ks.grad_stash_ref[integrator] : h->ks.grad_ref[integrator], p, tiles, false, (hipStream_t)stream);
+  }
   if (split) return launch_split(h, stash ? h->sp.grad_stash[integrator] : h->sp.grad[integrator], p, tiles, (hipStream_t)stream);
   return launch(h, stash ? h->ks.grad_stash[integrator] : h->ks.grad[integrator], p, tiles, false, (hipStream_t)stream);
+}
+
+int phnn_rollout_grad(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                      const phnn_cost* cost, int32_t integrator, float dt, const float* traj_dev,
+                      const void* workspace_dev, float* grad_u_dev, float* grad_x0_dev, void* stream) {
+  return rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, nullptr, nullptr,
+                     grad_u_dev, grad_x0_dev, nullptr, stream);
+}
+
+int phnn_rollout_grad_ref(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                          const phnn_cost* cost, const phnn_reference* ref, int32_t integrator, float dt,
+                          const float* traj_dev, const void* workspace_dev, float* grad_u_dev, float* grad_x0_dev,
+                          void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (!ref) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference is NULL");
+  return rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, nullptr, nullptr,
+                     grad_u_dev, grad_x0_dev, ref, stream);
+}
+
+int phnn_rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                     const phnn_cost* cost, int32_t integrator, float dt, const float* traj_dev,
+                     const void* workspace_dev, const float* traj_bar_dev, const float* cost_bar_dev,
+                     float* grad_u_dev, float* grad_x0_dev, void* stream) {
+  return rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, traj_bar_dev, cost_bar_dev,
+                     grad_u_dev, grad_x0_dev, nullptr, stream);
 }
 
 // ---- training side --------------------------------------------------------------------------
@@ -1045,14 +1128,15 @@ int phnn_adam_step(phnn_handle* h, float* u_dev, const float* grad_dev, float* e
   return PHNN_OK;
 }
 
-int phnn_solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
-               int32_t integrator, float dt, const phnn_solve_options* opt, float* exp_avg_dev, float* exp_avg_sq_dev,
-               float* grad_dev, float* cost_dev, float* traj_dev, void* workspace_dev, float* costs_dev,
-               float* best_cost_dev, float* best_u_dev, void* stream) {
+static int solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                 int32_t integrator, float dt, const phnn_solve_options* opt, float* exp_avg_dev, float* exp_avg_sq_dev,
+                 float* grad_dev, float* cost_dev, float* traj_dev, void* workspace_dev, float* costs_dev,
+                 float* best_cost_dev, float* best_u_dev, const phnn_reference* ref, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
   if (!opt || opt->iters < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_options: NULL or iters < 0");
   RollParams p;
   if (int rc = fill_roll(h, &p, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
+  if (int rc = fill_ref(h, &p, ref, B)) return rc;
   if (B == 0 || opt->iters == 0) return PHNN_OK;
   if (!exp_avg_dev || !exp_avg_sq_dev || !grad_dev || !cost_dev || !traj_dev)
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve: exp_avg, exp_avg_sq, grad, cost and traj buffers are required");
@@ -1068,12 +1152,14 @@ int phnn_solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int
   if (e == hipSuccess && opt->track_best) e = hipMemsetAsync(best_u_dev, 0, sizeof(float) * count, st);
   if (e != hipSuccess) return hip_fail(h, e, "phnn_solve: state reset");
   for (int k = 0; k < opt->iters; ++k) {
-    if (int rc = phnn_rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, cost_dev, traj_dev, workspace_dev, stream)) return rc;
+    if (int rc = rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, cost_dev, traj_dev, workspace_dev, ref, stream)) return rc;
     if (costs_dev) {
       e = hipMemcpyAsync(costs_dev + (size_t)k * B, cost_dev, sizeof(float) * (size_t)B, hipMemcpyDeviceToDevice, st);
       if (e != hipSuccess) return hip_fail(h, e, "phnn_solve: cost history copy");
     }
-    if (int rc = phnn_rollout_grad(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, grad_dev, nullptr, stream)) return rc;
+    if (int rc = rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, nullptr, nullptr, grad_dev,
+                             nullptr, ref, stream))
+      return rc;
     if (int rc = phnn_adam_step(h, u_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, (int64_t)count, opt->lr, opt->beta1, opt->beta2,
                                 opt->eps, k + 1, opt->track_best ? cost_dev : nullptr, opt->track_best ? best_cost_dev : nullptr,
                                 opt->track_best ? best_u_dev : nullptr, (int64_t)H * m, cost->u_min, cost->u_max,
@@ -1081,6 +1167,24 @@ int phnn_solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int
       return rc;
   }
   return PHNN_OK;
+}
+
+int phnn_solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+               int32_t integrator, float dt, const phnn_solve_options* opt, float* exp_avg_dev, float* exp_avg_sq_dev,
+               float* grad_dev, float* cost_dev, float* traj_dev, void* workspace_dev, float* costs_dev,
+               float* best_cost_dev, float* best_u_dev, void* stream) {
+  return solve(h, x0_dev, u_dev, B, H, cost, integrator, dt, opt, exp_avg_dev, exp_avg_sq_dev, grad_dev, cost_dev, traj_dev,
+               workspace_dev, costs_dev, best_cost_dev, best_u_dev, nullptr, stream);
+}
+
+int phnn_solve_ref(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                   const phnn_reference* ref, int32_t integrator, float dt, const phnn_solve_options* opt,
+                   float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_dev, float* cost_dev, float* traj_dev,
+                   void* workspace_dev, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (!ref) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference is NULL");
+  return solve(h, x0_dev, u_dev, B, H, cost, integrator, dt, opt, exp_avg_dev, exp_avg_sq_dev, grad_dev, cost_dev, traj_dev,
+               workspace_dev, costs_dev, best_cost_dev, best_u_dev, ref, stream);
 }
 
 int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, const float* action_dev,

@@ -112,6 +112,8 @@ using M_ODE_4_128_GELU = OdeModel<4, 128, MM_F32, ACT_GELU>;
 struct GradSet {
   void (*grad[2])(RollParams);     // Euler, RK4: recompute the tape
   void (*grad_stash[2])(RollParams);  // Euler, RK4: K2 reads the tape(s) K1 stashed
+  void (*grad_ref[2])(RollParams);    // the same two pairs with reference tracking (grad_march REF)
+  void (*grad_stash_ref[2])(RollParams);
   void (*mvjp)(PointParams);
 };
 
@@ -126,6 +128,10 @@ struct SplitSet {
   void (*grad[2])(RollParams);
   void (*fwd_stash[2])(RollParams);   // Euler, RK4
   void (*grad_stash[2])(RollParams);
+  void (*fwd_ref[2])(RollParams);     // the four pairs above with reference tracking (REF marches)
+  void (*grad_ref[2])(RollParams);
+  void (*fwd_stash_ref[2])(RollParams);
+  void (*grad_stash_ref[2])(RollParams);
   int lds_floats;  // image + 4 x per-wave scratch + exchange area
 };
 bool phnn_split_kernels(int variant, SplitSet* g);  // false: no split-tile kernels for this variant

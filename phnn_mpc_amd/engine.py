@@ -25,11 +25,41 @@ def _check(lib, handle, rc):
         raise PhnnError(f"phnn_mpc error {rc}: {msg}")
 
 
+def reference_view(x_ref, B, n, device=None):
+    """Strides of a reference trajectory for phnn_reference.
+
+    x_ref: anything broadcastable to (B, rows, n) -- (n,) a setpoint, (rows, n) one trajectory shared by the batch,
+    (1 | B, rows, n); a last dimension of 1 broadcasts over the state.  -> (t, batch_stride, time_stride, rows): a
+    float32 tensor on `device` (None: x_ref's own) whose element [b, row, i] sits at t.data_ptr() + 4 * (b * batch_stride +
+    row * time_stride + i).  A problem or row dimension that is broadcast (size 1, or stride 0 from expand) gets stride 0
+    and is not materialised; the data are copied only to make them float32 on `device` or to make the last dimension
+    contiguous (then only the distinct elements are copied)."""
+    t = torch.as_tensor(x_ref, dtype=torch.float32, device=device)
+    shape = tuple(t.shape)
+    if not 1 <= t.dim() <= 3:
+        raise ValueError(f"x_ref must have 1 to 3 dimensions (n,), (rows, n) or (B, rows, n), got shape {shape}")
+    while t.dim() < 3:
+        t = t.unsqueeze(0)
+    if t.shape[0] not in (1, B) or t.shape[2] not in (1, n) or t.shape[1] < 1 or t.shape[1] >= 2 ** 31:
+        raise ValueError(f"x_ref of shape {shape} does not broadcast to (B={B}, rows, n={n})")
+    t = t.expand(t.shape[0], t.shape[1], n)
+    if n > 1 and t.stride(2) != 1:
+        src = t[:1] if t.stride(0) == 0 else t
+        src = src[:, :1] if src.stride(1) == 0 else src
+        t = src.contiguous().expand(t.shape)
+    rows = int(t.shape[1])
+    bs = 0 if t.shape[0] == 1 else int(t.stride(0))
+    ts = 0 if rows == 1 else int(t.stride(1))
+    return t, bs, ts, rows
+
+
 class RolloutEngine:
     """One dynamics model resident on one GPU.
 
     state_dict: the reference's state_dict (torch tensors or numpy arrays), or a checkpoint wrapping it.
     """
+
+    supports_reference = True  # rollout_cost / rollout_cost_grad / solve track x_ref (phnn_reference)
 
     def __init__(self, state_dict, device="cuda:0", kind=None, activation="tanh", matmul=None, force_matmul=False,
                  max_waves=None, split="auto"):
@@ -142,6 +172,21 @@ class RolloutEngine:
     def _p(t):
         return C.c_void_p(t.data_ptr()) if t is not None else None
 
+    def _reference(self, x_ref, ref_offset, B):
+        """-> (phnn_reference, tensors to keep alive until the launches are enqueued).  ref_offset: int >= 0 or a
+        device int32 tensor (its first element is read by every launch; a captured graph follows it)."""
+        t, bs, ts, rows = reference_view(x_ref, B, self.n, self.device)
+        r = _capi.Reference()
+        r.x_ref = t.data_ptr() if t.numel() else None
+        r.batch_stride, r.time_stride, r.rows = bs, ts, rows
+        if isinstance(ref_offset, torch.Tensor):
+            if ref_offset.dtype != torch.int32 or ref_offset.device != self.device or ref_offset.numel() < 1:
+                raise ValueError("ref_offset: an int or an int32 tensor on the engine's device")
+            r.offset_dev = ref_offset.data_ptr()
+        else:
+            r.offset_host = int(ref_offset)
+        return r, (t, ref_offset)
+
     def _integ(self, integrator):
         if isinstance(integrator, str):
             if integrator not in _capi.INTEGRATORS:
@@ -172,8 +217,11 @@ class RolloutEngine:
         return xb, ub
 
     # ------------------------------------------------------------------ rollouts
-    def rollout_cost(self, x0, u, cost, integrator="euler", dt=0.02, want_traj=False, traj_out=None):
-        """K1.  x0 (B,n), u (B,H,m) -> cost (B) [, traj (B,H+1,n)]."""
+    def rollout_cost(self, x0, u, cost, integrator="euler", dt=0.02, want_traj=False, traj_out=None, x_ref=None,
+                     ref_offset=0):
+        """K1.  x0 (B,n), u (B,H,m) -> cost (B) [, traj (B,H+1,n)].  x_ref: a reference trajectory broadcastable to
+        (B, rows, n); step t of problem b is then costed about row min(ref_offset + t, rows - 1) of its reference
+        instead of cost.x_target (reference_view, phnn_reference)."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u, H = self._controls(u, B)
@@ -181,8 +229,14 @@ class RolloutEngine:
         traj = traj_out
         if traj is None and want_traj:
             traj = torch.empty(B, H + 1, self.n, dtype=torch.float32, device=self.device)
-        rc = self.lib.phnn_rollout_fwd(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), self._integ(integrator),
-                                       float(dt), self._p(c), self._p(traj), None, self._stream())
+        if x_ref is None:
+            rc = self.lib.phnn_rollout_fwd(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), self._integ(integrator),
+                                           float(dt), self._p(c), self._p(traj), None, self._stream())
+        else:
+            ref, _keep = self._reference(x_ref, ref_offset, B)
+            rc = self.lib.phnn_rollout_fwd_ref(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(ref),
+                                               self._integ(integrator), float(dt), self._p(c), self._p(traj), None,
+                                               self._stream())
         _check(self.lib, self.h, rc)
         return (c, traj) if (want_traj or traj_out is not None) else c
 
@@ -190,10 +244,11 @@ class RolloutEngine:
         return int(self.lib.phnn_workspace_bytes(self.h, int(B), int(H), self._integ(integrator)))
 
     def rollout_cost_grad(self, x0, u, cost, integrator="euler", dt=0.02, want_grad_x0=False, workspace=None,
-                          after_forward=None):
+                          after_forward=None, x_ref=None, ref_offset=0):
         """K1 + K2.  -> (cost (B), grad_u (B,H,m)[, grad_x0 (B,n)]).  `workspace`: optional dict reused across
         calls to avoid re-allocating the trajectory / outputs.  `after_forward(cost)` is called once K1 is enqueued
-        and before K2 is: the costs are final then, so a collective on them overlaps the adjoint kernel."""
+        and before K2 is: the costs are final then, so a collective on them overlaps the adjoint kernel.
+        x_ref, ref_offset: reference tracking as in rollout_cost."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u, H = self._controls(u, B)
@@ -211,14 +266,23 @@ class RolloutEngine:
             ws["grad_x0"] = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
         st = self._stream()
         stash = self._p(ws["stash"])
-        rc = self.lib.phnn_rollout_fwd(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt),
-                                       self._p(ws["cost"]), self._p(ws["traj"]), stash, st)
+        if x_ref is None:
+            rc = self.lib.phnn_rollout_fwd(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt),
+                                           self._p(ws["cost"]), self._p(ws["traj"]), stash, st)
+        else:
+            ref, _keep = self._reference(x_ref, ref_offset, B)
+            rc = self.lib.phnn_rollout_fwd_ref(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(ref), integ,
+                                               float(dt), self._p(ws["cost"]), self._p(ws["traj"]), stash, st)
         _check(self.lib, self.h, rc)
         if after_forward is not None:
             after_forward(ws["cost"])
-        rc = self.lib.phnn_rollout_grad(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt),
-                                        self._p(ws["traj"]), stash, self._p(ws["grad_u"]),
-                                        self._p(ws["grad_x0"]) if want_grad_x0 else None, st)
+        gx = self._p(ws["grad_x0"]) if want_grad_x0 else None
+        if x_ref is None:
+            rc = self.lib.phnn_rollout_grad(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt),
+                                            self._p(ws["traj"]), stash, self._p(ws["grad_u"]), gx, st)
+        else:
+            rc = self.lib.phnn_rollout_grad_ref(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(ref), integ,
+                                                float(dt), self._p(ws["traj"]), stash, self._p(ws["grad_u"]), gx, st)
         _check(self.lib, self.h, rc)
         if want_grad_x0:
             return ws["cost"], ws["grad_u"], ws["grad_x0"]
@@ -366,11 +430,11 @@ class RolloutEngine:
 
     # ------------------------------------------------------------------ the whole shooting solve (K1, K2, K3 x iters)
     def solve(self, x0, u_init, cost, integrator="euler", dt=0.02, lr=0.015, iters=30, track_best=False, record_costs=True,
-              beta1=0.9, beta2=0.999, eps=1e-8, workspace=None):
+              beta1=0.9, beta2=0.999, eps=1e-8, workspace=None, x_ref=None, ref_offset=0):
         """phnn_solve: Adam on the control sequences of B independent problems, the loops of
         src/mpc_controller.py:164-209 / src/mpc_controller_canonical.py:163-228, as ONE library call that enqueues the
         K1 / K2 / K3 launches of every iteration (no Python between them).  -> dict as solver.shooting_solve, same
-        results bit for bit."""
+        results bit for bit.  x_ref, ref_offset: every problem tracks its own reference (rollout_cost; phnn_solve_ref)."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u_init, H = self._controls(u_init, B)
@@ -391,10 +455,15 @@ class RolloutEngine:
         best_cost = torch.empty(B, **f) if track_best else None
         best_u = torch.empty(B, H, self.m, **f) if track_best else None
         opt = _capi.SolveOptions(int(iters), float(lr), float(beta1), float(beta2), float(eps), int(bool(track_best)))
-        rc = self.lib.phnn_solve(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt), C.byref(opt),
-                                 self._p(ws["s_m"]), self._p(ws["s_v"]), self._p(ws["s_grad"]), self._p(ws["s_cost"]),
-                                 self._p(ws["s_traj"]), self._p(ws["s_stash"]), self._p(costs), self._p(best_cost),
-                                 self._p(best_u), self._stream())
+        bufs = (self._p(ws["s_m"]), self._p(ws["s_v"]), self._p(ws["s_grad"]), self._p(ws["s_cost"]), self._p(ws["s_traj"]),
+                self._p(ws["s_stash"]), self._p(costs), self._p(best_cost), self._p(best_u), self._stream())
+        if x_ref is None:
+            rc = self.lib.phnn_solve(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt), C.byref(opt),
+                                     *bufs)
+        else:
+            ref, _keep = self._reference(x_ref, ref_offset, B)
+            rc = self.lib.phnn_solve_ref(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(ref), integ,
+                                         float(dt), C.byref(opt), *bufs)
         _check(self.lib, self.h, rc)
         out = {"u_last": u, "costs": costs}
         if track_best:

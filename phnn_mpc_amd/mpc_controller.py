@@ -115,8 +115,10 @@ class MPCController:
         return u0.detach().numpy()
 
     # ------------------------------------------------------------------ batched (new)
-    def solve_batch(self, states, record_costs=False):
-        """states (B,n) -> dict with the last iterate of B independent problems (all on the engine's device)."""
+    def solve_batch(self, states, record_costs=False, x_ref=None, ref_offset=0):
+        """states (B,n) -> dict with the last iterate of B independent problems (all on the engine's device).
+        x_ref: per-problem reference trajectories broadcastable to (B, rows, n), tracked from row ref_offset (int or
+        device int32 tensor; past its end a reference holds its last row) instead of target_state."""
         if self.optimizer_type == "LBFGS":
             raise NotImplementedError("L-BFGS keeps a curvature history per problem: use compute_control (one plant "
                                       "at a time); the batched solve is Adam only")
@@ -125,12 +127,13 @@ class MPCController:
         eng = self.engine
         x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
         u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
+        rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.lr, self.max_iterations,
-                                 track_best=False, u_min=self.u_min, u_max=self.u_max, record_costs=record_costs)
+                                 track_best=False, u_min=self.u_min, u_max=self.u_max, record_costs=record_costs, **rkw)
 
-    def compute_control_batch(self, states):
-        """states (B,n) -> np.ndarray (B,1): first control of each plant's optimised sequence."""
-        out = self.solve_batch(states)
+    def compute_control_batch(self, states, x_ref=None, ref_offset=0):
+        """states (B,n) -> np.ndarray (B,1): first control of each plant's optimised sequence (x_ref: solve_batch)."""
+        out = self.solve_batch(states) if x_ref is None else self.solve_batch(states, x_ref=x_ref, ref_offset=ref_offset)
         u0 = out["u_last"][:, 0, :]
         if self.u_min is not None and self.u_max is not None:
             u0 = torch.clamp(u0, self.u_min, self.u_max)

@@ -98,8 +98,10 @@ class MPCControllerCanonical:
         return u, info
 
     # ------------------------------------------------------------------ batched (new)
-    def optimize_control_batch(self, x0, u_init=None, record_costs=True):
-        """x0 (B,n), u_init (B,H,m) or None -> dict(best_u (B,H,m) clamped, best_cost (B), costs (steps,B), u_last)."""
+    def optimize_control_batch(self, x0, u_init=None, record_costs=True, x_ref=None, ref_offset=0):
+        """x0 (B,n), u_init (B,H,m) or None -> dict(best_u (B,H,m) clamped, best_cost (B), costs (steps,B), u_last).
+        x_ref: per-problem reference trajectories broadcastable to (B, rows, n), tracked from row ref_offset (int or
+        device int32 tensor; past its end a reference holds its last row) instead of x_target."""
         eng = self.engine
         x0 = torch.as_tensor(x0, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
         B = x0.shape[0]
@@ -107,17 +109,22 @@ class MPCControllerCanonical:
             u0 = torch.zeros(B, self.horizon, self.input_dim, dtype=torch.float32, device=eng.device)
         else:
             u0 = torch.as_tensor(u_init, dtype=torch.float32).reshape(B, self.horizon, self.input_dim).to(eng.device)
+        rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.learning_rate,
                                  self.optimizer_steps, track_best=True, u_min=self.u_min, u_max=self.u_max,
-                                 record_costs=record_costs)
+                                 record_costs=record_costs, **rkw)
 
-    def control_batch(self, x_current, u_prev=None):
-        """x_current (B,n), u_prev (B,H,m) or None -> (u (B,m), u_sequence (B,H,m), best_cost (B)) numpy arrays."""
+    def control_batch(self, x_current, u_prev=None, x_ref=None, ref_offset=0):
+        """x_current (B,n), u_prev (B,H,m) or None -> (u (B,m), u_sequence (B,H,m), best_cost (B)) numpy arrays.
+        x_ref, ref_offset: optimize_control_batch."""
         u_init = None
         if u_prev is not None:
             up = torch.as_tensor(u_prev, dtype=torch.float32)
             u_init = torch.cat([up[:, 1:], torch.zeros(up.shape[0], 1, self.input_dim)], dim=1)
-        out = self.optimize_control_batch(x_current, u_init, record_costs=False)
+        if x_ref is None:
+            out = self.optimize_control_batch(x_current, u_init, record_costs=False)
+        else:
+            out = self.optimize_control_batch(x_current, u_init, record_costs=False, x_ref=x_ref, ref_offset=ref_offset)
         seq = out["best_u"].cpu().numpy()
         return seq[:, 0, :], seq, out["best_cost"].cpu().numpy()
 

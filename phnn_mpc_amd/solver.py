@@ -13,14 +13,23 @@ import ctypes
 import torch
 
 
+def _need_reference(engine, x_ref):
+    if x_ref is not None and not getattr(engine, "supports_reference", False):
+        raise NotImplementedError(f"{type(engine).__name__} has no reference tracking (x_ref): RolloutEngine has")
+
+
 def shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=False, u_min=None, u_max=None,
-                   record_costs=True):
+                   record_costs=True, x_ref=None, ref_offset=0):
     """x0 (B,n), u_init (B,H,m) on engine.device -> dict(u_last, costs[, best_u, best_cost]).
 
     u_last   : unclamped last iterate (B,H,m)
     costs    : (iters,B) cost of each iterate (measured before its Adam step), if record_costs
     best_u   : clamped best iterate (track_best)
+    x_ref    : reference trajectory broadcastable to (B, rows, n), tracked from row ref_offset (int or device int32
+               tensor) on (RolloutEngine.rollout_cost); None: the cost's x_target
     """
+    _need_reference(engine, x_ref)
+    rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
     dev = x0.device
     u = u_init.detach().clone().contiguous()
     exp_avg = torch.zeros_like(u)
@@ -33,7 +42,7 @@ def shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_be
         best_u = torch.zeros_like(u)
     ws = {}
     for k in range(iters):
-        c, g = engine.rollout_cost_grad(x0, u, cost, integrator, dt, workspace=ws)
+        c, g = engine.rollout_cost_grad(x0, u, cost, integrator, dt, workspace=ws, **rkw)
         if record_costs:
             costs[k].copy_(c)
         engine.adam_step(u, g, exp_avg, exp_avg_sq, lr, k + 1, cost=c if track_best else None, best_cost=best_cost,
@@ -44,17 +53,21 @@ def shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_be
     return out
 
 
-def _eager(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=False, u_min=None, u_max=None, record_costs=True):
+def _eager(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=False, u_min=None, u_max=None, record_costs=True,
+           x_ref=None, ref_offset=0):
     """The solve without a captured graph: the library's own loop (phnn_solve: one call enqueues every launch) when the
     engine has one and the Adam-side bounds are the cost's (they are for both controller classes); else the Python loop.
-    Same launches, same order: identical results."""
+    Same launches, same order: identical results.  x_ref / ref_offset: see shooting_solve."""
+    _need_reference(engine, x_ref)
+    rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
     has_b = u_min is not None and u_max is not None
     same = bool(cost.has_u_bounds) == has_b and (not has_b or (float(cost.u_min) == float(ctypes.c_float(u_min).value)
                                                                 and float(cost.u_max) == float(ctypes.c_float(u_max).value)))
     if hasattr(engine, "solve") and same:
-        return engine.solve(x0, u_init, cost, integrator, dt, lr=lr, iters=iters, track_best=track_best, record_costs=record_costs)
+        return engine.solve(x0, u_init, cost, integrator, dt, lr=lr, iters=iters, track_best=track_best, record_costs=record_costs,
+                            **rkw)
     return shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=track_best, u_min=u_min, u_max=u_max,
-                          record_costs=record_costs)
+                          record_costs=record_costs, **rkw)
 
 
 def solver_for(engine, use_graph, previous=None):
@@ -75,6 +88,12 @@ class GraphedSolve:
     The graph is tied to (B, H, m, iters, cost struct, integrator, dt, lr, flags); a call with another signature
     re-captures.  Inputs are copied into the graph's static buffers, results are returned as fresh tensors.
     Same kernels, same order, same arithmetic as shooting_solve: results are bit-identical.
+
+    Reference tracking (x_ref, ref_offset): the graph reads the reference through the pointer it was captured with.
+    That pointer is a static buffer of the graph, (1 | B, rows, n) as reference_view leaves it before broadcasting,
+    and every call copies the caller's x_ref (and ref_offset, int or device int32 tensor) into it: a reference of
+    another shape re-captures, one updated in place is seen by the next call.  The static buffer stays alive as long
+    as this object holds the graph.
     """
 
     def __init__(self, engine):
@@ -82,11 +101,20 @@ class GraphedSolve:
         self.key = None
         self.graph = None
 
-    def _signature(self, x0, u_init, cost, integrator, dt, lr, iters, track_best, u_min, u_max, record_costs):
-        return (tuple(x0.shape), tuple(u_init.shape), bytes(ctypes.string_at(ctypes.addressof(cost), ctypes.sizeof(cost))),
-                integrator, float(dt), float(lr), int(iters), bool(track_best), u_min, u_max, bool(record_costs))
+    def _signature(self, x0, u_init, cost, integrator, dt, lr, iters, track_best, u_min, u_max, record_costs, ref=None):
+        key = (tuple(x0.shape), tuple(u_init.shape), bytes(ctypes.string_at(ctypes.addressof(cost), ctypes.sizeof(cost))),
+               integrator, float(dt), float(lr), int(iters), bool(track_best), u_min, u_max, bool(record_costs))
+        return key if ref is None else key + (tuple(ref.shape),)
 
-    def _capture(self, x0, u_init, cost, integrator, dt, lr, iters, track_best, u_min, u_max, record_costs):
+    def _compact_reference(self, x_ref, B, n):
+        """x_ref -> the (1 | B, rows, 1 | n) tensor reference_view broadcasts from (what the static buffer holds)."""
+        from .engine import reference_view
+        t, bs, ts, rows = reference_view(x_ref, B, n, self.engine.device)
+        t = t[:1] if bs == 0 else t
+        t = t[:, :1] if ts == 0 else t
+        return t
+
+    def _capture(self, x0, u_init, cost, integrator, dt, lr, iters, track_best, u_min, u_max, record_costs, ref=None):
         eng, dev = self.engine, x0.device
         self.x0 = x0.detach().clone().contiguous()
         self.u_init = u_init.detach().clone().contiguous()
@@ -97,6 +125,11 @@ class GraphedSolve:
         self.best_cost = torch.empty(B, dtype=torch.float32, device=dev) if track_best else None
         self.best_u = torch.empty_like(self.u) if track_best else None
         self.ws = {}
+        rkw = {}
+        if ref is not None:
+            self.x_ref = ref.clone()
+            self.ref_offset = torch.zeros(1, dtype=torch.int32, device=dev)
+            rkw = {"x_ref": self.x_ref, "ref_offset": self.ref_offset}
 
         def body():
             self.u.copy_(self.u_init)
@@ -106,7 +139,7 @@ class GraphedSolve:
                 self.best_cost.fill_(float("inf"))
                 self.best_u.zero_()
             for k in range(iters):
-                c, g = eng.rollout_cost_grad(self.x0, self.u, cost, integrator, dt, workspace=self.ws)
+                c, g = eng.rollout_cost_grad(self.x0, self.u, cost, integrator, dt, workspace=self.ws, **rkw)
                 if record_costs:
                     self.costs[k].copy_(c)
                 eng.adam_step(self.u, g, self.exp_avg, self.exp_avg_sq, lr, k + 1, cost=c if track_best else None,
@@ -123,14 +156,25 @@ class GraphedSolve:
             body()
 
     def __call__(self, engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=False, u_min=None, u_max=None,
-                 record_costs=True):
+                 record_costs=True, x_ref=None, ref_offset=0):
         assert engine is self.engine
-        key = self._signature(x0, u_init, cost, integrator, dt, lr, iters, track_best, u_min, u_max, record_costs)
+        _need_reference(engine, x_ref)
+        ref = None if x_ref is None else self._compact_reference(x_ref, x0.shape[0], engine.n)
+        key = self._signature(x0, u_init, cost, integrator, dt, lr, iters, track_best, u_min, u_max, record_costs, ref)
         if key != self.key:
-            self._capture(x0, u_init, cost, integrator, dt, lr, iters, track_best, u_min, u_max, record_costs)
+            self.key = None
+            self._capture(x0, u_init, cost, integrator, dt, lr, iters, track_best, u_min, u_max, record_costs, ref)
             self.key = key
         self.x0.copy_(x0)
         self.u_init.copy_(u_init)
+        if ref is not None:
+            self.x_ref.copy_(ref)
+            if isinstance(ref_offset, torch.Tensor):
+                self.ref_offset.copy_(ref_offset.reshape(-1)[:1])
+            elif int(ref_offset) < 0:
+                raise ValueError("ref_offset < 0")
+            else:
+                self.ref_offset.fill_(int(ref_offset))
         self.graph.replay()
         out = {"u_last": self.u.clone(), "costs": self.costs.clone() if record_costs else None}
         if track_best:
