@@ -332,6 +332,44 @@ int phnn_solve_ref(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B,
                    float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_dev, float* cost_dev, float* traj_dev,
                    void* workspace_dev, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream);
 
+/* ---- batched L-BFGS solve (src/mpc_controller.py:169-170,196-197: optimizer 'LBFGS') ---------------------------
+ * Problem b is its own torch.optim.LBFGS([u_b], lr, max_iter, max_eval, tolerance_grad, tolerance_change,
+ * history_size, line_search_fn=None), created fresh per call and stepped outer_steps times; its closure is the K1 cost
+ * and the K2 gradient (w.r.t. the unclamped u) of that problem.  The data-dependent loop of step() runs on a fixed
+ * schedule: per outer step, max_iter slots of (K1, K2, k_lbfgs) for all B problems; k_lbfgs consumes the slot's
+ * evaluation for the problems waiting on one and leaves the others idle (their K1 / K2 results are ignored).
+ * Arithmetic: vectors and the scalars ys, ro, H_diag, al, be, t, gtd in float32 with a fixed reduction order per
+ * problem (results do not depend on B or on a problem's position); the loss is the float32 cost widened to double.
+ * DESIGN.md 11. */
+typedef struct {
+  int32_t outer_steps;      /* optimizer.step(closure) calls */
+  int32_t max_iter;         /* >= 1 (torch default 20) */
+  int32_t max_eval;         /* 0: torch's default max_iter * 5 / 4 */
+  int32_t history_size;     /* >= 1 (torch default 100) */
+  double lr;                /* finite (torch default 1) */
+  double tolerance_grad;    /* torch default 1e-7 */
+  double tolerance_change;  /* torch default 1e-9 */
+  int32_t reserved[4];      /* zero */
+} phnn_lbfgs_options;
+/* Bytes of the L-BFGS workspace for B problems of horizon H and this handle's m: per-problem scalars, the (s, y)
+ * history ring [B][history_size][2][H*m] (rows padded to 16 bytes), direction, previous gradient and two-loop scratch.
+ * 0 for invalid arguments. */
+size_t phnn_lbfgs_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t history_size);
+/* u_dev (B,H,m) holds the initial iterate on entry and the last one on return (unclamped).  grad_dev (B,H,m),
+ * cost_dev (B), traj_dev (B,H+1,n) and stash_workspace (phnn_workspace_bytes, or NULL) serve K1 / K2 as in phnn_solve;
+ * lbfgs_workspace (lbfgs_workspace_size >= phnn_lbfgs_workspace_bytes) holds the optimizer state.  Optional outputs:
+ * costs_dev (outer_steps,B) the orig_loss of every step() call, n_iter_dev / func_evals_dev (B) int32 state['n_iter'] /
+ * state['func_evals'].  ref: NULL = the cost's x_target, else every K1 / K2 tracks it (phnn_solve_ref; offset_dev is
+ * read by every launch).  Enqueues the state reset (zero counters), then outer_steps x max_iter x (K1, K2, k_lbfgs);
+ * stream-ordered, capturable.  outer_steps == 0 or B == 0 returns PHNN_OK after the reset.  PHNN_ERR_INVALID_ARG for
+ * history_size < 1, max_iter < 1, max_eval < 0, outer_steps < 0, a non-finite lr, NULL required buffers or a too
+ * small workspace; PHNN_ERR_UNSUPPORTED for H*m > 256. */
+int phnn_solve_lbfgs(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                     const phnn_reference* ref, int32_t integrator, float dt, const phnn_lbfgs_options* opt,
+                     float* grad_dev, float* cost_dev, float* traj_dev, void* stash_workspace, void* lbfgs_workspace,
+                     size_t lbfgs_workspace_size, float* costs_dev, int32_t* n_iter_dev, int32_t* func_evals_dev,
+                     void* stream);
+
 /* ---- the plant on the other side of the path ------------------------------------------
  * Ground-truth cart-pole of src/cartpole_simulator.py:63-112: float64, explicit Euler, the standard cart-pole
  * equations in the reference's operation order; termination |x| > x_limit or |theta| > theta_limit.  Defaults of

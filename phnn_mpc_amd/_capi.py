@@ -31,7 +31,8 @@ EXPORTED = [
     "phnn_model_vjp", "phnn_rollout_fwd", "phnn_workspace_bytes", "phnn_rollout_grad", "phnn_rollout_vjp",
     "phnn_rollout_trajectory", "phnn_rollout_trajectory_ws", "phnn_wgrad_workspace_bytes", "phnn_wgrad_record_info", "phnn_rollout_wgrad", "phnn_model_wgrad",
     "phnn_adam_step", "phnn_solve", "phnn_plant_step", "phnn_shift_controls", "phnn_kernel_info", "phnn_variant_name",
-    "phnn_version", "phnn_rollout_fwd_ref", "phnn_rollout_grad_ref", "phnn_solve_ref",
+    "phnn_version", "phnn_rollout_fwd_ref", "phnn_rollout_grad_ref", "phnn_solve_ref", "phnn_lbfgs_workspace_bytes",
+    "phnn_solve_lbfgs",
 ]
 
 
@@ -60,6 +61,14 @@ class SolveOptions(C.Structure):
     """phnn_solve_options"""
     _fields_ = [("iters", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("track_best", C.c_int32)]
+
+
+class LbfgsOptions(C.Structure):
+    """phnn_lbfgs_options: torch.optim.LBFGS(lr, max_iter, max_eval, tolerance_grad, tolerance_change, history_size)
+    stepped outer_steps times; max_eval 0 = torch's default max_iter * 5 // 4."""
+    _fields_ = [("outer_steps", C.c_int32), ("max_iter", C.c_int32), ("max_eval", C.c_int32), ("history_size", C.c_int32),
+                ("lr", C.c_double), ("tolerance_grad", C.c_double), ("tolerance_change", C.c_double),
+                ("reserved", C.c_int32 * 4)]
 
 
 class Plant(C.Structure):
@@ -212,6 +221,11 @@ def load_library():
     lib.phnn_solve_ref.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
                                    C.POINTER(SolveOptions), f32p, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, vp]
     lib.phnn_solve_ref.restype = C.c_int
+    lib.phnn_lbfgs_workspace_bytes.argtypes = [vp, i64, i32, i32]
+    lib.phnn_lbfgs_workspace_bytes.restype = C.c_size_t
+    lib.phnn_solve_lbfgs.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
+                                     C.POINTER(LbfgsOptions), f32p, f32p, f32p, vp, vp, C.c_size_t, f32p, vp, vp, vp]
+    lib.phnn_solve_lbfgs.restype = C.c_int
     lib.phnn_plant_step.argtypes = [vp, C.POINTER(Plant), vp, f32p, i64, i64, i32, C.c_float, C.c_float, f32p, vp, vp, i32,
                                     vp, f32p, vp]
     lib.phnn_plant_step.restype = C.c_int

@@ -77,8 +77,9 @@ class DeviceClosedLoop:
     """Closed loop of B cart-poles resident on the engine's GPU (SURVEY.md 8 rows f1 + f3).
 
     controller: MPCController (cold start, last iterate, clamp(u_0)) or MPCControllerCanonical (warm start by shift,
-    best clamped iterate).  One control step enqueues: iters x (K1, K2, K3), k_plant_step, k_shift_controls; with
-    use_graph the step is captured once and replayed.  Per-plant arithmetic is identical to run_mpc_batch (same
+    best clamped iterate).  One control step enqueues: iters x (K1, K2, K3), k_plant_step, k_shift_controls (an
+    MPCController with optimizer_type='LBFGS': engine.solve_lbfgs, i.e. the state reset and max_iterations x 20 x (K1,
+    K2, k_lbfgs), then k_plant_step); with use_graph the step is captured once and replayed.  Per-plant arithmetic is identical to run_mpc_batch (same
     kernels, same order); the plant differs from the numpy one only by the device's double-precision sin/cos.
 
     x_ref: reference trajectories broadcastable to (B, rows, 4) (engine.reference_view); every solve tracks them from
@@ -119,13 +120,26 @@ class DeviceClosedLoop:
             self.x_ref = reference_view(x_ref, B, 4, dev)[0]
         self.iters = controller.optimizer_steps if self.canonical else controller.max_iterations
         self.lr = controller.learning_rate if self.canonical else controller.lr
-        if not self.canonical and controller.optimizer_type != "Adam":
-            raise NotImplementedError("the device closed loop runs the batched Adam solve")
+        self.lbfgs = not self.canonical and controller.optimizer_type == "LBFGS"
+        if not self.canonical and controller.optimizer_type not in ("Adam", "LBFGS"):
+            raise ValueError(f"Unknown optimizer type: {controller.optimizer_type}")
+        if self.lbfgs and not hasattr(eng, "solve_lbfgs"):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched L-BFGS solve (RolloutEngine has)")
         self.graph = None
         self.use_graph = use_graph and dev.type == "cuda"
 
     def _control_step(self):
         eng, c = self.eng, self.ctl
+        if self.lbfgs:  # cold start from zeros, the reference's L-BFGS solve, clamp(u_0) of the last iterate
+            rkw = {} if self.x_ref is None else {"x_ref": self.x_ref, "ref_offset": self.step_dev}
+            out = eng.solve_lbfgs(self.x32, self.u_init, self.cost, integrator=c.integrator, dt=c.dt, record_costs=False,
+                                  workspace=self.ws, **c.lbfgs_options(), **rkw)
+            H = self.u.shape[1] * self.u.shape[2]
+            eng.plant_step(self.plant, self.state, out["u_last"], H, u_min=c.u_min, u_max=c.u_max, state_f32=self.x32,
+                           done_step=self.done_step, step_dev=self.step_dev, log_states=self.log_states,
+                           log_controls=self.log_controls)
+            eng.advance_step(self.step_dev)
+            return
         self.u.copy_(self.u_init)
         self.exp_avg.zero_()
         self.exp_avg_sq.zero_()

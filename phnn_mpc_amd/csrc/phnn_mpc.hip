@@ -15,6 +15,7 @@
 // bf16x3 weight-fragment prefetch: the forward kernels gain 3 % (K1 1.53 -> 1.48 ms); the adjoint kernels, compiled in
 // phnn_grad.hip without it, would spill (K2 +5 %)
 #define PHNN_PREFETCH_BF
+#include "phnn_lbfgs.h"
 #include "phnn_pack.h"
 
 namespace {
@@ -549,7 +550,7 @@ int check_cost(phnn_handle* h, const phnn_cost* c) {
 
 extern "C" {
 
-int phnn_version(void) { return 230; }
+int phnn_version(void) { return 240; }
 
 const char* phnn_variant_name(const phnn_handle* h) { return h ? h->ks.name : ""; }
 
@@ -1185,6 +1186,82 @@ int phnn_solve_ref(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B,
   if (!ref) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference is NULL");
   return solve(h, x0_dev, u_dev, B, H, cost, integrator, dt, opt, exp_avg_dev, exp_avg_sq_dev, grad_dev, cost_dev, traj_dev,
                workspace_dev, costs_dev, best_cost_dev, best_u_dev, ref, stream);
+}
+
+size_t phnn_lbfgs_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t history_size) {
+  if (!h || B < 0 || H < 1 || history_size < 1) return 0;
+  return lbfgs_layout(B, H * h->desc.m, history_size).total;
+}
+
+int phnn_solve_lbfgs(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                     const phnn_reference* ref, int32_t integrator, float dt, const phnn_lbfgs_options* opt,
+                     float* grad_dev, float* cost_dev, float* traj_dev, void* stash_workspace, void* lbfgs_workspace,
+                     size_t lbfgs_workspace_size, float* costs_dev, int32_t* n_iter_dev, int32_t* func_evals_dev,
+                     void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_lbfgs_options is NULL");
+  if (opt->outer_steps < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_lbfgs_options: outer_steps < 0");
+  if (opt->max_iter < 1) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_lbfgs_options: max_iter < 1");
+  if (opt->max_eval < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_lbfgs_options: max_eval < 0");
+  if (opt->history_size < 1) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_lbfgs_options: history_size < 1");
+  if (!std::isfinite(opt->lr)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_lbfgs_options: lr is not finite");
+  RollParams p;
+  if (int rc = fill_roll(h, &p, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
+  if (int rc = fill_ref(h, &p, ref, B)) return rc;
+  const int N = H * h->desc.m;
+  if (N > kLbfgsMaxN) return fail(h, PHNN_ERR_UNSUPPORTED, "phnn_solve_lbfgs: H * m > 256");
+  if (B == 0) return PHNN_OK;
+  if (!grad_dev || !cost_dev || !traj_dev || !lbfgs_workspace)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_lbfgs: grad, cost, traj and L-BFGS workspace buffers are required");
+  const LbfgsLayout lay = lbfgs_layout(B, N, opt->history_size);
+  if (lbfgs_workspace_size < lay.total) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_lbfgs: L-BFGS workspace too small");
+  PHNN_ON_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)lbfgs_workspace;
+  // fresh optimizer per call (the reference builds one in every compute_control): zero counters, empty history
+  hipError_t e = hipMemsetAsync(ws + lay.st, 0, sizeof(LbfgsState) * (size_t)B, st);
+  if (e == hipSuccess && n_iter_dev) e = hipMemsetAsync(n_iter_dev, 0, sizeof(int32_t) * (size_t)B, st);
+  if (e == hipSuccess && func_evals_dev) e = hipMemsetAsync(func_evals_dev, 0, sizeof(int32_t) * (size_t)B, st);
+  if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_lbfgs: state reset");
+  LbfgsParams lp;
+  memset(&lp, 0, sizeof lp);
+  lp.u = u_dev;
+  lp.cost = cost_dev;
+  lp.grad = grad_dev;
+  lp.n_iter_out = n_iter_dev;
+  lp.func_evals_out = func_evals_dev;
+  lp.st = (LbfgsState*)(ws + lay.st);
+  lp.ro = (float*)(ws + lay.ro);
+  lp.al = (float*)(ws + lay.al);
+  lp.d = (float*)(ws + lay.d);
+  lp.pg = (float*)(ws + lay.pg);
+  lp.hist = (float*)(ws + lay.hist);
+  lp.B = B;
+  lp.N = N;
+  lp.Np = (N + 3) / 4 * 4;
+  lp.hs = opt->history_size;
+  lp.max_iter = opt->max_iter;
+  lp.max_eval = opt->max_eval > 0 ? opt->max_eval : opt->max_iter * 5 / 4;  // torch: max_iter * 5 // 4
+  // Python scalars compared with (or multiplied into) float32 tensors act as float32
+  lp.lr = (float)opt->lr;
+  lp.tol_grad = (float)opt->tolerance_grad;
+  lp.tol_change = (float)opt->tolerance_change;
+  lp.ys_min = (float)1e-10;
+  lp.tol_change_d = opt->tolerance_change;
+  for (int k = 0; k < opt->outer_steps; ++k) {
+    for (int slot = 0; slot < opt->max_iter; ++slot) {
+      if (int rc = rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, cost_dev, traj_dev, stash_workspace, ref, stream))
+        return rc;
+      if (int rc = rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, stash_workspace, nullptr, nullptr,
+                               grad_dev, nullptr, ref, stream))
+        return rc;
+      lp.slot = slot;
+      lp.costs_out = (slot == 0 && costs_dev) ? costs_dev + (size_t)k * B : nullptr;
+      e = lbfgs_launch(lp, st);
+      if (e != hipSuccess) return hip_fail(h, e, "k_lbfgs launch");
+    }
+  }
+  return PHNN_OK;
 }
 
 int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, const float* action_dev,

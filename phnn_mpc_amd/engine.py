@@ -470,6 +470,56 @@ class RolloutEngine:
             out["best_u"], out["best_cost"] = best_u, best_cost
         return out
 
+    # ------------------------------------------------------------------ batched L-BFGS solve (K1, K2, k_lbfgs)
+    def lbfgs_workspace_bytes(self, B, H, history_size=100):
+        return int(self.lib.phnn_lbfgs_workspace_bytes(self.h, int(B), int(H), int(history_size)))
+
+    def solve_lbfgs(self, x0, u_init, cost, integrator="euler", dt=0.02, lr=1.0, outer_steps=1, max_iter=20, max_eval=None,
+                    tolerance_grad=1e-7, tolerance_change=1e-9, history_size=100, record_costs=True, workspace=None,
+                    x_ref=None, ref_offset=0):
+        """phnn_solve_lbfgs: B independent torch.optim.LBFGS(lr, max_iter, max_eval, tolerance_grad, tolerance_change,
+        history_size) optimizers, each created fresh and stepped outer_steps times on its problem's K1 cost and K2
+        gradient (src/mpc_controller.py:169-170,196-197), as ONE library call: outer_steps x max_iter x (K1, K2,
+        k_lbfgs) launches.  -> dict(u_last (B,H,m) unclamped last iterate, costs (outer_steps,B) orig_loss of every
+        step() or None, n_iter (B) int32 state['n_iter'], func_evals (B) int32 state['func_evals']).
+        workspace: optional dict reused across calls (K1 / K2 buffers and the optimizer state).  x_ref, ref_offset:
+        every problem tracks its own reference (rollout_cost)."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u_init, H = self._controls(u_init, B)
+        integ = self._integ(integrator)
+        ws = workspace if workspace is not None else {}
+        key = ("lbfgs", B, H, integ, int(history_size))
+        if ws.get("lkey") != key:
+            ws["lkey"] = key
+            nbytes = self.workspace_bytes(B, H, integ) if self.use_stash else 0
+            ws["l_stash"] = (torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                             if 0 < nbytes <= self.max_stash_bytes else None)
+            f = dict(dtype=torch.float32, device=self.device)
+            ws["l_traj"], ws["l_cost"] = torch.empty(B, H + 1, self.n, **f), torch.empty(B, **f)
+            ws["l_grad"] = torch.empty(B, H, self.m, **f)
+            ws["l_state"] = torch.empty(max(self.lbfgs_workspace_bytes(B, H, history_size), 1), dtype=torch.uint8,
+                                        device=self.device)
+        u = u_init.detach().clone().contiguous()
+        costs = torch.empty(int(outer_steps), B, dtype=torch.float32, device=self.device) if record_costs else None
+        n_iter = torch.empty(B, dtype=torch.int32, device=self.device)
+        func_evals = torch.empty(B, dtype=torch.int32, device=self.device)
+        opt = _capi.LbfgsOptions()
+        opt.outer_steps, opt.max_iter = int(outer_steps), int(max_iter)
+        opt.max_eval = 0 if max_eval is None else int(max_eval)
+        opt.history_size = int(history_size)
+        opt.lr, opt.tolerance_grad, opt.tolerance_change = float(lr), float(tolerance_grad), float(tolerance_change)
+        if max_eval is not None and int(max_eval) < 1:
+            raise ValueError("max_eval must be >= 1 (None: torch's default max_iter * 5 // 4)")
+        ref, _keep = (None, None) if x_ref is None else self._reference(x_ref, ref_offset, B)
+        rc = self.lib.phnn_solve_lbfgs(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
+                                       None if ref is None else C.byref(ref), integ, float(dt), C.byref(opt),
+                                       self._p(ws["l_grad"]), self._p(ws["l_cost"]), self._p(ws["l_traj"]),
+                                       self._p(ws["l_stash"]), self._p(ws["l_state"]), ws["l_state"].numel(),
+                                       self._p(costs), self._p(n_iter), self._p(func_evals), self._stream())
+        _check(self.lib, self.h, rc)
+        return {"u_last": u, "costs": costs, "n_iter": n_iter, "func_evals": func_evals}
+
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
                    step=0, step_dev=None, log_states=None, log_controls=None):

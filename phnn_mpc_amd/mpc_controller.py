@@ -6,6 +6,8 @@ Reference behaviour kept:
   - controls are clamped inside the differentiated closure only when BOTH u_min and u_max are given;
   - every call cold-starts from zeros, runs max_iterations Adam steps and returns clamp(u_0) of the LAST iterate
     as a numpy array of shape (1,).
+optimizer_type='LBFGS': compute_control runs the reference's torch.optim.LBFGS on the host (one plant); solve_batch /
+compute_control_batch run B such optimizers at once on the device (engine.solve_lbfgs, kernel k_lbfgs).
 """
 import os
 
@@ -13,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import solver_for
+from .solver import lbfgs_solver_for, solver_for
 
 
 class MPCController:
@@ -120,8 +122,7 @@ class MPCController:
         x_ref: per-problem reference trajectories broadcastable to (B, rows, n), tracked from row ref_offset (int or
         device int32 tensor; past its end a reference holds its last row) instead of target_state."""
         if self.optimizer_type == "LBFGS":
-            raise NotImplementedError("L-BFGS keeps a curvature history per problem: use compute_control (one plant "
-                                      "at a time); the batched solve is Adam only")
+            return self._solve_batch_lbfgs(states, record_costs, x_ref, ref_offset)
         if self.optimizer_type != "Adam":
             raise ValueError(f"Unknown optimizer type: {self.optimizer_type}")
         eng = self.engine
@@ -130,6 +131,26 @@ class MPCController:
         rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.lr, self.max_iterations,
                                  track_best=False, u_min=self.u_min, u_max=self.u_max, record_costs=record_costs, **rkw)
+
+    def lbfgs_options(self):
+        """solve_lbfgs keyword arguments of the reference's optimizer: torch.optim.LBFGS([u], lr=self.lr, max_iter=20)
+        (torch's defaults for the rest) stepped max_iterations times (src/mpc_controller.py:169-170,196-197)."""
+        return dict(lr=self.lr, outer_steps=self.max_iterations, max_iter=20, max_eval=None, tolerance_grad=1e-7,
+                    tolerance_change=1e-9, history_size=100)
+
+    def _solve_batch_lbfgs(self, states, record_costs, x_ref, ref_offset):
+        """B independent copies of the reference's L-BFGS solve (cold start from zeros) in one batched device solve
+        (engine.solve_lbfgs).  Engines without it raise NotImplementedError."""
+        eng = self.engine
+        if not hasattr(eng, "solve_lbfgs"):
+            raise NotImplementedError("L-BFGS keeps a curvature history per problem: this engine has no batched "
+                                      "L-BFGS solve (RolloutEngine has); use compute_control (one plant at a time)")
+        self._graphed_lbfgs = lbfgs_solver_for(eng, self.use_graph, getattr(self, "_graphed_lbfgs", None))
+        x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
+        u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
+        rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
+        return self._graphed_lbfgs(x0, u0, self._cost(), integrator=self.integrator, dt=self.dt, record_costs=record_costs,
+                                   **self.lbfgs_options(), **rkw)
 
     def compute_control_batch(self, states, x_ref=None, ref_offset=0):
         """states (B,n) -> np.ndarray (B,1): first control of each plant's optimised sequence (x_ref: solve_batch)."""

@@ -180,3 +180,77 @@ class GraphedSolve:
         if track_best:
             out["best_u"], out["best_cost"] = self.best_u.clone(), self.best_cost.clone()
         return out
+
+
+def lbfgs_solver_for(engine, use_graph, previous=None):
+    """-> callable(**solve_lbfgs arguments) -> dict(u_last, costs, n_iter, func_evals): engine.solve_lbfgs, or a
+    GraphedLBFGS bound to `engine` (reused from `previous` when it already is one for this engine)."""
+    if not hasattr(engine, "solve_lbfgs"):
+        raise NotImplementedError(f"{type(engine).__name__} has no batched L-BFGS solve (RolloutEngine has): use "
+                                  "compute_control (one plant at a time)")
+    if not use_graph or engine.device.type != "cuda":
+        return engine.solve_lbfgs
+    if isinstance(previous, GraphedLBFGS) and previous.engine is engine:
+        return previous
+    return GraphedLBFGS(engine)
+
+
+class GraphedLBFGS:
+    """engine.solve_lbfgs captured once as a HIP graph (the state reset plus every outer_steps x max_iter x (K1, K2,
+    k_lbfgs) launch) and replayed per call.  Tied to (B, H, m, cost struct, integrator, dt and the L-BFGS options); a
+    call with another signature re-captures.  Inputs are copied into the graph's static buffers, results are returned
+    as fresh tensors; same launches in the same order as the eager call: identical results.  x_ref / ref_offset as in
+    GraphedSolve (a static reference buffer; another shape re-captures)."""
+
+    def __init__(self, engine):
+        self.engine = engine
+        self.key = None
+        self.graph = None
+
+    def _capture(self, x0, u_init, cost, kw, ref):
+        eng, dev = self.engine, x0.device
+        self.x0 = x0.detach().clone().contiguous()
+        self.u_init = u_init.detach().clone().contiguous()
+        self.ws = {}
+        rkw = {}
+        if ref is not None:
+            self.x_ref = ref.clone()
+            self.ref_offset = torch.zeros(1, dtype=torch.int32, device=dev)
+            rkw = {"x_ref": self.x_ref, "ref_offset": self.ref_offset}
+        # one eager pass on a side stream first: allocates the workspace outside the capture
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            eng.solve_lbfgs(self.x0, self.u_init, cost, workspace=self.ws, **kw, **rkw)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = eng.solve_lbfgs(self.x0, self.u_init, cost, workspace=self.ws, **kw, **rkw)
+
+    def __call__(self, x0, u_init, cost, integrator="euler", dt=0.02, lr=1.0, outer_steps=1, max_iter=20, max_eval=None,
+                 tolerance_grad=1e-7, tolerance_change=1e-9, history_size=100, record_costs=True, workspace=None,
+                 x_ref=None, ref_offset=0):
+        kw = dict(integrator=integrator, dt=float(dt), lr=float(lr), outer_steps=int(outer_steps), max_iter=int(max_iter),
+                  max_eval=max_eval, tolerance_grad=float(tolerance_grad), tolerance_change=float(tolerance_change),
+                  history_size=int(history_size), record_costs=bool(record_costs))
+        ref = None
+        if x_ref is not None:
+            ref = GraphedSolve._compact_reference(self, x_ref, x0.shape[0], self.engine.n)
+        key = (tuple(x0.shape), tuple(u_init.shape), bytes(ctypes.string_at(ctypes.addressof(cost), ctypes.sizeof(cost))),
+               tuple(sorted(kw.items())), None if ref is None else tuple(ref.shape))
+        if key != self.key:
+            self.key = None
+            self._capture(x0, u_init, cost, kw, ref)
+            self.key = key
+        self.x0.copy_(x0)
+        self.u_init.copy_(u_init)
+        if ref is not None:
+            self.x_ref.copy_(ref)
+            if isinstance(ref_offset, torch.Tensor):
+                self.ref_offset.copy_(ref_offset.reshape(-1)[:1])
+            elif int(ref_offset) < 0:
+                raise ValueError("ref_offset < 0")
+            else:
+                self.ref_offset.fill_(int(ref_offset))
+        self.graph.replay()
+        return {k: (None if v is None else v.clone()) for k, v in self.out.items()}
