@@ -9,6 +9,9 @@ optimizer_type='LBFGS' through solve_batch / compute_control_batch / DeviceClose
   tracking    per-problem setpoints through x_ref == separate solves with x_target set to each, bitwise
   graph/loop  graph replay == eager; DeviceClosedLoop with an L-BFGS controller == run_mpc_batch; x_ref loop runs
   arguments   PHNN_ERR_INVALID_ARG for bad options / buffers; outer_steps = 0 leaves u and the counters alone
+
+These check torch's semantics and the host path.  The kernel's own arithmetic is pinned bit for bit, against a float32
+model of k_lbfgs, at every kernel width, ragged N and m = 1 .. 4, in tests/test_gpu_lbfgs_kernel.py.
 """
 import ctypes as C
 import os

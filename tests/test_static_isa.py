@@ -2,7 +2,9 @@
 (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 / v_pk_mov_b32) were not bitwise repeatable at two waves per SIMD
 (DESIGN.md section 9).  The Makefile disables the target feature; this test disassembles every gfx950 code object inside
 libphnn_mpc.so and asserts that none of those opcodes is present -- so a toolchain bump, a dropped flag or a new
-translation unit cannot re-introduce them silently.  It also pins the matrix instructions the design rests on.
+translation unit cannot re-introduce them silently.  It also pins the matrix instructions the design rests on, and what
+the bit-exact model of k_lbfgs (tests/lbfgs_kernel_model.py) rests on: no contracted multiply-add in any k_lbfgs<E4>
+instantiation, the only FMAs being those inside its three correctly rounded float32 divisions.
 """
 import os
 import re
@@ -35,22 +37,54 @@ def _code_objects(path):
     return out
 
 
+def _linked_units():
+    """The translation units the Makefile links into libphnn_mpc.so (the .o prerequisites of its rule)."""
+    mk = open(os.path.join(ROOT, "phnn_mpc_amd", "csrc", "Makefile")).read()
+    rule = re.search(r"^libphnn_mpc\.so:(.*)$", mk, re.M)
+    assert rule, "no libphnn_mpc.so rule in the Makefile"
+    return [w for w in rule.group(1).split() if w.endswith(".o")]
+
+
 @pytest.fixture(scope="module")
-def opcodes():
+def disassembly():
+    """llvm-objdump -d text of every gfx950 code object, one per linked translation unit."""
     if not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
         pytest.skip("llvm-objdump not available")
     objs = _code_objects(LIB)
-    assert len(objs) >= 4, f"expected the four translation units' gfx950 code objects, found {len(objs)}"
-    counts = {}
+    units = _linked_units()
+    assert len(objs) == len(units), f"expected one gfx950 code object per linked unit {units}, found {len(objs)}"
+    out = []
     with tempfile.TemporaryDirectory() as tmp:
         for k, img in enumerate(objs):
             f = os.path.join(tmp, f"co{k}.elf")
             open(f, "wb").write(img)
-            txt = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", f], capture_output=True,
-                                 text=True, check=True).stdout
-            for m in re.finditer(r"^\s+([sv]_[a-z0-9_]+|ds_[a-z0-9_]+|global_[a-z0-9_]+|scratch_[a-z0-9_]+|buffer_[a-z0-9_]+)\b", txt, re.M):
-                counts[m.group(1)] = counts.get(m.group(1), 0) + 1
+            out.append(subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", f], capture_output=True,
+                                      text=True, check=True).stdout)
+    return out
+
+
+@pytest.fixture(scope="module")
+def opcodes(disassembly):
+    counts = {}
+    for txt in disassembly:
+        for m in re.finditer(r"^\s+([sv]_[a-z0-9_]+|ds_[a-z0-9_]+|global_[a-z0-9_]+|scratch_[a-z0-9_]+|buffer_[a-z0-9_]+)\b", txt, re.M):
+            counts[m.group(1)] = counts.get(m.group(1), 0) + 1
     return counts
+
+
+def _functions(txt):
+    """{symbol: [opcode, ...] in address order} of one disassembled code object; opcodes without their encoding
+    suffix (_e32, _e64, _dpp, _sdwa)."""
+    funcs, cur = {}, None
+    for line in txt.splitlines():
+        m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
+        if m:
+            cur = funcs.setdefault(m.group(1), [])
+            continue
+        m = re.match(r"^\s+([sv]_[a-z0-9_]+)\b", line)
+        if m and cur is not None:
+            cur.append(re.sub(r"_(e32|e64|dpp|sdwa)$", "", m.group(1)))
+    return funcs
 
 
 def test_no_packed_f32_valu_in_device_code(opcodes):
@@ -62,3 +96,32 @@ def test_matrix_instructions_the_design_rests_on_are_present(opcodes):
     for op in ("v_mfma_f32_16x16x32_f16", "v_mfma_f32_16x16x32_bf16", "v_mfma_f32_16x16x4_f32", "v_mfma_f32_4x4x1_16b_f32",
                "ds_read_b64_tr_b16"):
         assert opcodes.get(op, 0) > 0, f"{op} missing from the device code"
+
+
+def test_k_lbfgs_has_no_contracted_arithmetic(disassembly):
+    """Every k_lbfgs<E4> (E4 = 1 .. 4): each v_fma_f32 / v_fmac_f32 and v_rcp_f32 lies inside a v_div_scale_f32 ...
+    v_div_fixup_f32 window (a correctly rounded division), there are exactly three such windows (1/ys, ys/(y.y),
+    1/sum|g|), and no v_mad_f32, v_mac_f32, v_fmamk_f32 or v_fmaak_f32 at all.  A dropped -ffp-contract=off or a
+    fast-math flag breaks the bitwise model of tests/lbfgs_kernel_model.py; this catches it without a GPU."""
+    kernels = {}
+    for txt in disassembly:
+        for name, ops in _functions(txt).items():
+            m = re.fullmatch(r"_ZN12_GLOBAL__N_17k_lbfgsILi([1-4])EEEv11LbfgsParams", name)
+            if m:
+                kernels[int(m.group(1))] = ops
+    assert sorted(kernels) == [1, 2, 3, 4], f"k_lbfgs instantiations found: {sorted(kernels)}"
+    for e4, ops in sorted(kernels.items()):
+        banned = sorted({op for op in ops if op in ("v_mad_f32", "v_mac_f32", "v_fmamk_f32", "v_fmaak_f32")})
+        assert not banned, f"k_lbfgs<{e4}>: contracted multiply-add {banned}"
+        windows, inside, fmas = 0, False, 0
+        for op in ops:
+            if op == "v_div_scale_f32":
+                inside = True
+            elif op == "v_div_fixup_f32":
+                assert inside, f"k_lbfgs<{e4}>: v_div_fixup_f32 without v_div_scale_f32"
+                windows, inside = windows + 1, False
+            elif op in ("v_fma_f32", "v_fmac_f32", "v_rcp_f32"):
+                assert inside, f"k_lbfgs<{e4}>: {op} outside a division"
+                fmas += op != "v_rcp_f32"
+        assert windows == 3, f"k_lbfgs<{e4}>: {windows} division windows, expected 3 (1/ys, ys/(y.y), 1/sum|g|)"
+        assert fmas > 0, f"k_lbfgs<{e4}>: no FMA inside its divisions (is the division still correctly rounded?)"
