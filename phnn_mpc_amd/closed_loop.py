@@ -77,10 +77,12 @@ class DeviceClosedLoop:
     """Closed loop of B cart-poles resident on the engine's GPU (SURVEY.md 8 rows f1 + f3).
 
     controller: MPCController (cold start, last iterate, clamp(u_0)) or MPCControllerCanonical (warm start by shift,
-    best clamped iterate).  One control step enqueues: iters x (K1, K2, K3), k_plant_step, k_shift_controls (an
-    MPCController with optimizer_type='LBFGS': engine.solve_lbfgs, i.e. the state reset and max_iterations x 20 x (K1,
-    K2, k_lbfgs), then k_plant_step); with use_graph the step is captured once and replayed.  Per-plant arithmetic is identical to run_mpc_batch (same
-    kernels, same order); the plant differs from the numpy one only by the device's double-precision sin/cos.
+    best clamped iterate).  One control step enqueues engine.solve -- a copy of the initial iterate, the memsets that
+    reset Adam's state, iters x (K1, K2, K3) -- then k_plant_step and k_shift_controls (an MPCController with
+    optimizer_type='LBFGS': engine.solve_lbfgs, i.e. the state reset and max_iterations x 20 x (K1, K2, k_lbfgs), then
+    k_plant_step); with use_graph the step is captured once and replayed.  Per-plant arithmetic is identical to
+    run_mpc_batch (same kernels, same order); the plant differs from the numpy one only by the device's
+    double-precision sin/cos.
 
     x_ref: reference trajectories broadcastable to (B, rows, 4) (engine.reference_view); every solve tracks them from
     row step_dev, the device counter the plant step logs with and the shift advances, so each replay of the captured
@@ -108,11 +110,7 @@ class DeviceClosedLoop:
         self.done_step = torch.full((B,), -1, dtype=torch.int32, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.u_init = torch.zeros(B, H, m, dtype=torch.float32, device=dev)
-        self.u = torch.empty_like(self.u_init)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.u), torch.zeros_like(self.u)
-        self.best_cost = torch.empty(B, dtype=torch.float32, device=dev) if self.canonical else None
-        self.best_u = torch.empty_like(self.u) if self.canonical else None
-        self.ws = {}
+        self.ws = {}  # the engine's buffers of the solve, kept across steps
         self.cost = controller._cost()
         self.x_ref = None
         if x_ref is not None:
@@ -130,56 +128,30 @@ class DeviceClosedLoop:
 
     def _control_step(self):
         eng, c = self.eng, self.ctl
-        if self.lbfgs:  # cold start from zeros, the reference's L-BFGS solve, clamp(u_0) of the last iterate
-            rkw = {} if self.x_ref is None else {"x_ref": self.x_ref, "ref_offset": self.step_dev}
+        log = dict(state_f32=self.x32, done_step=self.done_step, step_dev=self.step_dev, log_states=self.log_states,
+                   log_controls=self.log_controls)
+        H = self.u_init.shape[1] * self.u_init.shape[2]
+        if self.lbfgs:  # the reference's L-BFGS solve
             out = eng.solve_lbfgs(self.x32, self.u_init, self.cost, integrator=c.integrator, dt=c.dt, record_costs=False,
-                                  workspace=self.ws, **c.lbfgs_options(), **rkw)
-            H = self.u.shape[1] * self.u.shape[2]
-            eng.plant_step(self.plant, self.state, out["u_last"], H, u_min=c.u_min, u_max=c.u_max, state_f32=self.x32,
-                           done_step=self.done_step, step_dev=self.step_dev, log_states=self.log_states,
-                           log_controls=self.log_controls)
-            eng.advance_step(self.step_dev)
-            return
-        self.u.copy_(self.u_init)
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        if self.canonical:
-            self.best_cost.fill_(float("inf"))
-            self.best_u.zero_()
-        rkw = {} if self.x_ref is None else {"x_ref": self.x_ref, "ref_offset": self.step_dev}
-        for k in range(self.iters):
-            cost, g = eng.rollout_cost_grad(self.x32, self.u, self.cost, c.integrator, c.dt, workspace=self.ws, **rkw)
-            eng.adam_step(self.u, g, self.exp_avg, self.exp_avg_sq, self.lr, k + 1,
-                          cost=cost if self.canonical else None, best_cost=self.best_cost, best_u=self.best_u,
-                          u_min=c.u_min, u_max=c.u_max)
-        H = self.u.shape[1] * self.u.shape[2]
+                                  workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, **c.lbfgs_options())
+        else:
+            out = eng.solve(self.x32, self.u_init, self.cost, c.integrator, c.dt, lr=self.lr, iters=self.iters,
+                            track_best=self.canonical, record_costs=False, workspace=self.ws, x_ref=self.x_ref,
+                            ref_offset=self.step_dev)
         if self.canonical:  # best clamped iterate; next call warm-starts from its shift
-            eng.plant_step(self.plant, self.state, self.best_u, H, state_f32=self.x32, done_step=self.done_step,
-                           step_dev=self.step_dev, log_states=self.log_states, log_controls=self.log_controls)
-            eng.shift_controls(self.best_u, self.u_init, step_dev=self.step_dev)
+            eng.plant_step(self.plant, self.state, out["best_u"], H, **log)
+            eng.shift_controls(out["best_u"], self.u_init, step_dev=self.step_dev)
         else:  # last iterate, clamp(u_0); every call cold-starts from zeros (u_init stays zero)
-            eng.plant_step(self.plant, self.state, self.u, H, u_min=c.u_min, u_max=c.u_max, state_f32=self.x32,
-                           done_step=self.done_step, step_dev=self.step_dev, log_states=self.log_states,
-                           log_controls=self.log_controls)
+            eng.plant_step(self.plant, self.state, out["u_last"], H, u_min=c.u_min, u_max=c.u_max, **log)
             eng.advance_step(self.step_dev)
 
     def run(self):
         torch = self.torch
         dev = self.eng.device
-        start = 0
         if self.use_graph and self.T > 1:
-            # first step eagerly on a side stream (allocates the workspace outside the capture), then capture
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                self._control_step()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            start = 1
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self._control_step()
-            # the capture itself does not execute: replay for steps 1 .. T-1
-            for _ in range(start, self.T):
+            from .solver import capture
+            self.graph, _ = capture(dev, self._control_step)  # runs step 0; replay for steps 1 .. T-1
+            for _ in range(1, self.T):
                 self.graph.replay()
         else:
             for _ in range(self.T):

@@ -8,14 +8,7 @@
 template <class M>
 static GradSet grad_set() {
   GradSet g;
-  g.grad[0] = k_rollout_grad<M, PHNN_INTEG_EULER, false>;
-  g.grad[1] = k_rollout_grad<M, PHNN_INTEG_RK4, false>;
-  g.grad_stash[0] = k_rollout_grad<M, PHNN_INTEG_EULER, true>;
-  g.grad_stash[1] = k_rollout_grad<M, PHNN_INTEG_RK4, true>;
-  g.grad_ref[0] = k_rollout_grad<M, PHNN_INTEG_EULER, false, false, true>;
-  g.grad_ref[1] = k_rollout_grad<M, PHNN_INTEG_RK4, false, false, true>;
-  g.grad_stash_ref[0] = k_rollout_grad<M, PHNN_INTEG_EULER, true, false, true>;
-  g.grad_stash_ref[1] = k_rollout_grad<M, PHNN_INTEG_RK4, true, false, true>;
+  fill_grad<M>(g.grad);
   g.mvjp = k_model_vjp<M>;
   return g;
 }

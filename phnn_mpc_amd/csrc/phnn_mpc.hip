@@ -23,16 +23,9 @@ namespace {
 thread_local std::string g_create_error;
 
 struct KernelSet {
-  void (*fwd[2])(RollParams);
-  void (*grad[2])(RollParams);
-  void (*fwd_stash[2])(RollParams);   // Euler, RK4: K1 keeps the tape(s) for K2
-  void (*grad_stash[2])(RollParams);  // K2 reads the tape(s) instead of recomputing them
-  void (*fwd_ref[2])(RollParams);     // the four pairs above with reference tracking (phnn_reference)
-  void (*grad_ref[2])(RollParams);
-  void (*fwd_stash_ref[2])(RollParams);
-  void (*grad_stash_ref[2])(RollParams);
-  int stash_floats[2];                // per wave (16 rollouts) per step
-  int scr_floats;                  // per-wave LDS scratch
+  RollTable fwd, grad;  // K1, K2: [ref][stash][integrator] (phnn_variants.h)
+  int stash_floats[2];  // per wave (16 rollouts) per step: Euler, RK4
+  int scr_floats;       // per-wave LDS scratch
   void (*mfwd)(PointParams);
   void (*mvjp)(PointParams);
   int img_floats;
@@ -42,14 +35,7 @@ struct KernelSet {
 template <class M>
 KernelSet make_set(const char* name) {
   KernelSet k;
-  k.fwd[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false>;
-  k.fwd[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false>;
-  k.fwd_stash[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true>;
-  k.fwd_stash[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true>;
-  k.fwd_ref[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false, true>;
-  k.fwd_ref[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false, true>;
-  k.fwd_stash_ref[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true, true>;
-  k.fwd_stash_ref[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true, true>;
+  fill_fwd<M>(k.fwd);
   k.stash_floats[0] = StashStep<M, PHNN_INTEG_EULER>::FLOATS;
   k.stash_floats[1] = StashStep<M, PHNN_INTEG_RK4>::FLOATS;
   k.scr_floats = M::SCR;
@@ -69,14 +55,7 @@ bool kernel_set(int v, KernelSet* k) {
 #undef PHNN_CASE
     default: return false;
   }
-  k->grad[0] = g.grad[0];
-  k->grad[1] = g.grad[1];
-  k->grad_stash[0] = g.grad_stash[0];
-  k->grad_stash[1] = g.grad_stash[1];
-  for (int i = 0; i < 2; ++i) {
-    k->grad_ref[i] = g.grad_ref[i];
-    k->grad_stash_ref[i] = g.grad_stash_ref[i];
-  }
+  memcpy(k->grad, g.grad, sizeof k->grad);
   k->mvjp = g.mvjp;
   return true;
 }
@@ -505,7 +484,12 @@ bool use_split(const phnn_handle* h, long long tiles) {
   return h->opt.split_tiles == 2 || tiles <= 2LL * h->n_cu;
 }
 
-int launch_split(phnn_handle* h, void (*kern)(RollParams), const RollParams& p, long long tiles, hipStream_t st) {
+// Launches the K1 (grad = false) or K2 (grad = true) kernel [ref][stash][integrator] of the handle's tables: the
+// split-tile one where use_split says so, else the whole-tile one.
+int launch_roll(phnn_handle* h, bool grad, bool ref, bool stash, int integrator, const RollParams& p, long long tiles,
+                hipStream_t st) {
+  if (!use_split(h, tiles)) return launch(h, (grad ? h->ks.grad : h->ks.fwd)[ref][stash][integrator], p, tiles, false, st);
+  RollKernel kern = (grad ? h->sp.grad : h->sp.fwd)[ref][stash][integrator];
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), sizeof(float) * (size_t)h->sp.lds_floats, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, e, "kernel launch (split-tile)");
@@ -632,20 +616,12 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
     delete h;
     return fail(nullptr, PHNN_ERR_UNSUPPORTED, "weight image does not fit the 160 KiB of LDS");
   }
-  e = allow_big_lds(h->ks.fwd[0]);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.fwd[1]);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.fwd_stash[0]);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.fwd_stash[1]);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.grad[0]);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.grad[1]);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.grad_stash[0]);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.grad_stash[1]);
-  for (int i = 0; i < 2; ++i) {
-    if (e == hipSuccess) e = allow_big_lds(h->ks.fwd_ref[i]);
-    if (e == hipSuccess) e = allow_big_lds(h->ks.fwd_stash_ref[i]);
-    if (e == hipSuccess) e = allow_big_lds(h->ks.grad_ref[i]);
-    if (e == hipSuccess) e = allow_big_lds(h->ks.grad_stash_ref[i]);
-  }
+  e = hipSuccess;
+  RollKernel* tables[] = {&h->ks.fwd[0][0][0], &h->ks.grad[0][0][0], h->has_split ? &h->sp.fwd[0][0][0] : nullptr,
+                          h->has_split ? &h->sp.grad[0][0][0] : nullptr};
+  for (RollKernel* t : tables)
+    for (int i = 0; t && i < 8; ++i)
+      if (e == hipSuccess) e = allow_big_lds(t[i]);
   if (e == hipSuccess) e = allow_big_lds(h->ks.mfwd);
   if (e == hipSuccess) e = allow_big_lds(h->ks.mvjp);
   if (h->has_wgrad) {
@@ -657,23 +633,7 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
     if (e == hipSuccess) e = allow_big_lds(h->wg.grad_t[1]);
     if (e == hipSuccess) e = allow_big_lds(h->wg.reduce_t);
   }
-  if (h->has_split) {
-    if (e == hipSuccess) e = allow_big_lds(h->sp.fwd[0]);
-    if (e == hipSuccess) e = allow_big_lds(h->sp.fwd[1]);
-    if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_stash[0]);
-    if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_stash[1]);
-    if (e == hipSuccess) e = allow_big_lds(h->sp.grad[0]);
-    if (e == hipSuccess) e = allow_big_lds(h->sp.grad[1]);
-    if (e == hipSuccess) e = allow_big_lds(h->sp.grad_stash[0]);
-    if (e == hipSuccess) e = allow_big_lds(h->sp.grad_stash[1]);
-    for (int i = 0; i < 2; ++i) {
-      if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_ref[i]);
-      if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_stash_ref[i]);
-      if (e == hipSuccess) e = allow_big_lds(h->sp.grad_ref[i]);
-      if (e == hipSuccess) e = allow_big_lds(h->sp.grad_stash_ref[i]);
-    }
-    if ((size_t)h->sp.lds_floats * sizeof(float) > 160 * 1024) h->has_split = false;
-  }
+  if (h->has_split && (size_t)h->sp.lds_floats * sizeof(float) > 160 * 1024) h->has_split = false;
   if (e != hipSuccess) {
     delete h;
     return hip_fail(nullptr, e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
@@ -864,15 +824,8 @@ static int rollout_fwd(phnn_handle* h, const float* x0_dev, const float* u_dev, 
   p.cost = cost_dev;
   p.traj = traj_dev;
   const long long tiles = (B + kTileB - 1) / kTileB;
-  const bool split = use_split(h, tiles);
-  const bool stash = workspace_dev != nullptr;
   p.stash = (float*)workspace_dev;
-  if (ref) {
-    if (split) return launch_split(h, stash ? h->sp.fwd_stash_ref[integrator] : h->sp.fwd_ref[integrator], p, tiles, (hipStream_t)stream);
-    return launch(h, stash ? h->ks.fwd_stash_ref[integrator] : h->ks.fwd_ref[integrator], p, tiles, false, (hipStream_t)stream);
-  }
-  if (split) return launch_split(h, stash ? h->sp.fwd_stash[integrator] : h->sp.fwd[integrator], p, tiles, (hipStream_t)stream);
-  return launch(h, stash ? h->ks.fwd_stash[integrator] : h->ks.fwd[integrator], p, tiles, false, (hipStream_t)stream);
+  return launch_roll(h, false, ref != nullptr, workspace_dev != nullptr, integrator, p, tiles, (hipStream_t)stream);
 }
 
 int phnn_rollout_fwd(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
@@ -906,15 +859,8 @@ static int rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, 
   p.grad_u = grad_u_dev;
   p.grad_x0 = grad_x0_dev;
   const long long tiles = (B + kTileB - 1) / kTileB;
-  const bool split = use_split(h, tiles);
-  const bool stash = workspace_dev != nullptr;
   p.stash = (float*)workspace_dev;
-  if (ref) {
-    if (split) return launch_split(h, stash ? h->sp.grad_stash_ref[integrator] : h->sp.grad_ref[integrator], p, tiles, (hipStream_t)stream);
-    return launch(h, stash ? h->ks.grad_stash_ref[integrator] : h->ks.grad_ref[integrator], p, tiles, false, (hipStream_t)stream);
-  }
-  if (split) return launch_split(h, stash ? h->sp.grad_stash[integrator] : h->sp.grad[integrator], p, tiles, (hipStream_t)stream);
-  return launch(h, stash ? h->ks.grad_stash[integrator] : h->ks.grad[integrator], p, tiles, false, (hipStream_t)stream);
+  return launch_roll(h, true, ref != nullptr, workspace_dev != nullptr, integrator, p, tiles, (hipStream_t)stream);
 }
 
 int phnn_rollout_grad(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
@@ -1016,9 +962,7 @@ int phnn_rollout_trajectory_ws(phnn_handle* h, const float* x0_dev, const float*
   const long long tiles = (B + kTileB - 1) / kTileB;
   const bool tapes = wgrad_workspace_dev != nullptr;
   if (tapes) p.stash = (float*)wgrad_workspace_dev + wgrad_tape_offset(h, wgrad_records(B, H, integrator));
-  if (use_split(h, tiles))
-    return launch_split(h, tapes ? h->sp.fwd_stash[integrator] : h->sp.fwd[integrator], p, tiles, (hipStream_t)stream);
-  return launch(h, tapes ? h->ks.fwd_stash[integrator] : h->ks.fwd[integrator], p, tiles, false, (hipStream_t)stream);
+  return launch_roll(h, false, false, tapes, integrator, p, tiles, (hipStream_t)stream);
 }
 
 int phnn_rollout_wgrad(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, int32_t integrator,

@@ -7,22 +7,8 @@
 template <class M>
 static SplitSet split_set() {
   SplitSet g;
-  g.fwd[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false>;
-  g.fwd[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false>;
-  g.fwd_stash[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true>;
-  g.fwd_stash[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true>;
-  g.grad[0] = k_rollout_grad<M, PHNN_INTEG_EULER, false>;
-  g.grad[1] = k_rollout_grad<M, PHNN_INTEG_RK4, false>;
-  g.grad_stash[0] = k_rollout_grad<M, PHNN_INTEG_EULER, true>;
-  g.grad_stash[1] = k_rollout_grad<M, PHNN_INTEG_RK4, true>;
-  g.fwd_ref[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false, true>;
-  g.fwd_ref[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false, true>;
-  g.fwd_stash_ref[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true, true>;
-  g.fwd_stash_ref[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true, true>;
-  g.grad_ref[0] = k_rollout_grad<M, PHNN_INTEG_EULER, false, false, true>;
-  g.grad_ref[1] = k_rollout_grad<M, PHNN_INTEG_RK4, false, false, true>;
-  g.grad_stash_ref[0] = k_rollout_grad<M, PHNN_INTEG_EULER, true, false, true>;
-  g.grad_stash_ref[1] = k_rollout_grad<M, PHNN_INTEG_RK4, true, false, true>;
+  fill_fwd<M>(g.fwd);
+  fill_grad<M>(g.grad);
   g.lds_floats = M::IMG + 4 * M::SCR + kXchFloats;
   return g;
 }

@@ -109,11 +109,38 @@ using M_ODE_2_128_GELU = OdeModel<2, 128, MM_F32, ACT_GELU>;
 using M_ODE_4_128_ELU = OdeModel<4, 128, MM_F32, ACT_ELU>;
 using M_ODE_4_128_GELU = OdeModel<4, 128, MM_F32, ACT_GELU>;
 
+// The march kernels of one model, K1 (fwd) or K2 (grad), indexed [ref][stash][integrator]: ref = reference tracking
+// (phnn_reference; the REF marches), stash = K1 keeps the tape(s) of every step and K2 reads them instead of recomputing
+// them, integrator = Euler, RK4.
+using RollKernel = void (*)(RollParams);
+using RollTable = RollKernel[2][2][2];
+
+template <class M>
+void fill_fwd(RollTable t) {
+  t[0][0][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false>;
+  t[0][0][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false>;
+  t[0][1][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true>;
+  t[0][1][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true>;
+  t[1][0][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false, true>;
+  t[1][0][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false, true>;
+  t[1][1][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true, true>;
+  t[1][1][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true, true>;
+}
+
+template <class M>
+void fill_grad(RollTable t) {
+  t[0][0][0] = k_rollout_grad<M, PHNN_INTEG_EULER, false>;
+  t[0][0][1] = k_rollout_grad<M, PHNN_INTEG_RK4, false>;
+  t[0][1][0] = k_rollout_grad<M, PHNN_INTEG_EULER, true>;
+  t[0][1][1] = k_rollout_grad<M, PHNN_INTEG_RK4, true>;
+  t[1][0][0] = k_rollout_grad<M, PHNN_INTEG_EULER, false, false, true>;
+  t[1][0][1] = k_rollout_grad<M, PHNN_INTEG_RK4, false, false, true>;
+  t[1][1][0] = k_rollout_grad<M, PHNN_INTEG_EULER, true, false, true>;
+  t[1][1][1] = k_rollout_grad<M, PHNN_INTEG_RK4, true, false, true>;
+}
+
 struct GradSet {
-  void (*grad[2])(RollParams);     // Euler, RK4: recompute the tape
-  void (*grad_stash[2])(RollParams);  // Euler, RK4: K2 reads the tape(s) K1 stashed
-  void (*grad_ref[2])(RollParams);    // the same two pairs with reference tracking (grad_march REF)
-  void (*grad_stash_ref[2])(RollParams);
+  RollTable grad;
   void (*mvjp)(PointParams);
 };
 
@@ -124,14 +151,7 @@ bool phnn_grad_kernels(int variant, GradSet* g);
 // defined in phnn_split.hip for the 128-wide f16x2 pHNN (fixed G) and canonical variants.  Bitwise the same results
 // and the same stash format as the whole-tile kernels.
 struct SplitSet {
-  void (*fwd[2])(RollParams);
-  void (*grad[2])(RollParams);
-  void (*fwd_stash[2])(RollParams);   // Euler, RK4
-  void (*grad_stash[2])(RollParams);
-  void (*fwd_ref[2])(RollParams);     // the four pairs above with reference tracking (REF marches)
-  void (*grad_ref[2])(RollParams);
-  void (*fwd_stash_ref[2])(RollParams);
-  void (*grad_stash_ref[2])(RollParams);
+  RollTable fwd, grad;
   int lds_floats;  // image + 4 x per-wave scratch + exchange area
 };
 bool phnn_split_kernels(int variant, SplitSet* g);  // false: no split-tile kernels for this variant

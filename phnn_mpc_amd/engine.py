@@ -173,8 +173,11 @@ class RolloutEngine:
         return C.c_void_p(t.data_ptr()) if t is not None else None
 
     def _reference(self, x_ref, ref_offset, B):
-        """-> (phnn_reference, tensors to keep alive until the launches are enqueued).  ref_offset: int >= 0 or a
-        device int32 tensor (its first element is read by every launch; a captured graph follows it)."""
+        """-> (phnn_reference, tensors to keep alive until the launches are enqueued), or (None, None) without x_ref.
+        ref_offset: int >= 0 or a device int32 tensor (its first element is read by every launch; a captured graph
+        follows it)."""
+        if x_ref is None:
+            return None, None
         t, bs, ts, rows = reference_view(x_ref, B, self.n, self.device)
         r = _capi.Reference()
         r.x_ref = t.data_ptr() if t.numel() else None
@@ -186,6 +189,30 @@ class RolloutEngine:
         else:
             r.offset_host = int(ref_offset)
         return r, (t, ref_offset)
+
+    def _roll_call(self, name, ref, x0, u, B, H, cost, *rest):
+        """lib.<name>(h, x0, u, B, H, cost, *rest, stream); with a phnn_reference its twin <name>_ref, which takes the
+        reference right after the cost."""
+        fn = getattr(self.lib, name if ref is None else name + "_ref")
+        mid = () if ref is None else (C.byref(ref),)
+        _check(self.lib, self.h, fn(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), *mid, *rest, self._stream()))
+
+    def _roll_workspace(self, ws, B, H, integ):
+        """The K1 / K2 buffers of a (B, H, integrator) problem in the dict `ws` (None: a fresh one): stash (None above
+        max_stash_bytes or without use_stash: K2 recomputes), traj, cost, grad_u, grad_x0.  rollout_cost_grad, solve and
+        solve_lbfgs share them, and add their own state next to them; another problem size starts the dict afresh."""
+        ws = {} if ws is None else ws
+        key = (B, H, integ)
+        if ws.get("key") != key:
+            ws.clear()
+            ws["key"] = key
+            nbytes = self.workspace_bytes(B, H, integ) if self.use_stash else 0
+            ws["stash"] = (torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                           if 0 < nbytes <= self.max_stash_bytes else None)
+            f = dict(dtype=torch.float32, device=self.device)
+            ws["traj"], ws["cost"] = torch.empty(B, H + 1, self.n, **f), torch.empty(B, **f)
+            ws["grad_u"], ws["grad_x0"] = torch.empty(B, H, self.m, **f), torch.empty(B, self.n, **f)
+        return ws
 
     def _integ(self, integrator):
         if isinstance(integrator, str):
@@ -229,15 +256,9 @@ class RolloutEngine:
         traj = traj_out
         if traj is None and want_traj:
             traj = torch.empty(B, H + 1, self.n, dtype=torch.float32, device=self.device)
-        if x_ref is None:
-            rc = self.lib.phnn_rollout_fwd(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), self._integ(integrator),
-                                           float(dt), self._p(c), self._p(traj), None, self._stream())
-        else:
-            ref, _keep = self._reference(x_ref, ref_offset, B)
-            rc = self.lib.phnn_rollout_fwd_ref(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(ref),
-                                               self._integ(integrator), float(dt), self._p(c), self._p(traj), None,
-                                               self._stream())
-        _check(self.lib, self.h, rc)
+        ref, _keep = self._reference(x_ref, ref_offset, B)
+        self._roll_call("phnn_rollout_fwd", ref, x0, u, B, H, cost, self._integ(integrator), float(dt), self._p(c),
+                        self._p(traj), None)
         return (c, traj) if (want_traj or traj_out is not None) else c
 
     def workspace_bytes(self, B, H, integrator="euler"):
@@ -252,38 +273,16 @@ class RolloutEngine:
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u, H = self._controls(u, B)
-        ws = workspace if workspace is not None else {}
         integ = self._integ(integrator)
-        key = (B, H, integ)
-        if ws.get("key") != key:
-            ws["key"] = key
-            nbytes = self.workspace_bytes(B, H, integ) if self.use_stash else 0
-            ws["stash"] = (torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                           if 0 < nbytes <= self.max_stash_bytes else None)
-            ws["traj"] = torch.empty(B, H + 1, self.n, dtype=torch.float32, device=self.device)
-            ws["cost"] = torch.empty(B, dtype=torch.float32, device=self.device)
-            ws["grad_u"] = torch.empty(B, H, self.m, dtype=torch.float32, device=self.device)
-            ws["grad_x0"] = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
-        st = self._stream()
+        ws = self._roll_workspace(workspace, B, H, integ)
         stash = self._p(ws["stash"])
-        if x_ref is None:
-            rc = self.lib.phnn_rollout_fwd(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt),
-                                           self._p(ws["cost"]), self._p(ws["traj"]), stash, st)
-        else:
-            ref, _keep = self._reference(x_ref, ref_offset, B)
-            rc = self.lib.phnn_rollout_fwd_ref(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(ref), integ,
-                                               float(dt), self._p(ws["cost"]), self._p(ws["traj"]), stash, st)
-        _check(self.lib, self.h, rc)
+        ref, _keep = self._reference(x_ref, ref_offset, B)
+        self._roll_call("phnn_rollout_fwd", ref, x0, u, B, H, cost, integ, float(dt), self._p(ws["cost"]),
+                        self._p(ws["traj"]), stash)
         if after_forward is not None:
             after_forward(ws["cost"])
-        gx = self._p(ws["grad_x0"]) if want_grad_x0 else None
-        if x_ref is None:
-            rc = self.lib.phnn_rollout_grad(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt),
-                                            self._p(ws["traj"]), stash, self._p(ws["grad_u"]), gx, st)
-        else:
-            rc = self.lib.phnn_rollout_grad_ref(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(ref), integ,
-                                                float(dt), self._p(ws["traj"]), stash, self._p(ws["grad_u"]), gx, st)
-        _check(self.lib, self.h, rc)
+        self._roll_call("phnn_rollout_grad", ref, x0, u, B, H, cost, integ, float(dt), self._p(ws["traj"]), stash,
+                        self._p(ws["grad_u"]), self._p(ws["grad_x0"]) if want_grad_x0 else None)
         if want_grad_x0:
             return ws["cost"], ws["grad_u"], ws["grad_x0"]
         return ws["cost"], ws["grad_u"]
@@ -434,37 +433,28 @@ class RolloutEngine:
         """phnn_solve: Adam on the control sequences of B independent problems, the loops of
         src/mpc_controller.py:164-209 / src/mpc_controller_canonical.py:163-228, as ONE library call that enqueues the
         K1 / K2 / K3 launches of every iteration (no Python between them).  -> dict as solver.shooting_solve, same
-        results bit for bit.  x_ref, ref_offset: every problem tracks its own reference (rollout_cost; phnn_solve_ref)."""
+        results bit for bit.  workspace: optional dict reused across calls (K1 / K2 buffers and Adam's moments).
+        x_ref, ref_offset: every problem tracks its own reference (rollout_cost; phnn_solve_ref)."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u_init, H = self._controls(u_init, B)
         integ = self._integ(integrator)
-        ws = workspace if workspace is not None else {}
-        key = ("solve", B, H, integ, int(iters))
-        if ws.get("skey") != key:
-            ws["skey"] = key
-            nbytes = self.workspace_bytes(B, H, integ) if self.use_stash else 0
-            ws["s_stash"] = (torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                             if 0 < nbytes <= self.max_stash_bytes else None)
-            f = dict(dtype=torch.float32, device=self.device)
-            ws["s_traj"], ws["s_cost"] = torch.empty(B, H + 1, self.n, **f), torch.empty(B, **f)
-            ws["s_grad"], ws["s_m"], ws["s_v"] = (torch.empty(B, H, self.m, **f) for _ in range(3))
-        u = u_init.detach().clone().contiguous()
+        ws = self._roll_workspace(workspace, B, H, integ)
         f = dict(dtype=torch.float32, device=self.device)
+        if "m" not in ws:  # Adam's moments; phnn_solve zeroes them
+            ws["m"], ws["v"] = torch.empty(B, H, self.m, **f), torch.empty(B, H, self.m, **f)
+        u = u_init.detach().clone().contiguous()
         costs = torch.empty(int(iters), B, **f) if record_costs else None
         best_cost = torch.empty(B, **f) if track_best else None
         best_u = torch.empty(B, H, self.m, **f) if track_best else None
+        if track_best and int(iters) == 0:  # phnn_solve returns before its state reset: shooting_solve's initial values
+            best_cost.fill_(float("inf"))
+            best_u.zero_()
         opt = _capi.SolveOptions(int(iters), float(lr), float(beta1), float(beta2), float(eps), int(bool(track_best)))
-        bufs = (self._p(ws["s_m"]), self._p(ws["s_v"]), self._p(ws["s_grad"]), self._p(ws["s_cost"]), self._p(ws["s_traj"]),
-                self._p(ws["s_stash"]), self._p(costs), self._p(best_cost), self._p(best_u), self._stream())
-        if x_ref is None:
-            rc = self.lib.phnn_solve(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), integ, float(dt), C.byref(opt),
-                                     *bufs)
-        else:
-            ref, _keep = self._reference(x_ref, ref_offset, B)
-            rc = self.lib.phnn_solve_ref(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(ref), integ,
-                                         float(dt), C.byref(opt), *bufs)
-        _check(self.lib, self.h, rc)
+        ref, _keep = self._reference(x_ref, ref_offset, B)
+        self._roll_call("phnn_solve", ref, x0, u, B, H, cost, integ, float(dt), C.byref(opt), self._p(ws["m"]),
+                        self._p(ws["v"]), self._p(ws["grad_u"]), self._p(ws["cost"]), self._p(ws["traj"]),
+                        self._p(ws["stash"]), self._p(costs), self._p(best_cost), self._p(best_u))
         out = {"u_last": u, "costs": costs}
         if track_best:
             out["best_u"], out["best_cost"] = best_u, best_cost
@@ -488,18 +478,11 @@ class RolloutEngine:
         B = x0.shape[0]
         u_init, H = self._controls(u_init, B)
         integ = self._integ(integrator)
-        ws = workspace if workspace is not None else {}
-        key = ("lbfgs", B, H, integ, int(history_size))
-        if ws.get("lkey") != key:
-            ws["lkey"] = key
-            nbytes = self.workspace_bytes(B, H, integ) if self.use_stash else 0
-            ws["l_stash"] = (torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                             if 0 < nbytes <= self.max_stash_bytes else None)
-            f = dict(dtype=torch.float32, device=self.device)
-            ws["l_traj"], ws["l_cost"] = torch.empty(B, H + 1, self.n, **f), torch.empty(B, **f)
-            ws["l_grad"] = torch.empty(B, H, self.m, **f)
-            ws["l_state"] = torch.empty(max(self.lbfgs_workspace_bytes(B, H, history_size), 1), dtype=torch.uint8,
-                                        device=self.device)
+        ws = self._roll_workspace(workspace, B, H, integ)
+        if ws.get("lbfgs_history") != int(history_size):
+            ws["lbfgs_history"] = int(history_size)
+            ws["lbfgs_state"] = torch.empty(max(self.lbfgs_workspace_bytes(B, H, history_size), 1), dtype=torch.uint8,
+                                            device=self.device)
         u = u_init.detach().clone().contiguous()
         costs = torch.empty(int(outer_steps), B, dtype=torch.float32, device=self.device) if record_costs else None
         n_iter = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -511,11 +494,11 @@ class RolloutEngine:
         opt.lr, opt.tolerance_grad, opt.tolerance_change = float(lr), float(tolerance_grad), float(tolerance_change)
         if max_eval is not None and int(max_eval) < 1:
             raise ValueError("max_eval must be >= 1 (None: torch's default max_iter * 5 // 4)")
-        ref, _keep = (None, None) if x_ref is None else self._reference(x_ref, ref_offset, B)
+        ref, _keep = self._reference(x_ref, ref_offset, B)
         rc = self.lib.phnn_solve_lbfgs(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
                                        None if ref is None else C.byref(ref), integ, float(dt), C.byref(opt),
-                                       self._p(ws["l_grad"]), self._p(ws["l_cost"]), self._p(ws["l_traj"]),
-                                       self._p(ws["l_stash"]), self._p(ws["l_state"]), ws["l_state"].numel(),
+                                       self._p(ws["grad_u"]), self._p(ws["cost"]), self._p(ws["traj"]),
+                                       self._p(ws["stash"]), self._p(ws["lbfgs_state"]), ws["lbfgs_state"].numel(),
                                        self._p(costs), self._p(n_iter), self._p(func_evals), self._stream())
         _check(self.lib, self.h, rc)
         return {"u_last": u, "costs": costs, "n_iter": n_iter, "func_evals": func_evals}

@@ -128,9 +128,9 @@ class MPCController:
         eng = self.engine
         x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
         u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
-        rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.lr, self.max_iterations,
-                                 track_best=False, u_min=self.u_min, u_max=self.u_max, record_costs=record_costs, **rkw)
+                                 track_best=False, u_min=self.u_min, u_max=self.u_max, record_costs=record_costs,
+                                 x_ref=x_ref, ref_offset=ref_offset)
 
     def lbfgs_options(self):
         """solve_lbfgs keyword arguments of the reference's optimizer: torch.optim.LBFGS([u], lr=self.lr, max_iter=20)
@@ -148,13 +148,12 @@ class MPCController:
         self._graphed_lbfgs = lbfgs_solver_for(eng, self.use_graph, getattr(self, "_graphed_lbfgs", None))
         x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
         u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
-        rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
         return self._graphed_lbfgs(x0, u0, self._cost(), integrator=self.integrator, dt=self.dt, record_costs=record_costs,
-                                   **self.lbfgs_options(), **rkw)
+                                   x_ref=x_ref, ref_offset=ref_offset, **self.lbfgs_options())
 
     def compute_control_batch(self, states, x_ref=None, ref_offset=0):
         """states (B,n) -> np.ndarray (B,1): first control of each plant's optimised sequence (x_ref: solve_batch)."""
-        out = self.solve_batch(states) if x_ref is None else self.solve_batch(states, x_ref=x_ref, ref_offset=ref_offset)
+        out = self.solve_batch(states, x_ref=x_ref, ref_offset=ref_offset)
         u0 = out["u_last"][:, 0, :]
         if self.u_min is not None and self.u_max is not None:
             u0 = torch.clamp(u0, self.u_min, self.u_max)

@@ -109,10 +109,9 @@ class MPCControllerCanonical:
             u0 = torch.zeros(B, self.horizon, self.input_dim, dtype=torch.float32, device=eng.device)
         else:
             u0 = torch.as_tensor(u_init, dtype=torch.float32).reshape(B, self.horizon, self.input_dim).to(eng.device)
-        rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.learning_rate,
                                  self.optimizer_steps, track_best=True, u_min=self.u_min, u_max=self.u_max,
-                                 record_costs=record_costs, **rkw)
+                                 record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset)
 
     def control_batch(self, x_current, u_prev=None, x_ref=None, ref_offset=0):
         """x_current (B,n), u_prev (B,H,m) or None -> (u (B,m), u_sequence (B,H,m), best_cost (B)) numpy arrays.
@@ -121,10 +120,7 @@ class MPCControllerCanonical:
         if u_prev is not None:
             up = torch.as_tensor(u_prev, dtype=torch.float32)
             u_init = torch.cat([up[:, 1:], torch.zeros(up.shape[0], 1, self.input_dim)], dim=1)
-        if x_ref is None:
-            out = self.optimize_control_batch(x_current, u_init, record_costs=False)
-        else:
-            out = self.optimize_control_batch(x_current, u_init, record_costs=False, x_ref=x_ref, ref_offset=ref_offset)
+        out = self.optimize_control_batch(x_current, u_init, record_costs=False, x_ref=x_ref, ref_offset=ref_offset)
         seq = out["best_u"].cpu().numpy()
         return seq[:, 0, :], seq, out["best_cost"].cpu().numpy()
 

@@ -48,11 +48,17 @@ def test_library_solve_equals_the_python_loop_bitwise(torch, name, integ, B):
 
 def test_solve_argument_checks(torch):
     from phnn_mpc_amd.engine import RolloutEngine
+    from phnn_mpc_amd.solver import shooting_solve
     g = ol.load_golden("phnn_cartpole")
     eng = RolloutEngine(ol.load_weights("phnn_cartpole"))
     cost = ol.cost_from_golden(g)
     x0, u0 = torch.zeros(2, 4, device=eng.device), torch.ones(2, 5, 1, device=eng.device)
     out = eng.solve(x0, u0, cost, "euler", 0.02, iters=0)  # nothing to do: the initial iterate comes back
     assert torch.equal(out["u_last"], u0)
+    out = eng.solve(x0, u0, cost, "euler", 0.02, iters=0, track_best=True)  # and no best iterate yet: shooting_solve's
+    ref = shooting_solve(eng, x0, u0, cost, "euler", 0.02, 0.015, 0, track_best=True)
+    for k in ("u_last", "best_u", "best_cost", "costs"):
+        assert torch.equal(out[k], ref[k]), k
+    assert torch.isinf(out["best_cost"]).all() and not out["best_u"].any()
     with pytest.raises(ValueError):
         eng.solve(x0, u0, cost, "leapfrog", 0.02, iters=3)
