@@ -370,6 +370,58 @@ int phnn_solve_lbfgs(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t 
                      size_t lbfgs_workspace_size, float* costs_dev, int32_t* n_iter_dev, int32_t* func_evals_dev,
                      void* stream);
 
+/* ---- batched sampling (MPPI) solve: gradient-free, K1 only -----------------------------------------------------
+ * Per problem b, `iters` times: sample  v_{b,k} = clamp(u_b + sigma o z_{b,k}), k = 0 .. samples-1, z standard normal
+ * and z_{b,0} = 0 (the nominal itself is always evaluated); cost S_{b,k} of all B * samples rollouts in ONE K1 launch
+ * (no K2, no stash); update  u_b = sum_k w_k v_{b,k} / sum_k w_k,  w_k = exp(-(S_k - min_k S) / lambda).  A non-finite
+ * S_k has weight 0; where all are non-finite u_b is kept.  The control effort u^T R u of a sample is inside S; there is
+ * no separate control-cost term.  DESIGN.md 12.
+ * Noise: Philox4x32-10, one call per float4 of a sample row, key = seed, counter = (gid low 32 bits,
+ * gid high 16 bits | iteration << 16, epoch, sample << 6 | float4 index) with gid = problem_offset + b; two Box-Muller
+ * pairs per call, uniforms ((x >> 8) + 0.5) * 2^-24.  Problem b's samples therefore depend on (seed, epoch, iteration,
+ * gid) only -- not on B, on its position in the batch, or on how the batch is split over calls.  Ranges: iters <= 65536,
+ * samples <= 2^26, 0 <= problem_offset, problem_offset + B <= 2^48.
+ * epoch: *epoch_dev when epoch_dev != NULL -- read by every launch, so a captured graph whose counter
+ * phnn_shift_controls advances draws fresh noise at every replay -- else epoch_host. */
+typedef struct {
+  int32_t iters;             /* >= 0 */
+  int32_t samples;           /* K >= 2, sample 0 included */
+  float lambda;              /* temperature, > 0 and finite */
+  float sigma[PHNN_MAX_M];   /* noise standard deviation per control component (leading m used), >= 0 and finite */
+  uint64_t seed;
+  int64_t problem_offset;    /* global id of problem 0 of this call */
+  const int32_t* epoch_dev;  /* device, or NULL */
+  int32_t epoch_host;        /* used when epoch_dev == NULL */
+  int32_t reserved[4];       /* zero */
+} phnn_mppi_options;
+/* Bytes of the MPPI workspace: the sample tensor (B*samples, H, m), the replicated x0 (B*samples, n) and K1's cost
+ * vector (B*samples), each region 256-byte aligned.  0 for invalid arguments. */
+size_t phnn_mppi_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t samples);
+/* The two kernels of one iteration, as phnn_adam_step stands next to phnn_solve.
+ * phnn_mppi_sample: u_dev (B,H,m) nominal, x0_dev (B,n) -> samples_dev (B*samples,H,m), x0_rep_dev (B*samples,n) (may be
+ *   NULL); clamps to the cost's bounds when has_u_bounds; `iteration` is the counter field (opt->iters is not read).
+ * phnn_mppi_update: samples_dev and their K1 costs sample_cost_dev (B*samples) -> u_dev (B,H,m) replaced by the weighted
+ *   mean, clamped to the cost's bounds when has_u_bounds (in exact arithmetic a convex combination of in-bound samples is
+ *   in bounds; float32 rounding can leave it one ulp outside); optional costs_row_dev (B) = S_{b,0}; optional best_cost_dev (B) / best_u_dev (B,H,m), updated where the lowest
+ *   finite sample cost is < best_cost (strict; lowest k on ties) with that cost and that sample's row. */
+int phnn_mppi_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                     const phnn_mppi_options* opt, int32_t iteration, float* samples_dev, float* x0_rep_dev, void* stream);
+int phnn_mppi_update(phnn_handle* h, float* u_dev, const float* samples_dev, const float* sample_cost_dev, int64_t B,
+                     int32_t H, const phnn_cost* cost, const phnn_mppi_options* opt, float* costs_row_dev,
+                     float* best_cost_dev, float* best_u_dev, void* stream);
+/* The whole solve.  u_dev (B,H,m): in = initial nominal, out = the last nominal (in bounds: clamped on entry when
+ * has_u_bounds, and every update is a clamped convex combination of in-bound samples).  best_cost_dev (B) / best_u_dev (B,H,m):
+ * the best sample over all iterations, reset to +inf / 0 first -- also when iters == 0.  costs_dev (iters,B) or NULL: the
+ * nominal's cost S_{b,0} at every iteration.  workspace: workspace_size >= phnn_mppi_workspace_bytes.  ref: NULL = the
+ * cost's x_target, else K1 tracks it; its batch_stride indexes the B*samples ROLLOUTS (rollout b*samples + k belongs to
+ * problem b), so a per-problem reference is passed with one row set per rollout and a shared one with batch_stride 0.
+ * Enqueues the clamp and the resets, then iters x (k_mppi_sample, K1, k_mppi_update); stream-ordered, capturable.
+ * PHNN_ERR_INVALID_ARG for samples < 2, lambda <= 0 or non-finite, a negative or non-finite sigma, iters < 0, values
+ * outside the ranges above, NULL required buffers or a too small workspace; PHNN_ERR_UNSUPPORTED for H*m > 256. */
+int phnn_solve_mppi(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                    const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt, void* workspace,
+                    size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream);
+
 /* ---- the plant on the other side of the path ------------------------------------------
  * Ground-truth cart-pole of src/cartpole_simulator.py:63-112: float64, explicit Euler, the standard cart-pole
  * equations in the reference's operation order; termination |x| > x_limit or |theta| > theta_limit.  Defaults of

@@ -32,7 +32,7 @@ EXPORTED = [
     "phnn_rollout_trajectory", "phnn_rollout_trajectory_ws", "phnn_wgrad_workspace_bytes", "phnn_wgrad_record_info", "phnn_rollout_wgrad", "phnn_model_wgrad",
     "phnn_adam_step", "phnn_solve", "phnn_plant_step", "phnn_shift_controls", "phnn_kernel_info", "phnn_variant_name",
     "phnn_version", "phnn_rollout_fwd_ref", "phnn_rollout_grad_ref", "phnn_solve_ref", "phnn_lbfgs_workspace_bytes",
-    "phnn_solve_lbfgs",
+    "phnn_solve_lbfgs", "phnn_mppi_workspace_bytes", "phnn_mppi_sample", "phnn_mppi_update", "phnn_solve_mppi",
 ]
 
 
@@ -69,6 +69,14 @@ class LbfgsOptions(C.Structure):
     _fields_ = [("outer_steps", C.c_int32), ("max_iter", C.c_int32), ("max_eval", C.c_int32), ("history_size", C.c_int32),
                 ("lr", C.c_double), ("tolerance_grad", C.c_double), ("tolerance_change", C.c_double),
                 ("reserved", C.c_int32 * 4)]
+
+
+class MppiOptions(C.Structure):
+    """phnn_mppi_options: K = samples perturbations of the nominal per iteration (sample 0 is the nominal), noise
+    sigma per control component, softmin temperature lambda; Philox counter fields seed / problem_offset / epoch."""
+    _fields_ = [("iters", C.c_int32), ("samples", C.c_int32), ("lambda", C.c_float), ("sigma", C.c_float * PHNN_MAX_M),
+                ("seed", C.c_uint64), ("problem_offset", C.c_int64), ("epoch_dev", C.c_void_p), ("epoch_host", C.c_int32),
+                ("reserved", C.c_int32 * 4)]  # 'lambda' is a Python keyword: setattr(opt, "lambda", v)
 
 
 class Plant(C.Structure):
@@ -226,6 +234,16 @@ def load_library():
     lib.phnn_solve_lbfgs.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
                                      C.POINTER(LbfgsOptions), f32p, f32p, f32p, vp, vp, C.c_size_t, f32p, vp, vp, vp]
     lib.phnn_solve_lbfgs.restype = C.c_int
+    lib.phnn_mppi_workspace_bytes.argtypes = [vp, i64, i32, i32]
+    lib.phnn_mppi_workspace_bytes.restype = C.c_size_t
+    lib.phnn_mppi_sample.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(MppiOptions), i32, f32p, f32p, vp]
+    lib.phnn_mppi_sample.restype = C.c_int
+    lib.phnn_mppi_update.argtypes = [vp, f32p, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(MppiOptions), f32p, f32p, f32p,
+                                     vp]
+    lib.phnn_mppi_update.restype = C.c_int
+    lib.phnn_solve_mppi.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
+                                    C.POINTER(MppiOptions), vp, C.c_size_t, f32p, f32p, f32p, vp]
+    lib.phnn_solve_mppi.restype = C.c_int
     lib.phnn_plant_step.argtypes = [vp, C.POINTER(Plant), vp, f32p, i64, i64, i32, C.c_float, C.c_float, f32p, vp, vp, i32,
                                     vp, f32p, vp]
     lib.phnn_plant_step.restype = C.c_int

@@ -57,10 +57,11 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None):
     done_step = np.full(B, -1, dtype=np.int64)
     canonical = hasattr(controller, "control_batch")
     u_prev = None
-    rkw = {}
+    mppi = getattr(controller, "optimizer", getattr(controller, "optimizer_type", None)) == "MPPI"
     for step in range(num_steps):
+        rkw = {"epoch": step} if mppi else {}  # the noise counter of an MPPI solve: the control step
         if x_ref is not None:
-            rkw = {"x_ref": x_ref, "ref_offset": step}
+            rkw.update(x_ref=x_ref, ref_offset=step)
         if canonical:
             u, u_prev, _ = controller.control_batch(x.astype(np.float32), u_prev, **rkw)
         else:
@@ -82,7 +83,9 @@ class DeviceClosedLoop:
     optimizer_type='LBFGS': engine.solve_lbfgs, i.e. the state reset and max_iterations x 20 x (K1, K2, k_lbfgs), then
     k_plant_step); with use_graph the step is captured once and replayed.  Per-plant arithmetic is identical to
     run_mpc_batch (same kernels, same order); the plant differs from the numpy one only by the device's
-    double-precision sin/cos.
+    double-precision sin/cos.  An MPPI controller (optimizer_type / optimizer 'MPPI'): engine.solve_mppi -- the clamp
+    and resets, iters x (k_mppi_sample, K1, k_mppi_update) -- with step_dev as the noise epoch, so every replay draws the
+    noise run_mpc_batch draws at that step.
 
     x_ref: reference trajectories broadcastable to (B, rows, 4) (engine.reference_view); every solve tracks them from
     row step_dev, the device counter the plant step logs with and the shift advances, so each replay of the captured
@@ -116,10 +119,15 @@ class DeviceClosedLoop:
         if x_ref is not None:
             from .engine import reference_view
             self.x_ref = reference_view(x_ref, B, 4, dev)[0]
+        self.mppi = (controller.optimizer if self.canonical else controller.optimizer_type) == "MPPI"
+        if self.mppi and not hasattr(eng, "solve_mppi"):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched MPPI solve (RolloutEngine has)")
+        if self.mppi and x_ref is not None:  # one row set per rollout, expanded once, here (samples x the bytes)
+            self.x_ref = eng.mppi_reference(self.x_ref, B, controller.samples)
         self.iters = controller.optimizer_steps if self.canonical else controller.max_iterations
         self.lr = controller.learning_rate if self.canonical else controller.lr
         self.lbfgs = not self.canonical and controller.optimizer_type == "LBFGS"
-        if not self.canonical and controller.optimizer_type not in ("Adam", "LBFGS"):
+        if not self.canonical and controller.optimizer_type not in ("Adam", "LBFGS", "MPPI"):
             raise ValueError(f"Unknown optimizer type: {controller.optimizer_type}")
         if self.lbfgs and not hasattr(eng, "solve_lbfgs"):
             raise NotImplementedError(f"{type(eng).__name__} has no batched L-BFGS solve (RolloutEngine has)")
@@ -131,7 +139,9 @@ class DeviceClosedLoop:
         log = dict(state_f32=self.x32, done_step=self.done_step, step_dev=self.step_dev, log_states=self.log_states,
                    log_controls=self.log_controls)
         H = self.u_init.shape[1] * self.u_init.shape[2]
-        if self.lbfgs:  # the reference's L-BFGS solve
+        if self.mppi:
+            out = self._solve_mppi()
+        elif self.lbfgs:  # the reference's L-BFGS solve
             out = eng.solve_lbfgs(self.x32, self.u_init, self.cost, integrator=c.integrator, dt=c.dt, record_costs=False,
                                   workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, **c.lbfgs_options())
         else:
@@ -144,6 +154,14 @@ class DeviceClosedLoop:
         else:  # last iterate, clamp(u_0); every call cold-starts from zeros (u_init stays zero)
             eng.plant_step(self.plant, self.state, out["u_last"], H, u_min=c.u_min, u_max=c.u_max, **log)
             eng.advance_step(self.step_dev)
+
+    def _solve_mppi(self):
+        """engine.solve_mppi with the step counter as the noise epoch.  self.x_ref is already one row set per rollout
+        (or shared): it is handed to phnn_solve_mppi as it is, not expanded again."""
+        eng, c = self.eng, self.ctl
+        return eng.solve_mppi(self.x32, self.u_init, self.cost, c.integrator, c.dt, epoch=self.step_dev, record_costs=False,
+                              workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, expanded_ref=True,
+                              **c.mppi_options())
 
     def run(self):
         torch = self.torch

@@ -16,6 +16,7 @@
 // phnn_grad.hip without it, would spill (K2 +5 %)
 #define PHNN_PREFETCH_BF
 #include "phnn_lbfgs.h"
+#include "phnn_mppi.h"
 #include "phnn_pack.h"
 
 namespace {
@@ -534,7 +535,7 @@ int check_cost(phnn_handle* h, const phnn_cost* c) {
 
 extern "C" {
 
-int phnn_version(void) { return 240; }
+int phnn_version(void) { return 250; }
 
 const char* phnn_variant_name(const phnn_handle* h) { return h ? h->ks.name : ""; }
 
@@ -1204,6 +1205,132 @@ int phnn_solve_lbfgs(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t 
       e = lbfgs_launch(lp, st);
       if (e != hipSuccess) return hip_fail(h, e, "k_lbfgs launch");
     }
+  }
+  return PHNN_OK;
+}
+
+// ---- batched sampling (MPPI) solve: kernels in phnn_mppi.hip ------------------------------------------------------
+static int check_mppi(phnn_handle* h, const phnn_mppi_options* opt, int64_t B, int32_t H, int32_t iteration) {
+  if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options is NULL");
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (opt->samples < 2 || opt->samples > kMppiMaxSamples)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: samples < 2 or > 2^26");
+  if (!(opt->lambda > 0.f) || !std::isfinite(opt->lambda))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: lambda must be > 0 and finite");
+  for (int i = 0; i < h->desc.m; ++i)
+    if (!(opt->sigma[i] >= 0.f) || !std::isfinite(opt->sigma[i]))
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: sigma must be >= 0 and finite");
+  if (iteration < 0 || iteration >= kMppiMaxIters || opt->iters < 0 || opt->iters > kMppiMaxIters)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: iteration count outside 0 .. 65536");
+  if (opt->problem_offset < 0 || opt->problem_offset > kMppiMaxProblem - B)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: problem ids outside 0 .. 2^48");
+  if ((int64_t)H * h->desc.m > kMppiMaxN) return fail(h, PHNN_ERR_UNSUPPORTED, "MPPI: H * m > 256");
+  return PHNN_OK;
+}
+
+size_t phnn_mppi_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t samples) {
+  if (!h || B < 0 || H < 1 || samples < 2 || samples > kMppiMaxSamples) return 0;
+  return mppi_layout(B, H * h->desc.m, h->desc.n, samples).total;
+}
+
+int phnn_mppi_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                     const phnn_mppi_options* opt, int32_t iteration, float* samples_dev, float* x0_rep_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_mppi(h, opt, B, H, iteration)) return rc;
+  if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!u_dev || !samples_dev || (x0_rep_dev && !x0_dev)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_sample: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  MppiSampleParams p;
+  memset(&p, 0, sizeof p);
+  p.u = u_dev;
+  p.x0 = x0_dev;
+  p.v = samples_dev;
+  p.x0_rep = x0_rep_dev;
+  p.B = B;
+  p.K = opt->samples;
+  p.N = H * h->desc.m;
+  p.n = h->desc.n;
+  p.m = h->desc.m;
+  for (int i = 0; i < h->desc.m; ++i) p.sigma[i] = opt->sigma[i];
+  p.u_min = cost->u_min;
+  p.u_max = cost->u_max;
+  p.has_u_bounds = cost->has_u_bounds;
+  p.key0 = (unsigned)(opt->seed & 0xffffffffu);
+  p.key1 = (unsigned)(opt->seed >> 32);
+  p.problem_offset = opt->problem_offset;
+  p.epoch_dev = opt->epoch_dev;
+  p.epoch_host = opt->epoch_host;
+  p.iteration = iteration;
+  hipError_t e = mppi_sample_launch(p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "k_mppi_sample launch");
+  return PHNN_OK;
+}
+
+int phnn_mppi_update(phnn_handle* h, float* u_dev, const float* samples_dev, const float* sample_cost_dev, int64_t B,
+                     int32_t H, const phnn_cost* cost, const phnn_mppi_options* opt, float* costs_row_dev,
+                     float* best_cost_dev, float* best_u_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_mppi(h, opt, B, H, 0)) return rc;
+  if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!u_dev || !samples_dev || !sample_cost_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_update: NULL tensor");
+  if ((best_cost_dev != nullptr) != (best_u_dev != nullptr))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_update: best_cost_dev and best_u_dev go together");
+  PHNN_ON_DEVICE(h);
+  MppiUpdateParams p;
+  memset(&p, 0, sizeof p);
+  p.u = u_dev;
+  p.v = samples_dev;
+  p.s = sample_cost_dev;
+  p.costs_out = costs_row_dev;
+  p.best_cost = best_cost_dev;
+  p.best_u = best_u_dev;
+  p.B = B;
+  p.K = opt->samples;
+  p.N = H * h->desc.m;
+  p.lambda = opt->lambda;
+  p.u_min = cost->u_min;
+  p.u_max = cost->u_max;
+  p.has_u_bounds = cost->has_u_bounds;
+  hipError_t e = mppi_update_launch(p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "k_mppi_update launch");
+  return PHNN_OK;
+}
+
+int phnn_solve_mppi(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                    const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt, void* workspace,
+                    size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_mppi(h, opt, B, H, 0)) return rc;
+  RollParams rp;
+  if (int rc = fill_roll(h, &rp, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
+  if (int rc = fill_ref(h, &rp, ref, B)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!best_cost_dev || !best_u_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_mppi: best_cost_dev and best_u_dev are required");
+  const int N = H * h->desc.m;
+  const MppiLayout lay = mppi_layout(B, N, h->desc.n, opt->samples);
+  if (opt->iters > 0 && (!workspace || workspace_size < lay.total))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_mppi: workspace is NULL or too small");
+  PHNN_ON_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  // the entry state, before any early return: nominal in bounds, best = (+inf, 0)
+  hipError_t e = hipMemsetD32Async((hipDeviceptr_t)best_cost_dev, 0x7F800000, (size_t)B, st);
+  if (e == hipSuccess) e = hipMemsetAsync(best_u_dev, 0, sizeof(float) * (size_t)B * N, st);
+  if (e == hipSuccess && cost->has_u_bounds) e = mppi_clamp_launch(u_dev, (long long)B * N, cost->u_min, cost->u_max, st);
+  if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_mppi: state reset");
+  if (opt->iters == 0) return PHNN_OK;
+  char* ws = (char*)workspace;
+  float* v = (float*)(ws + lay.v);
+  float* x0_rep = (float*)(ws + lay.x0_rep);
+  float* s = (float*)(ws + lay.s);
+  const int64_t rollouts = B * (int64_t)opt->samples;
+  for (int it = 0; it < opt->iters; ++it) {
+    if (int rc = phnn_mppi_sample(h, x0_dev, u_dev, B, H, cost, opt, it, v, it == 0 ? x0_rep : nullptr, stream)) return rc;
+    if (int rc = rollout_fwd(h, x0_rep, v, rollouts, H, cost, integrator, dt, s, nullptr, nullptr, ref, stream)) return rc;
+    if (int rc = phnn_mppi_update(h, u_dev, v, s, B, H, cost, opt, costs_dev ? costs_dev + (size_t)it * B : nullptr, best_cost_dev,
+                                  best_u_dev, stream))
+      return rc;
   }
   return PHNN_OK;
 }

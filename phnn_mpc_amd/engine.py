@@ -503,6 +503,121 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return {"u_last": u, "costs": costs, "n_iter": n_iter, "func_evals": func_evals}
 
+    # ------------------------------------------------------------------ batched sampling (MPPI) solve (k_mppi_sample, K1, k_mppi_update)
+    def mppi_workspace_bytes(self, B, H, samples):
+        return int(self.lib.phnn_mppi_workspace_bytes(self.h, int(B), int(H), int(samples)))
+
+    def _mppi_options(self, iters, samples, lam, sigma, seed, epoch, problem_offset):
+        """-> (phnn_mppi_options, what to keep alive).  sigma: one value or one per control component; epoch: int or a
+        device int32 tensor (its first element is read by every launch; a captured graph follows it)."""
+        opt = _capi.MppiOptions()
+        opt.iters, opt.samples = int(iters), int(samples)
+        setattr(opt, "lambda", float(lam))
+        sig = np.asarray(sigma, dtype=np.float64).reshape(-1)
+        if sig.size == 1:
+            sig = np.repeat(sig, self.m)
+        if sig.shape != (self.m,):
+            raise ValueError(f"sigma: one value or one per control component (m = {self.m}), got {sigma!r}")
+        for i in range(self.m):
+            opt.sigma[i] = float(sig[i])
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must fit 64 bits")
+        opt.seed, opt.problem_offset = int(seed), int(problem_offset)
+        if isinstance(epoch, torch.Tensor):
+            if epoch.dtype != torch.int32 or epoch.device != self.device or epoch.numel() < 1:
+                raise ValueError("epoch: an int or an int32 tensor on the engine's device")
+            opt.epoch_dev = epoch.data_ptr()
+        else:
+            opt.epoch_host = int(epoch)
+        return opt, epoch
+
+    def _mppi_buffers(self, ws, B, H, samples):
+        """The sample tensor (B*K, H, m), replicated x0 (B*K, n) and K1 cost vector (B*K) of an MPPI problem, as views of
+        one phnn_mppi_workspace_bytes buffer kept in the dict `ws` (the layout phnn_solve_mppi uses)."""
+        key = (B, H, int(samples))
+        if ws.get("mppi_key") != key:
+            ws["mppi_key"] = key
+            nbytes = self.mppi_workspace_bytes(B, H, samples)  # 0: arguments the library call itself will refuse
+            buf = ws["mppi"] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            R, N = (B * int(samples) if nbytes else 0), H * self.m
+            a256 = lambda x: (x + 255) & ~255
+            o_x0 = a256(4 * R * N)
+            o_s = a256(o_x0 + 4 * R * self.n)
+            ws["mppi_v"] = buf[: 4 * R * N].view(torch.float32).view(R, H, self.m)
+            ws["mppi_x0"] = buf[o_x0: o_x0 + 4 * R * self.n].view(torch.float32).view(R, self.n)
+            ws["mppi_s"] = buf[o_s: o_s + 4 * R].view(torch.float32)
+        return ws
+
+    def mppi_reference(self, x_ref, B, samples):
+        """The reference as the B * samples rollouts of an MPPI solve see it: one shared by all problems goes straight
+        through (batch stride 0); a per-problem one is expanded on the device to one row set per rollout (rollout
+        b * samples + k tracks problem b's), samples times its bytes."""
+        if x_ref is None:
+            return None
+        t, bs, ts, _rows = reference_view(x_ref, B, self.n, self.device)
+        if bs == 0:
+            return t[:1]
+        return (t[:, :1] if ts == 0 else t).repeat_interleave(int(samples), dim=0)
+
+    def mppi_sample(self, x0, u, cost, samples, sigma, seed, iteration, epoch=0, problem_offset=0, workspace=None):
+        """k_mppi_sample.  x0 (B,n), nominal u (B,H,m) -> (v (B*samples,H,m), x0 replicated (B*samples,n)): sample
+        b * samples + k is clamp(u_b + sigma o z), z standard normal from the Philox counter (seed, epoch, iteration,
+        problem_offset + b, k) and zero for k = 0.  The outputs are views of `workspace` (a dict reused across calls)."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u, H = self._controls(u, B)
+        ws = self._mppi_buffers({} if workspace is None else workspace, B, H, samples)
+        opt, _keep = self._mppi_options(0, samples, 1.0, sigma, seed, epoch, problem_offset)
+        rc = self.lib.phnn_mppi_sample(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(opt), int(iteration),
+                                       self._p(ws["mppi_v"]), self._p(ws["mppi_x0"]), self._stream())
+        _check(self.lib, self.h, rc)
+        return ws["mppi_v"], ws["mppi_x0"]
+
+    def mppi_update(self, u, v, s, lam, cost, costs_row=None, best_cost=None, best_u=None):
+        """k_mppi_update, in place on the nominal u (B,H,m): u_b = clamp(sum_k w_k v_{b,k} / sum_k w_k) with
+        w_k = exp(-(s_{b,k} - min_k s_b) / lam) over the samples v (B*K,H,m) of costs s (B*K); the clamp is the cost's.  costs_row (B) receives
+        s_{b,0}; best_cost (B) / best_u (B,H,m) the lowest-cost sample seen so far (strict '<', lowest k on ties)."""
+        for t in (u, v, s, costs_row, best_cost, best_u):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device)
+        B, H = u.shape[0], u.shape[1]
+        samples = s.numel() // max(B, 1)
+        assert v.numel() == B * samples * H * self.m and s.numel() == B * samples
+        opt, _keep = self._mppi_options(0, samples, lam, 0.0, 0, 0, 0)
+        rc = self.lib.phnn_mppi_update(self.h, self._p(u), self._p(v), self._p(s), B, H, C.byref(cost), C.byref(opt),
+                                       self._p(costs_row),
+                                       self._p(best_cost), self._p(best_u), self._stream())
+        _check(self.lib, self.h, rc)
+
+    def solve_mppi(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=4, samples=64, lam=1.0, sigma=1.0, seed=0,
+                   epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0, expanded_ref=False):
+        """phnn_solve_mppi: sampling MPC (MPPI) on B independent problems as ONE library call: the nominal is clamped,
+        then iters x (k_mppi_sample, K1 over B * samples rollouts, k_mppi_update); no gradient is taken anywhere.
+        -> dict(u_last (B,H,m) last nominal (in bounds), costs (iters,B) the nominal's cost at every iteration or None,
+        best_u (B,H,m) / best_cost (B) the best sample over all iterations), same results bit for bit as
+        solver.mppi_solve.  sigma: noise standard deviation, one value or one per control component; lam: softmin
+        temperature in units of the cost; seed, epoch (int or device int32 tensor), problem_offset: the noise counter
+        (problem b's noise depends on problem_offset + b, not on the batch).  x_ref, ref_offset: as in rollout_cost; a
+        per-problem reference is expanded to one row set per rollout (mppi_reference: samples times its bytes) once per
+        call, unless expanded_ref says x_ref already is what mppi_reference returned (a closed loop expands it once)."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u_init, H = self._controls(u_init, B)
+        integ = self._integ(integrator)
+        ws = self._mppi_buffers(self._roll_workspace(workspace, B, H, integ), B, H, samples)
+        f = dict(dtype=torch.float32, device=self.device)
+        u = u_init.detach().clone().contiguous()
+        costs = torch.empty(max(int(iters), 0), B, **f) if record_costs else None
+        best_cost, best_u = torch.empty(B, **f), torch.empty(B, H, self.m, **f)
+        opt, _keep = self._mppi_options(iters, samples, lam, sigma, seed, epoch, problem_offset)
+        ref, _keep_ref = self._reference(x_ref if expanded_ref else self.mppi_reference(x_ref, B, samples), ref_offset,
+                                         B * int(samples))
+        rc = self.lib.phnn_solve_mppi(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
+                                      None if ref is None else C.byref(ref), integ, float(dt), C.byref(opt),
+                                      self._p(ws["mppi"]), ws["mppi"].numel(), self._p(costs), self._p(best_cost),
+                                      self._p(best_u), self._stream())
+        _check(self.lib, self.h, rc)
+        return {"u_last": u, "costs": costs, "best_u": best_u, "best_cost": best_cost}
+
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
                    step=0, step_dev=None, log_states=None, log_controls=None):

@@ -8,6 +8,9 @@ Reference behaviour kept:
     as a numpy array of shape (1,).
 optimizer_type='LBFGS': compute_control runs the reference's torch.optim.LBFGS on the host (one plant); solve_batch /
 compute_control_batch run B such optimizers at once on the device (engine.solve_lbfgs, kernel k_lbfgs).
+optimizer_type='MPPI' (not in the reference): the gradient-free sampling solve (engine.solve_mppi): every call
+cold-starts the nominal from zeros, runs max_iterations iterations of `samples` perturbed rollouts per plant and returns
+clamp(u_0) of the last nominal.  lr is not used.
 """
 import os
 
@@ -15,12 +18,12 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import lbfgs_solver_for, solver_for
+from .solver import lbfgs_solver_for, mppi_solver_for, solver_for
 
 
 class MPCController:
     def __init__(self, phnn_model, horizon, dt, Q, R, target_state=None, u_min=None, u_max=None, x_min=None, x_max=None,
-                 optimizer_type="Adam", lr=0.1, max_iterations=50):
+                 optimizer_type="Adam", lr=0.1, max_iterations=50, samples=64, lam=1.0, sigma=1.0, seed=0):
         self.model = phnn_model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -35,6 +38,9 @@ class MPCController:
         self.x_min = torch.tensor(x_min, dtype=torch.float32) if x_min is not None else None
         self.x_max = torch.tensor(x_max, dtype=torch.float32) if x_max is not None else None
         self.optimizer_type, self.lr, self.max_iterations = optimizer_type, lr, max_iterations
+        # optimizer_type='MPPI': samples per plant and iteration, softmin temperature (units of the cost), noise standard
+        # deviation, noise seed; `epoch` numbers the solves that are not given one (fresh noise at every control step)
+        self.samples, self.lam, self.sigma, self.seed, self.epoch = samples, lam, sigma, seed, 0
         self.integrator = "euler"  # src/mpc_controller.py:137-138
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -117,12 +123,15 @@ class MPCController:
         return u0.detach().numpy()
 
     # ------------------------------------------------------------------ batched (new)
-    def solve_batch(self, states, record_costs=False, x_ref=None, ref_offset=0):
+    def solve_batch(self, states, record_costs=False, x_ref=None, ref_offset=0, epoch=None):
         """states (B,n) -> dict with the last iterate of B independent problems (all on the engine's device).
         x_ref: per-problem reference trajectories broadcastable to (B, rows, n), tracked from row ref_offset (int or
-        device int32 tensor; past its end a reference holds its last row) instead of target_state."""
+        device int32 tensor; past its end a reference holds its last row) instead of target_state.
+        epoch (MPPI only): the noise counter of this solve; None: self.epoch, which then advances by one."""
         if self.optimizer_type == "LBFGS":
             return self._solve_batch_lbfgs(states, record_costs, x_ref, ref_offset)
+        if self.optimizer_type == "MPPI":
+            return self._solve_batch_mppi(states, record_costs, x_ref, ref_offset, epoch)
         if self.optimizer_type != "Adam":
             raise ValueError(f"Unknown optimizer type: {self.optimizer_type}")
         eng = self.engine
@@ -151,13 +160,46 @@ class MPCController:
         return self._graphed_lbfgs(x0, u0, self._cost(), integrator=self.integrator, dt=self.dt, record_costs=record_costs,
                                    x_ref=x_ref, ref_offset=ref_offset, **self.lbfgs_options())
 
-    def compute_control_batch(self, states, x_ref=None, ref_offset=0):
-        """states (B,n) -> np.ndarray (B,1): first control of each plant's optimised sequence (x_ref: solve_batch)."""
-        out = self.solve_batch(states, x_ref=x_ref, ref_offset=ref_offset)
+    def mppi_options(self):
+        """solve_mppi keyword arguments of this controller."""
+        return dict(iters=self.max_iterations, samples=self.samples, lam=self.lam,
+                    sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), seed=self.seed)
+
+    def _mppi_epoch(self, eng, epoch):
+        """The epoch argument of one solve: `epoch` (None: the controller's own counter, advanced here); with use_graph
+        a device counter holding it, so that the captured graph is replayed, not re-captured, when it changes."""
+        if epoch is None:
+            epoch, self.epoch = self.epoch, self.epoch + 1
+        if not self.use_graph or eng.device.type != "cuda" or isinstance(epoch, torch.Tensor):
+            return epoch
+        if getattr(self, "_epoch_dev", None) is None or self._epoch_dev.device != eng.device:
+            self._epoch_dev = torch.zeros(1, dtype=torch.int32, device=eng.device)
+        self._epoch_dev.fill_(int(epoch))
+        return self._epoch_dev
+
+    def _solve_batch_mppi(self, states, record_costs, x_ref, ref_offset, epoch):
+        """B independent sampling solves (cold start from zeros) in one batched device solve (engine.solve_mppi)."""
+        eng = self.engine
+        self._graphed_mppi = mppi_solver_for(eng, self.use_graph, getattr(self, "_graphed_mppi", None))
+        x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
+        u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
+        return self._graphed_mppi(eng, x0, u0, self._cost(), self.integrator, self.dt, epoch=self._mppi_epoch(eng, epoch),
+                                  record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **self.mppi_options())
+
+    def compute_control_batch(self, states, x_ref=None, ref_offset=0, epoch=None):
+        """states (B,n) -> np.ndarray (B,1): first control of each plant's optimised sequence (x_ref, epoch:
+        solve_batch)."""
+        kw = {"epoch": epoch} if self.optimizer_type == "MPPI" else {}
+        out = self.solve_batch(states, x_ref=x_ref, ref_offset=ref_offset, **kw)
         u0 = out["u_last"][:, 0, :]
         if self.u_min is not None and self.u_max is not None:
             u0 = torch.clamp(u0, self.u_min, self.u_max)
         return u0.cpu().numpy()
+
+
+def _mppi_keys(mpc):
+    """The MPPI keywords present in the `mpc` config section (optimizer: MPPI): samples, lam, sigma, seed."""
+    return {k: mpc[k] for k in ("samples", "lam", "sigma", "seed") if k in mpc}
 
 
 def create_mpc_from_config(phnn_model, config):
@@ -168,10 +210,10 @@ def create_mpc_from_config(phnn_model, config):
         return MPCController(phnn_model=phnn_model, horizon=mpc.get("horizon", 20), dt=config["cartpole"]["dt"],
                              Q=mpc.get("Q_diag", [10.0, 100.0, 1.0, 10.0]), R=mpc.get("R_diag", [0.01])[0],
                              target_state=mpc.get("x_target", [0.0, 0.0, 0.0, 0.0]), u_min=mpc.get("u_min", -10.0),
-                             u_max=mpc.get("u_max", 10.0), optimizer_type="Adam", lr=mpc.get("learning_rate", 0.1),
-                             max_iterations=mpc.get("optimizer_steps", 50))
+                             u_max=mpc.get("u_max", 10.0), optimizer_type=mpc.get("optimizer", "Adam"),
+                             lr=mpc.get("learning_rate", 0.1), max_iterations=mpc.get("optimizer_steps", 50), **_mppi_keys(mpc))
     return MPCController(phnn_model=phnn_model, horizon=mpc["horizon"], dt=mpc["dt"], Q=mpc["Q"], R=mpc["R"],
                          target_state=mpc.get("target_state", None), u_min=mpc.get("u_min", None),
                          u_max=mpc.get("u_max", None), x_min=mpc.get("x_min", None), x_max=mpc.get("x_max", None),
                          optimizer_type=mpc.get("optimizer", "Adam"), lr=mpc.get("lr", 0.1),
-                         max_iterations=mpc.get("max_iterations", 50))
+                         max_iterations=mpc.get("max_iterations", 50), **_mppi_keys(mpc))

@@ -5,6 +5,9 @@ Reference behaviour kept: full Q (n,n) and R (m,m) matrices; Euler rollout; the 
 clamped one (cost measured before the Adam step of the same iteration, strict '<', src/mpc_controller_canonical.py:
 208-214); control() warm-starts by shifting the previous sequence by one and zero-filling the tail (:252-255) and
 returns (u (m,), info{'u_sequence','solve_time','optimization'{'costs','final_cost','num_steps'}}).
+optimizer='MPPI' (not in the reference): the same calls solved by the gradient-free sampling solve (engine.solve_mppi):
+optimizer_steps iterations of `samples` perturbed rollouts per plant; the sequence returned is the best SAMPLE seen,
+'costs' the nominal's cost at every iteration; learning_rate is not used.
 """
 import os
 import time
@@ -13,12 +16,13 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import solver_for
+from .solver import mppi_solver_for, solver_for
 
 
 class MPCControllerCanonical:
     def __init__(self, model, horizon=20, dt=0.02, Q=None, R=None, x_target=None, u_min=-10.0, u_max=10.0,
-                 optimizer_steps=50, learning_rate=0.1, verbose=False):
+                 optimizer_steps=50, learning_rate=0.1, verbose=False, optimizer="Adam", samples=64, lam=1.0, sigma=1.0,
+                 seed=0):
         self.model = model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -34,6 +38,11 @@ class MPCControllerCanonical:
             x_target = np.zeros(self.state_dim)
         self.x_target = torch.tensor(x_target, dtype=torch.float32)
         self.u_min, self.u_max = u_min, u_max
+        if optimizer not in ("Adam", "MPPI"):
+            raise ValueError(f"Unknown optimizer type: {optimizer}")
+        # optimizer='MPPI': samples per plant and iteration, softmin temperature (units of the cost), noise standard
+        # deviation (one value or one per input), noise seed; `epoch` numbers the solves that are not given one
+        self.optimizer, self.samples, self.lam, self.sigma, self.seed, self.epoch = optimizer, samples, lam, sigma, seed, 0
         self.integrator = "euler"
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -98,10 +107,28 @@ class MPCControllerCanonical:
         return u, info
 
     # ------------------------------------------------------------------ batched (new)
-    def optimize_control_batch(self, x0, u_init=None, record_costs=True, x_ref=None, ref_offset=0):
+    def mppi_options(self):
+        """solve_mppi keyword arguments of this controller."""
+        return dict(iters=self.optimizer_steps, samples=self.samples, lam=self.lam,
+                    sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), seed=self.seed)
+
+    def _mppi_epoch(self, eng, epoch):
+        """The epoch argument of one solve: `epoch` (None: the controller's own counter, advanced here); with use_graph
+        a device counter holding it, so that the captured graph is replayed, not re-captured, when it changes."""
+        if epoch is None:
+            epoch, self.epoch = self.epoch, self.epoch + 1
+        if not self.use_graph or eng.device.type != "cuda" or isinstance(epoch, torch.Tensor):
+            return epoch
+        if getattr(self, "_epoch_dev", None) is None or self._epoch_dev.device != eng.device:
+            self._epoch_dev = torch.zeros(1, dtype=torch.int32, device=eng.device)
+        self._epoch_dev.fill_(int(epoch))
+        return self._epoch_dev
+
+    def optimize_control_batch(self, x0, u_init=None, record_costs=True, x_ref=None, ref_offset=0, epoch=None):
         """x0 (B,n), u_init (B,H,m) or None -> dict(best_u (B,H,m) clamped, best_cost (B), costs (steps,B), u_last).
         x_ref: per-problem reference trajectories broadcastable to (B, rows, n), tracked from row ref_offset (int or
-        device int32 tensor; past its end a reference holds its last row) instead of x_target."""
+        device int32 tensor; past its end a reference holds its last row) instead of x_target.
+        epoch (MPPI only): the noise counter of this solve; None: self.epoch, which then advances by one."""
         eng = self.engine
         x0 = torch.as_tensor(x0, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
         B = x0.shape[0]
@@ -109,18 +136,24 @@ class MPCControllerCanonical:
             u0 = torch.zeros(B, self.horizon, self.input_dim, dtype=torch.float32, device=eng.device)
         else:
             u0 = torch.as_tensor(u_init, dtype=torch.float32).reshape(B, self.horizon, self.input_dim).to(eng.device)
+        if self.optimizer == "MPPI":
+            self._graphed_mppi = mppi_solver_for(eng, self.use_graph, getattr(self, "_graphed_mppi", None))
+            return self._graphed_mppi(eng, x0, u0, self._cost(), self.integrator, self.dt,
+                                      epoch=self._mppi_epoch(eng, epoch), record_costs=record_costs, x_ref=x_ref,
+                                      ref_offset=ref_offset, **self.mppi_options())
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.learning_rate,
                                  self.optimizer_steps, track_best=True, u_min=self.u_min, u_max=self.u_max,
                                  record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset)
 
-    def control_batch(self, x_current, u_prev=None, x_ref=None, ref_offset=0):
+    def control_batch(self, x_current, u_prev=None, x_ref=None, ref_offset=0, epoch=None):
         """x_current (B,n), u_prev (B,H,m) or None -> (u (B,m), u_sequence (B,H,m), best_cost (B)) numpy arrays.
-        x_ref, ref_offset: optimize_control_batch."""
+        x_ref, ref_offset, epoch: optimize_control_batch."""
         u_init = None
         if u_prev is not None:
             up = torch.as_tensor(u_prev, dtype=torch.float32)
             u_init = torch.cat([up[:, 1:], torch.zeros(up.shape[0], 1, self.input_dim)], dim=1)
-        out = self.optimize_control_batch(x_current, u_init, record_costs=False, x_ref=x_ref, ref_offset=ref_offset)
+        out = self.optimize_control_batch(x_current, u_init, record_costs=False, x_ref=x_ref, ref_offset=ref_offset,
+                                          epoch=epoch)
         seq = out["best_u"].cpu().numpy()
         return seq[:, 0, :], seq, out["best_cost"].cpu().numpy()
 
@@ -133,4 +166,5 @@ def create_mpc_controller(model, config):
         Q=np.diag(mpc.get("Q_diag", [10.0, 100.0, 1.0, 10.0])), R=np.diag(mpc.get("R_diag", [0.01])),
         x_target=np.array(mpc.get("x_target", [0.0, 0.0, 0.0, 0.0])), u_min=mpc.get("u_min", -10.0),
         u_max=mpc.get("u_max", 10.0), optimizer_steps=mpc.get("optimizer_steps", 50),
-        learning_rate=mpc.get("learning_rate", 0.1), verbose=mpc.get("verbose", False))
+        learning_rate=mpc.get("learning_rate", 0.1), verbose=mpc.get("verbose", False),
+        **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed") if k in mpc})

@@ -10,6 +10,10 @@ is the library's (engine.solve: phnn_solve enqueues K1, K2, K3 of every iteratio
 in Python over rollout_cost_grad (K1+K2) and adam_step (K3), for engines that have only those, and the reference
 engine.solve is pinned to bit for bit.  With use_graph either one (and engine.solve_lbfgs) is captured as a HIP
 graph by the same class, Graphed.
+
+mppi_solve is the gradient-free solver next to them (MPPI: sample K perturbations of the nominal, cost all of them in
+one K1 launch, move the nominal to their softmin-weighted mean): the Python loop over engine.mppi_sample,
+engine.rollout_cost and engine.mppi_update that engine.solve_mppi (phnn_solve_mppi) is pinned to bit for bit.
 """
 import ctypes
 import inspect
@@ -72,6 +76,49 @@ def _eager(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=False
                             workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
     return shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=track_best, u_min=u_min, u_max=u_max,
                           record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, workspace=workspace)
+
+
+def mppi_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, sigma, seed, epoch=0, problem_offset=0,
+               record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+    """Sampling MPC (MPPI) on B independent problems: x0 (B,n), u_init (B,H,m) -> dict(u_last, costs, best_u, best_cost).
+
+    The nominal u starts at clamp(u_init) (the cost's bounds); `iters` times: v = engine.mppi_sample (samples
+    perturbed copies per problem, sample 0 the nominal itself), S = engine.rollout_cost of all B * samples rollouts,
+    engine.mppi_update moves the nominal to sum_k w_k v_k / sum_k w_k with w_k = exp(-(S_k - min S) / lam).
+    u_last   : the last nominal (B,H,m), in bounds
+    costs    : (iters,B) cost of the nominal at every iteration (its sample 0), if record_costs
+    best_u   : the best sample seen over all iterations (strict '<', lowest sample index on ties), best_cost its cost
+    seed, epoch (int or device int32 tensor), problem_offset: the noise counter; problem b draws the noise of global
+    problem problem_offset + b whatever batch it is solved in.  x_ref, ref_offset: as in shooting_solve."""
+    _need_reference(engine, x_ref)
+    rkw = {}
+    B = u_init.shape[0]
+    if x_ref is not None:  # one reference per rollout: shared as it is, per-problem expanded once per solve
+        rkw = {"x_ref": engine.mppi_reference(x_ref, B, samples), "ref_offset": ref_offset}
+    u = u_init.detach().clone().contiguous()
+    if cost.has_u_bounds:
+        u = torch.clamp(u, float(cost.u_min), float(cost.u_max))
+    dev = u.device
+    costs = torch.empty(iters, B, dtype=torch.float32, device=dev) if record_costs else None
+    best_cost = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
+    best_u = torch.zeros_like(u)
+    ws = {} if workspace is None else workspace
+    for i in range(iters):
+        v, x0_rep = engine.mppi_sample(x0, u, cost, samples, sigma, seed, i, epoch=epoch, problem_offset=problem_offset,
+                                       workspace=ws)
+        s = engine.rollout_cost(x0_rep, v, cost, integrator, dt, **rkw)
+        engine.mppi_update(u, v, s, lam, cost, costs_row=costs[i] if record_costs else None, best_cost=best_cost, best_u=best_u)
+    return {"u_last": u, "costs": costs, "best_u": best_u, "best_cost": best_cost}
+
+
+def _mppi_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, sigma, seed, epoch=0, problem_offset=0,
+                record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+    """The MPPI solve without a captured graph: the library's own loop (engine.solve_mppi) where the engine has one, else
+    the Python loop over its primitives.  Same launches, same order: identical results."""
+    fn = engine.solve_mppi if hasattr(engine, "solve_mppi") else lambda *a, **k: mppi_solve(engine, *a, **k)
+    return fn(x0, u_init, cost, integrator, dt, iters=iters, samples=samples, lam=lam, sigma=sigma, seed=seed, epoch=epoch,
+              problem_offset=problem_offset, record_costs=record_costs, workspace=workspace, x_ref=x_ref,
+              ref_offset=ref_offset)
 
 
 def capture(device, fn):
@@ -172,6 +219,17 @@ class GraphedLBFGS(Graphed):
         super().__init__(engine, engine.solve_lbfgs)
 
 
+class GraphedMPPI(Graphed):
+    """The MPPI solve (_mppi_eager) as a graph: the clamp and resets plus every iters x (k_mppi_sample, K1,
+    k_mppi_update) launch.  `epoch` is part of the graph's signature: an int re-captures when it changes, a device int32
+    tensor is read through its pointer at every replay (fill it in place between calls to draw fresh noise).  sigma
+    must be hashable (a float or a tuple).  A per-problem x_ref lives in the graph's static buffer as given and its
+    expansion to one row set per rollout is part of the replayed graph."""
+
+    def __init__(self, engine):
+        super().__init__(engine, _mppi_eager)
+
+
 def _graphed_or(eager, cls, engine, use_graph, previous):
     if not use_graph or engine.device.type != "cuda":
         return eager
@@ -193,3 +251,11 @@ def lbfgs_solver_for(engine, use_graph, previous=None):
         raise NotImplementedError(f"{type(engine).__name__} has no batched L-BFGS solve (RolloutEngine has): use "
                                   "compute_control (one plant at a time)")
     return _graphed_or(engine.solve_lbfgs, GraphedLBFGS, engine, use_graph, previous)
+
+
+def mppi_solver_for(engine, use_graph, previous=None):
+    """-> callable(engine, x0, u_init, cost, ...) as _mppi_eager: itself, or a GraphedMPPI bound to `engine` (reused from
+    `previous` when it already is one for this engine)."""
+    if not hasattr(engine, "mppi_sample"):
+        raise NotImplementedError(f"{type(engine).__name__} has no MPPI kernels (RolloutEngine has)")
+    return _graphed_or(_mppi_eager, GraphedMPPI, engine, use_graph, previous)
