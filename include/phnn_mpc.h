@@ -297,7 +297,9 @@ int phnn_model_wgrad(phnn_handle* h, const float* x_dev, const float* u_dev, con
  * src/mpc_controller_canonical.py:186,206.  `step` is the 1-based step count after the increment.
  * Optionally fuses the best-iterate tracking of src/mpc_controller_canonical.py:208-214: when
  * best_cost_dev != NULL, rollouts whose cost_dev[b] < best_cost_dev[b] copy clamp(u_b) (the pre-step
- * iterate that produced cost_dev) into best_u_dev and update best_cost_dev.  count = B*H*m, per = H*m. */
+ * iterate that produced cost_dev) into best_u_dev and update best_cost_dev.  count = B*H*m, per = H*m.
+ * Known deviation: lr, beta1, beta2 and eps arrive as C floats and are widened back, so the defaults are 0.9f and 0.999f,
+ * not torch's doubles 0.9 and 0.999 (1 - beta2 is 1.3e-5 relative off). */
 int phnn_adam_step(phnn_handle* h, float* u_dev, const float* grad_dev, float* exp_avg_dev,
                    float* exp_avg_sq_dev, int64_t count, float lr, float beta1, float beta2, float eps,
                    int32_t step, const float* cost_dev, float* best_cost_dev, float* best_u_dev, int64_t per,
@@ -445,7 +447,9 @@ int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, 
                     double* log_states_dev, float* log_controls_dev, void* stream);
 
 /* Warm start of the next solve, src/mpc_controller_canonical.py:252-255: dst[b,t] = src[b,t+1] for t < H-1,
- * dst[b,H-1] = 0 (u (B,H,m), shift by one step).  Also advances *step_dev by one when step_dev != NULL. */
+ * dst[b,H-1] = 0 (u (B,H,m), shift by one step).  Also advances *step_dev by one when step_dev != NULL; B == 0 with a
+ * step_dev only advances the counter (src_dev / dst_dev may be NULL).  Not an in-place operation: src_dev and dst_dev
+ * must not overlap, in whole or in part -- PHNN_ERR_INVALID_ARG, nothing is launched and the counter stays. */
 int phnn_shift_controls(phnn_handle* h, const float* src_dev, float* dst_dev, int64_t B, int32_t H, int32_t m,
                         int32_t* step_dev, void* stream);
 

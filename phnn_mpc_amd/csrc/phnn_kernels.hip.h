@@ -3548,8 +3548,9 @@ __global__ void k_adam(AdamParams p) {
   float u = p.u[idx];
   if (p.best_cost) {
     long long b = idx / p.per;
-    // strict '<' against the value before this step's update (src/mpc_controller_canonical.py:212)
-    if (p.cost[b] < p.best_cost[b]) p.best_u[idx] = p.has_u_bounds ? fminf(fmaxf(u, p.u_min), p.u_max) : u;
+    // strict '<' against the value before this step's update (src/mpc_controller_canonical.py:212); a NaN control
+    // stays NaN as in torch.clamp (fminf / fmaxf alone would turn it into u_min)
+    if (p.cost[b] < p.best_cost[b]) p.best_u[idx] = p.has_u_bounds && u == u ? fminf(fmaxf(u, p.u_min), p.u_max) : u;
   }
   float g = p.g[idx], m = p.m[idx], v = p.v[idx];
   m = __builtin_fmaf(p.w1, g - m, m);

@@ -1374,8 +1374,11 @@ int phnn_shift_controls(phnn_handle* h, const float* src_dev, float* dst_dev, in
                         int32_t* step_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
   if (B < 0 || H < 1 || m < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch, H < 1 or m < 1");
-  if (B > 0 && (!src_dev || !dst_dev || src_dev == dst_dev))
-    return fail(h, PHNN_ERR_INVALID_ARG, "NULL or aliased control tensors");
+  if (B > 0 && (!src_dev || !dst_dev)) return fail(h, PHNN_ERR_INVALID_ARG, "NULL control tensors");
+  // k_shift_controls reads src[idx + m] while another thread writes dst[idx]: the two ranges must not share a byte
+  const uintptr_t s0 = (uintptr_t)src_dev, d0 = (uintptr_t)dst_dev, bytes = sizeof(float) * (uintptr_t)B * H * m;
+  if (B > 0 && s0 < d0 + bytes && d0 < s0 + bytes)
+    return fail(h, PHNN_ERR_INVALID_ARG, "overlapping control tensors (the shift is not in place)");
   if (B == 0 && !step_dev) return PHNN_OK;  // B == 0 with a counter: only advance the step
   PHNN_ON_DEVICE(h);
   const int threads = 256;

@@ -211,7 +211,9 @@ def test_graphed_solve_is_bit_identical(torch, ctl):
 
 
 def test_adam_kernel_matches_torch_adam_order(torch):
-    """K3 against the float32 Adam restatement of the oracle AND against torch.optim.Adam itself on the CPU."""
+    """K3 against torch.optim.Adam itself on the CPU: one shape, five steps, default hyper-parameters, no tracking, to 2e-6
+    (torch's vectorised float32 Adam is not bit-identical to the scalar order, tests/test_adam_model.py).  The bit-for-bit
+    pin against the oracle's float32 restatement is tests/test_gpu_adam_kernel.py."""
     from phnn_mpc_amd.engine import RolloutEngine
     eng = RolloutEngine(ol.load_weights("phnn_cartpole"))
     rng = np.random.default_rng(2)

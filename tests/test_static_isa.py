@@ -4,7 +4,8 @@
 libphnn_mpc.so and asserts that none of those opcodes is present -- so a toolchain bump, a dropped flag or a new
 translation unit cannot re-introduce them silently.  It also pins the matrix instructions the design rests on, and what
 the bit-exact model of k_lbfgs (tests/lbfgs_kernel_model.py) rests on: no contracted multiply-add in any k_lbfgs<E4>
-instantiation, the only FMAs being those inside its three correctly rounded float32 divisions.
+instantiation, the only FMAs being those inside its three correctly rounded float32 divisions.  The same for k_adam and
+its bit-exact model (tests/adam_model.py): two divisions, a correctly rounded square root, one fused lerp, nothing else fused.
 """
 import os
 import re
@@ -87,6 +88,20 @@ def _functions(txt):
     return funcs
 
 
+def _function_lines(txt):
+    """{symbol: [(opcode, operands), ...] in address order}; opcodes without their encoding suffix."""
+    funcs, cur = {}, None
+    for line in txt.splitlines():
+        m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
+        if m:
+            cur = funcs.setdefault(m.group(1), [])
+            continue
+        m = re.match(r"^\s+([sv]_[a-z0-9_]+)\s*(.*?)\s*(//.*)?$", line)
+        if m and cur is not None:
+            cur.append((re.sub(r"_(e32|e64|dpp|sdwa)$", "", m.group(1)), m.group(2)))
+    return funcs
+
+
 def test_no_packed_f32_valu_in_device_code(opcodes):
     packed = {op: n for op, n in opcodes.items() if re.match(r"v_pk_(fma|mul|add)_f32|v_pk_mov_b32", op)}
     assert not packed, f"packed-f32 VALU instructions in the shipped device code (Makefile: NOPK flag lost?): {packed}"
@@ -125,3 +140,50 @@ def test_k_lbfgs_has_no_contracted_arithmetic(disassembly):
                 fmas += op != "v_rcp_f32"
         assert windows == 3, f"k_lbfgs<{e4}>: {windows} division windows, expected 3 (1/ys, ys/(y.y), 1/sum|g|)"
         assert fmas > 0, f"k_lbfgs<{e4}>: no FMA inside its divisions (is the division still correctly rounded?)"
+
+
+def test_k_adam_arithmetic_is_the_models(disassembly):
+    """k_adam, operation by operation, is what tests/adam_model.py models -- checked on the shipped code, without a GPU:
+
+      * exactly two v_div_scale_f32 ... v_div_fixup_f32 windows: sqrt(v) / bc2s and (step_neg * m) / denom, both
+        correctly rounded (fast math would turn them into v_rcp_f32 and a multiplication);
+      * outside them exactly ONE fused multiply-add whose product is not negated: the lerp m + w1 * (g - m)
+        (__builtin_fmaf).  A second one means a contracted v * b2 + (w2 * g) * g (-ffp-contract=off dropped), none means
+        the lerp lost its FMA;
+      * outside them exactly TWO v_fma_f32 with a negated first factor, both after the v_sqrt_f32: the residuals
+        x - s * s' with which the compiler's correctly rounded sqrtf picks among the neighbours of the hardware estimate
+        (read in the disassembly: v_sqrt_f32, two v_fma_f32 -vA, vB, vX, compares, selects, v_cmp_class_f32).  They are
+        why the issue's plain "FMAs outside the divisions = the lerp" count does not fit: with fast math they vanish;
+      * no v_mad_f32 / v_mac_f32.  v_fmamk_f32 / v_fmaak_f32 appear, but only with the literals 2^32 and -2^32
+        (0x4f800000, 0xcf800000): the 64-bit integer division idx / per of the best-iterate row index seeds its
+        reciprocal with them (v_cvt_f32_u32 in, v_cvt_u32_f32 out).  No value of the Adam arithmetic passes through."""
+    found = [ops for txt in disassembly for name, ops in _function_lines(txt).items() if name == "_Z6k_adam10AdamParams"]
+    assert len(found) == 1, f"k_adam found {len(found)} times in the device code"
+    ops = found[0]
+    names = [op for op, _ in ops]
+    assert not {"v_mad_f32", "v_mac_f32"} & set(names)
+    for op, args in ops:
+        if op in ("v_fmamk_f32", "v_fmaak_f32"):
+            assert re.search(r"\b0x[4c]f800000\b", args), f"k_adam: {op} {args} is not the integer division's 2^32 scaling"
+    windows, inside, lerp, residuals, fma_inside, seen_sqrt = 0, False, [], [], 0, False
+    for op, args in ops:
+        if op == "v_div_scale_f32":
+            inside = True
+        elif op == "v_div_fixup_f32":
+            assert inside, "k_adam: v_div_fixup_f32 without v_div_scale_f32"
+            windows, inside = windows + 1, False
+        elif op == "v_sqrt_f32":
+            assert not inside
+            seen_sqrt = True
+        elif op in ("v_fma_f32", "v_fmac_f32"):
+            if inside:
+                fma_inside += 1
+            elif op == "v_fma_f32" and re.match(r"v\d+, -", args):
+                assert seen_sqrt, f"k_adam: negated-product FMA before the square root: {args}"
+                residuals.append(args)
+            else:
+                lerp.append(f"{op} {args}")
+    assert windows == 2, f"k_adam: {windows} division windows, expected 2 (sqrt(v) / bc2s, (step_neg * m) / denom)"
+    assert fma_inside > 0 and names.count("v_sqrt_f32") == 1
+    assert len(lerp) == 1, f"k_adam: fused multiply-adds outside the divisions and the square root: {lerp} (expected the lerp alone)"
+    assert len(residuals) == 2, f"k_adam: square-root residuals {residuals}"
