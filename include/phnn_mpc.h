@@ -68,7 +68,12 @@ typedef enum { PHNN_ACT_TANH = 0, PHNN_ACT_OTHER = 1, PHNN_ACT_SILU = 2, PHNN_AC
 
 /* How the hidden x hidden products are evaluated.  DEFAULT: f16x2 for 128-wide models, f32 for
  * narrower ones (f16x2 on the 64-wide trained pendulum model is known to exceed the stated tolerance in long
- * rollouts: phnn_create_ex refuses it there unless force_matmul is set). */
+ * rollouts: phnn_create_ex refuses it there unless force_matmul is set).
+ * Input range: the f16x2 rollout kernels and phnn_model_forward split the raw state into float16 hi + lo in the
+ * input layers, so they hold the stated tolerances for |x_i| < 65520 (the float16 range) and return NaN for a rollout
+ * with a larger component -- never a finite wrong value; phnn_model_vjp and the f32 and bf16x3 kernels have no such
+ * limit.  Cotangents and cost weights may have any float32 magnitude in every mode: they are normalised per rollout
+ * by exact powers of two. */
 typedef enum { PHNN_MATMUL_DEFAULT = 0, PHNN_MATMUL_F32 = 1, PHNN_MATMUL_BF16X3 = 2, PHNN_MATMUL_F16X2 = 3 } phnn_matmul_mode;
 
 /* MLP shape: Linear(in,h[0]) tanh ... Linear(h[depth-1],out); src/NN.py:6-40 with activation nn.Tanh,

@@ -934,7 +934,8 @@ template <int ACT>
 DEV float act_d2(float z) {  // phi''(z)
   if (ACT == ACT_RELU) return 0.0f;
   if (ACT == ACT_ELU) return z > 0.f ? 0.0f : __builtin_amdgcn_exp2f(z * 1.4426950408889634f);
-  if (ACT == ACT_GELU) return gelu_pdf(z) * __builtin_fmaf(-z, z, 2.0f);
+  // the polynomial factor is kept finite: past |z| = 1.8e19 z^2 overflows and pdf(z) * -inf would be 0 * inf
+  if (ACT == ACT_GELU) return gelu_pdf(z) * fmaxf(__builtin_fmaf(-z, z, 2.0f), -3.0e38f);
   const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f));
   return s * (1.0f - s) * __builtin_fmaf(z, 1.0f - 2.0f * s, 2.0f);
 }
@@ -1132,7 +1133,7 @@ DEV void hnet_layer1(const float* L, Lane ln, f32x4 z, Act<HID / 16>& a1) {
 
 // Hv = (d^2 H / dz^2) v : forward-over-reverse through the kept tape (a1, a2, q1).  Consumes the tape
 // (q1 is overwritten) to keep the live register set at five activation vectors.
-template <int HID, int MM = MM_F32, bool WG = false, int ACT = ACT_TANH>
+template <int HID, int MM = MM_F32, bool WG = false, int ACT = ACT_TANH, int SITE = kInHHvp>
 DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec = nullptr) {
   if constexpr (ACT != ACT_TANH) {
     static_assert(!WG, "weight-gradient kernels exist for Tanh models only");
@@ -1151,7 +1152,7 @@ DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec 
   }
   Act<T> ad1, w;
   zero_act<T>(ad1);
-  in_layer_mm<T, MM, kInHHvp>(ad1, L, Y::oW1f, Y::oW1h, ln, v);
+  in_layer_mm<T, MM, SITE>(ad1, L, Y::oW1f, Y::oW1h, ln, v);
 #pragma unroll
   for (int t = 0; t < T; ++t) ad1.v[t] = dtanh(tp.a1.v[t]) * ad1.v[t];
   // gdot1 = qdot1*(1-a1^2) + q1*(-2 a1 adot1) and gdot2 = w3 (-2 a2 (1-a2^2) zdot2): both carry a factor -2, so the
@@ -1475,7 +1476,7 @@ struct PhnnModel {
 
   // xbar = (df/dx)^T lam, ubar = (df/du)^T lam at (x,u); recomputes the forward tape it needs.
   // WG: also writes the weight-gradient record of this evaluation to `rec` (Hbar = cotangent on H, adds Hbar dH to xbar).
-  template <bool ST = false, bool WG = false>
+  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, f32x4 lam, f32x4& xbar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     keep_lds_reads_local();
@@ -1492,7 +1493,7 @@ struct PhnnModel {
       // (a1 is recomputed further down, right before the Hessian-vector product: it is not live through the R_net part,
       // which is where this kernel's register peak sits.  K2 1.179 -> 1.154 ms.  Issuing a2's loads later too: no change.)
     } else {
-      dH = hnet_grad<HID, false, MM, kInHRecomp, ACT>(L + oH, ln, x, tp, Hdummy);
+      dH = hnet_grad<HID, false, MM, INH & kInHRecomp, ACT>(L + oH, ln, x, tp, Hdummy);
     }
     if (WG && !ST) {  // with the tapes of K1 the reduction reads a2, q1 from there (their record slots stay unwritten)
       store_rec<T>(rec, ln, tp.a2);
@@ -1503,9 +1504,9 @@ struct PhnnModel {
     {
       Act<T> hR;
       if (ST) {  // R_net's outputs came with the tape: only its hidden layer is re-evaluated
-        h1_hidden<HID, MM, kInHNet1Adj, ACT>(L + oR, ln, x, hR);
+        h1_hidden<HID, MM, INH & kInHNet1Adj, ACT>(L + oR, ln, x, hR);
       } else {
-        h1_fwd<HID, MM, kInHNet1Adj, ACT>(L + oR, scr, ln, x, hR, rf);
+        h1_fwd<HID, MM, INH & kInHNet1Adj, ACT>(L + oR, scr, ln, x, hR, rf);
       }
       sym_from_rf<N>(rf, S);
 #pragma unroll
@@ -1538,7 +1539,7 @@ struct PhnnModel {
     } else {
       Act<T> hG;
       float gf[16], gbar[16];
-      h1_fwd<HID, MM, kInHNet1Adj, ACT>(L + oGn, scr, ln, x, hG, gf);
+      h1_fwd<HID, MM, INH & kInHNet1Adj, ACT>(L + oGn, scr, ln, x, hG, gf);
 #pragma unroll
       for (int k = 0; k < 16; ++k) gbar[k] = 0.f;
 #pragma unroll
@@ -1571,7 +1572,7 @@ struct PhnnModel {
       sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
     }
     if (ST) hnet_layer1<HID, MM, ACT>(L + oH, ln, x, tp.a1);
-    xbar = xb + hnet_hvp<HID, MM, WG, ACT>(L + oH, ln, tp, v, rec);
+    xbar = xb + hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp>(L + oH, ln, tp, v, rec);
     if (WG) xbar = xbar + Hbar * dH;
   }
 };
@@ -1746,7 +1747,7 @@ struct CanonModel {
   using Rec = WRec<T, NBIG>;
 
   // WG: also writes the weight-gradient record (a2, q1, ad2, qd; small: z, v, lam, dH, the two R_diag cotangents)
-  template <bool ST = false, bool WG = false>
+  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, f32x4 lam, f32x4& ybar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     keep_lds_reads_local();
@@ -1768,7 +1769,7 @@ struct CanonModel {
         load_act<T>(stash + T * 256, ln, tp.q1);
         hnet_layer1<HID, MM, ACT>(L + oH, ln, z, tp.a1);
       } else {
-        dH = hnet_grad<HID, false, MM, kInHRecomp, ACT>(L + oH, ln, z, tp, Hdummy);
+        dH = hnet_grad<HID, false, MM, INH & kInHRecomp, ACT>(L + oH, ln, z, tp, Hdummy);
       }
       const float Rd2 = L[oC + 6], Rd3 = L[oC + 7];
       const float dp0 = (-dH[0] - Rd2 * dH[2]) + Base_Gu(L, 2, u);
@@ -1793,7 +1794,7 @@ struct CanonModel {
           sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
         }
       }
-      f32x4 zb = hnet_hvp<HID, MM, WG, ACT>(L + oH, ln, tp, v, rec);
+      f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp>(L + oH, ln, tp, v, rec);
       if (WG) zb = zb + Hbar * dH;
       zb[2] += pb0;
       zb[3] += pb1;
@@ -1838,7 +1839,7 @@ struct CanonModel {
       load_act<T>(stash + T * 256, ln, tp.q1);
       hnet_layer1<HID, MM, ACT>(L + oH, ln, z, tp.a1);
     } else {
-      dH = hnet_grad<HID, false, MM, kInHRecomp, ACT>(L + oH, ln, z, tp, Hdummy);
+      dH = hnet_grad<HID, false, MM, INH & kInHRecomp, ACT>(L + oH, ln, z, tp, Hdummy);
     }
     float Rd2 = L[oC + 6], Rd3 = L[oC + 7];
     float dp0 = (-dH[0] - Rd2 * dH[2]) + Base_Gu(L, 2, u);
@@ -1870,7 +1871,7 @@ struct CanonModel {
         sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
       }
     }
-    f32x4 zb = hnet_hvp<HID, MM, WG, ACT>(L + oH, ln, tp, v, rec);
+    f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp>(L + oH, ln, tp, v, rec);
     if (WG) zb = zb + Hbar * dH;
     zb[2] += pb0;
     zb[3] += pb1;
@@ -2149,7 +2150,7 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     return Base::combine(L, rf, dH, G, u);
   }
 
-  template <bool ST = false, bool WG = false>
+  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, f32x4 lam, f32x4& xbar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     static_assert(!WG, "weight-gradient records come from the whole-tile kernels");
@@ -2272,7 +2273,7 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
                  mi01 * dp0 + mi11 * dp1};
   }
 
-  template <bool ST = false, bool WG = false>
+  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, f32x4 lam, f32x4& ybar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     static_assert(!WG, "weight-gradient records come from the whole-tile kernels");
@@ -2442,7 +2443,7 @@ struct OdeModel {
     return dx;
   }
 
-  template <bool ST = false, bool WG = false>
+  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 x, f32x4 uv, f32x4 lam, f32x4& xbar, f32x4& ubar4,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     static_assert(!WG, "ODEFunc has no weight-gradient kernels");
@@ -2998,7 +2999,9 @@ __global__ __launch_bounds__(64 * kMaxWaves) void k_model_vjp(PointParams p) {
       M::template vjp<false, true>(lds, scr, ln, x, u, lam * live, xb, ub, nullptr,
                                    p.wrec + tile * (long long)M::Rec::SIZE, p.Hbar ? p.Hbar[b] * live : 0.0f);
     } else {
-      M::vjp(lds, scr, ln, x, u, lam, xb, ub);
+      // single evaluations take the f32 input layers (INH = 0): the f16 form carries 22 bits of the state and of W1,
+      // which at |x| ~ 1e3 costs the VJP more than its 2e-5 tolerance; the march kernels keep the f16 form
+      M::template vjp<false, false, 0>(lds, scr, ln, x, u, lam, xb, ub);
     }
     if (valid && ln.q == 0) {
       store_state<N>(p.dx + b * N, xb);
