@@ -429,6 +429,61 @@ int phnn_solve_mppi(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B
                     const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt, void* workspace,
                     size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream);
 
+/* ---- batched cross-entropy (CEM) solve: gradient-free, K1 only, adaptive per-element noise ------------------------
+ * Per problem b a mean u_b (H,m), started at clamp(u_init_b), and a standard deviation sig_b (H,m), element (t,c) started
+ * at sigma_init[c] (fresh at every solve).  `iters` times: sample  v_{b,k} = clamp(u_b + sig_b o z_{b,k}), k = 0 ..
+ * samples-1, z standard normal and z_{b,0} = 0 (the mean itself is always evaluated and is an ordinary candidate); cost
+ * S_{b,k} of all B * samples rollouts in ONE K1 launch (no K2, no stash); elites: of the samples with finite cost the
+ * `elites` lowest in the order (cost as floats, -0 == +0, then k ascending) -- all of them when fewer are finite; refit
+ *   em = mean of the elite rows,  ev = mean of their squared deviations from em (two passes, each k ascending),
+ *   u_b = clamp(alpha u_b + (1 - alpha) em),  sig_b = max(sigma_min, sqrt(alpha sig_b^2 + (1 - alpha) ev)),
+ * float32 with separate multiplications and additions and correctly rounded division and square root.  Where no cost is
+ * finite u_b and sig_b are kept bit for bit.  The only cost-related parameter is the count `elites`: the solve is
+ * invariant to any monotone rescaling of the cost.  DESIGN.md 13.
+ * Noise: the MPPI counter layout above (key = seed, counter = (gid, iteration, epoch, sample, float4)), so problem b's
+ * samples depend on (seed, epoch, iteration, gid = problem_offset + b) only; same ranges; epoch as in phnn_mppi_options. */
+typedef struct {
+  int32_t iters;                  /* >= 0 */
+  int32_t samples;                /* K >= 2, sample 0 (the mean) included */
+  int32_t elites;                 /* E, 1 <= E <= samples */
+  float alpha;                    /* smoothing in [0, 1): 0 = plain refit */
+  float sigma_init[PHNN_MAX_M];   /* initial standard deviation per control component (leading m used), >= 0 and finite */
+  float sigma_min;                /* floor of the refitted standard deviation, >= 0 and finite */
+  uint64_t seed;
+  int64_t problem_offset;         /* global id of problem 0 of this call */
+  const int32_t* epoch_dev;       /* device, or NULL */
+  int32_t epoch_host;             /* used when epoch_dev == NULL */
+  int32_t reserved[4];            /* zero */
+} phnn_cem_options;
+/* Bytes of the CEM workspace: the MPPI layout (sample tensor, replicated x0, K1's cost vector) plus the sigma state
+ * (B, H, m), each region 256-byte aligned.  0 for invalid arguments. */
+size_t phnn_cem_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t samples);
+/* The two kernels of one iteration.
+ * phnn_cem_sample: mean u_dev (B,H,m), sigma_dev (B,H,m), x0_dev (B,n) -> samples_dev (B*samples,H,m), x0_rep_dev
+ *   (B*samples,n) (may be NULL); clamps to the cost's bounds when has_u_bounds; `iteration` is the counter field.
+ * phnn_cem_update: samples_dev and their K1 costs sample_cost_dev (B*samples) -> u_dev and sigma_dev refitted in place;
+ *   optional costs_row_dev (B) = S_{b,0}; optional best_cost_dev (B) / best_u_dev (B,H,m), updated where the lowest finite
+ *   sample cost is < best_cost (strict; lowest k on ties) with that cost and that sample's row. */
+int phnn_cem_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* sigma_dev, int64_t B, int32_t H,
+                    const phnn_cost* cost, const phnn_cem_options* opt, int32_t iteration, float* samples_dev,
+                    float* x0_rep_dev, void* stream);
+int phnn_cem_update(phnn_handle* h, float* u_dev, float* sigma_dev, const float* samples_dev, const float* sample_cost_dev,
+                    int64_t B, int32_t H, const phnn_cost* cost, const phnn_cem_options* opt, float* costs_row_dev,
+                    float* best_cost_dev, float* best_u_dev, void* stream);
+/* The whole solve.  u_dev (B,H,m): in = initial mean, out = the last mean (in bounds when has_u_bounds).  best_cost_dev
+ * (B) / best_u_dev (B,H,m): the best sample over all iterations, reset to +inf / 0 first -- also when iters == 0.
+ * costs_dev (iters,B) or NULL: the mean's cost S_{b,0} at every iteration.  sigma_out_dev (B,H,m) or NULL: the last
+ * standard deviation (sigma_init when iters == 0).  workspace: workspace_size >= phnn_cem_workspace_bytes.  ref: as in
+ * phnn_solve_mppi -- its batch_stride indexes the B*samples ROLLOUTS.
+ * Enqueues the clamp and the resets, then iters x (k_cem_sample, K1, k_cem_update); stream-ordered, capturable.  B == 0
+ * or iters == 0 returns PHNN_OK after the resets.  PHNN_ERR_INVALID_ARG for samples < 2, elites outside 1 .. samples,
+ * alpha outside [0, 1), a negative or non-finite sigma_init / sigma_min, iters < 0, counter fields outside their ranges,
+ * NULL required buffers or a too small workspace; PHNN_ERR_UNSUPPORTED for H*m > 256. */
+int phnn_solve_cem(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                   const phnn_reference* ref, int32_t integrator, float dt, const phnn_cem_options* opt, void* workspace,
+                   size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, float* sigma_out_dev,
+                   void* stream);
+
 /* ---- the plant on the other side of the path ------------------------------------------
  * Ground-truth cart-pole of src/cartpole_simulator.py:63-112: float64, explicit Euler, the standard cart-pole
  * equations in the reference's operation order; termination |x| > x_limit or |theta| > theta_limit.  Defaults of

@@ -33,6 +33,7 @@ EXPORTED = [
     "phnn_adam_step", "phnn_solve", "phnn_plant_step", "phnn_shift_controls", "phnn_kernel_info", "phnn_variant_name",
     "phnn_version", "phnn_rollout_fwd_ref", "phnn_rollout_grad_ref", "phnn_solve_ref", "phnn_lbfgs_workspace_bytes",
     "phnn_solve_lbfgs", "phnn_mppi_workspace_bytes", "phnn_mppi_sample", "phnn_mppi_update", "phnn_solve_mppi",
+    "phnn_cem_workspace_bytes", "phnn_cem_sample", "phnn_cem_update", "phnn_solve_cem",
 ]
 
 
@@ -77,6 +78,16 @@ class MppiOptions(C.Structure):
     _fields_ = [("iters", C.c_int32), ("samples", C.c_int32), ("lambda", C.c_float), ("sigma", C.c_float * PHNN_MAX_M),
                 ("seed", C.c_uint64), ("problem_offset", C.c_int64), ("epoch_dev", C.c_void_p), ("epoch_host", C.c_int32),
                 ("reserved", C.c_int32 * 4)]  # 'lambda' is a Python keyword: setattr(opt, "lambda", v)
+
+
+class CemOptions(C.Structure):
+    """phnn_cem_options: K = samples perturbations of the mean per iteration (sample 0 is the mean), refit of mean and
+    per-element standard deviation to the `elites` lowest-cost samples with smoothing alpha, initial sigma per control
+    component and its floor sigma_min; Philox counter fields seed / problem_offset / epoch as in MppiOptions."""
+    _fields_ = [("iters", C.c_int32), ("samples", C.c_int32), ("elites", C.c_int32), ("alpha", C.c_float),
+                ("sigma_init", C.c_float * PHNN_MAX_M), ("sigma_min", C.c_float), ("seed", C.c_uint64),
+                ("problem_offset", C.c_int64), ("epoch_dev", C.c_void_p), ("epoch_host", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 class Plant(C.Structure):
@@ -244,6 +255,16 @@ def load_library():
     lib.phnn_solve_mppi.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
                                     C.POINTER(MppiOptions), vp, C.c_size_t, f32p, f32p, f32p, vp]
     lib.phnn_solve_mppi.restype = C.c_int
+    lib.phnn_cem_workspace_bytes.argtypes = [vp, i64, i32, i32]
+    lib.phnn_cem_workspace_bytes.restype = C.c_size_t
+    lib.phnn_cem_sample.argtypes = [vp, f32p, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(CemOptions), i32, f32p, f32p, vp]
+    lib.phnn_cem_sample.restype = C.c_int
+    lib.phnn_cem_update.argtypes = [vp, f32p, f32p, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(CemOptions), f32p, f32p,
+                                    f32p, vp]
+    lib.phnn_cem_update.restype = C.c_int
+    lib.phnn_solve_cem.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
+                                   C.POINTER(CemOptions), vp, C.c_size_t, f32p, f32p, f32p, f32p, vp]
+    lib.phnn_solve_cem.restype = C.c_int
     lib.phnn_plant_step.argtypes = [vp, C.POINTER(Plant), vp, f32p, i64, i64, i32, C.c_float, C.c_float, f32p, vp, vp, i32,
                                     vp, f32p, vp]
     lib.phnn_plant_step.restype = C.c_int

@@ -57,9 +57,9 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None):
     done_step = np.full(B, -1, dtype=np.int64)
     canonical = hasattr(controller, "control_batch")
     u_prev = None
-    mppi = getattr(controller, "optimizer", getattr(controller, "optimizer_type", None)) == "MPPI"
+    sampling = getattr(controller, "optimizer", getattr(controller, "optimizer_type", None)) in ("MPPI", "CrossEntropy")
     for step in range(num_steps):
-        rkw = {"epoch": step} if mppi else {}  # the noise counter of an MPPI solve: the control step
+        rkw = {"epoch": step} if sampling else {}  # the noise counter of an MPPI / CrossEntropy solve: the control step
         if x_ref is not None:
             rkw.update(x_ref=x_ref, ref_offset=step)
         if canonical:
@@ -85,7 +85,7 @@ class DeviceClosedLoop:
     run_mpc_batch (same kernels, same order); the plant differs from the numpy one only by the device's
     double-precision sin/cos.  An MPPI controller (optimizer_type / optimizer 'MPPI'): engine.solve_mppi -- the clamp
     and resets, iters x (k_mppi_sample, K1, k_mppi_update) -- with step_dev as the noise epoch, so every replay draws the
-    noise run_mpc_batch draws at that step.
+    noise run_mpc_batch draws at that step.  A 'CrossEntropy' controller: engine.solve_cem in the same way.
 
     x_ref: reference trajectories broadcastable to (B, rows, 4) (engine.reference_view); every solve tracks them from
     row step_dev, the device counter the plant step logs with and the shift advances, so each replay of the captured
@@ -120,14 +120,17 @@ class DeviceClosedLoop:
             from .engine import reference_view
             self.x_ref = reference_view(x_ref, B, 4, dev)[0]
         self.mppi = (controller.optimizer if self.canonical else controller.optimizer_type) == "MPPI"
+        self.cem = (controller.optimizer if self.canonical else controller.optimizer_type) == "CrossEntropy"
         if self.mppi and not hasattr(eng, "solve_mppi"):
             raise NotImplementedError(f"{type(eng).__name__} has no batched MPPI solve (RolloutEngine has)")
-        if self.mppi and x_ref is not None:  # one row set per rollout, expanded once, here (samples x the bytes)
+        if self.cem and not hasattr(eng, "solve_cem"):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched CEM solve (RolloutEngine has)")
+        if (self.mppi or self.cem) and x_ref is not None:  # one row set per rollout, expanded once, here (samples x the bytes)
             self.x_ref = eng.mppi_reference(self.x_ref, B, controller.samples)
         self.iters = controller.optimizer_steps if self.canonical else controller.max_iterations
         self.lr = controller.learning_rate if self.canonical else controller.lr
         self.lbfgs = not self.canonical and controller.optimizer_type == "LBFGS"
-        if not self.canonical and controller.optimizer_type not in ("Adam", "LBFGS", "MPPI"):
+        if not self.canonical and controller.optimizer_type not in ("Adam", "LBFGS", "MPPI", "CrossEntropy"):
             raise ValueError(f"Unknown optimizer type: {controller.optimizer_type}")
         if self.lbfgs and not hasattr(eng, "solve_lbfgs"):
             raise NotImplementedError(f"{type(eng).__name__} has no batched L-BFGS solve (RolloutEngine has)")
@@ -141,6 +144,8 @@ class DeviceClosedLoop:
         H = self.u_init.shape[1] * self.u_init.shape[2]
         if self.mppi:
             out = self._solve_mppi()
+        elif self.cem:
+            out = self._solve_cem()
         elif self.lbfgs:  # the reference's L-BFGS solve
             out = eng.solve_lbfgs(self.x32, self.u_init, self.cost, integrator=c.integrator, dt=c.dt, record_costs=False,
                                   workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, **c.lbfgs_options())
@@ -162,6 +167,13 @@ class DeviceClosedLoop:
         return eng.solve_mppi(self.x32, self.u_init, self.cost, c.integrator, c.dt, epoch=self.step_dev, record_costs=False,
                               workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, expanded_ref=True,
                               **c.mppi_options())
+
+    def _solve_cem(self):
+        """engine.solve_cem with the step counter as the noise epoch; the reference as in _solve_mppi."""
+        eng, c = self.eng, self.ctl
+        return eng.solve_cem(self.x32, self.u_init, self.cost, c.integrator, c.dt, epoch=self.step_dev, record_costs=False,
+                             workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, expanded_ref=True,
+                             **c.cem_options())
 
     def run(self):
         torch = self.torch

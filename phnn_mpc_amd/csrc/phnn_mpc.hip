@@ -17,6 +17,7 @@
 #define PHNN_PREFETCH_BF
 #include "phnn_lbfgs.h"
 #include "phnn_mppi.h"
+#include "phnn_cem.h"
 #include "phnn_pack.h"
 
 namespace {
@@ -535,7 +536,7 @@ int check_cost(phnn_handle* h, const phnn_cost* c) {
 
 extern "C" {
 
-int phnn_version(void) { return 250; }
+int phnn_version(void) { return 260; }
 
 const char* phnn_variant_name(const phnn_handle* h) { return h ? h->ks.name : ""; }
 
@@ -1331,6 +1332,151 @@ int phnn_solve_mppi(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B
     if (int rc = phnn_mppi_update(h, u_dev, v, s, B, H, cost, opt, costs_dev ? costs_dev + (size_t)it * B : nullptr, best_cost_dev,
                                   best_u_dev, stream))
       return rc;
+  }
+  return PHNN_OK;
+}
+
+// ---- batched cross-entropy (CEM) solve: kernels in phnn_cem.hip ---------------------------------------------------
+static int check_cem(phnn_handle* h, const phnn_cem_options* opt, int64_t B, int32_t H, int32_t iteration) {
+  if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options is NULL");
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (opt->samples < 2 || opt->samples > kMppiMaxSamples)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: samples < 2 or > 2^26");
+  if (opt->elites < 1 || opt->elites > opt->samples)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: elites outside 1 .. samples");
+  if (!(opt->alpha >= 0.f) || !(opt->alpha < 1.f))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: alpha must be in [0, 1)");
+  for (int i = 0; i < h->desc.m; ++i)
+    if (!(opt->sigma_init[i] >= 0.f) || !std::isfinite(opt->sigma_init[i]))
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: sigma_init must be >= 0 and finite");
+  if (!(opt->sigma_min >= 0.f) || !std::isfinite(opt->sigma_min))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: sigma_min must be >= 0 and finite");
+  if (iteration < 0 || iteration >= kMppiMaxIters || opt->iters < 0 || opt->iters > kMppiMaxIters)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: iteration count outside 0 .. 65536");
+  if (opt->problem_offset < 0 || opt->problem_offset > kMppiMaxProblem - B)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: problem ids outside 0 .. 2^48");
+  if ((int64_t)H * h->desc.m > kMppiMaxN) return fail(h, PHNN_ERR_UNSUPPORTED, "CEM: H * m > 256");
+  return PHNN_OK;
+}
+
+size_t phnn_cem_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t samples) {
+  if (!h || B < 0 || H < 1 || samples < 2 || samples > kMppiMaxSamples) return 0;
+  return cem_layout(B, H * h->desc.m, h->desc.n, samples).total;
+}
+
+int phnn_cem_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* sigma_dev, int64_t B, int32_t H,
+                    const phnn_cost* cost, const phnn_cem_options* opt, int32_t iteration, float* samples_dev,
+                    float* x0_rep_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_cem(h, opt, B, H, iteration)) return rc;
+  if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!u_dev || !sigma_dev || !samples_dev || (x0_rep_dev && !x0_dev))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_sample: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  CemSampleParams p;
+  memset(&p, 0, sizeof p);
+  p.u = u_dev;
+  p.sig = sigma_dev;
+  p.x0 = x0_dev;
+  p.v = samples_dev;
+  p.x0_rep = x0_rep_dev;
+  p.B = B;
+  p.K = opt->samples;
+  p.N = H * h->desc.m;
+  p.n = h->desc.n;
+  p.u_min = cost->u_min;
+  p.u_max = cost->u_max;
+  p.has_u_bounds = cost->has_u_bounds;
+  p.key0 = (unsigned)(opt->seed & 0xffffffffu);
+  p.key1 = (unsigned)(opt->seed >> 32);
+  p.problem_offset = opt->problem_offset;
+  p.epoch_dev = opt->epoch_dev;
+  p.epoch_host = opt->epoch_host;
+  p.iteration = iteration;
+  hipError_t e = cem_sample_launch(p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "k_cem_sample launch");
+  return PHNN_OK;
+}
+
+int phnn_cem_update(phnn_handle* h, float* u_dev, float* sigma_dev, const float* samples_dev, const float* sample_cost_dev,
+                    int64_t B, int32_t H, const phnn_cost* cost, const phnn_cem_options* opt, float* costs_row_dev,
+                    float* best_cost_dev, float* best_u_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_cem(h, opt, B, H, 0)) return rc;
+  if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!u_dev || !sigma_dev || !samples_dev || !sample_cost_dev)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_update: NULL tensor");
+  if ((best_cost_dev != nullptr) != (best_u_dev != nullptr))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_update: best_cost_dev and best_u_dev go together");
+  PHNN_ON_DEVICE(h);
+  CemUpdateParams p;
+  memset(&p, 0, sizeof p);
+  p.u = u_dev;
+  p.sig = sigma_dev;
+  p.v = samples_dev;
+  p.s = sample_cost_dev;
+  p.costs_out = costs_row_dev;
+  p.best_cost = best_cost_dev;
+  p.best_u = best_u_dev;
+  p.B = B;
+  p.K = opt->samples;
+  p.N = H * h->desc.m;
+  p.elites = opt->elites;
+  p.alpha = opt->alpha;
+  p.sigma_min = opt->sigma_min;
+  p.u_min = cost->u_min;
+  p.u_max = cost->u_max;
+  p.has_u_bounds = cost->has_u_bounds;
+  hipError_t e = cem_update_launch(p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "k_cem_update launch");
+  return PHNN_OK;
+}
+
+int phnn_solve_cem(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                   const phnn_reference* ref, int32_t integrator, float dt, const phnn_cem_options* opt, void* workspace,
+                   size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, float* sigma_out_dev,
+                   void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_cem(h, opt, B, H, 0)) return rc;
+  RollParams rp;
+  if (int rc = fill_roll(h, &rp, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
+  if (int rc = fill_ref(h, &rp, ref, B)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!best_cost_dev || !best_u_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_cem: best_cost_dev and best_u_dev are required");
+  const int N = H * h->desc.m;
+  const CemLayout lay = cem_layout(B, N, h->desc.n, opt->samples);
+  if (opt->iters > 0 && (!workspace || workspace_size < lay.total))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_cem: workspace is NULL or too small");
+  PHNN_ON_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  // the entry state, before any early return: mean in bounds, best = (+inf, 0), sigma = sigma_init
+  hipError_t e = hipMemsetD32Async((hipDeviceptr_t)best_cost_dev, 0x7F800000, (size_t)B, st);
+  if (e == hipSuccess) e = hipMemsetAsync(best_u_dev, 0, sizeof(float) * (size_t)B * N, st);
+  if (e == hipSuccess && cost->has_u_bounds) e = mppi_clamp_launch(u_dev, (long long)B * N, cost->u_min, cost->u_max, st);
+  if (e == hipSuccess && opt->iters == 0 && sigma_out_dev)
+    e = cem_sigma_init_launch(sigma_out_dev, (long long)B * N, h->desc.m, opt->sigma_init, st);
+  if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_cem: state reset");
+  if (opt->iters == 0) return PHNN_OK;
+  char* ws = (char*)workspace;
+  float* v = (float*)(ws + lay.v);
+  float* x0_rep = (float*)(ws + lay.x0_rep);
+  float* s = (float*)(ws + lay.s);
+  float* sig = (float*)(ws + lay.sig);
+  e = cem_sigma_init_launch(sig, (long long)B * N, h->desc.m, opt->sigma_init, st);
+  if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_cem: sigma reset");
+  const int64_t rollouts = B * (int64_t)opt->samples;
+  for (int it = 0; it < opt->iters; ++it) {
+    if (int rc = phnn_cem_sample(h, x0_dev, u_dev, sig, B, H, cost, opt, it, v, it == 0 ? x0_rep : nullptr, stream)) return rc;
+    if (int rc = rollout_fwd(h, x0_rep, v, rollouts, H, cost, integrator, dt, s, nullptr, nullptr, ref, stream)) return rc;
+    if (int rc = phnn_cem_update(h, u_dev, sig, v, s, B, H, cost, opt, costs_dev ? costs_dev + (size_t)it * B : nullptr,
+                                 best_cost_dev, best_u_dev, stream))
+      return rc;
+  }
+  if (sigma_out_dev) {
+    e = hipMemcpyAsync(sigma_out_dev, sig, sizeof(float) * (size_t)B * N, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_cem: sigma copy");
   }
   return PHNN_OK;
 }

@@ -618,6 +618,102 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return {"u_last": u, "costs": costs, "best_u": best_u, "best_cost": best_cost}
 
+    # ------------------------------------------------------------------ batched cross-entropy (CEM) solve (k_cem_sample, K1, k_cem_update)
+    def cem_workspace_bytes(self, B, H, samples):
+        return int(self.lib.phnn_cem_workspace_bytes(self.h, int(B), int(H), int(samples)))
+
+    def _cem_options(self, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch, problem_offset):
+        """-> (phnn_cem_options, what to keep alive).  sigma: the initial standard deviation, one value or one per control
+        component; the counter fields as in _mppi_options."""
+        mo, keep = self._mppi_options(iters, samples, 1.0, sigma, seed, epoch, problem_offset)
+        opt = _capi.CemOptions()
+        opt.iters, opt.samples, opt.elites = mo.iters, mo.samples, int(elites)
+        opt.alpha, opt.sigma_min = float(alpha), float(sigma_min)
+        for i in range(self.m):
+            opt.sigma_init[i] = mo.sigma[i]
+        opt.seed, opt.problem_offset, opt.epoch_dev, opt.epoch_host = mo.seed, mo.problem_offset, mo.epoch_dev, mo.epoch_host
+        return opt, keep
+
+    def _cem_buffers(self, ws, B, H, samples):
+        """The MPPI views (_mppi_buffers: sample tensor, replicated x0, K1 cost vector) and the sigma state (B, H, m) of a
+        CEM problem, as views of one phnn_cem_workspace_bytes buffer kept in the dict `ws` (phnn_solve_cem's layout)."""
+        key = (B, H, int(samples))
+        if ws.get("cem_key") != key:
+            ws["cem_key"] = key
+            nbytes = self.cem_workspace_bytes(B, H, samples)  # 0: arguments the library call itself will refuse
+            buf = ws["cem"] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            R, N = (B * int(samples) if nbytes else 0), H * self.m
+            a256 = lambda x: (x + 255) & ~255
+            o_x0 = a256(4 * R * N)
+            o_s = a256(o_x0 + 4 * R * self.n)
+            o_sig = a256(o_s + 4 * R)
+            nb = B if nbytes else 0
+            ws["cem_v"] = buf[: 4 * R * N].view(torch.float32).view(R, H, self.m)
+            ws["cem_x0"] = buf[o_x0: o_x0 + 4 * R * self.n].view(torch.float32).view(R, self.n)
+            ws["cem_s"] = buf[o_s: o_s + 4 * R].view(torch.float32)
+            ws["cem_sig"] = buf[o_sig: o_sig + 4 * nb * N].view(torch.float32).view(nb, H, self.m)
+        return ws
+
+    def cem_sample(self, x0, u, sig, cost, samples, seed, iteration, epoch=0, problem_offset=0, workspace=None):
+        """k_cem_sample.  x0 (B,n), mean u (B,H,m), standard deviation sig (B,H,m) -> (v (B*samples,H,m), x0 replicated
+        (B*samples,n)): sample b * samples + k is clamp(u_b + sig_b o z), z standard normal from the Philox counter (seed,
+        epoch, iteration, problem_offset + b, k) and zero for k = 0.  The outputs are views of `workspace`."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u, H = self._controls(u, B)
+        assert sig.is_contiguous() and sig.dtype == torch.float32 and sig.device == self.device and sig.numel() == u.numel()
+        ws = self._cem_buffers({} if workspace is None else workspace, B, H, samples)
+        opt, _keep = self._cem_options(0, samples, 1, 0.0, 0.0, 0.0, seed, epoch, problem_offset)
+        rc = self.lib.phnn_cem_sample(self.h, self._p(x0), self._p(u), self._p(sig), B, H, C.byref(cost), C.byref(opt),
+                                      int(iteration), self._p(ws["cem_v"]), self._p(ws["cem_x0"]), self._stream())
+        _check(self.lib, self.h, rc)
+        return ws["cem_v"], ws["cem_x0"]
+
+    def cem_update(self, u, sig, v, s, elites, alpha, sigma_min, cost, costs_row=None, best_cost=None, best_u=None):
+        """k_cem_update, in place on the mean u and the standard deviation sig (B,H,m): both refitted to the `elites`
+        samples of lowest finite cost (cost, then sample index) among v (B*K,H,m) with costs s (B*K):
+        u = clamp(alpha u + (1 - alpha) mean), sig = max(sigma_min, sqrt(alpha sig^2 + (1 - alpha) var)); the clamp is
+        the cost's.  costs_row (B) receives s_{b,0}; best_cost (B) / best_u (B,H,m) the lowest-cost sample seen so far."""
+        for t in (u, sig, v, s, costs_row, best_cost, best_u):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device)
+        B, H = u.shape[0], u.shape[1]
+        samples = s.numel() // max(B, 1)
+        assert v.numel() == B * samples * H * self.m and s.numel() == B * samples and sig.numel() == u.numel()
+        opt, _keep = self._cem_options(0, samples, elites, alpha, 0.0, sigma_min, 0, 0, 0)
+        rc = self.lib.phnn_cem_update(self.h, self._p(u), self._p(sig), self._p(v), self._p(s), B, H, C.byref(cost),
+                                      C.byref(opt), self._p(costs_row), self._p(best_cost), self._p(best_u), self._stream())
+        _check(self.lib, self.h, rc)
+
+    def solve_cem(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=4, samples=64, elites=8, alpha=0.25, sigma=1.0,
+                  sigma_min=0.05, seed=0, epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None,
+                  ref_offset=0, expanded_ref=False):
+        """phnn_solve_cem: sampling MPC by the cross-entropy method on B independent problems as ONE library call: the
+        mean is clamped and the standard deviation set to sigma, then iters x (k_cem_sample, K1 over B * samples
+        rollouts, k_cem_update); no gradient is taken anywhere.  -> dict(u_last (B,H,m) last mean (in bounds), sigma_last
+        (B,H,m) last standard deviation, costs (iters,B) the mean's cost at every iteration or None, best_u (B,H,m) /
+        best_cost (B) the best sample over all iterations), same results bit for bit as solver.cem_solve.  elites: how
+        many of the lowest-cost samples mean and standard deviation are refitted to; alpha: smoothing in [0, 1);
+        sigma: initial standard deviation, one value or one per control component; sigma_min: its floor.  seed, epoch,
+        problem_offset, x_ref, ref_offset, expanded_ref: as in solve_mppi."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u_init, H = self._controls(u_init, B)
+        integ = self._integ(integrator)
+        ws = self._cem_buffers(self._roll_workspace(workspace, B, H, integ), B, H, samples)
+        f = dict(dtype=torch.float32, device=self.device)
+        u = u_init.detach().clone().contiguous()
+        costs = torch.empty(max(int(iters), 0), B, **f) if record_costs else None
+        best_cost, best_u, sig = torch.empty(B, **f), torch.empty(B, H, self.m, **f), torch.empty(B, H, self.m, **f)
+        opt, _keep = self._cem_options(iters, samples, elites, alpha, sigma, sigma_min, seed, epoch, problem_offset)
+        ref, _keep_ref = self._reference(x_ref if expanded_ref else self.mppi_reference(x_ref, B, samples), ref_offset,
+                                         B * int(samples))
+        rc = self.lib.phnn_solve_cem(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
+                                     None if ref is None else C.byref(ref), integ, float(dt), C.byref(opt),
+                                     self._p(ws["cem"]), ws["cem"].numel(), self._p(costs), self._p(best_cost),
+                                     self._p(best_u), self._p(sig), self._stream())
+        _check(self.lib, self.h, rc)
+        return {"u_last": u, "sigma_last": sig, "costs": costs, "best_u": best_u, "best_cost": best_cost}
+
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
                    step=0, step_dev=None, log_states=None, log_controls=None):

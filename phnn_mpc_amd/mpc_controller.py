@@ -11,6 +11,8 @@ compute_control_batch run B such optimizers at once on the device (engine.solve_
 optimizer_type='MPPI' (not in the reference): the gradient-free sampling solve (engine.solve_mppi): every call
 cold-starts the nominal from zeros, runs max_iterations iterations of `samples` perturbed rollouts per plant and returns
 clamp(u_0) of the last nominal.  lr is not used.
+optimizer_type='CrossEntropy' (not in the reference): the cross-entropy sampling solve (engine.solve_cem), called as
+the MPPI one is; returns clamp(u_0) of the last mean.  (The name is not 'CEM': that string stays an unknown optimizer.)
 """
 import os
 
@@ -18,12 +20,13 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import lbfgs_solver_for, mppi_solver_for, solver_for
+from .solver import cem_solver_for, lbfgs_solver_for, mppi_solver_for, solver_for
 
 
 class MPCController:
     def __init__(self, phnn_model, horizon, dt, Q, R, target_state=None, u_min=None, u_max=None, x_min=None, x_max=None,
-                 optimizer_type="Adam", lr=0.1, max_iterations=50, samples=64, lam=1.0, sigma=1.0, seed=0):
+                 optimizer_type="Adam", lr=0.1, max_iterations=50, samples=64, lam=1.0, sigma=1.0, seed=0, elites=8,
+                 alpha=0.25, sigma_min=0.05):
         self.model = phnn_model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -41,6 +44,9 @@ class MPCController:
         # optimizer_type='MPPI': samples per plant and iteration, softmin temperature (units of the cost), noise standard
         # deviation, noise seed; `epoch` numbers the solves that are not given one (fresh noise at every control step)
         self.samples, self.lam, self.sigma, self.seed, self.epoch = samples, lam, sigma, seed, 0
+        # optimizer_type='CrossEntropy': samples, sigma (the initial standard deviation), seed and epoch as above; elites:
+        # how many lowest-cost samples the distribution is refitted to, smoothing alpha in [0, 1), floor of sigma
+        self.elites, self.alpha, self.sigma_min = elites, alpha, sigma_min
         self.integrator = "euler"  # src/mpc_controller.py:137-138
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -127,11 +133,13 @@ class MPCController:
         """states (B,n) -> dict with the last iterate of B independent problems (all on the engine's device).
         x_ref: per-problem reference trajectories broadcastable to (B, rows, n), tracked from row ref_offset (int or
         device int32 tensor; past its end a reference holds its last row) instead of target_state.
-        epoch (MPPI only): the noise counter of this solve; None: self.epoch, which then advances by one."""
+        epoch (MPPI, CrossEntropy): the noise counter of this solve; None: self.epoch, which then advances by one."""
         if self.optimizer_type == "LBFGS":
             return self._solve_batch_lbfgs(states, record_costs, x_ref, ref_offset)
         if self.optimizer_type == "MPPI":
             return self._solve_batch_mppi(states, record_costs, x_ref, ref_offset, epoch)
+        if self.optimizer_type == "CrossEntropy":
+            return self._solve_batch_cem(states, record_costs, x_ref, ref_offset, epoch)
         if self.optimizer_type != "Adam":
             raise ValueError(f"Unknown optimizer type: {self.optimizer_type}")
         eng = self.engine
@@ -186,10 +194,25 @@ class MPCController:
         return self._graphed_mppi(eng, x0, u0, self._cost(), self.integrator, self.dt, epoch=self._mppi_epoch(eng, epoch),
                                   record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **self.mppi_options())
 
+    def cem_options(self):
+        """solve_cem keyword arguments of this controller."""
+        return dict(iters=self.max_iterations, samples=self.samples, elites=self.elites, alpha=self.alpha,
+                    sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), sigma_min=self.sigma_min,
+                    seed=self.seed)
+
+    def _solve_batch_cem(self, states, record_costs, x_ref, ref_offset, epoch):
+        """B independent cross-entropy solves (cold start from zeros) in one batched device solve (engine.solve_cem)."""
+        eng = self.engine
+        self._graphed_cem = cem_solver_for(eng, self.use_graph, getattr(self, "_graphed_cem", None))
+        x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
+        u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
+        return self._graphed_cem(eng, x0, u0, self._cost(), self.integrator, self.dt, epoch=self._mppi_epoch(eng, epoch),
+                                 record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **self.cem_options())
+
     def compute_control_batch(self, states, x_ref=None, ref_offset=0, epoch=None):
         """states (B,n) -> np.ndarray (B,1): first control of each plant's optimised sequence (x_ref, epoch:
         solve_batch)."""
-        kw = {"epoch": epoch} if self.optimizer_type == "MPPI" else {}
+        kw = {"epoch": epoch} if self.optimizer_type in ("MPPI", "CrossEntropy") else {}
         out = self.solve_batch(states, x_ref=x_ref, ref_offset=ref_offset, **kw)
         u0 = out["u_last"][:, 0, :]
         if self.u_min is not None and self.u_max is not None:
@@ -198,8 +221,9 @@ class MPCController:
 
 
 def _mppi_keys(mpc):
-    """The MPPI keywords present in the `mpc` config section (optimizer: MPPI): samples, lam, sigma, seed."""
-    return {k: mpc[k] for k in ("samples", "lam", "sigma", "seed") if k in mpc}
+    """The sampling-solver keywords present in the `mpc` config section (optimizer: MPPI or CrossEntropy): samples, lam,
+    sigma, seed, elites, alpha, sigma_min."""
+    return {k: mpc[k] for k in ("samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min") if k in mpc}
 
 
 def create_mpc_from_config(phnn_model, config):

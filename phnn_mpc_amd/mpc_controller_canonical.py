@@ -8,6 +8,8 @@ returns (u (m,), info{'u_sequence','solve_time','optimization'{'costs','final_co
 optimizer='MPPI' (not in the reference): the same calls solved by the gradient-free sampling solve (engine.solve_mppi):
 optimizer_steps iterations of `samples` perturbed rollouts per plant; the sequence returned is the best SAMPLE seen,
 'costs' the nominal's cost at every iteration; learning_rate is not used.
+optimizer='CrossEntropy' (not in the reference): the cross-entropy sampling solve (engine.solve_cem), called and
+returning as the MPPI one does.  (The name is not 'CEM': that string stays an unknown optimizer.)
 """
 import os
 import time
@@ -16,13 +18,13 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import mppi_solver_for, solver_for
+from .solver import cem_solver_for, mppi_solver_for, solver_for
 
 
 class MPCControllerCanonical:
     def __init__(self, model, horizon=20, dt=0.02, Q=None, R=None, x_target=None, u_min=-10.0, u_max=10.0,
                  optimizer_steps=50, learning_rate=0.1, verbose=False, optimizer="Adam", samples=64, lam=1.0, sigma=1.0,
-                 seed=0):
+                 seed=0, elites=8, alpha=0.25, sigma_min=0.05):
         self.model = model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -38,11 +40,14 @@ class MPCControllerCanonical:
             x_target = np.zeros(self.state_dim)
         self.x_target = torch.tensor(x_target, dtype=torch.float32)
         self.u_min, self.u_max = u_min, u_max
-        if optimizer not in ("Adam", "MPPI"):
+        if optimizer not in ("Adam", "MPPI", "CrossEntropy"):
             raise ValueError(f"Unknown optimizer type: {optimizer}")
         # optimizer='MPPI': samples per plant and iteration, softmin temperature (units of the cost), noise standard
         # deviation (one value or one per input), noise seed; `epoch` numbers the solves that are not given one
         self.optimizer, self.samples, self.lam, self.sigma, self.seed, self.epoch = optimizer, samples, lam, sigma, seed, 0
+        # optimizer='CrossEntropy': samples, sigma (the initial standard deviation), seed and epoch as above; elites: how
+        # many lowest-cost samples the distribution is refitted to, smoothing alpha in [0, 1), floor of sigma
+        self.elites, self.alpha, self.sigma_min = elites, alpha, sigma_min
         self.integrator = "euler"
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -112,6 +117,12 @@ class MPCControllerCanonical:
         return dict(iters=self.optimizer_steps, samples=self.samples, lam=self.lam,
                     sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), seed=self.seed)
 
+    def cem_options(self):
+        """solve_cem keyword arguments of this controller."""
+        return dict(iters=self.optimizer_steps, samples=self.samples, elites=self.elites, alpha=self.alpha,
+                    sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), sigma_min=self.sigma_min,
+                    seed=self.seed)
+
     def _mppi_epoch(self, eng, epoch):
         """The epoch argument of one solve: `epoch` (None: the controller's own counter, advanced here); with use_graph
         a device counter holding it, so that the captured graph is replayed, not re-captured, when it changes."""
@@ -128,7 +139,7 @@ class MPCControllerCanonical:
         """x0 (B,n), u_init (B,H,m) or None -> dict(best_u (B,H,m) clamped, best_cost (B), costs (steps,B), u_last).
         x_ref: per-problem reference trajectories broadcastable to (B, rows, n), tracked from row ref_offset (int or
         device int32 tensor; past its end a reference holds its last row) instead of x_target.
-        epoch (MPPI only): the noise counter of this solve; None: self.epoch, which then advances by one."""
+        epoch (MPPI, CrossEntropy): the noise counter of this solve; None: self.epoch, which then advances by one."""
         eng = self.engine
         x0 = torch.as_tensor(x0, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
         B = x0.shape[0]
@@ -141,6 +152,11 @@ class MPCControllerCanonical:
             return self._graphed_mppi(eng, x0, u0, self._cost(), self.integrator, self.dt,
                                       epoch=self._mppi_epoch(eng, epoch), record_costs=record_costs, x_ref=x_ref,
                                       ref_offset=ref_offset, **self.mppi_options())
+        if self.optimizer == "CrossEntropy":
+            self._graphed_cem = cem_solver_for(eng, self.use_graph, getattr(self, "_graphed_cem", None))
+            return self._graphed_cem(eng, x0, u0, self._cost(), self.integrator, self.dt,
+                                     epoch=self._mppi_epoch(eng, epoch), record_costs=record_costs, x_ref=x_ref,
+                                     ref_offset=ref_offset, **self.cem_options())
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.learning_rate,
                                  self.optimizer_steps, track_best=True, u_min=self.u_min, u_max=self.u_max,
                                  record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset)
@@ -167,4 +183,4 @@ def create_mpc_controller(model, config):
         x_target=np.array(mpc.get("x_target", [0.0, 0.0, 0.0, 0.0])), u_min=mpc.get("u_min", -10.0),
         u_max=mpc.get("u_max", 10.0), optimizer_steps=mpc.get("optimizer_steps", 50),
         learning_rate=mpc.get("learning_rate", 0.1), verbose=mpc.get("verbose", False),
-        **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed") if k in mpc})
+        **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min") if k in mpc})

@@ -14,10 +14,14 @@ graph by the same class, Graphed.
 mppi_solve is the gradient-free solver next to them (MPPI: sample K perturbations of the nominal, cost all of them in
 one K1 launch, move the nominal to their softmin-weighted mean): the Python loop over engine.mppi_sample,
 engine.rollout_cost and engine.mppi_update that engine.solve_mppi (phnn_solve_mppi) is pinned to bit for bit.
+cem_solve is the cross-entropy solver of the same shape (a mean and a standard deviation per problem and element, both
+refitted to the lowest-cost samples): the Python loop over engine.cem_sample, engine.rollout_cost and engine.cem_update
+that engine.solve_cem (phnn_solve_cem) is pinned to bit for bit.
 """
 import ctypes
 import inspect
 
+import numpy as np
 import torch
 
 
@@ -119,6 +123,58 @@ def _mppi_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, s
     return fn(x0, u_init, cost, integrator, dt, iters=iters, samples=samples, lam=lam, sigma=sigma, seed=seed, epoch=epoch,
               problem_offset=problem_offset, record_costs=record_costs, workspace=workspace, x_ref=x_ref,
               ref_offset=ref_offset)
+
+
+def cem_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch=0,
+              problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+    """Sampling MPC by the cross-entropy method on B independent problems: x0 (B,n), u_init (B,H,m) ->
+    dict(u_last, sigma_last, costs, best_u, best_cost).
+
+    The mean u starts at clamp(u_init) (the cost's bounds), the standard deviation sig at sigma (one value or one per
+    control component) in every element; `iters` times: v = engine.cem_sample (samples perturbed copies per problem,
+    sample 0 the mean itself), S = engine.rollout_cost of all B * samples rollouts, engine.cem_update refits u and sig
+    to the `elites` samples of lowest finite cost with smoothing alpha, sig floored at sigma_min.
+    u_last   : the last mean (B,H,m), in bounds;  sigma_last: the last standard deviation (B,H,m)
+    costs    : (iters,B) cost of the mean at every iteration (its sample 0), if record_costs
+    best_u   : the best sample seen over all iterations (strict '<', lowest sample index on ties), best_cost its cost
+    seed, epoch, problem_offset, x_ref, ref_offset: as in mppi_solve."""
+    _need_reference(engine, x_ref)
+    rkw = {}
+    B = u_init.shape[0]
+    if x_ref is not None:
+        rkw = {"x_ref": engine.mppi_reference(x_ref, B, samples), "ref_offset": ref_offset}
+    u = u_init.detach().clone().contiguous()
+    if cost.has_u_bounds:
+        u = torch.clamp(u, float(cost.u_min), float(cost.u_max))
+    dev = u.device
+    m = u.shape[2]
+    s0 = np.asarray(sigma, dtype=np.float64).reshape(-1)
+    if s0.size not in (1, m):
+        raise ValueError(f"sigma: one value or one per control component (m = {m}), got {sigma!r}")
+    if not np.all((s0 >= 0) & np.isfinite(s0)):
+        raise ValueError("sigma must be >= 0 and finite")
+    sig = torch.tensor(np.broadcast_to(s0, (m,)).copy(), dtype=torch.float32, device=dev).expand_as(u).contiguous()
+    costs = torch.empty(iters, B, dtype=torch.float32, device=dev) if record_costs else None
+    best_cost = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
+    best_u = torch.zeros_like(u)
+    ws = {} if workspace is None else workspace
+    for i in range(iters):
+        v, x0_rep = engine.cem_sample(x0, u, sig, cost, samples, seed, i, epoch=epoch, problem_offset=problem_offset,
+                                      workspace=ws)
+        s = engine.rollout_cost(x0_rep, v, cost, integrator, dt, **rkw)
+        engine.cem_update(u, sig, v, s, elites, alpha, sigma_min, cost, costs_row=costs[i] if record_costs else None,
+                          best_cost=best_cost, best_u=best_u)
+    return {"u_last": u, "sigma_last": sig, "costs": costs, "best_u": best_u, "best_cost": best_cost}
+
+
+def _cem_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch=0,
+               problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+    """The CEM solve without a captured graph: the library's own loop (engine.solve_cem) where the engine has one, else
+    the Python loop over its primitives.  Same launches, same order: identical results."""
+    fn = engine.solve_cem if hasattr(engine, "solve_cem") else lambda *a, **k: cem_solve(engine, *a, **k)
+    return fn(x0, u_init, cost, integrator, dt, iters=iters, samples=samples, elites=elites, alpha=alpha, sigma=sigma,
+              sigma_min=sigma_min, seed=seed, epoch=epoch, problem_offset=problem_offset, record_costs=record_costs,
+              workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
 
 
 def capture(device, fn):
@@ -230,6 +286,14 @@ class GraphedMPPI(Graphed):
         super().__init__(engine, _mppi_eager)
 
 
+class GraphedCEM(Graphed):
+    """The CEM solve (_cem_eager) as a graph: the clamp and resets plus every iters x (k_cem_sample, K1, k_cem_update)
+    launch.  `epoch`, sigma and x_ref behave as in GraphedMPPI."""
+
+    def __init__(self, engine):
+        super().__init__(engine, _cem_eager)
+
+
 def _graphed_or(eager, cls, engine, use_graph, previous):
     if not use_graph or engine.device.type != "cuda":
         return eager
@@ -259,3 +323,11 @@ def mppi_solver_for(engine, use_graph, previous=None):
     if not hasattr(engine, "mppi_sample"):
         raise NotImplementedError(f"{type(engine).__name__} has no MPPI kernels (RolloutEngine has)")
     return _graphed_or(_mppi_eager, GraphedMPPI, engine, use_graph, previous)
+
+
+def cem_solver_for(engine, use_graph, previous=None):
+    """-> callable(engine, x0, u_init, cost, ...) as _cem_eager: itself, or a GraphedCEM bound to `engine` (reused from
+    `previous` when it already is one for this engine)."""
+    if not hasattr(engine, "cem_sample"):
+        raise NotImplementedError(f"{type(engine).__name__} has no CEM kernels (RolloutEngine has)")
+    return _graphed_or(_cem_eager, GraphedCEM, engine, use_graph, previous)
