@@ -3323,8 +3323,10 @@ __global__ __launch_bounds__(64 * M::T) void k_wgrad_reduce(WgradParams p) {
     aB3 += Hbar;
     if (PHNN) {  // lane (i,q) keeps row q of Jbar
       const float lq = sel4(lam, ln.q), hq = sel4(dH, ln.q);
+      // two rounded products, then their difference: entry (q, q) is lam_q dH_q - lam_q dH_q = 0 exactly and Jbar is
+      // antisymmetric bit for bit, as in the reference (a fused a + l h - l h leaves the rounding of a - l h behind)
 #pragma unroll
-      for (int j = 0; j < N; ++j) aJ[j] = __builtin_fmaf(lq, dH[j], __builtin_fmaf(-lam[j], hq, aJ[j]));
+      for (int j = 0; j < N; ++j) aJ[j] += lq * dH[j] - lam[j] * hq;
     } else {
       aRd[0] += cur.rv[2];  // lanes q = 0 hold small vector 4 (the R_diag cotangents); only lane 0's sum is written
       aRd[1] += cur.rv[3];

@@ -318,6 +318,12 @@ class RolloutEngine:
             self._tape_token = None  # a new buffer: whatever tapes the old one held are gone
         return self._wg_ws
 
+    @property
+    def wgrad_workspace(self):
+        """The uint8 buffer records, slab and tapes share (None before the first weight-gradient call).  The kernels
+        write every byte they later read, so its earlier contents never matter (tests fill it to show that)."""
+        return self._wg_ws
+
     def rollout_trajectory(self, x0, u, integrator="euler", dt=0.02, want_dx=False, tapes=False):
         """Training rollout (no clamp, no cost): x0 (B,n), u (B,H,m) -> traj (B,H+1,n) [, dX (B,H,n) = f(x_t,u_t)].
         tapes=True (models with weight-gradient kernels): K1 also keeps the tapes of every dynamics evaluation in the

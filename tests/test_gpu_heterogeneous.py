@@ -8,7 +8,7 @@ A  Power-of-two homogeneity, bit for bit, every spec of the census (tests/test_h
    the float64 oracle (A3), so that a consistently wrong kernel does not pass.
 B  Isolation, bit for bit: rollouts {0, 9, 15, 16, 36} carry a NaN / +inf / 1e30 / 7e4 state, a NaN control without
    bounds or +-inf controls under the clamp; every output row of every other rollout equals the clean batch's.  The
-   same for one problem of a solve, Adam, L-BFGS and MPPI.
+   same for one problem of a solve, Adam, L-BFGS, MPPI and CEM.
 C  The state-magnitude ladder against the float64 oracle: on every admitted rung (heterogeneous.DROPPED) the device is
    within the stated tolerance or non-finite, never finite and outside it; f32 and bf16x3 kernels are within tolerance
    everywhere, f16x2 kernels up to and including the 6.0e4 rung, and non-finite at 7.0e4 (the input layers of the march
@@ -309,6 +309,26 @@ def test_solve_mppi_isolates_a_nan_problem(torch):
     rep.same("u_last of the NaN problem is the clamped nominal", dirty["u_last"][SOLVE_BAD],
              np.clip(d["U"][SOLVE_BAD], np.float32(vc.U_MIN), np.float32(vc.U_MAX)))
     rep.true("best_cost of the NaN problem is +inf", f32(dirty["best_cost"])[SOLVE_BAD] == np.inf)
+    rep.finish()
+
+
+def test_solve_cem_isolates_a_nan_problem(torch):
+    eng, d, x0p, keep = _solve_inputs(torch)
+    rep = Bits("solve_cem")
+    kw = dict(integrator="euler", dt=d["dt"], iters=3, samples=30, elites=6, alpha=0.25, sigma=0.5, sigma_min=0.05, seed=5)
+    clean, dirty = eng.solve_cem(d["x0"], d["U"], d["cost"], **kw), eng.solve_cem(x0p, d["U"], d["cost"], **kw)
+    for k in ("u_last", "sigma_last", "best_u", "best_cost"):
+        rep.same(k, dirty[k], clean[k], rows=keep)
+    rep.same("costs", dirty["costs"].T, clean["costs"].T, rows=keep)
+    rep.true("clean finite", bool(np.isfinite(f32(clean["best_cost"])).all() and np.isfinite(f32(clean["costs"])).all()))
+    nominal = np.clip(d["U"], np.float32(vc.U_MIN), np.float32(vc.U_MAX))
+    rep.true("mean and standard deviation move in the clean solve",
+             not het.same_bits(f32(clean["u_last"]), nominal) and bool((f32(clean["sigma_last"]) != np.float32(0.5)).any()))
+    # no sample cost of the NaN problem is finite: no elite, mean and standard deviation are kept, nothing is a best
+    rep.same("u_last of the NaN problem is the clamped nominal", dirty["u_last"][SOLVE_BAD], nominal[SOLVE_BAD])
+    rep.true("sigma_last of the NaN problem is the initial sigma", bool((f32(dirty["sigma_last"])[SOLVE_BAD] == np.float32(0.5)).all()))
+    rep.true("best_cost of the NaN problem is +inf", f32(dirty["best_cost"])[SOLVE_BAD] == np.inf)
+    rep.true("its costs are not finite", not np.isfinite(f32(dirty["costs"])[:, SOLVE_BAD]).any())
     rep.finish()
 
 
