@@ -17,6 +17,28 @@
  *   - one handle per (model, device); calls on one handle are not re-entrant from several host threads;
  *   - a call leaves the calling thread's current HIP device as it found it (the handle's device is made current
  *     only for the duration of the call).
+ *
+ * Buffer contract (pinned by tests/test_gpu_footprint.py with guarded buffers of exactly the stated sizes)
+ *   - sizes are exact: a tensor argument has the shape stated at its entry point and a workspace the bytes its
+ *     phnn_*_workspace_bytes() returns (positive for valid arguments, 0 for invalid ones, non-decreasing in B, H, samples
+ *     and history_size); no call needs a byte more, and none reads or writes a byte outside those extents -- not in front
+ *     of a buffer, not behind it, not for the lanes of a partly filled 16-rollout tile.  Inputs are never written;
+ *   - what outputs and workspaces hold on entry is ignored: every byte a call reads from them it has written itself in
+ *     that call (or, for a workspace, in the call documented to fill it: phnn_rollout_fwd before phnn_rollout_grad /
+ *     _vjp, phnn_rollout_trajectory_ws before phnn_rollout_wgrad with PHNN_WGRAD_TAPES).  The exceptions accumulate, so
+ *     their contents on entry are data: grad_theta_dev with PHNN_WGRAD_ACCUMULATE / accumulate = 1; best_cost_dev and
+ *     best_u_dev of phnn_adam_step, phnn_mppi_update and phnn_cem_update (the solves reset them first); done_step_dev of
+ *     phnn_plant_step (initialise to -1); log_states_dev / log_controls_dev, of which a call writes one row; and the
+ *     documented in-place states (u_dev of the solves and updates, sigma_dev, exp_avg / exp_avg_sq of phnn_adam_step,
+ *     state_dev, *step_dev);
+ *   - alignment: float32 / int32 tensors need 4-byte and float64 tensors 8-byte alignment, with two exceptions.
+ *     Workspaces must be 16-byte aligned (their sub-regions sit at multiples of 256 bytes from the base, and the kernels
+ *     access them with 16-byte vectors).  For a model with state_dim n = 4 every tensor of state rows -- x0, traj,
+ *     traj_bar, dx / dx_bar, grad_x0, x, lam, xbar, x0_rep -- must be 16-byte aligned: K1, K2 and the point kernels load
+ *     and store a state row as one 16-byte access (n = 2, 3 use element accesses).  Controls, costs and gradients
+ *     w.r.t. controls are accessed by element; the MPPI / CEM row kernels use 16-byte accesses only where H*m is a
+ *     multiple of 4 and the pointers they are given are 16-byte aligned, which the library tests itself.  A row slice
+ *     t[1:] of a contiguous tensor that satisfies this still does.
  */
 #ifndef PHNN_MPC_H
 #define PHNN_MPC_H
@@ -276,7 +298,7 @@ size_t phnn_wgrad_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, in
  * CANONICAL handles with a MassMatrixNetwork (mass_type != PHNN_MASS_CARTPOLE) floats 20..23 of a point's block are the
  * cotangent of the 2 x 2 matrix M(q) (row-major) of that evaluation and floats 24, 25 its q: the gradient of the mass
  * network's parameters -- which the kernels leave at zero in grad_theta -- is one autograd pass of the caller's
- * MassMatrixNetwork over those points (phnn_mpc_amd/models.py does exactly that); points beyond B carry zeros. */
+ * MassMatrixNetwork over those points (phnn_mpc_amd/models.py does exactly that); points beyond B carry zero cotangents. */
 int phnn_wgrad_record_info(const phnn_handle* h, int32_t* record_floats, int32_t* small_offset, int32_t* small_stride);
 
 /* Reverse pass of the training rollout.  traj_dev: the states phnn_rollout_trajectory wrote; traj_bar_dev (B,H+1,n) and

@@ -908,7 +908,7 @@ static size_t wgrad_tape_offset(const phnn_handle* h, long long n_rec) {
   return (o + 63) / 64 * 64;
 }
 size_t phnn_wgrad_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t integrator) {
-  if (!h || !h->has_wgrad || B <= 0) return 0;
+  if (!h || !h->has_wgrad || B <= 0 || H < 0) return 0;  // H == 0 is the point mode; a negative horizon is no mode at all
   if (H > 0 && integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return 0;
   long long n_rec = wgrad_records(B, H, integrator);
   size_t floats = wgrad_tape_offset(h, n_rec);
