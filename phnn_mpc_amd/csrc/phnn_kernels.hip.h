@@ -965,6 +965,16 @@ DEV void mul_d1(Act<T>& g, const Act<T>& z) {  // g *= phi'(z)
 // ------------------------------------------------------------------------------------------------
 // H_net: value, gradient and Hessian-vector product (src/pHNN.py:72-73, src/pHNN_canonical.py:208-215)
 // ------------------------------------------------------------------------------------------------
+// K1 -> K2 tape kinds.  TAPE_MPC: what the MPC adjoint reads -- for the f16x2 Tanh pHNN / canonical models (M::CURV) the
+// compact tape a2, dH [, rf], C (hnet_curv), else the same as TAPE_TRAIN.  TAPE_TRAIN: a2, q1, dH [, rf] -- the
+// weight-gradient adjoint and k_wgrad_reduce need q1 itself (phnn_rollout_trajectory_ws, the TAPES kernels).
+constexpr int TAPE_NONE = 0, TAPE_MPC = 1, TAPE_TRAIN = 2;
+template <class M, int TK>
+constexpr int tape_floats() {  // floats one wave writes per dynamics evaluation
+  if constexpr (TK == TAPE_MPC && M::CURV) return M::TAPE_C;
+  else return M::STASH;
+}
+
 template <int HID>
 struct HTape {
   Act<HID / 16> a1, a2, q1;  // activations (SiLU / ReLU variants: PRE-activations z1, z2), and q1 = W2^T g2
@@ -1131,10 +1141,125 @@ DEV void hnet_layer1(const float* L, Lane ln, f32x4 z, Act<HID / 16>& a1) {
   tanh_act_pre<Y::T>(a1);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Curvature block of H_net (f16x2 Tanh models whose image has room for it: M::CURV).  The second term of the
+// Hessian-vector product,
+//   W1^T [ q1 (-2 a1 (1 - a1^2)) (W1 v) ] = C v,   C = W1^T diag(c) W1,   c = -2 q1 a1 (1 - a1^2),
+// is the only use the MPC adjoint has for q1 = W2^T g2.  C is a symmetric nin x nin block (nin <= 4) that does not depend
+// on v and is linear in c with weights-only coefficients, C_ij = sum_k P[(i,j)][k] c_k, P[(i,j)][k] = W1[k][i] W1[k][j]:
+// whoever holds q1 and a1 forms the 16 numbers once (K1, or the adjoint in recompute mode right after hnet_grad) and the
+// K1 -> K2 tape carries them instead of the 16T x 16 values of q1.  c is taken as the kernel holds it,
+// (S Sb q1) a1 (1 - a1^2) (O(1) by the image's scales: without them it would sit in f16's denormals), split hi/lo like
+// every other MFMA operand.  The coefficient image (CurvImg, at M::oP; packed once per weight update, phnn_pack.h) holds
+// the 10 distinct rows (i <= j) of Sp * P, Sp a power of two, as f16 hi and lo parts in the row layout of LayH1's forward
+// image; lane (i,q) of the A operand reads the row of pair (i >> 2, i & 3), so the MFMA still delivers all 16 entries:
+// lane (rollout, q) receives row q of C.  -2 / (S Sb Sp) is the one float32 constant behind the parts.
+// Association (part of the bitwise contract between the whole-tile and the split-tile kernels): per 32-unit k-step one
+// chain lo(P) hi(c), hi(P) lo(c), hi(P) hi(c) from a zero accumulator; the k-step sums are added left to right.  A tile
+// split over four waves (wave w = k-step w) reproduces exactly this.
+// ------------------------------------------------------------------------------------------------
+template <int HID>
+struct CurvImg {
+  static constexpr int RS = HID + 16, PART = 10 * RS * 2;  // f16 per row (as HfImg), bytes per part
+  static constexpr int oConst = 2 * PART / 4;                // [4] (-2 / (S Sb Sp), 0, 0, 0)
+  static constexpr int FLOATS = oConst + 4;
+};
+struct Curv {
+  float m[16];  // row-major 4 x 4, all 16 in every lane of the rollout
+};
+// hi/lo fragments of c for the tiles given (whole-tile: all; split-tile: the wave's own two)
+template <int T>
+DEV void hnet_curv_operand(const Act<T>& q1, const Act<T>& a1, Split2<T>& sp) {
+  Act<T> c;
+#pragma unroll
+  for (int t = 0; t < T; ++t) c.v[t] = (q1.v[t] * dtanh(a1.v[t])) * a1.v[t];
+  split_act_h<T>(c, sp);
+}
+// the sum over the 32 units of k-step s (image columns) of P c, unscaled
+template <int HID>
+DEV f32x4 hnet_curv_kstep(const float* P, Lane ln, int s, f16x8 ch, f16x8 cl) {
+  using I = CurvImg<HID>;
+  keep_lds_reads_local();
+  const int a = ln.i >> 2, b = ln.i & 3, lo = a < b ? a : b, hi = a < b ? b : a;
+  const int row = (lo * (9 - lo)) / 2 + (hi - lo);  // (0,0..3) (1,1..3) (2,2..3) (3,3)
+  const char* base = reinterpret_cast<const char*>(P) + row * (I::RS * 2) + ln.q * 16 + s * 64;
+  const f16x8 ah = *reinterpret_cast<const f16x8*>(base);
+  const f16x8 al = *reinterpret_cast<const f16x8*>(base + I::PART);
+  return mfma_h(ah, ch, mfma_h(ah, cl, mfma_h(al, ch, splat4(0.f))));
+}
+// C of a whole tile: lane (i,q) receives row q (entries 4q .. 4q+3) of rollout i, as store_rf takes it
+template <int HID>
+DEV f32x4 hnet_curv(const float* P, Lane ln, const HTape<HID>& tp) {
+  constexpr int T = HID / 16;
+  Split2<T> sp;
+  hnet_curv_operand<T>(tp.q1, tp.a1, sp);
+  f32x4 tot = hnet_curv_kstep<HID>(P, ln, 0, sp.h[0], sp.l[0]);
+#pragma unroll
+  for (int s = 1; s < T / 2; ++s) tot = tot + hnet_curv_kstep<HID>(P, ln, s, sp.h[s], sp.l[s]);
+  return tot * P[CurvImg<HID>::oConst];
+}
+// row q in lane (i,q) -> all four rows in every lane of the rollout (values only move: ds_bpermute, no LDS allocation)
+DEV void spread_curv(f32x4 mine, Lane ln, Curv& c) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c.m[4 * r + j] = __shfl(mine[j], 16 * r + ln.i);
+}
+DEV f32x4 curv_apply(const Curv& c, f32x4 v) {  // C v
+  f32x4 o;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s = __builtin_fmaf(c.m[4 * r + j], v[j], s);
+    o[r] = s;
+  }
+  return o;
+}
+
+// H_net's part of the tape (it leads the slot).  Training format: a2, q1 (T x 256 each), dH (16 x 4).  Compact format:
+// a2, dH, then -- at oC, behind whatever the model keeps in between -- the curvature block (16 x 16, one coalesced
+// 1 KiB store / load like store_rf / load_rf; the symmetric duplicates are written too, K2 reads all 16).
+template <int HID, bool COMPACT>
+DEV void hnet_tape_store(float* stash, int oC, const float* P, Lane ln, const HTape<HID>& tp, f32x4 dH) {
+  constexpr int T = HID / 16;
+  store_act<T>(stash, ln, tp.a2);
+  if constexpr (COMPACT) {
+    if (ln.q == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + T * 256) + ln.i);
+    PHNN_NT_STORE(hnet_curv<HID>(P, ln, tp), reinterpret_cast<f32x4*>(stash + oC) + ln.i * 4 + ln.q);
+  } else {
+    store_act<T>(stash + T * 256, ln, tp.q1);
+    if (ln.q == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + 2 * T * 256) + ln.i);
+  }
+}
+template <int T, bool COMPACT>
+DEV f32x4 tape_load_dH(const float* stash, Lane ln) {
+  return PHNN_NT_LOAD(reinterpret_cast<const f32x4*>(stash + (COMPACT ? 1 : 2) * T * 256) + ln.i);
+}
+DEV void load_curv(const float* src, Lane ln, Curv& c) {  // all 16 of the lane's rollout (as load_rf)
+  const f32x4* p = reinterpret_cast<const f32x4*>(src) + ln.i * 4;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    f32x4 v = PHNN_NT_LOAD(p + k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) c.m[4 * k + e] = v[e];
+  }
+}
+template <int HID, bool COMPACT>
+DEV void hnet_tape_load(const float* stash, int oC, Lane ln, HTape<HID>& tp, Curv& cv) {  // a2 and q1 or C (dH: tape_load_dH)
+  constexpr int T = HID / 16;
+  load_act<T>(stash, ln, tp.a2);
+  if constexpr (COMPACT) load_curv(stash + oC, ln, cv);
+  else load_act<T>(stash + T * 256, ln, tp.q1);
+}
+
 // Hv = (d^2 H / dz^2) v : forward-over-reverse through the kept tape (a1, a2, q1).  Consumes the tape
 // (q1 is overwritten) to keep the live register set at five activation vectors.
-template <int HID, int MM = MM_F32, bool WG = false, int ACT = ACT_TANH, int SITE = kInHHvp>
-DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec = nullptr) {
+// cv != null (f16x2 Tanh, no weight-gradient record): the q1 term comes as the curvature block, tp.q1 is not touched;
+// C v is added on the finished 4-vector, with the normalised v, and the power of two is undone once on the sum.
+template <int HID, int MM = MM_F32, bool WG = false, int ACT = ACT_TANH, int SITE = kInHHvp, bool CQ = false>
+DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec = nullptr, const Curv* cv = nullptr) {
+  static_assert(!CQ || (MM == MM_F16X2 && ACT == ACT_TANH && !WG), "the curvature block exists for f16x2 Tanh MPC kernels");
   if constexpr (ACT != ACT_TANH) {
     static_assert(!WG, "weight-gradient kernels exist for Tanh models only");
     return hnet_hvp_g<HID, ACT>(L, ln, tp, v);
@@ -1158,8 +1283,10 @@ DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec 
   // gdot1 = qdot1*(1-a1^2) + q1*(-2 a1 adot1) and gdot2 = w3 (-2 a2 (1-a2^2) zdot2): both carry a factor -2, so the
   // rest of this function works with -1/2 of the true quantities and the factor is restored on the final 4-vector.
   // Second term of gdot1 folded now, adot1 dies after the product.
+  if constexpr (!CQ) {
 #pragma unroll
-  for (int t = 0; t < T; ++t) tp.q1.v[t] = tp.q1.v[t] * (tp.a1.v[t] * ad1.v[t]);
+    for (int t = 0; t < T; ++t) tp.q1.v[t] = tp.q1.v[t] * (tp.a1.v[t] * ad1.v[t]);
+  }
   zero_act<T>(w);
   if (MM == MM_BF16X3) {
     Split3<T> sp;
@@ -1197,9 +1324,11 @@ DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec 
   if (WG) store_rec_scaled<T>(rec + 3 * T * 256, ln, qd, unscale);
 #pragma unroll
   for (int t = 0; t < T; ++t) {
-    qd.v[t] = __builtin_elementwise_fma(qd.v[t], dtanh(tp.a1.v[t]), tp.q1.v[t]);
+    if constexpr (CQ) qd.v[t] = qd.v[t] * dtanh(tp.a1.v[t]);
+    else qd.v[t] = __builtin_elementwise_fma(qd.v[t], dtanh(tp.a1.v[t]), tp.q1.v[t]);
   }
   f32x4 Hv = to4_rep<T>(L + Y::oW1T, ln, qd);
+  if constexpr (CQ) return (Hv * (-2.0f * L[Y::oB3 + 2]) + curv_apply(*cv, v)) * unscale;
   return Hv * (-2.0f * unscale * L[Y::oB3 + 2]);  // oB3[2]: 1 / (scale folded into W1)
 }
 
@@ -1402,27 +1531,32 @@ struct PhnnModel {
   static constexpr int oGn = oR + LayH1<HID, MM>::SIZE;
   static constexpr int oJ = oGn + (FIXG ? 0 : LayH1<HID, MM>::SIZE);  // [16] J - J^T, row-major N x N
   static constexpr int oG = oJ + 16;                               // [16] G_fixed, row-major N x MI
-  static constexpr int IMG = oG + 16;
+  static constexpr int oP = oG + 16;                               // CURV: CurvImg<HID>, coefficients of the curvature block
+  // f16x2 Tanh: the MPC tape is compact -- a2 (T x 256), dH (64), rf (256), C (256; hnet_curv) -- and the MPC adjoint
+  // never holds q1; the training tape keeps the format below (tape_floats).  The 5.6 KiB of coefficients have to fit
+  // the 160 KiB of LDS next to the image and eight waves' scratch: the 128-wide learned-G variants (146 + 10 KiB
+  // already) have no room and keep q1 in their tape.
+  static constexpr bool CURV = MM == MM_F16X2 && ACT == ACT_TANH &&
+                               4 * (oP + CurvImg<HID>::FLOATS + kMaxWaves * SCR) <= 160 * 1024;
+  static constexpr int IMG = oP + (CURV ? CurvImg<HID>::FLOATS : 0);
 
   // floats one wave stashes per step for the adjoint: a2, q1 (T x 256 each) + dH (16 x 4) + the 16 outputs of R_net
   // (16 x 16; K2 then needs only R_net's hidden layer); a1 is recomputed
   static constexpr int oStashRf = 2 * T * 256 + 64;
   static constexpr int STASH = oStashRf + 256;
+  static constexpr int oTapeRf = T * 256 + 64, oTapeC = oTapeRf + 256, TAPE_C = oTapeC + 256;
 
-  // dx = (Jeff - S S^T) dH + G u, with S = sym(R_raw).  stash != null: keep the H_net tape for K2.
-  template <bool WANT_H, bool ST = false>
+  // dx = (Jeff - S S^T) dH + G u, with S = sym(R_raw).  TK != TAPE_NONE: keep the tape of this evaluation for K2.
+  template <bool WANT_H, int TK = TAPE_NONE>
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, float& Hval, float* stash = nullptr) {
+    constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC && CURV;
     keep_lds_reads_local();
     HTape<HID> tp;
     f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT>(L + oH, ln, x, tp, Hval);
-    if (ST) {
-      store_act<T>(stash, ln, tp.a2);
-      store_act<T>(stash + T * 256, ln, tp.q1);
-      if (ln.q == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + 2 * T * 256) + ln.i);
-    }
+    if (ST) hnet_tape_store<HID, CT>(stash, oTapeC, L + oP, ln, tp, dH);
     Act<T> hR;
     float rf[16];
-    h1_fwd<HID, MM, kInHNet1, ACT>(L + oR, scr, ln, x, hR, rf, ST ? stash + oStashRf : nullptr);
+    h1_fwd<HID, MM, kInHNet1, ACT>(L + oR, scr, ln, x, hR, rf, ST ? stash + (CT ? oTapeRf : oStashRf) : nullptr);
     float G[N * MI];  // G(x) row-major (N, MI): G_fixed buffer or G_net(x).view(n, m)  (src/pHNN.py:86-92)
     if (FIXG) {
 #pragma unroll
@@ -1475,25 +1609,30 @@ struct PhnnModel {
   using Rec = WRec<T, NBIG>;
 
   // xbar = (df/dx)^T lam, ubar = (df/du)^T lam at (x,u); recomputes the forward tape it needs.
-  // WG: also writes the weight-gradient record of this evaluation to `rec` (Hbar = cotangent on H, adds Hbar dH to xbar).
+  // WG: also writes the weight-gradient record of this evaluation to `rec` (Hbar = cotangent on H, adds Hbar dH to xbar);
+  // the tape it reads (ST) is the training tape and the q1 arithmetic stays.  Otherwise, CURV models: the tape is the
+  // compact one and the q1 term of the Hessian-vector product is C v in both modes (CQ) -- in recompute mode C is
+  // formed right behind hnet_grad by the function K1 uses, so the two modes run the same arithmetic.
   template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, f32x4 lam, f32x4& xbar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
+    constexpr bool CQ = CURV && !WG;
     keep_lds_reads_local();
     HTape<HID> tp;
+    Curv cv;
     float Hdummy;
     f32x4 dH;
     float rf[16];
     if (ST) {  // tape written by K1: the loads fly while a1 is recomputed and the R_net part below runs.  Loads return
       // in issue order (vmcnt): the small vectors the R_net part needs first are requested first, the big ones after
-      dH = PHNN_NT_LOAD(reinterpret_cast<const f32x4*>(stash + 2 * T * 256) + ln.i);
-      load_rf(stash + oStashRf, ln, rf);
-      load_act<T>(stash, ln, tp.a2);
-      load_act<T>(stash + T * 256, ln, tp.q1);
+      dH = tape_load_dH<T, CQ>(stash, ln);
+      load_rf(stash + (CQ ? oTapeRf : oStashRf), ln, rf);
+      hnet_tape_load<HID, CQ>(stash, oTapeC, ln, tp, cv);
       // (a1 is recomputed further down, right before the Hessian-vector product: it is not live through the R_net part,
       // which is where this kernel's register peak sits.  K2 1.179 -> 1.154 ms.  Issuing a2's loads later too: no change.)
     } else {
       dH = hnet_grad<HID, false, MM, INH & kInHRecomp, ACT>(L + oH, ln, x, tp, Hdummy);
+      if constexpr (CQ) spread_curv(hnet_curv<HID>(L + oP, ln, tp), ln, cv);
     }
     if (WG && !ST) {  // with the tapes of K1 the reduction reads a2, q1 from there (their record slots stay unwritten)
       store_rec<T>(rec, ln, tp.a2);
@@ -1572,7 +1711,7 @@ struct PhnnModel {
       sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
     }
     if (ST) hnet_layer1<HID, MM, ACT>(L + oH, ln, x, tp.a1);
-    xbar = xb + hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp>(L + oH, ln, tp, v, rec);
+    xbar = xb + hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ>(L + oH, ln, tp, v, rec, &cv);
     if (WG) xbar = xbar + Hbar * dH;
   }
 };
@@ -1676,7 +1815,9 @@ struct CanonModel {
   static constexpr int oCG = oC + 12;
   static constexpr int oCW = oC + 28;  // MT = constant: M^-1 entries (w00, w01, w11, 0); M itself sits in a, b, c
   static constexpr int oMn = oC + 32;  // MT = diagonal / full: LayM image of M_net.mlp
-  static constexpr int IMG = oMn + (MT_ >= MASS_DIAGONAL ? LayM::SIZE : 0);
+  static constexpr int oP = oMn + (MT_ >= MASS_DIAGONAL ? LayM::SIZE : 0);  // CURV: CurvImg<HID> (as PhnnModel)
+  static constexpr bool CURV = MM_ == MM_F16X2 && ACT_ == ACT_TANH;
+  static constexpr int IMG = oP + (CURV ? CurvImg<HID>::FLOATS : 0);
 
   // M(q) and M^-1(q) for the MassMatrixNetwork types (MT >= 1)
   DEV static void mass_eval(const float* L, Lane ln, f32x4 y, float (&m)[3], float (&w)[3], MTape& mt) {
@@ -1703,9 +1844,12 @@ struct CanonModel {
   }
 
   static constexpr int STASH = 2 * T * 256 + 64;
+  // f16x2 Tanh (CURV): compact MPC tape a2 (T x 256), dH (64), C (256), as PhnnModel's without rf
+  static constexpr int oTapeC = T * 256 + 64, TAPE_C = oTapeC + 256;
 
-  template <bool WANT_H, bool ST = false>
+  template <bool WANT_H, int TK = TAPE_NONE>
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, float& Hval, float* stash = nullptr) {
+    constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC && CURV;
     keep_lds_reads_local();
     if constexpr (MT != MASS_CARTPOLE) {  // general MassMatrixNetwork: no det fudge, M^-1 as the reference forms it
       float m[3], w[3];
@@ -1714,11 +1858,7 @@ struct CanonModel {
       f32x4 z = {y[0], y[1], m[0] * y[2] + m[1] * y[3], m[1] * y[2] + m[2] * y[3]};
       HTape<HID> tp;
       f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT>(L + oH, ln, z, tp, Hval);
-      if (ST) {
-        store_act<T>(stash, ln, tp.a2);
-        store_act<T>(stash + T * 256, ln, tp.q1);
-        if (ln.q == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + 2 * T * 256) + ln.i);
-      }
+      if (ST) hnet_tape_store<HID, CT>(stash, oTapeC, L + oP, ln, tp, dH);
       float dp0 = (-dH[0] - L[oC + 6] * dH[2]) + Base_Gu(L, 2, u);
       float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
       return f32x4{w[0] * z[2] + w[1] * z[3], w[1] * z[2] + w[2] * z[3], w[0] * dp0 + w[1] * dp1, w[1] * dp0 + w[2] * dp1};
@@ -1730,11 +1870,7 @@ struct CanonModel {
     f32x4 z = {y[0], y[1], a * y[2] + bc * y[3], bc * y[2] + c * y[3]};
     HTape<HID> tp;
     f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT>(L + oH, ln, z, tp, Hval);
-    if (ST) {
-      store_act<T>(stash, ln, tp.a2);
-      store_act<T>(stash + T * 256, ln, tp.q1);
-      if (ln.q == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + 2 * T * 256) + ln.i);
-    }
+    if (ST) hnet_tape_store<HID, CT>(stash, oTapeC, L + oP, ln, tp, dH);
     float dp0 = (-dH[0] - L[oC + 6] * dH[2]) + Base_Gu(L, 2, u);
     float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
     float det = (a * c - bc * bc) + 1e-6f;
@@ -1750,6 +1886,8 @@ struct CanonModel {
   template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, f32x4 lam, f32x4& ybar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
+    constexpr bool CQ = CURV && !WG;  // compact tape / curvature block instead of q1 (as PhnnModel::vjp)
+    Curv cv;
     keep_lds_reads_local();
     if constexpr (MT != MASS_CARTPOLE) {
       // WG (MassMatrixNetwork): the record carries what H_net and R_diag_raw need, as below, plus -- per evaluation and
@@ -1764,12 +1902,12 @@ struct CanonModel {
       float Hdummy;
       f32x4 dH;
       if (ST) {
-        dH = PHNN_NT_LOAD(reinterpret_cast<const f32x4*>(stash + 2 * T * 256) + ln.i);  // needed first: requested first
-        load_act<T>(stash, ln, tp.a2);
-        load_act<T>(stash + T * 256, ln, tp.q1);
+        dH = tape_load_dH<T, CQ>(stash, ln);  // needed first: requested first
+        hnet_tape_load<HID, CQ>(stash, oTapeC, ln, tp, cv);
         hnet_layer1<HID, MM, ACT>(L + oH, ln, z, tp.a1);
       } else {
         dH = hnet_grad<HID, false, MM, INH & kInHRecomp, ACT>(L + oH, ln, z, tp, Hdummy);
+        if constexpr (CQ) spread_curv(hnet_curv<HID>(L + oP, ln, tp), ln, cv);
       }
       const float Rd2 = L[oC + 6], Rd3 = L[oC + 7];
       const float dp0 = (-dH[0] - Rd2 * dH[2]) + Base_Gu(L, 2, u);
@@ -1794,7 +1932,7 @@ struct CanonModel {
           sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
         }
       }
-      f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp>(L + oH, ln, tp, v, rec);
+      f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ>(L + oH, ln, tp, v, rec, &cv);
       if (WG) zb = zb + Hbar * dH;
       zb[2] += pb0;
       zb[3] += pb1;
@@ -1834,12 +1972,12 @@ struct CanonModel {
     float Hdummy;
     f32x4 dH;
     if (ST) {
-      dH = PHNN_NT_LOAD(reinterpret_cast<const f32x4*>(stash + 2 * T * 256) + ln.i);  // needed first: requested first
-      load_act<T>(stash, ln, tp.a2);
-      load_act<T>(stash + T * 256, ln, tp.q1);
+      dH = tape_load_dH<T, CQ>(stash, ln);  // needed first: requested first
+      hnet_tape_load<HID, CQ>(stash, oTapeC, ln, tp, cv);
       hnet_layer1<HID, MM, ACT>(L + oH, ln, z, tp.a1);
     } else {
       dH = hnet_grad<HID, false, MM, INH & kInHRecomp, ACT>(L + oH, ln, z, tp, Hdummy);
+      if constexpr (CQ) spread_curv(hnet_curv<HID>(L + oP, ln, tp), ln, cv);
     }
     float Rd2 = L[oC + 6], Rd3 = L[oC + 7];
     float dp0 = (-dH[0] - Rd2 * dH[2]) + Base_Gu(L, 2, u);
@@ -1871,7 +2009,7 @@ struct CanonModel {
         sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
       }
     }
-    f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp>(L + oH, ln, tp, v, rec);
+    f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ>(L + oH, ln, tp, v, rec, &cv);
     if (WG) zb = zb + Hbar * dH;
     zb[2] += pb0;
     zb[3] += pb1;
@@ -1899,6 +2037,14 @@ struct CanonModel {
 // whole-tile kernels, with the same rollouts run alone by these).  The stash format is the same too.
 // Exchange area (floats): three fragment regions [part 2][k-step 4][lane 64] x 16 B, two partial-sum sets
 // [wave 4][lane 64] x 16 B.  HID = 128, f16x2 products only.
+// Curvature block (hnet_curv): wave w forms the k-step sum of its own 32 units (hnet_curv_kstep) and the four are added
+// in the whole-tile order -- bitwise the whole-tile C; wave 0 stores.  The partials travel in set 1, next to the dH
+// partials in set 0 and behind the same barriers: written after the second barrier of hnet_grad_w, read after the
+// barrier that precedes xch_sum_partials.  No wave can still be reading them when the set is rewritten: in the adjoint
+// its next use (the partials of the Hessian-vector product) follows the two barriers of hnet_hvp_w, in K1 the next
+// write follows the two barriers of the NEXT hnet_grad_w (next step or RK4 stage), and no wave passes those before all
+// four have arrived, i.e. have finished these reads; the same holds the other way round for the adjoint's final read of
+// set 1 and the next call's write.  (The fragment regions are rewritten BEFORE such a barrier and could not be shared.)
 // ------------------------------------------------------------------------------------------------
 constexpr int kXR0 = 0, kXR1 = 2048, kXR2 = 4096, kXP0 = 6144, kXP1 = 7168, kXchFloats = 8192;
 using ActW = Act<2>;
@@ -1981,6 +2127,16 @@ DEV void sq_bwd_h_w(ActW& o, const float* Wimg, Lane ln, const Split2<8>& in) {
 struct HTapeW {
   ActW a1, a2, q1;
 };
+// the wave's k-step sum of the curvature block into set 1 (before the barrier) / C from the four (after it)
+DEV void curv_put_w(const float* P, Lane ln, const HTapeW& tp) {
+  Split2<2> sp;
+  hnet_curv_operand<2>(tp.q1, tp.a1, sp);
+  xch_put_partial(ln.xch + kXP1, ln, hnet_curv_kstep<128>(P, ln, ln.w, sp.h[0], sp.l[0]));
+}
+DEV f32x4 curv_get_w(const float* P, Lane ln) {  // ((p0 + p1) + p2) + p3: hnet_curv's order
+  const f32x4* p = reinterpret_cast<const f32x4*>(ln.xch + kXP1) + ln.lane;
+  return (((p[0] + p[64]) + p[128]) + p[192]) * P[CurvImg<128>::oConst];
+}
 
 template <int SITE = kInHFwd, class PreBarrier>
 DEV f32x4 hnet_grad_w(const float* L, Lane ln, f32x4 z, HTapeW& tp, PreBarrier pre_barrier) {
@@ -2036,9 +2192,10 @@ DEV f32x4 hnet_grad_w(const float* L, Lane ln, f32x4 z, HTapeW& tp, PreBarrier p
   return to4_group<2>(L + Y::oW1T + (ln.i & 3) * Y::LR + 16 * t0, ln, g.v);
 }
 
-// Hessian-vector product of a split tile: the wave's partial (before the partial sum, the k-slot sum and the final
-// scale); `scale` receives that final factor.  Two barriers inside.  Consumes tp.q1 like hnet_hvp.
-DEV f32x4 hnet_hvp_w(const float* L, Lane ln, HTapeW& tp, f32x4 v, float& scale) {
+// Hessian-vector product of a split tile without its q1 term: the wave's partial (before the partial sum, the k-slot
+// sum and the final scale).  The caller finishes it as hnet_hvp does: (sum * scale + C vn) * unscale, vn = the
+// normalised v.  Two barriers inside.
+DEV f32x4 hnet_hvp_w(const float* L, Lane ln, HTapeW& tp, f32x4 v, float& scale, float& unscale, f32x4& vn) {
   using Y = LayH2<128, MM_F16X2>;
   const int t0 = 2 * ln.w;
   float mx = fmaxf(fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])));
@@ -2046,14 +2203,13 @@ DEV f32x4 hnet_hvp_w(const float* L, Lane ln, HTapeW& tp, f32x4 v, float& scale)
   (void)__builtin_frexpf(mx, &e);
   e = (mx > 0.f && mx < 3.0e38f) ? e : 0;
   v = v * __builtin_ldexpf(1.0f, -e);
-  const float unscale = __builtin_ldexpf(1.0f, e);
+  vn = v;
+  unscale = __builtin_ldexpf(1.0f, e);
   ActW ad1, w;
   zero_act<2>(ad1);
   in_layer_mm<2, MM_F16X2, kInHHvp>(ad1, L, Y::oW1f, Y::oW1h, ln, v, t0);
 #pragma unroll
   for (int t = 0; t < 2; ++t) ad1.v[t] = dtanh(tp.a1.v[t]) * ad1.v[t];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) tp.q1.v[t] = tp.q1.v[t] * (tp.a1.v[t] * ad1.v[t]);
   {
     Split2<2> sp;
     split_act_h<2>(ad1, sp);
@@ -2088,8 +2244,8 @@ DEV f32x4 hnet_hvp_w(const float* L, Lane ln, HTapeW& tp, f32x4 v, float& scale)
     sq_bwd_h_w(qd, L + Y::oW2, ln, all);
   }
 #pragma unroll
-  for (int t = 0; t < 2; ++t) qd.v[t] = __builtin_elementwise_fma(qd.v[t], dtanh(tp.a1.v[t]), tp.q1.v[t]);
-  scale = -2.0f * unscale * L[Y::oB3 + 2];
+  for (int t = 0; t < 2; ++t) qd.v[t] = qd.v[t] * dtanh(tp.a1.v[t]);
+  scale = -2.0f * L[Y::oB3 + 2];
   keep_lds_reads_local();
   return to4_group<2>(L + Y::oW1T + (ln.i & 3) * Y::LR + 16 * t0, ln, qd.v);
 }
@@ -2099,7 +2255,8 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
   using Base = PhnnModel<N_, 128, true, MM_F16X2>;
   static constexpr int N = N_, HID = 128, T = 8, MM = MM_F16X2;
   static constexpr bool FIXG = true, SPLIT = true;
-  static constexpr int SCR = Base::SCR, IMG = Base::IMG, STASH = Base::STASH, MI = 1;
+  static constexpr int SCR = Base::SCR, IMG = Base::IMG, STASH = Base::STASH, TAPE_C = Base::TAPE_C, MI = 1;
+  static constexpr bool CURV = true;
   static constexpr int oH = Base::oH, oR = Base::oR, oJ = Base::oJ, oG = Base::oG;
   using YR = LayH1<128, MM_F16X2>;
 
@@ -2127,23 +2284,26 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     gather16(scr, ln, o, rf);
   }
 
-  template <bool WANT_H, bool ST = false>
+  template <bool WANT_H, int TK = TAPE_NONE>
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, float& Hval, float* stash = nullptr) {
     static_assert(!WANT_H, "the split-tile kernels are rollout kernels");
+    constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC;  // tape formats: PhnnModel
     keep_lds_reads_local();
     HTapeW tp;
     ActW hR;
     f32x4 P = hnet_grad_w(L + oH, ln, x, tp, [&]() { rnet_layer1(L, ln, x, hR); });
     xch_put_partial(ln.xch + kXP0, ln, P);
+    if (CT) curv_put_w(L + Base::oP, ln, tp);
     float rf[16];
-    rnet_out(L, scr, ln, rf, ST ? stash + Base::oStashRf : nullptr);
+    rnet_out(L, scr, ln, rf, ST ? stash + (CT ? Base::oTapeRf : Base::oStashRf) : nullptr);
     if (ST) {
       store_act<2>(stash + 2 * ln.w * 256, ln, tp.a2);
-      store_act<2>(stash + T * 256 + 2 * ln.w * 256, ln, tp.q1);
+      if (!CT) store_act<2>(stash + T * 256 + 2 * ln.w * 256, ln, tp.q1);
     }
     __syncthreads();
     f32x4 dH = xch_sum_partials(ln.xch + kXP0, ln);
-    if (ST && ln.q == 0 && ln.w == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + 2 * T * 256) + ln.i);
+    if (ST && ln.q == 0 && ln.w == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + (CT ? 1 : 2) * T * 256) + ln.i);
+    if (CT) store_rf(stash + Base::oTapeC, ln, curv_get_w(L + Base::oP, ln));  // wave 0 writes
     float G[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) G[i] = L[oG + i];
@@ -2158,14 +2318,15 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     const int t0 = 2 * ln.w;
     HTapeW tp;
     ActW hR;
+    Curv cv;
     f32x4 dH;
     float rf[16];
-    if (ST) {
+    if (ST) {  // the compact tape (the split-tile adjoint writes no weight-gradient records)
       // small vectors first (vmcnt returns loads in issue order; the R_net part needs them first)
-      dH = PHNN_NT_LOAD(reinterpret_cast<const f32x4*>(stash + 2 * T * 256) + ln.i);
-      load_rf(stash + Base::oStashRf, ln, rf);  // R_net's outputs come with the tape: no fragment exchange, no barrier
+      dH = tape_load_dH<T, true>(stash, ln);
+      load_rf(stash + Base::oTapeRf, ln, rf);  // R_net's outputs come with the tape: no fragment exchange, no barrier
       load_act<2>(stash + t0 * 256, ln, tp.a2);
-      load_act<2>(stash + T * 256 + t0 * 256, ln, tp.q1);
+      load_curv(stash + Base::oTapeC, ln, cv);
       using Y = LayH2<128, MM_F16X2>;
       load_vec<2>(tp.a1, L + oH + Y::oB1 + 16 * t0, ln);
       in_layer_mm<2, MM_F16X2, kInHRecomp>(tp.a1, L + oH, Y::oW1f, Y::oW1h, ln, x, t0);
@@ -2174,9 +2335,11 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     } else {
       f32x4 P = hnet_grad_w<kInHRecomp>(L + oH, ln, x, tp, [&]() { rnet_layer1<kInHNet1Adj>(L, ln, x, hR); });
       xch_put_partial(ln.xch + kXP0, ln, P);
+      curv_put_w(L + Base::oP, ln, tp);
       rnet_out(L, scr, ln, rf);
       __syncthreads();
       dH = xch_sum_partials(ln.xch + kXP0, ln);
+      spread_curv(curv_get_w(L + Base::oP, ln), ln, cv);
     }
     float S[N][N], Stl[N], StdH[N];
     sym_from_rf<N>(rf, S);
@@ -2226,14 +2389,15 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
       for (int k = 0; k < N; ++k) acc = __builtin_fmaf(-S[j][k], Stl[k], acc);
       v[j] = acc;
     }
-    float scaleH;
-    f32x4 PH = hnet_hvp_w(L + oH, ln, tp, v, scaleH);
+    float scaleH, unscaleH;
+    f32x4 vn;
+    f32x4 PH = hnet_hvp_w(L + oH, ln, tp, v, scaleH, unscaleH, vn);
     xch_put_partial(ln.xch + kXP0, ln, PR);
     xch_put_partial(ln.xch + kXP1, ln, PH);
     __syncthreads();
     f32x4 xb = splat4(0.f);
     xb += xch_sum_partials(ln.xch + kXP0, ln) * unscaleR;
-    xbar = xb + xch_sum_partials(ln.xch + kXP1, ln) * scaleH;
+    xbar = xb + (xch_sum_partials(ln.xch + kXP1, ln) * scaleH + curv_apply(cv, vn)) * unscaleH;  // hnet_hvp's association
   }
 };
 
@@ -2242,13 +2406,15 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
   using Base = CanonModel<128, MM_F16X2>;
   static constexpr int N = 4, HID = 128, T = 8, MM = MM_F16X2;
   static constexpr bool SPLIT = true;
-  static constexpr int SCR = 0, IMG = Base::IMG, STASH = Base::STASH, oH = Base::oH, oC = Base::oC, MI = 1;
+  static constexpr int SCR = 0, IMG = Base::IMG, STASH = Base::STASH, TAPE_C = Base::TAPE_C, oH = Base::oH, oC = Base::oC, MI = 1;
+  static constexpr bool CURV = true;
   DEV static float Base_Gu(const float* L, int row, f32x4 u) { return Base::Base_Gu(L, row, u); }
   DEV static f32x4 Base_Gt(const float* L, float dpb0, float dpb1) { return Base::Base_Gt(L, dpb0, dpb1); }
 
-  template <bool WANT_H, bool ST = false>
+  template <bool WANT_H, int TK = TAPE_NONE>
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, float& Hval, float* stash = nullptr) {
     static_assert(!WANT_H, "the split-tile kernels are rollout kernels");
+    constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC;  // tape formats: CanonModel
     keep_lds_reads_local();
     float a = L[oC + 0], b = L[oC + 1], c = L[oC + 2];
     float sn, cs;
@@ -2258,13 +2424,15 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
     HTapeW tp;
     f32x4 P = hnet_grad_w(L + oH, ln, z, tp, []() {});
     xch_put_partial(ln.xch + kXP0, ln, P);
+    if (CT) curv_put_w(L + Base::oP, ln, tp);
     if (ST) {
       store_act<2>(stash + 2 * ln.w * 256, ln, tp.a2);
-      store_act<2>(stash + T * 256 + 2 * ln.w * 256, ln, tp.q1);
+      if (!CT) store_act<2>(stash + T * 256 + 2 * ln.w * 256, ln, tp.q1);
     }
     __syncthreads();
     f32x4 dH = xch_sum_partials(ln.xch + kXP0, ln);
-    if (ST && ln.q == 0 && ln.w == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + 2 * T * 256) + ln.i);
+    if (ST && ln.q == 0 && ln.w == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + (CT ? 1 : 2) * T * 256) + ln.i);
+    if (CT) store_rf(stash + Base::oTapeC, ln, curv_get_w(L + Base::oP, ln));  // wave 0 writes
     float dp0 = (-dH[0] - L[oC + 6] * dH[2]) + Base_Gu(L, 2, u);
     float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
     float det = (a * c - bc * bc) + 1e-6f;
@@ -2285,11 +2453,12 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
     float bc = b * cs;
     f32x4 z = {y[0], y[1], a * y[2] + bc * y[3], bc * y[2] + c * y[3]};
     HTapeW tp;
+    Curv cv;
     f32x4 dH;
-    if (ST) {
-      dH = PHNN_NT_LOAD(reinterpret_cast<const f32x4*>(stash + 2 * T * 256) + ln.i);  // needed first: requested first
+    if (ST) {  // the compact tape
+      dH = tape_load_dH<T, true>(stash, ln);  // needed first: requested first
       load_act<2>(stash + t0 * 256, ln, tp.a2);
-      load_act<2>(stash + T * 256 + t0 * 256, ln, tp.q1);
+      load_curv(stash + Base::oTapeC, ln, cv);
       using Y = LayH2<128, MM_F16X2>;
       load_vec<2>(tp.a1, L + oH + Y::oB1 + 16 * t0, ln);
       in_layer_mm<2, MM_F16X2, kInHRecomp>(tp.a1, L + oH, Y::oW1f, Y::oW1h, ln, z, t0);
@@ -2297,8 +2466,10 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
     } else {
       f32x4 P = hnet_grad_w<kInHRecomp>(L + oH, ln, z, tp, []() {});
       xch_put_partial(ln.xch + kXP0, ln, P);
+      curv_put_w(L + Base::oP, ln, tp);
       __syncthreads();
       dH = xch_sum_partials(ln.xch + kXP0, ln);
+      spread_curv(curv_get_w(L + Base::oP, ln), ln, cv);
     }
     float Rd2 = L[oC + 6], Rd3 = L[oC + 7];
     float dp0 = (-dH[0] - Rd2 * dH[2]) + Base_Gu(L, 2, u);
@@ -2313,11 +2484,12 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
     float mb11 = lam[1] * z[3] + lam[3] * dp1;
     f32x4 v = {-dpb0, -dpb1, -Rd2 * dpb0, -Rd3 * dpb1};
     ubar = Base_Gt(L, dpb0, dpb1);
-    float scaleH;
-    f32x4 PH = hnet_hvp_w(L + oH, ln, tp, v, scaleH);
+    float scaleH, unscaleH;
+    f32x4 vn;
+    f32x4 PH = hnet_hvp_w(L + oH, ln, tp, v, scaleH, unscaleH, vn);
     xch_put_partial(ln.xch + kXP1, ln, PH);
     __syncthreads();
-    f32x4 zb = xch_sum_partials(ln.xch + kXP1, ln) * scaleH;
+    f32x4 zb = (xch_sum_partials(ln.xch + kXP1, ln) * scaleH + curv_apply(cv, vn)) * unscaleH;  // hnet_hvp's association
     zb[2] += pb0;
     zb[3] += pb1;
     float bcb = zb[2] * y[3] + zb[3] * y[2];
@@ -2424,9 +2596,11 @@ struct OdeModel {
   // (SiLU / ReLU: the pre-activations z2, z3 are unbounded: plain float32, T x 256 floats each)
   static constexpr int VEC24 = ACT == ACT_TANH ? T * 192 : T * 256;
   static constexpr int STASH = 2 * VEC24;
+  static constexpr bool CURV = false;  // one tape format (tape_floats)
 
-  template <bool WANT_H, bool ST = false>
+  template <bool WANT_H, int TK = TAPE_NONE>
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 x, f32x4 uv, float& Hval, float* stash = nullptr) {
+    constexpr bool ST = TK != TAPE_NONE;
     const float u = uv[0];
     Tape tp;
     if (WANT_H) Hval = 0.f;
@@ -2590,7 +2764,7 @@ struct RollParams {
   float* traj;         // (B,H+1,N) or null
   float* grad_u;       // (B,H)
   float* grad_x0;      // (B,N) or null
-  float* stash;        // K1 -> K2 tape workspace (Euler only) or null: [tile][t][M::STASH] floats
+  float* stash;        // K1 -> K2 tape workspace or null: [tile][t][StashStep::FLOATS] floats
   const float* dx_bar;  // (B,H,N) or null: cotangent on the per-step derivatives f(x_t,u_t) (training losses on dX_pred)
   float* dx_out;       // (B,H,N) or null: K1 also returns f(x_t,u_t) of every step (first stage)
   float* wrec;         // weight-gradient records [tile][t][stage][M::Rec::SIZE] (adjoint kernels built with WG)
@@ -2679,12 +2853,13 @@ DEV float control_cost(const phnn_cost& c, f32x4 u) {
 }
 
 // K1 -> K2 stash of one rollout step of one 16-rollout tile.  Euler: the tape of the one dynamics evaluation
-// (M::STASH floats).  RK4: four stage slots, each the tape of that stage's evaluation followed by the stage state
+// (tape_floats<M, TK>() floats).  RK4: four stage slots, each the tape of that stage's evaluation followed by the stage state
 // (16 rollouts x float4), so that K2 runs four tape-reading VJPs and no forward evaluation at all.
-template <class M, int INTEG>
+template <class M, int INTEG, int TK = TAPE_MPC>
 struct StashStep {
-  static constexpr int SLOT = M::STASH + 64;
-  static constexpr int FLOATS = INTEG == PHNN_INTEG_EULER ? M::STASH : 4 * SLOT;
+  static constexpr int TAPE = tape_floats<M, TK>();
+  static constexpr int SLOT = TAPE + 64;
+  static constexpr int FLOATS = INTEG == PHNN_INTEG_EULER ? TAPE : 4 * SLOT;
 };
 DEV void store_stage(float* dst, Lane ln, f32x4 y) {  // ln.w: wave within a split tile (0 for whole-tile models)
   if (ln.q == 0 && ln.w == 0) PHNN_NT_STORE(y, reinterpret_cast<f32x4*>(dst) + ln.i);
@@ -2748,9 +2923,11 @@ struct RefRows {
 
 // K1: forward march of one tile.  REF: the target of every stage cost is the rollout's reference row of that step
 // (loaded at the top of the step, used after the dynamics) instead of p.c.x_target.
-template <class M, int INTEG, bool STASH, bool REF = false>
+template <class M, int INTEG, int TK, bool REF = false>
 DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
   constexpr int N = M::N;
+  constexpr bool STASH = TK != TAPE_NONE;
+  using SS = StashStep<M, INTEG, STASH ? TK : TAPE_MPC>;
   const Lane ln = tc.ln;
   float* scr = tc.scr;
   const long long tile = tc.tile, b = tc.b;
@@ -2774,22 +2951,22 @@ DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
     f32x4 u = clamp_u4<MI>(p.c, load_u<MI>(up, t));
     if (MI == 1) cost = __builtin_fmaf(u[0] * p.c.R[0], u[0], cost);
     else cost += control_cost<MI>(p.c, u);
-    float* sl = STASH ? p.stash + (tile * p.H + t) * (long long)StashStep<M, INTEG>::FLOATS : nullptr;
-    f32x4 k1 = M::template f<false, STASH>(L, scr, ln, x, u, Hd, sl);
+    float* sl = STASH ? p.stash + (tile * p.H + t) * (long long)SS::FLOATS : nullptr;
+    f32x4 k1 = M::template f<false, TK>(L, scr, ln, x, u, Hd, sl);
     if (p.dx_out && writer) store_state<N>(p.dx_out + (b * p.H + t) * N, k1);
     if (INTEG == PHNN_INTEG_EULER) {
       x = x + p.dt * k1;
     } else {
       // stages 2..4 as a rolled loop (one copy of f in the instruction stream; nothing of one stage is hoisted into
       // another).  x + dt/6 (((k1 + 2 k2) + 2 k3) + k4), the association of src/integrators.py:97-109.
-      constexpr int SLOT = StashStep<M, INTEG>::SLOT;  // one stage: the tape of f at the stage state + the stage state
+      constexpr int SLOT = SS::SLOT;  // one stage: the tape of f at the stage state + the stage state
       f32x4 acc = k1, kp = k1;
 #pragma unroll 1
       for (int s = 1; s < 4; ++s) {
         const f32x4 y = x + (s == 3 ? p.dt : p.half_dt) * kp;
         float* ss = STASH ? sl + s * SLOT : nullptr;
-        if (STASH) store_stage(ss + M::STASH, ln, y);
-        kp = M::template f<false, STASH>(L, scr, ln, y, u, Hd, ss);
+        if (STASH) store_stage(ss + SS::TAPE, ln, y);
+        kp = M::template f<false, TK>(L, scr, ln, y, u, Hd, ss);
         acc = acc + (s == 3 ? 1.0f : 2.0f) * kp;
       }
       x = x + p.sixth_dt * acc;
@@ -2801,13 +2978,13 @@ DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
   if (writer && p.cost) p.cost[b] = cost;
 }
 
-template <class M, int INTEG, bool STASH, bool REF = false>
+template <class M, int INTEG, int TK, bool REF = false>  // TK: the tape K1 keeps (TAPE_NONE / TAPE_MPC / TAPE_TRAIN)
 __global__ __launch_bounds__(64 * kMaxWaves) void k_rollout_fwd(RollParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   stage_image<M::IMG>(lds, p.img);
   TileCtx tc;
   if (!tile_ctx<M>(tc, lds, p.B)) return;
-  fwd_march<M, INTEG, STASH, REF>(p, lds, tc);
+  fwd_march<M, INTEG, TK, REF>(p, lds, tc);
 }
 
 // K2: adjoint march over the states K1 stored.  WG: every dynamics VJP also emits its weight-gradient record
@@ -2818,6 +2995,7 @@ __global__ __launch_bounds__(64 * kMaxWaves) void k_rollout_fwd(RollParams p) {
 template <class M, int INTEG, bool STASH, bool WG = false, bool REF = false>
 DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
   constexpr int N = M::N;
+  using SS = StashStep<M, INTEG, WG ? TAPE_TRAIN : TAPE_MPC>;  // the record-writing adjoint reads the training tape
   const Lane ln = tc.ln;
   float* scr = tc.scr;
   const long long tile = tc.tile, b = tc.b;
@@ -2856,18 +3034,18 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
     if constexpr (INTEG == PHNN_INTEG_EULER) {
       if constexpr (WG) {
         M::template vjp<STASH, true>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
-                                     STASH ? p.stash + (tile * p.H + t) * (long long)M::STASH : nullptr, rec);
+                                     STASH ? p.stash + (tile * p.H + t) * (long long)SS::TAPE : nullptr, rec);
       } else {
         M::template vjp<STASH>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
-                               STASH ? p.stash + (tile * p.H + t) * (long long)M::STASH : nullptr);
+                               STASH ? p.stash + (tile * p.H + t) * (long long)SS::TAPE : nullptr);
       }
       lam = lam + xb;
       utot = ub;
     } else {
       // RK4, stages as rolled loops (one copy of f / vjp in the instruction stream, no cross-stage hoisting of tape
       // loads: that is what made the unrolled form spill).  STASH: the stage states and tapes come from K1's stash.
-      constexpr int SLOT = StashStep<M, INTEG>::SLOT;
-      const float* sl = STASH ? p.stash + (tile * p.H + t) * (long long)StashStep<M, INTEG>::FLOATS : nullptr;
+      constexpr int SLOT = SS::SLOT;
+      const float* sl = STASH ? p.stash + (tile * p.H + t) * (long long)SS::FLOATS : nullptr;
       f32x4 y2 = x, y3 = x, y4 = x;
       if constexpr (!STASH) {
         f32x4 y = x;
@@ -2888,7 +3066,7 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
 #pragma unroll 1
       for (int s = 3; s >= 0; --s) {
         f32x4 y;
-        if constexpr (STASH) y = s == 0 ? load_state<N>(tr + (long long)t * N) : load_stage(sl + s * SLOT + M::STASH, ln);
+        if constexpr (STASH) y = s == 0 ? load_state<N>(tr + (long long)t * N) : load_stage(sl + s * SLOT + SS::TAPE, ln);
         else y = s == 0 ? load_state<N>(tr + (long long)t * N) : (s == 1 ? y2 : (s == 2 ? y3 : y4));
         const f32x4 us = p.no_cost ? load_u<MI>(up, t) : clamp_u4<MI>(p.c, load_u<MI>(up, t));
         // cotangent on k_s: dt/6 (1,2,2,1) lam + the next stage's state cotangent times its step factor

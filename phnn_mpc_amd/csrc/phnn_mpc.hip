@@ -38,8 +38,8 @@ template <class M>
 KernelSet make_set(const char* name) {
   KernelSet k;
   fill_fwd<M>(k.fwd);
-  k.stash_floats[0] = StashStep<M, PHNN_INTEG_EULER>::FLOATS;
-  k.stash_floats[1] = StashStep<M, PHNN_INTEG_RK4>::FLOATS;
+  k.stash_floats[0] = StashStep<M, PHNN_INTEG_EULER, TAPE_MPC>::FLOATS;
+  k.stash_floats[1] = StashStep<M, PHNN_INTEG_RK4, TAPE_MPC>::FLOATS;
   k.scr_floats = M::SCR;
   k.mfwd = k_model_forward<M>;
   k.img_floats = M::IMG;
@@ -488,10 +488,15 @@ bool use_split(const phnn_handle* h, long long tiles) {
 
 // Launches the K1 (grad = false) or K2 (grad = true) kernel [ref][stash][integrator] of the handle's tables: the
 // split-tile one where use_split says so, else the whole-tile one.
+// train_tape: K1 keeping the training tape (the weight-gradient kernels read q1 from it) instead of the MPC one.
 int launch_roll(phnn_handle* h, bool grad, bool ref, bool stash, int integrator, const RollParams& p, long long tiles,
-                hipStream_t st) {
-  if (!use_split(h, tiles)) return launch(h, (grad ? h->ks.grad : h->ks.fwd)[ref][stash][integrator], p, tiles, false, st);
-  RollKernel kern = (grad ? h->sp.grad : h->sp.fwd)[ref][stash][integrator];
+                hipStream_t st, bool train_tape = false) {
+  train_tape = train_tape && h->has_wgrad && h->wg.fwd_t[integrator];  // null: the model has one tape format
+  if (!use_split(h, tiles)) {
+    RollKernel whole = train_tape ? h->wg.fwd_t[integrator] : (grad ? h->ks.grad : h->ks.fwd)[ref][stash][integrator];
+    return launch(h, whole, p, tiles, false, st);
+  }
+  RollKernel kern = train_tape ? h->sp.fwd_t[integrator] : (grad ? h->sp.grad : h->sp.fwd)[ref][stash][integrator];
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), sizeof(float) * (size_t)h->sp.lds_floats, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, e, "kernel launch (split-tile)");
@@ -634,6 +639,12 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
     if (e == hipSuccess) e = allow_big_lds(h->wg.grad_t[0]);
     if (e == hipSuccess) e = allow_big_lds(h->wg.grad_t[1]);
     if (e == hipSuccess) e = allow_big_lds(h->wg.reduce_t);
+    if (e == hipSuccess) e = allow_big_lds(h->wg.fwd_t[0]);
+    if (e == hipSuccess) e = allow_big_lds(h->wg.fwd_t[1]);
+  }
+  if (h->has_split) {
+    if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_t[0]);
+    if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_t[1]);
   }
   if (h->has_split && (size_t)h->sp.lds_floats * sizeof(float) > 160 * 1024) h->has_split = false;
   if (e != hipSuccess) {
@@ -964,7 +975,7 @@ int phnn_rollout_trajectory_ws(phnn_handle* h, const float* x0_dev, const float*
   const long long tiles = (B + kTileB - 1) / kTileB;
   const bool tapes = wgrad_workspace_dev != nullptr;
   if (tapes) p.stash = (float*)wgrad_workspace_dev + wgrad_tape_offset(h, wgrad_records(B, H, integrator));
-  return launch_roll(h, false, false, tapes, integrator, p, tiles, (hipStream_t)stream);
+  return launch_roll(h, false, false, tapes, integrator, p, tiles, (hipStream_t)stream, tapes);
 }
 
 int phnn_rollout_wgrad(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, int32_t integrator,

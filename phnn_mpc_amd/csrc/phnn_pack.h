@@ -148,7 +148,7 @@ PK_HD float pack_f16x2(float* dstf, const float* W, float sc, float* red) {
 
 // FOLD: Tanh models only -- SiLU / ReLU images carry the plain weights (S = Sb = k1 = 1)
 template <int HID, int MM, bool FOLD = true>
-PK_HD const float* pack_h2(float* dst, const float* p, int nin, float* red) {  // H_net: consumes W1,b1,W2,b2,W3,b3 from p
+PK_HD const float* pack_h2(float* dst, const float* p, int nin, float* red, float* ssb = nullptr) {  // H_net: consumes W1,b1,W2,b2,W3,b3 from p; *ssb = S Sb
   using Y = LayH2<HID, MM>;
   const float* W1 = p; p += (size_t)HID * nin;
   const float* b1 = p; p += HID;
@@ -192,6 +192,7 @@ PK_HD const float* pack_h2(float* dst, const float* p, int nin, float* red) {  /
     dst[Y::oW3B + k] = W3[k] * Sb;
     dst[Y::oW3S + k] = W3[k] * Sb / S;
   }
+  if (ssb) *ssb = S * Sb;
   pack_cols_as_rows(dst + Y::oW1T, W1, HID, nin, Y::LR, S * Sb);
   PK_FOR(k, 1) {
     dst[Y::oB3] = b3[0];
@@ -200,6 +201,31 @@ PK_HD const float* pack_h2(float* dst, const float* p, int nin, float* red) {  /
     dst[Y::oB3 + 3] = Sb;
   }
   return p;
+}
+
+// Coefficients of the curvature block (CurvImg; hnet_curv in the kernels): the 10 rows (i <= j) of Sp * W1[k][i] W1[k][j]
+// over the units k in k-slot order, the product formed in float32, Sp = 2^k with max|P| Sp in [0.5, 1); rows with j >= nin
+// are zero.  Every constant between c as the kernels hold it, (S Sb q1) a1 (1 - a1^2), and C goes into one factor.
+template <int HID>
+PK_HD void pack_curv(float* dst, const float* W1, int nin, float ssb, float* red) {
+  using I = CurvImg<HID>;
+  auto pval = [&](int row, int u) {
+    int i = 0, r = row;
+    while (r >= 4 - i) { r -= 4 - i; ++i; }  // row -> pair (i, j = i + r)
+    const int j = i + r;
+    return j < nin ? W1[(size_t)u * nin + i] * W1[(size_t)u * nin + j] : 0.f;
+  };
+  const float pmx = pk_max(10 * HID, red, [&](int e) { return __builtin_fabsf(pval(e / HID, e % HID)); });
+  const float Sp = pk_pow2_scale(pmx, true);
+  _Float16* pw = reinterpret_cast<_Float16*>(dst);
+  PK_FOR(e, 10 * HID) {
+    const int row = e / HID, pos = e % HID;
+    const float x = pval(row, pk_unit_of_pos(pos)) * Sp;
+    const _Float16 h = (_Float16)x, l = (_Float16)(x - (float)h);
+    pw[(size_t)row * I::RS + pos] = h;
+    pw[(size_t)I::PART / 2 + (size_t)row * I::RS + pos] = l;
+  }
+  PK_FOR(k, 1) dst[I::oConst] = -2.0f / (ssb * Sp);
 }
 
 template <int HID, int MM, bool FOLD = true>
@@ -255,7 +281,10 @@ struct PackOf<PhnnModel<N, HID, FIXG, MM, MI, ACT>> {
     if (d->fixed_G) { G = p; p += N * MI; }
     constexpr bool FOLD = ACT == ACT_TANH;
     p = pack_h1<HID, MM, FOLD>(img + M::oR, p, N, N * N, red);
-    p = pack_h2<HID, MM, FOLD>(img + M::oH, p, N, red);
+    const float* W1h = p;  // H_net's first-layer weights lead its block
+    float ssb = 1.0f;
+    p = pack_h2<HID, MM, FOLD>(img + M::oH, p, N, red, &ssb);
+    if constexpr (M::CURV) pack_curv<HID>(img + M::oP, W1h, N, ssb, red);
     if (!d->fixed_G) p = pack_h1<HID, MM, FOLD>(img + M::oGn, p, N, N * MI, red);
     PK_FOR(e, N * N) {
       const int i = e / N, j = e % N;
@@ -314,7 +343,10 @@ struct PackOf<CanonModel<HID, MM, MI, MT, ACT>> {
       pack_in_frag_T<64>(dm + LayM::oWoTf, Wo, nout);
       pack_cols_as_rows(dm + LayM::oW1T, W1, 64, 2, LayM::LR);
     }
-    p = pack_h2<HID, MM, ACT == ACT_TANH>(img + M::oH, p, 4, red);
+    const float* W1h = p;  // H_net's first-layer weights lead its block
+    float ssb = 1.0f;
+    p = pack_h2<HID, MM, ACT == ACT_TANH>(img + M::oH, p, 4, red, &ssb);
+    if constexpr (M::CURV) pack_curv<HID>(img + M::oP, W1h, 4, ssb, red);
     PK_FOR(i, 4) {
       c[4 + i] = pk_softplus(Rd[i]) + 1e-4f;  // src/pHNN_canonical.py:162
       // softplus'(raw) = sigmoid(raw) (threshold 20 as torch.nn.functional.softplus): the weight-gradient kernels need it

@@ -9,6 +9,7 @@ static SplitSet split_set() {
   SplitSet g;
   fill_fwd<M>(g.fwd);
   fill_grad<M>(g.grad);
+  fill_fwd_train<M>(g.fwd_t);
   g.lds_floats = M::IMG + 4 * M::SCR + kXchFloats;
   return g;
 }

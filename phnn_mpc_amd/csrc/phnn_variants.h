@@ -117,14 +117,25 @@ using RollTable = RollKernel[2][2][2];
 
 template <class M>
 void fill_fwd(RollTable t) {
-  t[0][0][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false>;
-  t[0][0][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false>;
-  t[0][1][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true>;
-  t[0][1][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true>;
-  t[1][0][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, false, true>;
-  t[1][0][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, false, true>;
-  t[1][1][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, true, true>;
-  t[1][1][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, true, true>;
+  t[0][0][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, TAPE_NONE>;
+  t[0][0][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, TAPE_NONE>;
+  t[0][1][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, TAPE_MPC>;
+  t[0][1][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, TAPE_MPC>;
+  t[1][0][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, TAPE_NONE, true>;
+  t[1][0][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, TAPE_NONE, true>;
+  t[1][1][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, TAPE_MPC, true>;
+  t[1][1][1] = k_rollout_fwd<M, PHNN_INTEG_RK4, TAPE_MPC, true>;
+}
+
+// K1 keeping the training tape (phnn_rollout_trajectory_ws with a weight-gradient workspace): Euler, RK4.  Null for
+// models with one tape format (no M::CURV): they use the MPC kernels of the table above.
+template <class M>
+void fill_fwd_train(RollKernel (&t)[2]) {
+  t[0] = t[1] = nullptr;
+  if constexpr (M::CURV) {
+    t[0] = k_rollout_fwd<M, PHNN_INTEG_EULER, TAPE_TRAIN>;
+    t[1] = k_rollout_fwd<M, PHNN_INTEG_RK4, TAPE_TRAIN>;
+  }
 }
 
 template <class M>
@@ -149,9 +160,10 @@ bool phnn_grad_kernels(int variant, GradSet* g);
 
 // Split-tile kernels (small batches: four waves share one 16-rollout tile; phnn_kernels.hip.h "Split-tile models"),
 // defined in phnn_split.hip for the 128-wide f16x2 pHNN (fixed G) and canonical variants.  Bitwise the same results
-// and the same stash format as the whole-tile kernels.
+// and the same tape formats as the whole-tile kernels.
 struct SplitSet {
   RollTable fwd, grad;
+  RollKernel fwd_t[2];  // K1 keeping the training tape: Euler, RK4
   int lds_floats;  // image + 4 x per-wave scratch + exchange area
 };
 bool phnn_split_kernels(int variant, SplitSet* g);  // false: no split-tile kernels for this variant
@@ -161,6 +173,7 @@ bool phnn_split_kernels(int variant, SplitSet* g);  // false: no split-tile kern
 struct WgradSet {
   void (*grad[2])(RollParams);  // K2 + records: Euler, RK4
   void (*grad_t[2])(RollParams);  // the same fed by K1's tapes (a2, q1 stay out of the record)
+  RollKernel fwd_t[2];            // K1 writing those tapes (TAPE_TRAIN: they carry q1): Euler, RK4
   void (*mvjp)(PointParams);    // single-evaluation VJP + record
   void (*reduce)(WgradParams);
   void (*reduce_t)(WgradParams);  // reads a2, q1 from the tapes

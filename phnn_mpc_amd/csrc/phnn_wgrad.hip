@@ -17,8 +17,9 @@ static WgradSet wgrad_set() {
   g.mvjp = k_model_vjp<M, true>;
   g.reduce = k_wgrad_reduce<M, false>;
   g.reduce_t = k_wgrad_reduce<M, true>;
-  g.tape_floats[0] = StashStep<M, PHNN_INTEG_EULER>::FLOATS;
-  g.tape_floats[1] = StashStep<M, PHNN_INTEG_RK4>::SLOT;  // four slots per step = one per record
+  fill_fwd_train<M>(g.fwd_t);
+  g.tape_floats[0] = StashStep<M, PHNN_INTEG_EULER, TAPE_TRAIN>::FLOATS;
+  g.tape_floats[1] = StashStep<M, PHNN_INTEG_RK4, TAPE_TRAIN>::SLOT;  // four slots per step = one per record
   g.rec_floats = M::Rec::SIZE;
   g.blob_floats = BlobOf<M>::SIZE;
   g.reduce_waves = M::T;
