@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/phnn_mpc.h"
 
 #define DEV __device__ __forceinline__
@@ -547,8 +549,42 @@ DEV void mfma3x2(f32x4& o0, f32x4& o1, const f16x8 (&a)[2][2], f16x8 xh, f16x8 x
   o1 = mfma_h(a[1][0], xh, o1);
 }
 
-template <int T>
-DEV void sq_fwd_h(Act<T>& o, const float* Wimg, Lane ln, const Split2<T>& in) {
+// Per-pair epilogue of a 128 x 128 product (PHNN_NO_FUSED_EPILOGUE compiles the callers without it).  Both products run
+// output-tile pair outermost, so tiles 2P and 2P+1 are final after the T/2 groups of pair P, and the element-wise pass
+// that follows the product works per pair too (split_act_h's k-step P is exactly those two tiles).  epi(P, j), j = 0..3,
+// is that pass for dword j of k-step P's fragment: values 2(j&1), 2(j&1)+1 of tile 2P + (j>>1).  The driver places the
+// slices of pair P inside the fenced MFMA groups of pair P + 1, where the scheduler interleaves them with the six MFMAs
+// (an MFMA holds the vector issue port for 8 of its 16 cycles); the last pair's slices follow the stream.  Fragment
+// double buffer, fences and the MFMA order per accumulator are those of the plain form: bitwise the same product.
+struct NoEpi {
+  DEV void operator()(int, int) const {}
+};
+#ifndef PHNN_FUSE_SITES  // which sites use it: 1 K1 tanh/g2/split, 2 K1 g1/reduction, 4 K2 gdot2/split, 8 K2 gdot1/reduction
+#define PHNN_FUSE_SITES 15
+#endif
+#ifdef PHNN_NO_FUSED_EPILOGUE
+constexpr int kFuseSites = 0;
+#else
+constexpr int kFuseSites = PHNN_FUSE_SITES;
+#endif
+constexpr int kFuseK1Act = 1, kFuseK1Red = 2, kFuseK2Act = 4, kFuseK2Red = 8;
+#define PHNN_FUSE_K1 (kFuseK1Act | kFuseK1Red)
+#define PHNN_FUSE_K2 (kFuseK2Act | kFuseK2Red)
+template <int T, class Epi>
+DEV void epi_slices(Epi& epi, int P, int s) {  // the share of pair P's four slices that rides in group s of T/2
+  constexpr int NS = T / 2;
+#pragma unroll
+  for (int j = (4 * s) / NS; j < (4 * (s + 1)) / NS; ++j) epi(P, j);
+}
+template <int T, class Epi>
+DEV void epi_tail(Epi& epi) {  // the last pair's epilogue, behind the stream
+#pragma unroll
+  for (int j = 0; j < 4; ++j) epi(T / 2 - 1, j);
+}
+
+template <int T, class Epi = NoEpi>
+DEV void sq_fwd_h(Act<T>& o, const float* Wimg, Lane ln, const Split2<T>& in, Epi epi = Epi()) {
+  constexpr bool FUSED = !std::is_same_v<Epi, NoEpi>;
   using I = HfImg<16 * T>;
   keep_lds_reads_local();
   matrix_phase_begin();
@@ -579,14 +615,22 @@ DEV void sq_fwd_h(Act<T>& o, const float* Wimg, Lane ln, const Split2<T>& in) {
       __builtin_amdgcn_sched_barrier(0);
       const int n0 = 2 * (g / (T / 2)), s = g % (T / 2);
       mfma3x2(o.v[n0], o.v[n0 + 1], a[g % NB], in.h[s], in.l[s]);
+      if constexpr (FUSED)
+        if (n0 > 0) epi_slices<T>(epi, n0 / 2 - 1, s);
       __builtin_amdgcn_sched_barrier(0);
     }
     matrix_phase_end();
+    if constexpr (FUSED) epi_tail<T>(epi);
     return;
   }
 #endif
 #pragma unroll
   for (int n0 = 0; n0 < T; n0 += 2) {
+    if constexpr (FUSED)
+      if (n0 > 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) epi(n0 / 2 - 1, j);
+      }
 #pragma unroll
     for (int s = 0; s < T / 2; ++s) {
       f16x8 a[2][2];
@@ -599,10 +643,12 @@ DEV void sq_fwd_h(Act<T>& o, const float* Wimg, Lane ln, const Split2<T>& in) {
     }
   }
   matrix_phase_end();
+  if constexpr (FUSED) epi_tail<T>(epi);
 }
 
-template <int T>
-DEV void sq_bwd_h(Act<T>& o, const float* Wimg, Lane ln, const Split2<T>& in) {
+template <int T, class Epi = NoEpi>
+DEV void sq_bwd_h(Act<T>& o, const float* Wimg, Lane ln, const Split2<T>& in, Epi epi = Epi()) {
+  constexpr bool FUSED = !std::is_same_v<Epi, NoEpi>;
   using I = HfImg<16 * T>;
   keep_lds_reads_local();
   matrix_phase_begin();
@@ -637,14 +683,22 @@ DEV void sq_bwd_h(Act<T>& o, const float* Wimg, Lane ln, const Split2<T>& in) {
       __builtin_amdgcn_sched_barrier(0);
       const int n0 = 2 * (g / (T / 2)), s = g % (T / 2);
       mfma3x2(o.v[n0], o.v[n0 + 1], a[g % NB], in.h[s], in.l[s]);
+      if constexpr (FUSED)
+        if (n0 > 0) epi_slices<T>(epi, n0 / 2 - 1, s);
       __builtin_amdgcn_sched_barrier(0);
     }
     matrix_phase_end();
+    if constexpr (FUSED) epi_tail<T>(epi);
     return;
   }
 #endif
 #pragma unroll
   for (int n0 = 0; n0 < T; n0 += 2) {
+    if constexpr (FUSED)
+      if (n0 > 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) epi(n0 / 2 - 1, j);
+      }
 #pragma unroll
     for (int s = 0; s < T / 2; ++s) {
       f16x8 a[2][2];
@@ -663,6 +717,7 @@ DEV void sq_bwd_h(Act<T>& o, const float* Wimg, Lane ln, const Split2<T>& in) {
     }
   }
   matrix_phase_end();
+  if constexpr (FUSED) epi_tail<T>(epi);
 }
 
 // 16*TI units -> 4 outputs, every lane receives all 4.  Wt is [4][LR], LR = 16*TI + 8, row c = weights of output c.
@@ -730,6 +785,42 @@ DEV f32x4 to4_rep(const float* Wt, Lane ln, const Act<TI>& in) {
   for (int g = 1; g < NG; ++g) tot = tot + to4_group<TG>(row + 16 * TG * g, ln, &in.v[TG * g]);
   return to4_kslots(tot);
 }
+
+// The pieces the per-pair epilogues (sq_fwd_h / sq_bwd_h with epi) are made of.
+// split_put_h: dword j of k-step P's hi/lo fragments from the two values it packs -- split_act_h's arithmetic.
+template <int T>
+DEV void split_put_h(Split2<T>& o, int P, int j, f32x2 x) {
+  f16x2 hb = __builtin_convertvector(x, f16x2);
+  f32x2 r = residual_h(hb, x);
+  u32x4 H = __builtin_bit_cast(u32x4, o.h[P]), Lo = __builtin_bit_cast(u32x4, o.l[P]);
+  H[j] = __builtin_bit_cast(unsigned, hb);
+  Lo[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
+  o.h[P] = __builtin_bit_cast(f16x8, H);
+  o.l[P] = __builtin_bit_cast(f16x8, Lo);
+}
+// To4Pairs: to4_rep fed slice by slice.  to4_rep sums the units in groups of two tiles -- the pairs of the product -- and
+// adds the group sums left to right, so pair P's group can be formed as soon as its tiles are final: same 4x4x1 MFMAs on
+// the same chains o0 (even registers), o1 (odd), P = o0 + o1, tot += P in pair order, the k-slots at the end.
+template <int TI>
+struct To4Pairs {
+  static_assert(TI >= 2 && TI % 2 == 0, "pairs of tiles");
+  const float* row;  // Wt + (i & 3) LR + 4 q
+  f32x4 tot, o0, o1, a;
+  // the weights of a tile are requested one slice before their first use (tile 0: before the product), so that the
+  // read is behind the fragment reads it would otherwise make its MFMA group wait for (LDS returns in order)
+  DEV To4Pairs(const float* Wt, Lane ln) : row(Wt + (ln.i & 3) * (16 * TI + 8) + 4 * ln.q) {
+    a = *reinterpret_cast<const f32x4*>(row);
+  }
+  DEV void put(int P, int j, float x0, float x1) {  // values 2(j&1), 2(j&1)+1 of tile 2P + (j>>1)
+    const int t = 2 * P + (j >> 1), e = 2 * (j & 1);
+    if (j == 0) o0 = o1 = splat4(0.f);
+    o0 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[e], x0, o0, 0, 0, 0);
+    o1 = __builtin_amdgcn_mfma_f32_4x4x1f32(a[e + 1], x1, o1, 0, 0, 0);
+    if (e == 2 && t + 1 < TI) a = *reinterpret_cast<const f32x4*>(row + 16 * (t + 1));
+    if (j == 3) tot = P == 0 ? o0 + o1 : tot + (o0 + o1);
+  }
+  DEV f32x4 finish() const { return to4_kslots(tot); }
+};
 
 // Per-wave stash in HBM (K1 -> K2): one activation vector = T x 64 lanes x float4, i.e. one fully coalesced
 // 1 KB store/load per tile.  Streamed once each way, so non-temporal.
@@ -1060,7 +1151,7 @@ DEV f32x4 hnet_hvp_g(const float* L, Lane ln, HTape<HID>& tp, f32x4 v) {
 
 // (Measured, round 3, not kept: streaming a2 out right behind its tanh, so that its stores drain underneath the transposed
 // product instead of queueing with q1's: K1 +0.8 %, K2 unchanged.)
-template <int HID, bool WANT_H, int MM = MM_F32, int SITE = kInHFwd, int ACT = ACT_TANH>
+template <int HID, bool WANT_H, int MM = MM_F32, int SITE = kInHFwd, int ACT = ACT_TANH, int FE = 0>
 DEV f32x4 hnet_grad(const float* L, Lane ln, f32x4 z, HTape<HID>& tp, float& Hval) {
   if constexpr (ACT != ACT_TANH) {
     static_assert(MM == MM_F32, "SiLU / ReLU run on the all-f32 kernels");
@@ -1072,7 +1163,43 @@ DEV f32x4 hnet_grad(const float* L, Lane ln, f32x4 z, HTape<HID>& tp, float& Hva
   in_layer_mm<T, MM, SITE>(tp.a1, L, Y::oW1f, Y::oW1h, ln, z);
   tanh_act_pre<T>(tp.a1);
   load_vec<T>(tp.a2, L + Y::oB2, ln);
-  if (MM == MM_BF16X3) {
+  // per-pair epilogues (sq_fwd_h / sq_bwd_h): the forward march of the f16x2 models
+  constexpr bool FUSABLE = MM == MM_F16X2 && SITE == kInHFwd && T >= 2 && T % 2 == 0;
+  constexpr bool FUSE_ACT = FUSABLE && (FE & kFuseSites & kFuseK1Act) != 0, FUSE_RED = FUSABLE && (FE & kFuseSites & kFuseK1Red) != 0;
+  Split2<T> spg{};  // FUSE_ACT: hi/lo fragments of g2, filled by the epilogue of W2 a1
+  float s = 0.f;
+  if constexpr (FUSE_ACT) {
+    // tanh of pair P, the value sum, g2 = w3 (1 - a2^2) and its split ride under the MFMAs of pair P + 1: the same
+    // operations per value as the passes below
+    Split2<T> sp;
+    split_act_h<T>(tp.a1, sp);
+    const float c = L[Y::oB3 + 1];
+    // (w3 of a tile is requested one slice before its first use, tile 0 before the product: To4Pairs)
+    f32x4 w3 = splat4(0.f), w3b = *reinterpret_cast<const f32x4*>(L + Y::oW3B + 4 * ln.q);
+    if (WANT_H) w3 = *reinterpret_cast<const f32x4*>(L + Y::oW3 + 4 * ln.q);
+    auto act = [&](auto pre) {
+      return [&](int P, int j) {
+        const int t = 2 * P + (j >> 1), e = 2 * (j & 1);
+        f32x2 g;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const float x = tp.a2.v[t][e + k];
+          const float a = decltype(pre)::value ? __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x) + 1.0f), 1.0f)
+                                               : tanh_scaled(x, c);
+          tp.a2.v[t][e + k] = a;
+          if (WANT_H) s = __builtin_fmaf(w3[e + k], a, s);
+          g[k] = w3b[e + k] * __builtin_fmaf(-a, a, 1.0f);
+        }
+        if (e == 2 && t + 1 < T) {
+          if (WANT_H) w3 = *reinterpret_cast<const f32x4*>(L + Y::oW3 + 16 * (t + 1) + 4 * ln.q);
+          w3b = *reinterpret_cast<const f32x4*>(L + Y::oW3B + 16 * (t + 1) + 4 * ln.q);
+        }
+        split_put_h<T>(spg, P, j, g);
+      };
+    };
+    if (kPreScaled<T> && c == 1.0f) sq_fwd_h<T>(tp.a2, L + Y::oW2, ln, sp, act(std::true_type()));
+    else sq_fwd_h<T>(tp.a2, L + Y::oW2, ln, sp, act(std::false_type()));
+  } else if (MM == MM_BF16X3) {
     Split3<T> sp;
     split_act<T>(tp.a1, sp);
     sq_fwd_bf<T>(tp.a2, L + Y::oW2, ln, sp);
@@ -1083,7 +1210,9 @@ DEV f32x4 hnet_grad(const float* L, Lane ln, f32x4 z, HTape<HID>& tp, float& Hva
   } else {
     sq_fwd<T, T>(tp.a2, L + Y::oW2, ln, tp.a1);
   }
-  if (MM == MM_F16X2 || kPreScaled<T>) {
+  if constexpr (FUSE_ACT) {
+    // tanh was the epilogue's
+  } else if (MM == MM_F16X2 || kPreScaled<T>) {
     // the accumulator holds S * z2; c = 2 log2(e) / S.  128-wide: 2 log2(e) is folded into the image and the f16
     // image needs no further power of two for ordinary weights (max |2.89 w| in [0.5, 1024)), so c == 1 and the
     // multiply disappears; the branch is uniform.
@@ -1100,25 +1229,40 @@ DEV f32x4 hnet_grad(const float* L, Lane ln, f32x4 z, HTape<HID>& tp, float& Hva
     tanh_act<T>(tp.a2);
   }
   Act<T> g;
-  float s = 0.f;
   keep_lds_reads_local();
+  if constexpr (!FUSE_ACT) {
 #pragma unroll
-  for (int t = 0; t < T; ++t) {
-    if (WANT_H) {
-      f32x4 w3 = *reinterpret_cast<const f32x4*>(L + Y::oW3 + 16 * t + 4 * ln.q);
+    for (int t = 0; t < T; ++t) {
+      if (WANT_H) {
+        f32x4 w3 = *reinterpret_cast<const f32x4*>(L + Y::oW3 + 16 * t + 4 * ln.q);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) s = __builtin_fmaf(w3[r], tp.a2.v[t][r], s);
+        for (int r = 0; r < 4; ++r) s = __builtin_fmaf(w3[r], tp.a2.v[t][r], s);
+      }
+      f32x4 w3b = *reinterpret_cast<const f32x4*>(L + Y::oW3B + 16 * t + 4 * ln.q);
+      g.v[t] = w3b * dtanh(tp.a2.v[t]);
     }
-    f32x4 w3b = *reinterpret_cast<const f32x4*>(L + Y::oW3B + 16 * t + 4 * ln.q);
-    g.v[t] = w3b * dtanh(tp.a2.v[t]);
   }
   if (WANT_H) Hval = reduce_q(s) + L[Y::oB3];
   zero_act<T>(tp.q1);
-  if (MM == MM_BF16X3) {
+  if constexpr (FUSABLE) {  // q1 comes out times S; W1^T in the image is divided by S
+    if constexpr (!FUSE_ACT) split_act_h<T>(g, spg);
+    if constexpr (FUSE_RED) {
+      // g1 = q1 (1 - a1^2) of pair P and its share of the 128 -> 4 reduction ride under the MFMAs of pair P + 1
+      To4Pairs<T> red(L + Y::oW1T, ln);
+      sq_bwd_h<T>(tp.q1, L + Y::oW2, ln, spg, [&](int P, int j) {
+        const int t = 2 * P + (j >> 1), e = 2 * (j & 1);
+        const float a0 = tp.a1.v[t][e], a1 = tp.a1.v[t][e + 1];
+        red.put(P, j, tp.q1.v[t][e] * __builtin_fmaf(-a0, a0, 1.0f), tp.q1.v[t][e + 1] * __builtin_fmaf(-a1, a1, 1.0f));
+      });
+      return red.finish();
+    } else {
+      sq_bwd_h<T>(tp.q1, L + Y::oW2, ln, spg);
+    }
+  } else if (MM == MM_BF16X3) {
     Split3<T> sp;
     split_act<T>(g, sp);
     sq_bwd_bf<T>(tp.q1, L + Y::oW2, ln, sp);
-  } else if (MM == MM_F16X2) {  // q1 comes out times S; W1^T in the image is divided by S
+  } else if (MM == MM_F16X2) {
     Split2<T> sp;
     split_act_h<T>(g, sp);
     sq_bwd_h<T>(tp.q1, L + Y::oW2, ln, sp);
@@ -1257,7 +1401,7 @@ DEV void hnet_tape_load(const float* stash, int oC, Lane ln, HTape<HID>& tp, Cur
 // (q1 is overwritten) to keep the live register set at five activation vectors.
 // cv != null (f16x2 Tanh, no weight-gradient record): the q1 term comes as the curvature block, tp.q1 is not touched;
 // C v is added on the finished 4-vector, with the normalised v, and the power of two is undone once on the sum.
-template <int HID, int MM = MM_F32, bool WG = false, int ACT = ACT_TANH, int SITE = kInHHvp, bool CQ = false>
+template <int HID, int MM = MM_F32, bool WG = false, int ACT = ACT_TANH, int SITE = kInHHvp, bool CQ = false, int FE = 0>
 DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec = nullptr, const Curv* cv = nullptr) {
   static_assert(!CQ || (MM == MM_F16X2 && ACT == ACT_TANH && !WG), "the curvature block exists for f16x2 Tanh MPC kernels");
   if constexpr (ACT != ACT_TANH) {
@@ -1288,29 +1432,68 @@ DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec 
     for (int t = 0; t < T; ++t) tp.q1.v[t] = tp.q1.v[t] * (tp.a1.v[t] * ad1.v[t]);
   }
   zero_act<T>(w);
-  if (MM == MM_BF16X3) {
-    Split3<T> sp;
-    split_act<T>(ad1, sp);
-    sq_fwd_bf<T>(w, L + Y::oW2, ln, sp);
-  } else if (MM == MM_F16X2) {
+  // per-pair epilogues (sq_fwd_h / sq_bwd_h): the MPC adjoint of the f16x2 models
+  constexpr bool FUSABLE = CQ && T >= 2 && T % 2 == 0;
+  constexpr bool FUSE_ACT = FUSABLE && (FE & kFuseSites & kFuseK2Act) != 0, FUSE_RED = FUSABLE && (FE & kFuseSites & kFuseK2Red) != 0;
+  Split2<T> spw{};  // FUSE_ACT: hi/lo fragments of -gdot2 / 2, filled by the epilogue of W2 adot1
+  if constexpr (FUSE_ACT) {
+    // -gdot2 / 2 of pair P and its split ride under the MFMAs of pair P + 1 (the same operations per value as the loop
+    // below); the transposed product starts from fragments that already exist
     Split2<T> sp;
     split_act_h<T>(ad1, sp);
-    sq_fwd_h<T>(w, L + Y::oW2, ln, sp);
-  } else {
-    sq_fwd<T, T>(w, L + Y::oW2, ln, ad1);
-  }
-  keep_lds_reads_local();
+    // (w3 / S of a tile is requested one slice before its first use, tile 0 before the product: To4Pairs)
+    f32x4 w3 = *reinterpret_cast<const f32x4*>(L + Y::oW3S + 4 * ln.q);
+    sq_fwd_h<T>(w, L + Y::oW2, ln, sp, [&](int P, int j) {
+      const int t = 2 * P + (j >> 1), e = 2 * (j & 1);
+      f32x2 x;
 #pragma unroll
-  for (int t = 0; t < T; ++t) {
-    f32x4 w3 = *reinterpret_cast<const f32x4*>(L + Y::oW3S + 16 * t + 4 * ln.q);  // w3 / S: w holds S * zdot2
-    f32x4 a2 = tp.a2.v[t];
-    f32x4 ad2 = dtanh(a2) * w.v[t];
-    if (WG) PHNN_REC_STORE(ad2 * unscale, reinterpret_cast<f32x4*>(rec + 2 * T * 256) + t * 64 + ln.lane);
-    w.v[t] = w3 * (a2 * ad2);  // -gdot2 / 2
+      for (int k = 0; k < 2; ++k) {
+        const float a2 = tp.a2.v[t][e + k];
+        const float ad2 = __builtin_fmaf(-a2, a2, 1.0f) * w.v[t][e + k];
+        x[k] = w3[e + k] * (a2 * ad2);
+      }
+      if (e == 2 && t + 1 < T) w3 = *reinterpret_cast<const f32x4*>(L + Y::oW3S + 16 * (t + 1) + 4 * ln.q);
+      split_put_h<T>(spw, P, j, x);
+    });
+  } else {
+    if (MM == MM_BF16X3) {
+      Split3<T> sp;
+      split_act<T>(ad1, sp);
+      sq_fwd_bf<T>(w, L + Y::oW2, ln, sp);
+    } else if (MM == MM_F16X2) {
+      Split2<T> sp;
+      split_act_h<T>(ad1, sp);
+      sq_fwd_h<T>(w, L + Y::oW2, ln, sp);
+    } else {
+      sq_fwd<T, T>(w, L + Y::oW2, ln, ad1);
+    }
+    keep_lds_reads_local();
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      f32x4 w3 = *reinterpret_cast<const f32x4*>(L + Y::oW3S + 16 * t + 4 * ln.q);  // w3 / S: w holds S * zdot2
+      f32x4 a2 = tp.a2.v[t];
+      f32x4 ad2 = dtanh(a2) * w.v[t];
+      if (WG) PHNN_REC_STORE(ad2 * unscale, reinterpret_cast<f32x4*>(rec + 2 * T * 256) + t * 64 + ln.lane);
+      w.v[t] = w3 * (a2 * ad2);  // -gdot2 / 2
+    }
   }
   Act<T> qd;
   zero_act<T>(qd);
-  if (MM == MM_BF16X3) {
+  if constexpr (FUSABLE) {
+    if constexpr (!FUSE_ACT) split_act_h<T>(w, spw);
+    if constexpr (FUSE_RED) {
+      // qdot1 (1 - a1^2) of pair P and its share of the 128 -> 4 reduction ride under the MFMAs of pair P + 1
+      To4Pairs<T> red(L + Y::oW1T, ln);
+      sq_bwd_h<T>(qd, L + Y::oW2, ln, spw, [&](int P, int j) {
+        const int t = 2 * P + (j >> 1), e = 2 * (j & 1);
+        const float a0 = tp.a1.v[t][e], a1 = tp.a1.v[t][e + 1];
+        red.put(P, j, qd.v[t][e] * __builtin_fmaf(-a0, a0, 1.0f), qd.v[t][e + 1] * __builtin_fmaf(-a1, a1, 1.0f));
+      });
+      return (red.finish() * (-2.0f * L[Y::oB3 + 2]) + curv_apply(*cv, v)) * unscale;
+    } else {
+      sq_bwd_h<T>(qd, L + Y::oW2, ln, spw);
+    }
+  } else if (MM == MM_BF16X3) {
     Split3<T> sp;
     split_act<T>(w, sp);
     sq_bwd_bf<T>(qd, L + Y::oW2, ln, sp);
@@ -1539,6 +1722,10 @@ struct PhnnModel {
   static constexpr bool CURV = MM == MM_F16X2 && ACT == ACT_TANH &&
                                4 * (oP + CurvImg<HID>::FLOATS + kMaxWaves * SCR) <= 160 * 1024;
   static constexpr int IMG = oP + (CURV ? CurvImg<HID>::FLOATS : 0);
+  // per-pair epilogue sites (kFuseEpi) the kernels of this model have the registers for, by tools/resource_usage.py: a
+  // fused product keeps a second set of operand fragments live, and G_net's hidden vector or further control columns
+  // leave no room for it (they would spill).  128-wide only: the 64-wide forward kernel would cross 128 registers.
+  static constexpr int FUSE = (HID_ != 128 || !FIXG_) ? 0 : ((MI_ <= 2 ? PHNN_FUSE_K1 : 0) | (MI_ == 1 ? PHNN_FUSE_K2 : 0));
 
   // floats one wave stashes per step for the adjoint: a2, q1 (T x 256 each) + dH (16 x 4) + the 16 outputs of R_net
   // (16 x 16; K2 then needs only R_net's hidden layer); a1 is recomputed
@@ -1547,12 +1734,12 @@ struct PhnnModel {
   static constexpr int oTapeRf = T * 256 + 64, oTapeC = oTapeRf + 256, TAPE_C = oTapeC + 256;
 
   // dx = (Jeff - S S^T) dH + G u, with S = sym(R_raw).  TK != TAPE_NONE: keep the tape of this evaluation for K2.
-  template <bool WANT_H, int TK = TAPE_NONE>
+  template <bool WANT_H, int TK = TAPE_NONE, int FE = 0>  // FE: per-pair epilogue sites (kFuse*)
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, float& Hval, float* stash = nullptr) {
     constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC && CURV;
     keep_lds_reads_local();
     HTape<HID> tp;
-    f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT>(L + oH, ln, x, tp, Hval);
+    f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT, FE>(L + oH, ln, x, tp, Hval);
     if (ST) hnet_tape_store<HID, CT>(stash, oTapeC, L + oP, ln, tp, dH);
     Act<T> hR;
     float rf[16];
@@ -1613,7 +1800,7 @@ struct PhnnModel {
   // the tape it reads (ST) is the training tape and the q1 arithmetic stays.  Otherwise, CURV models: the tape is the
   // compact one and the q1 term of the Hessian-vector product is C v in both modes (CQ) -- in recompute mode C is
   // formed right behind hnet_grad by the function K1 uses, so the two modes run the same arithmetic.
-  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
+  template <bool ST = false, bool WG = false, int INH = -1, int FE = 0>  // INH: mask on the f16 input-layer sites (in_layer_mm); FE: as f
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, f32x4 lam, f32x4& xbar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     constexpr bool CQ = CURV && !WG;
@@ -1711,7 +1898,7 @@ struct PhnnModel {
       sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
     }
     if (ST) hnet_layer1<HID, MM, ACT>(L + oH, ln, x, tp.a1);
-    xbar = xb + hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ>(L + oH, ln, tp, v, rec, &cv);
+    xbar = xb + hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ, ST ? FE : 0>(L + oH, ln, tp, v, rec, &cv);
     if (WG) xbar = xbar + Hbar * dH;
   }
 };
@@ -1817,6 +2004,9 @@ struct CanonModel {
   static constexpr int oMn = oC + 32;  // MT = diagonal / full: LayM image of M_net.mlp
   static constexpr int oP = oMn + (MT_ >= MASS_DIAGONAL ? LayM::SIZE : 0);  // CURV: CurvImg<HID> (as PhnnModel)
   static constexpr bool CURV = MM_ == MM_F16X2 && ACT_ == ACT_TANH;
+  // per-pair epilogue sites (kFuseEpi; PhnnModel::FUSE): the forward march of the cart-pole and constant mass matrices;
+  // the adjoint and the MassMatrixNetwork kernels have no registers to spare
+  static constexpr int FUSE = (HID_ == 128 && MT_ <= MASS_CONSTANT) ? PHNN_FUSE_K1 : 0;
   static constexpr int IMG = oP + (CURV ? CurvImg<HID>::FLOATS : 0);
 
   // M(q) and M^-1(q) for the MassMatrixNetwork types (MT >= 1)
@@ -1847,7 +2037,7 @@ struct CanonModel {
   // f16x2 Tanh (CURV): compact MPC tape a2 (T x 256), dH (64), C (256), as PhnnModel's without rf
   static constexpr int oTapeC = T * 256 + 64, TAPE_C = oTapeC + 256;
 
-  template <bool WANT_H, int TK = TAPE_NONE>
+  template <bool WANT_H, int TK = TAPE_NONE, int FE = 0>  // FE: per-pair epilogue sites (kFuse*)
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, float& Hval, float* stash = nullptr) {
     constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC && CURV;
     keep_lds_reads_local();
@@ -1857,7 +2047,7 @@ struct CanonModel {
       mass_eval(L, ln, y, m, w, mt);
       f32x4 z = {y[0], y[1], m[0] * y[2] + m[1] * y[3], m[1] * y[2] + m[2] * y[3]};
       HTape<HID> tp;
-      f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT>(L + oH, ln, z, tp, Hval);
+      f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT, FE>(L + oH, ln, z, tp, Hval);
       if (ST) hnet_tape_store<HID, CT>(stash, oTapeC, L + oP, ln, tp, dH);
       float dp0 = (-dH[0] - L[oC + 6] * dH[2]) + Base_Gu(L, 2, u);
       float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
@@ -1869,7 +2059,7 @@ struct CanonModel {
     float bc = b * cs;
     f32x4 z = {y[0], y[1], a * y[2] + bc * y[3], bc * y[2] + c * y[3]};
     HTape<HID> tp;
-    f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT>(L + oH, ln, z, tp, Hval);
+    f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT, FE>(L + oH, ln, z, tp, Hval);
     if (ST) hnet_tape_store<HID, CT>(stash, oTapeC, L + oP, ln, tp, dH);
     float dp0 = (-dH[0] - L[oC + 6] * dH[2]) + Base_Gu(L, 2, u);
     float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
@@ -1883,7 +2073,7 @@ struct CanonModel {
   using Rec = WRec<T, NBIG>;
 
   // WG: also writes the weight-gradient record (a2, q1, ad2, qd; small: z, v, lam, dH, the two R_diag cotangents)
-  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
+  template <bool ST = false, bool WG = false, int INH = -1, int FE = 0>  // INH: mask on the f16 input-layer sites (in_layer_mm); FE: as f
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, f32x4 lam, f32x4& ybar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     constexpr bool CQ = CURV && !WG;  // compact tape / curvature block instead of q1 (as PhnnModel::vjp)
@@ -1932,7 +2122,7 @@ struct CanonModel {
           sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
         }
       }
-      f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ>(L + oH, ln, tp, v, rec, &cv);
+      f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ, ST ? FE : 0>(L + oH, ln, tp, v, rec, &cv);
       if (WG) zb = zb + Hbar * dH;
       zb[2] += pb0;
       zb[3] += pb1;
@@ -2009,7 +2199,7 @@ struct CanonModel {
         sm[9] = f32x4{Hbar, 0.f, 0.f, 0.f};
       }
     }
-    f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ>(L + oH, ln, tp, v, rec, &cv);
+    f32x4 zb = hnet_hvp<HID, MM, WG, ACT, INH & kInHHvp, CQ, ST ? FE : 0>(L + oH, ln, tp, v, rec, &cv);
     if (WG) zb = zb + Hbar * dH;
     zb[2] += pb0;
     zb[3] += pb1;
@@ -2284,7 +2474,7 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     gather16(scr, ln, o, rf);
   }
 
-  template <bool WANT_H, int TK = TAPE_NONE>
+  template <bool WANT_H, int TK = TAPE_NONE, int FE = 0>  // FE: unused (the marches pass it to every model)
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, float& Hval, float* stash = nullptr) {
     static_assert(!WANT_H, "the split-tile kernels are rollout kernels");
     constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC;  // tape formats: PhnnModel
@@ -2310,7 +2500,7 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     return Base::combine(L, rf, dH, G, u);
   }
 
-  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
+  template <bool ST = false, bool WG = false, int INH = -1, int FE = 0>  // INH: mask on the f16 input-layer sites (in_layer_mm); FE: as f
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, f32x4 lam, f32x4& xbar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     static_assert(!WG, "weight-gradient records come from the whole-tile kernels");
@@ -2411,7 +2601,7 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
   DEV static float Base_Gu(const float* L, int row, f32x4 u) { return Base::Base_Gu(L, row, u); }
   DEV static f32x4 Base_Gt(const float* L, float dpb0, float dpb1) { return Base::Base_Gt(L, dpb0, dpb1); }
 
-  template <bool WANT_H, int TK = TAPE_NONE>
+  template <bool WANT_H, int TK = TAPE_NONE, int FE = 0>  // FE: unused (the marches pass it to every model)
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, float& Hval, float* stash = nullptr) {
     static_assert(!WANT_H, "the split-tile kernels are rollout kernels");
     constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC;  // tape formats: CanonModel
@@ -2441,7 +2631,7 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
                  mi01 * dp0 + mi11 * dp1};
   }
 
-  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
+  template <bool ST = false, bool WG = false, int INH = -1, int FE = 0>  // INH: mask on the f16 input-layer sites (in_layer_mm); FE: as f
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, f32x4 lam, f32x4& ybar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     static_assert(!WG, "weight-gradient records come from the whole-tile kernels");
@@ -2598,7 +2788,7 @@ struct OdeModel {
   static constexpr int STASH = 2 * VEC24;
   static constexpr bool CURV = false;  // one tape format (tape_floats)
 
-  template <bool WANT_H, int TK = TAPE_NONE>
+  template <bool WANT_H, int TK = TAPE_NONE, int FE = 0>  // FE: per-pair epilogue sites (kFuse*)
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 x, f32x4 uv, float& Hval, float* stash = nullptr) {
     constexpr bool ST = TK != TAPE_NONE;
     const float u = uv[0];
@@ -2617,7 +2807,7 @@ struct OdeModel {
     return dx;
   }
 
-  template <bool ST = false, bool WG = false, int INH = -1>  // INH: mask on the f16 input-layer sites (in_layer_mm)
+  template <bool ST = false, bool WG = false, int INH = -1, int FE = 0>  // INH: mask on the f16 input-layer sites (in_layer_mm); FE: as f
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 x, f32x4 uv, f32x4 lam, f32x4& xbar, f32x4& ubar4,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
     static_assert(!WG, "ODEFunc has no weight-gradient kernels");
@@ -2923,6 +3113,21 @@ struct RefRows {
 
 // K1: forward march of one tile.  REF: the target of every stage cost is the rollout's reference row of that step
 // (loaded at the top of the step, used after the dynamics) instead of p.c.x_target.
+// Which march kernels run the per-pair epilogues (sq_fwd_h with epi): the MPC kernels of the Euler march without a
+// per-problem reference, stash mode.  The RK4, reference and training-tape instantiations have no registers to spare for
+// the second set of operand fragments that is live through a fused product (they would spill) and keep the plain order.
+// A model names the sites its kernels have the registers for (M::FUSE; none where it says nothing).
+template <class M, class = void>
+struct FuseOf {
+  static constexpr int value = 0;
+};
+template <class M>
+struct FuseOf<M, decltype((void)M::FUSE)> {
+  static constexpr int value = M::FUSE;
+};
+template <class M, int INTEG, bool REF, bool MPC_TAPE, int SITES>
+constexpr int kFuseEpi = (INTEG == PHNN_INTEG_EULER && !REF && MPC_TAPE) ? (FuseOf<M>::value & SITES) : 0;
+
 template <class M, int INTEG, int TK, bool REF = false>
 DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
   constexpr int N = M::N;
@@ -2952,7 +3157,7 @@ DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
     if (MI == 1) cost = __builtin_fmaf(u[0] * p.c.R[0], u[0], cost);
     else cost += control_cost<MI>(p.c, u);
     float* sl = STASH ? p.stash + (tile * p.H + t) * (long long)SS::FLOATS : nullptr;
-    f32x4 k1 = M::template f<false, TK>(L, scr, ln, x, u, Hd, sl);
+    f32x4 k1 = M::template f<false, TK, kFuseEpi<M, INTEG, REF, TK == TAPE_MPC, kFuseK1Act | kFuseK1Red>>(L, scr, ln, x, u, Hd, sl);
     if (p.dx_out && writer) store_state<N>(p.dx_out + (b * p.H + t) * N, k1);
     if (INTEG == PHNN_INTEG_EULER) {
       x = x + p.dt * k1;
@@ -3036,7 +3241,7 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
         M::template vjp<STASH, true>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
                                      STASH ? p.stash + (tile * p.H + t) * (long long)SS::TAPE : nullptr, rec);
       } else {
-        M::template vjp<STASH>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
+        M::template vjp<STASH, false, -1, kFuseEpi<M, INTEG, REF, STASH, kFuseK2Act | kFuseK2Red>>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
                                STASH ? p.stash + (tile * p.H + t) * (long long)SS::TAPE : nullptr);
       }
       lam = lam + xb;

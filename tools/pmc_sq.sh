@@ -4,6 +4,7 @@
 set -e
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/gpurun_out/pmc_sq"
+rm -rf "$OUT"  # the summary below reads the first csv of each pass: never one left by an earlier run (of another library)
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 run() {
