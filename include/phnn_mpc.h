@@ -445,7 +445,7 @@ int phnn_mppi_update(phnn_handle* h, float* u_dev, const float* samples_dev, con
  * nominal's cost S_{b,0} at every iteration.  workspace: workspace_size >= phnn_mppi_workspace_bytes.  ref: NULL = the
  * cost's x_target, else K1 tracks it; its batch_stride indexes the B*samples ROLLOUTS (rollout b*samples + k belongs to
  * problem b), so a per-problem reference is passed with one row set per rollout and a shared one with batch_stride 0.
- * Enqueues the clamp and the resets, then iters x (k_mppi_sample, K1, k_mppi_update); stream-ordered, capturable.
+ * Enqueues the clamp and the resets, then iters x (k_sample, K1, k_mppi_update); stream-ordered, capturable.
  * PHNN_ERR_INVALID_ARG for samples < 2, lambda <= 0 or non-finite, a negative or non-finite sigma, iters < 0, values
  * outside the ranges above, NULL required buffers or a too small workspace; PHNN_ERR_UNSUPPORTED for H*m > 256. */
 int phnn_solve_mppi(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
@@ -498,7 +498,7 @@ int phnn_cem_update(phnn_handle* h, float* u_dev, float* sigma_dev, const float*
  * costs_dev (iters,B) or NULL: the mean's cost S_{b,0} at every iteration.  sigma_out_dev (B,H,m) or NULL: the last
  * standard deviation (sigma_init when iters == 0).  workspace: workspace_size >= phnn_cem_workspace_bytes.  ref: as in
  * phnn_solve_mppi -- its batch_stride indexes the B*samples ROLLOUTS.
- * Enqueues the clamp and the resets, then iters x (k_cem_sample, K1, k_cem_update); stream-ordered, capturable.  B == 0
+ * Enqueues the clamp and the resets, then iters x (k_sample, K1, k_cem_update); stream-ordered, capturable.  B == 0
  * or iters == 0 returns PHNN_OK after the resets.  PHNN_ERR_INVALID_ARG for samples < 2, elites outside 1 .. samples,
  * alpha outside [0, 1), a negative or non-finite sigma_init / sigma_min, iters < 0, counter fields outside their ranges,
  * NULL required buffers or a too small workspace; PHNN_ERR_UNSUPPORTED for H*m > 256. */

@@ -57,7 +57,8 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None):
     done_step = np.full(B, -1, dtype=np.int64)
     canonical = hasattr(controller, "control_batch")
     u_prev = None
-    sampling = getattr(controller, "optimizer", getattr(controller, "optimizer_type", None)) in ("MPPI", "CrossEntropy")
+    from .solver import SAMPLING
+    sampling = getattr(controller, "optimizer", getattr(controller, "optimizer_type", None)) in SAMPLING
     for step in range(num_steps):
         rkw = {"epoch": step} if sampling else {}  # the noise counter of an MPPI / CrossEntropy solve: the control step
         if x_ref is not None:
@@ -84,7 +85,7 @@ class DeviceClosedLoop:
     k_plant_step); with use_graph the step is captured once and replayed.  Per-plant arithmetic is identical to
     run_mpc_batch (same kernels, same order); the plant differs from the numpy one only by the device's
     double-precision sin/cos.  An MPPI controller (optimizer_type / optimizer 'MPPI'): engine.solve_mppi -- the clamp
-    and resets, iters x (k_mppi_sample, K1, k_mppi_update) -- with step_dev as the noise epoch, so every replay draws the
+    and resets, iters x (k_sample, K1, k_mppi_update) -- with step_dev as the noise epoch, so every replay draws the
     noise run_mpc_batch draws at that step.  A 'CrossEntropy' controller: engine.solve_cem in the same way.
 
     x_ref: reference trajectories broadcastable to (B, rows, 4) (engine.reference_view); every solve tracks them from
@@ -119,13 +120,12 @@ class DeviceClosedLoop:
         if x_ref is not None:
             from .engine import reference_view
             self.x_ref = reference_view(x_ref, B, 4, dev)[0]
-        self.mppi = (controller.optimizer if self.canonical else controller.optimizer_type) == "MPPI"
-        self.cem = (controller.optimizer if self.canonical else controller.optimizer_type) == "CrossEntropy"
-        if self.mppi and not hasattr(eng, "solve_mppi"):
-            raise NotImplementedError(f"{type(eng).__name__} has no batched MPPI solve (RolloutEngine has)")
-        if self.cem and not hasattr(eng, "solve_cem"):
-            raise NotImplementedError(f"{type(eng).__name__} has no batched CEM solve (RolloutEngine has)")
-        if (self.mppi or self.cem) and x_ref is not None:  # one row set per rollout, expanded once, here (samples x the bytes)
+        from .solver import SAMPLING
+        # "mppi" / "cem" for a sampling controller, else None
+        self.sampling = SAMPLING.get(controller.optimizer if self.canonical else controller.optimizer_type, (None,))[0]
+        if self.sampling and not hasattr(eng, "solve_" + self.sampling):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched {self.sampling.upper()} solve (RolloutEngine has)")
+        if self.sampling and x_ref is not None:  # one row set per rollout, expanded once, here (samples x the bytes)
             self.x_ref = eng.mppi_reference(self.x_ref, B, controller.samples)
         self.iters = controller.optimizer_steps if self.canonical else controller.max_iterations
         self.lr = controller.learning_rate if self.canonical else controller.lr
@@ -142,10 +142,8 @@ class DeviceClosedLoop:
         log = dict(state_f32=self.x32, done_step=self.done_step, step_dev=self.step_dev, log_states=self.log_states,
                    log_controls=self.log_controls)
         H = self.u_init.shape[1] * self.u_init.shape[2]
-        if self.mppi:
-            out = self._solve_mppi()
-        elif self.cem:
-            out = self._solve_cem()
+        if self.sampling:
+            out = self._solve_sampling()
         elif self.lbfgs:  # the reference's L-BFGS solve
             out = eng.solve_lbfgs(self.x32, self.u_init, self.cost, integrator=c.integrator, dt=c.dt, record_costs=False,
                                   workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, **c.lbfgs_options())
@@ -160,20 +158,13 @@ class DeviceClosedLoop:
             eng.plant_step(self.plant, self.state, out["u_last"], H, u_min=c.u_min, u_max=c.u_max, **log)
             eng.advance_step(self.step_dev)
 
-    def _solve_mppi(self):
-        """engine.solve_mppi with the step counter as the noise epoch.  self.x_ref is already one row set per rollout
-        (or shared): it is handed to phnn_solve_mppi as it is, not expanded again."""
+    def _solve_sampling(self):
+        """engine.solve_mppi / engine.solve_cem with the step counter as the noise epoch.  self.x_ref is already one row
+        set per rollout (or shared): it is handed to the library as it is, not expanded again."""
         eng, c = self.eng, self.ctl
-        return eng.solve_mppi(self.x32, self.u_init, self.cost, c.integrator, c.dt, epoch=self.step_dev, record_costs=False,
-                              workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, expanded_ref=True,
-                              **c.mppi_options())
-
-    def _solve_cem(self):
-        """engine.solve_cem with the step counter as the noise epoch; the reference as in _solve_mppi."""
-        eng, c = self.eng, self.ctl
-        return eng.solve_cem(self.x32, self.u_init, self.cost, c.integrator, c.dt, epoch=self.step_dev, record_costs=False,
-                             workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, expanded_ref=True,
-                             **c.cem_options())
+        return getattr(eng, "solve_" + self.sampling)(
+            self.x32, self.u_init, self.cost, c.integrator, c.dt, epoch=self.step_dev, record_costs=False, workspace=self.ws,
+            x_ref=self.x_ref, ref_offset=self.step_dev, expanded_ref=True, **getattr(c, self.sampling + "_options")())
 
     def run(self):
         torch = self.torch

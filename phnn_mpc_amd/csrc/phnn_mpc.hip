@@ -16,8 +16,7 @@
 // phnn_grad.hip without it, would spill (K2 +5 %)
 #define PHNN_PREFETCH_BF
 #include "phnn_lbfgs.h"
-#include "phnn_mppi.h"
-#include "phnn_cem.h"
+#include "phnn_sampling.h"
 #include "phnn_pack.h"
 
 namespace {
@@ -1221,69 +1220,136 @@ int phnn_solve_lbfgs(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t 
   return PHNN_OK;
 }
 
-// ---- batched sampling (MPPI) solve: kernels in phnn_mppi.hip ------------------------------------------------------
-static int check_mppi(phnn_handle* h, const phnn_mppi_options* opt, int64_t B, int32_t H, int32_t iteration) {
-  if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options is NULL");
+// ---- batched sampling solves, MPPI and cross-entropy (CEM): kernels in phnn_sampling.hip ---------------------------
+// What phnn_mppi_options and phnn_cem_options have in common: the two counts and the noise counter's fields.
+struct SamplingCommon {
+  const char* opts;   // "phnn_mppi_options" / "phnn_cem_options": how the checks name the struct
+  const char* name;   // "MPPI" / "CEM"
+  int32_t iters, samples;
+  uint64_t seed;
+  int64_t problem_offset;
+  const int32_t* epoch_dev;
+  int32_t epoch_host;
+};
+
+// the checks both methods make, but for the width limit, which stays the last one (check_width)
+static int check_sampling(phnn_handle* h, const SamplingCommon& c, int64_t B, int32_t H, int32_t iteration) {
   if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
-  if (opt->samples < 2 || opt->samples > kMppiMaxSamples)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: samples < 2 or > 2^26");
+  if (c.samples < 2 || c.samples > kSamplingMaxSamples)
+    return fail(h, PHNN_ERR_INVALID_ARG, std::string(c.opts) + ": samples < 2 or > 2^26");
+  if (iteration < 0 || iteration >= kSamplingMaxIters || c.iters < 0 || c.iters > kSamplingMaxIters)
+    return fail(h, PHNN_ERR_INVALID_ARG, std::string(c.opts) + ": iteration count outside 0 .. 65536");
+  if (c.problem_offset < 0 || c.problem_offset > kSamplingMaxProblem - B)
+    return fail(h, PHNN_ERR_INVALID_ARG, std::string(c.opts) + ": problem ids outside 0 .. 2^48");
+  return PHNN_OK;
+}
+
+static int check_width(phnn_handle* h, const SamplingCommon& c, int32_t H) {
+  if ((int64_t)H * h->desc.m > kSamplingMaxN) return fail(h, PHNN_ERR_UNSUPPORTED, std::string(c.name) + ": H * m > 256");
+  return PHNN_OK;
+}
+
+static int check_mppi(phnn_handle* h, const phnn_mppi_options* opt, int64_t B, int32_t H, int32_t iteration, SamplingCommon* c) {
+  if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options is NULL");
+  *c = {"phnn_mppi_options", "MPPI", opt->iters, opt->samples, opt->seed, opt->problem_offset, opt->epoch_dev, opt->epoch_host};
+  if (int rc = check_sampling(h, *c, B, H, iteration)) return rc;
   if (!(opt->lambda > 0.f) || !std::isfinite(opt->lambda))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: lambda must be > 0 and finite");
   for (int i = 0; i < h->desc.m; ++i)
     if (!(opt->sigma[i] >= 0.f) || !std::isfinite(opt->sigma[i]))
       return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: sigma must be >= 0 and finite");
-  if (iteration < 0 || iteration >= kMppiMaxIters || opt->iters < 0 || opt->iters > kMppiMaxIters)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: iteration count outside 0 .. 65536");
-  if (opt->problem_offset < 0 || opt->problem_offset > kMppiMaxProblem - B)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: problem ids outside 0 .. 2^48");
-  if ((int64_t)H * h->desc.m > kMppiMaxN) return fail(h, PHNN_ERR_UNSUPPORTED, "MPPI: H * m > 256");
-  return PHNN_OK;
+  return check_width(h, *c, H);
+}
+
+static int check_cem(phnn_handle* h, const phnn_cem_options* opt, int64_t B, int32_t H, int32_t iteration, SamplingCommon* c) {
+  if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options is NULL");
+  *c = {"phnn_cem_options", "CEM", opt->iters, opt->samples, opt->seed, opt->problem_offset, opt->epoch_dev, opt->epoch_host};
+  if (int rc = check_sampling(h, *c, B, H, iteration)) return rc;
+  if (opt->elites < 1 || opt->elites > opt->samples)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: elites outside 1 .. samples");
+  if (!(opt->alpha >= 0.f) || !(opt->alpha < 1.f))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: alpha must be in [0, 1)");
+  for (int i = 0; i < h->desc.m; ++i)
+    if (!(opt->sigma_init[i] >= 0.f) || !std::isfinite(opt->sigma_init[i]))
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: sigma_init must be >= 0 and finite");
+  if (!(opt->sigma_min >= 0.f) || !std::isfinite(opt->sigma_min))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: sigma_min must be >= 0 and finite");
+  return check_width(h, *c, H);
+}
+
+static size_t sampling_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t samples, bool sigma_state) {
+  if (!h || B < 0 || H < 1 || samples < 2 || samples > kSamplingMaxSamples) return 0;
+  return sampling_layout(B, H * h->desc.m, h->desc.n, samples, sigma_state).total;
 }
 
 size_t phnn_mppi_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t samples) {
-  if (!h || B < 0 || H < 1 || samples < 2 || samples > kMppiMaxSamples) return 0;
-  return mppi_layout(B, H * h->desc.m, h->desc.n, samples).total;
+  return sampling_workspace_bytes(h, B, H, samples, false);
+}
+
+size_t phnn_cem_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t samples) {
+  return sampling_workspace_bytes(h, B, H, samples, true);
+}
+
+// One k_sample launch.  sigma_dev: the (B, N) standard deviations (CEM), or NULL: the table sigma[m] (MPPI).
+// `who`: the entry point, for the NULL-tensor message.
+static int sample(phnn_handle* h, const char* who, const SamplingCommon& c, const float* x0_dev, const float* u_dev,
+                  const float* sigma_dev, const float* sigma, int64_t B, int32_t H, const phnn_cost* cost, int32_t iteration,
+                  float* samples_dev, float* x0_rep_dev, void* stream) {
+  if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!u_dev || (!sigma && !sigma_dev) || !samples_dev || (x0_rep_dev && !x0_dev))
+    return fail(h, PHNN_ERR_INVALID_ARG, std::string(who) + ": NULL tensor");
+  PHNN_ON_DEVICE(h);
+  SampleParams p;
+  memset(&p, 0, sizeof p);
+  p.u = u_dev;
+  p.sig = sigma_dev;
+  p.x0 = x0_dev;
+  p.v = samples_dev;
+  p.x0_rep = x0_rep_dev;
+  p.B = B;
+  p.K = c.samples;
+  p.N = H * h->desc.m;
+  p.n = h->desc.n;
+  p.m = h->desc.m;
+  for (int i = 0; sigma && i < h->desc.m; ++i) p.sigma[i] = sigma[i];
+  p.u_min = cost->u_min;
+  p.u_max = cost->u_max;
+  p.has_u_bounds = cost->has_u_bounds;
+  p.key0 = (unsigned)(c.seed & 0xffffffffu);
+  p.key1 = (unsigned)(c.seed >> 32);
+  p.problem_offset = c.problem_offset;
+  p.epoch_dev = c.epoch_dev;
+  p.epoch_host = c.epoch_host;
+  p.iteration = iteration;
+  hipError_t e = sample_launch(p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "k_sample launch");
+  return PHNN_OK;
 }
 
 int phnn_mppi_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
                      const phnn_mppi_options* opt, int32_t iteration, float* samples_dev, float* x0_rep_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_mppi(h, opt, B, H, iteration)) return rc;
-  if (int rc = check_cost(h, cost)) return rc;
-  if (B == 0) return PHNN_OK;
-  if (!u_dev || !samples_dev || (x0_rep_dev && !x0_dev)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_sample: NULL tensor");
-  PHNN_ON_DEVICE(h);
-  MppiSampleParams p;
-  memset(&p, 0, sizeof p);
-  p.u = u_dev;
-  p.x0 = x0_dev;
-  p.v = samples_dev;
-  p.x0_rep = x0_rep_dev;
-  p.B = B;
-  p.K = opt->samples;
-  p.N = H * h->desc.m;
-  p.n = h->desc.n;
-  p.m = h->desc.m;
-  for (int i = 0; i < h->desc.m; ++i) p.sigma[i] = opt->sigma[i];
-  p.u_min = cost->u_min;
-  p.u_max = cost->u_max;
-  p.has_u_bounds = cost->has_u_bounds;
-  p.key0 = (unsigned)(opt->seed & 0xffffffffu);
-  p.key1 = (unsigned)(opt->seed >> 32);
-  p.problem_offset = opt->problem_offset;
-  p.epoch_dev = opt->epoch_dev;
-  p.epoch_host = opt->epoch_host;
-  p.iteration = iteration;
-  hipError_t e = mppi_sample_launch(p, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "k_mppi_sample launch");
-  return PHNN_OK;
+  SamplingCommon c;
+  if (int rc = check_mppi(h, opt, B, H, iteration, &c)) return rc;
+  return sample(h, "phnn_mppi_sample", c, x0_dev, u_dev, nullptr, opt->sigma, B, H, cost, iteration, samples_dev, x0_rep_dev, stream);
+}
+
+int phnn_cem_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* sigma_dev, int64_t B, int32_t H,
+                    const phnn_cost* cost, const phnn_cem_options* opt, int32_t iteration, float* samples_dev,
+                    float* x0_rep_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  SamplingCommon c;
+  if (int rc = check_cem(h, opt, B, H, iteration, &c)) return rc;
+  return sample(h, "phnn_cem_sample", c, x0_dev, u_dev, sigma_dev, nullptr, B, H, cost, iteration, samples_dev, x0_rep_dev, stream);
 }
 
 int phnn_mppi_update(phnn_handle* h, float* u_dev, const float* samples_dev, const float* sample_cost_dev, int64_t B,
                      int32_t H, const phnn_cost* cost, const phnn_mppi_options* opt, float* costs_row_dev,
                      float* best_cost_dev, float* best_u_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_mppi(h, opt, B, H, 0)) return rc;
+  SamplingCommon c;
+  if (int rc = check_mppi(h, opt, B, H, 0, &c)) return rc;
   if (int rc = check_cost(h, cost)) return rc;
   if (B == 0) return PHNN_OK;
   if (!u_dev || !samples_dev || !sample_cost_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_update: NULL tensor");
@@ -1310,111 +1376,12 @@ int phnn_mppi_update(phnn_handle* h, float* u_dev, const float* samples_dev, con
   return PHNN_OK;
 }
 
-int phnn_solve_mppi(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
-                    const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt, void* workspace,
-                    size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream) {
-  if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_mppi(h, opt, B, H, 0)) return rc;
-  RollParams rp;
-  if (int rc = fill_roll(h, &rp, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
-  if (int rc = fill_ref(h, &rp, ref, B)) return rc;
-  if (B == 0) return PHNN_OK;
-  if (!best_cost_dev || !best_u_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_mppi: best_cost_dev and best_u_dev are required");
-  const int N = H * h->desc.m;
-  const MppiLayout lay = mppi_layout(B, N, h->desc.n, opt->samples);
-  if (opt->iters > 0 && (!workspace || workspace_size < lay.total))
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_mppi: workspace is NULL or too small");
-  PHNN_ON_DEVICE(h);
-  hipStream_t st = (hipStream_t)stream;
-  // the entry state, before any early return: nominal in bounds, best = (+inf, 0)
-  hipError_t e = hipMemsetD32Async((hipDeviceptr_t)best_cost_dev, 0x7F800000, (size_t)B, st);
-  if (e == hipSuccess) e = hipMemsetAsync(best_u_dev, 0, sizeof(float) * (size_t)B * N, st);
-  if (e == hipSuccess && cost->has_u_bounds) e = mppi_clamp_launch(u_dev, (long long)B * N, cost->u_min, cost->u_max, st);
-  if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_mppi: state reset");
-  if (opt->iters == 0) return PHNN_OK;
-  char* ws = (char*)workspace;
-  float* v = (float*)(ws + lay.v);
-  float* x0_rep = (float*)(ws + lay.x0_rep);
-  float* s = (float*)(ws + lay.s);
-  const int64_t rollouts = B * (int64_t)opt->samples;
-  for (int it = 0; it < opt->iters; ++it) {
-    if (int rc = phnn_mppi_sample(h, x0_dev, u_dev, B, H, cost, opt, it, v, it == 0 ? x0_rep : nullptr, stream)) return rc;
-    if (int rc = rollout_fwd(h, x0_rep, v, rollouts, H, cost, integrator, dt, s, nullptr, nullptr, ref, stream)) return rc;
-    if (int rc = phnn_mppi_update(h, u_dev, v, s, B, H, cost, opt, costs_dev ? costs_dev + (size_t)it * B : nullptr, best_cost_dev,
-                                  best_u_dev, stream))
-      return rc;
-  }
-  return PHNN_OK;
-}
-
-// ---- batched cross-entropy (CEM) solve: kernels in phnn_cem.hip ---------------------------------------------------
-static int check_cem(phnn_handle* h, const phnn_cem_options* opt, int64_t B, int32_t H, int32_t iteration) {
-  if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options is NULL");
-  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
-  if (opt->samples < 2 || opt->samples > kMppiMaxSamples)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: samples < 2 or > 2^26");
-  if (opt->elites < 1 || opt->elites > opt->samples)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: elites outside 1 .. samples");
-  if (!(opt->alpha >= 0.f) || !(opt->alpha < 1.f))
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: alpha must be in [0, 1)");
-  for (int i = 0; i < h->desc.m; ++i)
-    if (!(opt->sigma_init[i] >= 0.f) || !std::isfinite(opt->sigma_init[i]))
-      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: sigma_init must be >= 0 and finite");
-  if (!(opt->sigma_min >= 0.f) || !std::isfinite(opt->sigma_min))
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: sigma_min must be >= 0 and finite");
-  if (iteration < 0 || iteration >= kMppiMaxIters || opt->iters < 0 || opt->iters > kMppiMaxIters)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: iteration count outside 0 .. 65536");
-  if (opt->problem_offset < 0 || opt->problem_offset > kMppiMaxProblem - B)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: problem ids outside 0 .. 2^48");
-  if ((int64_t)H * h->desc.m > kMppiMaxN) return fail(h, PHNN_ERR_UNSUPPORTED, "CEM: H * m > 256");
-  return PHNN_OK;
-}
-
-size_t phnn_cem_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t samples) {
-  if (!h || B < 0 || H < 1 || samples < 2 || samples > kMppiMaxSamples) return 0;
-  return cem_layout(B, H * h->desc.m, h->desc.n, samples).total;
-}
-
-int phnn_cem_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* sigma_dev, int64_t B, int32_t H,
-                    const phnn_cost* cost, const phnn_cem_options* opt, int32_t iteration, float* samples_dev,
-                    float* x0_rep_dev, void* stream) {
-  if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_cem(h, opt, B, H, iteration)) return rc;
-  if (int rc = check_cost(h, cost)) return rc;
-  if (B == 0) return PHNN_OK;
-  if (!u_dev || !sigma_dev || !samples_dev || (x0_rep_dev && !x0_dev))
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_sample: NULL tensor");
-  PHNN_ON_DEVICE(h);
-  CemSampleParams p;
-  memset(&p, 0, sizeof p);
-  p.u = u_dev;
-  p.sig = sigma_dev;
-  p.x0 = x0_dev;
-  p.v = samples_dev;
-  p.x0_rep = x0_rep_dev;
-  p.B = B;
-  p.K = opt->samples;
-  p.N = H * h->desc.m;
-  p.n = h->desc.n;
-  p.u_min = cost->u_min;
-  p.u_max = cost->u_max;
-  p.has_u_bounds = cost->has_u_bounds;
-  p.key0 = (unsigned)(opt->seed & 0xffffffffu);
-  p.key1 = (unsigned)(opt->seed >> 32);
-  p.problem_offset = opt->problem_offset;
-  p.epoch_dev = opt->epoch_dev;
-  p.epoch_host = opt->epoch_host;
-  p.iteration = iteration;
-  hipError_t e = cem_sample_launch(p, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "k_cem_sample launch");
-  return PHNN_OK;
-}
-
 int phnn_cem_update(phnn_handle* h, float* u_dev, float* sigma_dev, const float* samples_dev, const float* sample_cost_dev,
                     int64_t B, int32_t H, const phnn_cost* cost, const phnn_cem_options* opt, float* costs_row_dev,
                     float* best_cost_dev, float* best_u_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_cem(h, opt, B, H, 0)) return rc;
+  SamplingCommon c;
+  if (int rc = check_cem(h, opt, B, H, 0, &c)) return rc;
   if (int rc = check_cost(h, cost)) return rc;
   if (B == 0) return PHNN_OK;
   if (!u_dev || !sigma_dev || !samples_dev || !sample_cost_dev)
@@ -1445,51 +1412,89 @@ int phnn_cem_update(phnn_handle* h, float* u_dev, float* sigma_dev, const float*
   return PHNN_OK;
 }
 
+// The solve of both methods, after the method's argument check: the entry state (best = (+inf, 0), u in bounds, and
+// with sigma_init -- CEM -- a sigma state (B, N) in the workspace set to it), then iters x (sample, K1, update).
+//   sample_step(it, sig, v, x0_rep) and update_step(sig, v, s, costs_row) are the method's entry points; sig is NULL
+//   without a sigma state.  sigma_out_dev (or NULL) receives the last sigma state, sigma_init when iters == 0.
+extern "C++" {  // a template: the steps are the callers' lambdas
+template <class SampleStep, class UpdateStep>
+static int solve_sampling(phnn_handle* h, const char* who, const SamplingCommon& c, const float* x0_dev, float* u_dev, int64_t B,
+                          int32_t H, const phnn_cost* cost, const phnn_reference* ref, int32_t integrator, float dt,
+                          const float* sigma_init, void* workspace, size_t workspace_size, float* costs_dev, float* best_cost_dev,
+                          float* best_u_dev, float* sigma_out_dev, void* stream, SampleStep sample_step, UpdateStep update_step) {
+  RollParams rp;
+  if (int rc = fill_roll(h, &rp, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
+  if (int rc = fill_ref(h, &rp, ref, B)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!best_cost_dev || !best_u_dev) return fail(h, PHNN_ERR_INVALID_ARG, std::string(who) + ": best_cost_dev and best_u_dev are required");
+  const int N = H * h->desc.m;
+  const SamplingLayout lay = sampling_layout(B, N, h->desc.n, c.samples, sigma_init != nullptr);
+  if (c.iters > 0 && (!workspace || workspace_size < lay.total))
+    return fail(h, PHNN_ERR_INVALID_ARG, std::string(who) + ": workspace is NULL or too small");
+  PHNN_ON_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  // the entry state, before any early return
+  hipError_t e = hipMemsetD32Async((hipDeviceptr_t)best_cost_dev, 0x7F800000, (size_t)B, st);
+  if (e == hipSuccess) e = hipMemsetAsync(best_u_dev, 0, sizeof(float) * (size_t)B * N, st);
+  if (e == hipSuccess && cost->has_u_bounds) e = clamp_launch(u_dev, (long long)B * N, cost->u_min, cost->u_max, st);
+  if (e == hipSuccess && c.iters == 0 && sigma_init && sigma_out_dev)
+    e = sigma_init_launch(sigma_out_dev, (long long)B * N, h->desc.m, sigma_init, st);
+  if (e != hipSuccess) return hip_fail(h, e, (std::string(who) + ": state reset").c_str());
+  if (c.iters == 0) return PHNN_OK;
+  char* ws = (char*)workspace;
+  float* v = (float*)(ws + lay.v);
+  float* x0_rep = (float*)(ws + lay.x0_rep);
+  float* s = (float*)(ws + lay.s);
+  float* sig = sigma_init ? (float*)(ws + lay.sig) : nullptr;
+  if (sig) {
+    e = sigma_init_launch(sig, (long long)B * N, h->desc.m, sigma_init, st);
+    if (e != hipSuccess) return hip_fail(h, e, (std::string(who) + ": sigma reset").c_str());
+  }
+  const int64_t rollouts = B * (int64_t)c.samples;
+  for (int it = 0; it < c.iters; ++it) {
+    if (int rc = sample_step(it, sig, v, it == 0 ? x0_rep : nullptr)) return rc;
+    if (int rc = rollout_fwd(h, x0_rep, v, rollouts, H, cost, integrator, dt, s, nullptr, nullptr, ref, stream)) return rc;
+    if (int rc = update_step(sig, v, s, costs_dev ? costs_dev + (size_t)it * B : nullptr)) return rc;
+  }
+  if (sig && sigma_out_dev) {
+    e = hipMemcpyAsync(sigma_out_dev, sig, sizeof(float) * (size_t)B * N, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return hip_fail(h, e, (std::string(who) + ": sigma copy").c_str());
+  }
+  return PHNN_OK;
+}
+}  // extern "C++"
+
+int phnn_solve_mppi(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                    const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt, void* workspace,
+                    size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  SamplingCommon c;
+  if (int rc = check_mppi(h, opt, B, H, 0, &c)) return rc;
+  return solve_sampling(
+      h, "phnn_solve_mppi", c, x0_dev, u_dev, B, H, cost, ref, integrator, dt, nullptr, workspace, workspace_size, costs_dev,
+      best_cost_dev, best_u_dev, nullptr, stream,
+      [&](int it, float*, float* v, float* x0_rep) { return phnn_mppi_sample(h, x0_dev, u_dev, B, H, cost, opt, it, v, x0_rep, stream); },
+      [&](float*, const float* v, const float* s, float* costs_row) {
+        return phnn_mppi_update(h, u_dev, v, s, B, H, cost, opt, costs_row, best_cost_dev, best_u_dev, stream);
+      });
+}
+
 int phnn_solve_cem(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
                    const phnn_reference* ref, int32_t integrator, float dt, const phnn_cem_options* opt, void* workspace,
                    size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, float* sigma_out_dev,
                    void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_cem(h, opt, B, H, 0)) return rc;
-  RollParams rp;
-  if (int rc = fill_roll(h, &rp, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
-  if (int rc = fill_ref(h, &rp, ref, B)) return rc;
-  if (B == 0) return PHNN_OK;
-  if (!best_cost_dev || !best_u_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_cem: best_cost_dev and best_u_dev are required");
-  const int N = H * h->desc.m;
-  const CemLayout lay = cem_layout(B, N, h->desc.n, opt->samples);
-  if (opt->iters > 0 && (!workspace || workspace_size < lay.total))
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_cem: workspace is NULL or too small");
-  PHNN_ON_DEVICE(h);
-  hipStream_t st = (hipStream_t)stream;
-  // the entry state, before any early return: mean in bounds, best = (+inf, 0), sigma = sigma_init
-  hipError_t e = hipMemsetD32Async((hipDeviceptr_t)best_cost_dev, 0x7F800000, (size_t)B, st);
-  if (e == hipSuccess) e = hipMemsetAsync(best_u_dev, 0, sizeof(float) * (size_t)B * N, st);
-  if (e == hipSuccess && cost->has_u_bounds) e = mppi_clamp_launch(u_dev, (long long)B * N, cost->u_min, cost->u_max, st);
-  if (e == hipSuccess && opt->iters == 0 && sigma_out_dev)
-    e = cem_sigma_init_launch(sigma_out_dev, (long long)B * N, h->desc.m, opt->sigma_init, st);
-  if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_cem: state reset");
-  if (opt->iters == 0) return PHNN_OK;
-  char* ws = (char*)workspace;
-  float* v = (float*)(ws + lay.v);
-  float* x0_rep = (float*)(ws + lay.x0_rep);
-  float* s = (float*)(ws + lay.s);
-  float* sig = (float*)(ws + lay.sig);
-  e = cem_sigma_init_launch(sig, (long long)B * N, h->desc.m, opt->sigma_init, st);
-  if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_cem: sigma reset");
-  const int64_t rollouts = B * (int64_t)opt->samples;
-  for (int it = 0; it < opt->iters; ++it) {
-    if (int rc = phnn_cem_sample(h, x0_dev, u_dev, sig, B, H, cost, opt, it, v, it == 0 ? x0_rep : nullptr, stream)) return rc;
-    if (int rc = rollout_fwd(h, x0_rep, v, rollouts, H, cost, integrator, dt, s, nullptr, nullptr, ref, stream)) return rc;
-    if (int rc = phnn_cem_update(h, u_dev, sig, v, s, B, H, cost, opt, costs_dev ? costs_dev + (size_t)it * B : nullptr,
-                                 best_cost_dev, best_u_dev, stream))
-      return rc;
-  }
-  if (sigma_out_dev) {
-    e = hipMemcpyAsync(sigma_out_dev, sig, sizeof(float) * (size_t)B * N, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_cem: sigma copy");
-  }
-  return PHNN_OK;
+  SamplingCommon c;
+  if (int rc = check_cem(h, opt, B, H, 0, &c)) return rc;
+  return solve_sampling(
+      h, "phnn_solve_cem", c, x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt->sigma_init, workspace, workspace_size, costs_dev,
+      best_cost_dev, best_u_dev, sigma_out_dev, stream,
+      [&](int it, float* sig, float* v, float* x0_rep) {
+        return phnn_cem_sample(h, x0_dev, u_dev, sig, B, H, cost, opt, it, v, x0_rep, stream);
+      },
+      [&](float* sig, const float* v, const float* s, float* costs_row) {
+        return phnn_cem_update(h, u_dev, sig, v, s, B, H, cost, opt, costs_row, best_cost_dev, best_u_dev, stream);
+      });
 }
 
 int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, const float* action_dev,

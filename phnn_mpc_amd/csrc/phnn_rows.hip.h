@@ -1,4 +1,4 @@
-// phnn_rows.hip.h -- device helpers shared by the sampling solves (phnn_mppi.hip, phnn_cem.hip): the Philox4x32-10
+// phnn_rows.hip.h -- device helpers shared by the sampling solves (phnn_sampling.hip): the Philox4x32-10
 // noise source with its uniforms and Box-Muller, and the 16-lane (one DPP row) per-problem geometry: butterfly
 // reductions that leave identical bits in every lane, and loads / stores of a lane's float4s of an unpadded row.
 // DESIGN.md sections 12 and 13.

@@ -509,23 +509,25 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return {"u_last": u, "costs": costs, "n_iter": n_iter, "func_evals": func_evals}
 
-    # ------------------------------------------------------------------ batched sampling (MPPI) solve (k_mppi_sample, K1, k_mppi_update)
+    # ------------------------------------------------------------------ batched sampling solves, MPPI and CEM (k_sample, K1, k_mppi_update / k_cem_update)
     def mppi_workspace_bytes(self, B, H, samples):
         return int(self.lib.phnn_mppi_workspace_bytes(self.h, int(B), int(H), int(samples)))
 
-    def _mppi_options(self, iters, samples, lam, sigma, seed, epoch, problem_offset):
-        """-> (phnn_mppi_options, what to keep alive).  sigma: one value or one per control component; epoch: int or a
-        device int32 tensor (its first element is read by every launch; a captured graph follows it)."""
-        opt = _capi.MppiOptions()
+    def cem_workspace_bytes(self, B, H, samples):
+        return int(self.lib.phnn_cem_workspace_bytes(self.h, int(B), int(H), int(samples)))
+
+    def _sampling_options(self, opt, sigma_field, iters, samples, sigma, seed, epoch, problem_offset):
+        """Fills what phnn_mppi_options and phnn_cem_options share -> (opt, what to keep alive).  sigma (into the struct's
+        sigma_field): one value or one per control component; epoch: int or a device int32 tensor (its first element is
+        read by every launch; a captured graph follows it)."""
         opt.iters, opt.samples = int(iters), int(samples)
-        setattr(opt, "lambda", float(lam))
         sig = np.asarray(sigma, dtype=np.float64).reshape(-1)
         if sig.size == 1:
             sig = np.repeat(sig, self.m)
         if sig.shape != (self.m,):
             raise ValueError(f"sigma: one value or one per control component (m = {self.m}), got {sigma!r}")
         for i in range(self.m):
-            opt.sigma[i] = float(sig[i])
+            sigma_field[i] = float(sig[i])
         if not 0 <= int(seed) < 2 ** 64:
             raise ValueError("seed must fit 64 bits")
         opt.seed, opt.problem_offset = int(seed), int(problem_offset)
@@ -537,25 +539,45 @@ class RolloutEngine:
             opt.epoch_host = int(epoch)
         return opt, epoch
 
-    def _mppi_buffers(self, ws, B, H, samples):
-        """The sample tensor (B*K, H, m), replicated x0 (B*K, n) and K1 cost vector (B*K) of an MPPI problem, as views of
-        one phnn_mppi_workspace_bytes buffer kept in the dict `ws` (the layout phnn_solve_mppi uses)."""
+    def _mppi_options(self, iters, samples, lam, sigma, seed, epoch, problem_offset):
+        """-> (phnn_mppi_options, what to keep alive); sigma and the counter fields as in _sampling_options."""
+        opt = _capi.MppiOptions()
+        setattr(opt, "lambda", float(lam))
+        return self._sampling_options(opt, opt.sigma, iters, samples, sigma, seed, epoch, problem_offset)
+
+    def _cem_options(self, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch, problem_offset):
+        """-> (phnn_cem_options, what to keep alive).  sigma: the initial standard deviation."""
+        opt = _capi.CemOptions()
+        opt.elites, opt.alpha, opt.sigma_min = int(elites), float(alpha), float(sigma_min)
+        return self._sampling_options(opt, opt.sigma_init, iters, samples, sigma, seed, epoch, problem_offset)
+
+    def _sampling_buffers(self, ws, meth, B, H, samples):
+        """The sample tensor (B*K, H, m), replicated x0 (B*K, n), K1 cost vector (B*K) and, for CEM, the sigma state
+        (B, H, m) of a sampling problem, as views ws[meth + "_v" | "_x0" | "_s" | "_sig"] of one
+        phnn_<meth>_workspace_bytes buffer ws[meth] kept in the dict `ws` (the layout phnn_solve_<meth> uses)."""
         key = (B, H, int(samples))
-        if ws.get("mppi_key") != key:
-            ws["mppi_key"] = key
-            nbytes = self.mppi_workspace_bytes(B, H, samples)  # 0: arguments the library call itself will refuse
-            buf = ws["mppi"] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-            R, N = (B * int(samples) if nbytes else 0), H * self.m
-            a256 = lambda x: (x + 255) & ~255
-            o_x0 = a256(4 * R * N)
-            o_s = a256(o_x0 + 4 * R * self.n)
-            ws["mppi_v"] = buf[: 4 * R * N].view(torch.float32).view(R, H, self.m)
-            ws["mppi_x0"] = buf[o_x0: o_x0 + 4 * R * self.n].view(torch.float32).view(R, self.n)
-            ws["mppi_s"] = buf[o_s: o_s + 4 * R].view(torch.float32)
+        if ws.get(meth + "_key") != key:
+            ws[meth + "_key"] = key
+            nbytes = getattr(self, meth + "_workspace_bytes")(B, H, samples)  # 0: arguments the library call itself will refuse
+            buf = ws[meth] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            nb = B if nbytes else 0
+            R = nb * int(samples)
+            regions = [("_v", (R, H, self.m)), ("_x0", (R, self.n)), ("_s", (R,))] + [("_sig", (nb, H, self.m))] * (meth == "cem")
+            off = 0
+            for name, shape in regions:  # each region 256-byte aligned
+                end = off + 4 * int(np.prod(shape))
+                ws[meth + name] = buf[off:end].view(torch.float32).view(shape)
+                off = (end + 255) & ~255
         return ws
 
+    def _mppi_buffers(self, ws, B, H, samples):
+        return self._sampling_buffers(ws, "mppi", B, H, samples)
+
+    def _cem_buffers(self, ws, B, H, samples):
+        return self._sampling_buffers(ws, "cem", B, H, samples)
+
     def mppi_reference(self, x_ref, B, samples):
-        """The reference as the B * samples rollouts of an MPPI solve see it: one shared by all problems goes straight
+        """The reference as the B * samples rollouts of a sampling solve see it: one shared by all problems goes straight
         through (batch stride 0); a per-problem one is expanded on the device to one row set per rollout (rollout
         b * samples + k tracks problem b's), samples times its bytes."""
         if x_ref is None:
@@ -565,39 +587,89 @@ class RolloutEngine:
             return t[:1]
         return (t[:, :1] if ts == 0 else t).repeat_interleave(int(samples), dim=0)
 
-    def mppi_sample(self, x0, u, cost, samples, sigma, seed, iteration, epoch=0, problem_offset=0, workspace=None):
-        """k_mppi_sample.  x0 (B,n), nominal u (B,H,m) -> (v (B*samples,H,m), x0 replicated (B*samples,n)): sample
-        b * samples + k is clamp(u_b + sigma o z), z standard normal from the Philox counter (seed, epoch, iteration,
-        problem_offset + b, k) and zero for k = 0.  The outputs are views of `workspace` (a dict reused across calls)."""
+    def _assert_device_f32(self, *tensors):
+        for t in tensors:
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device)
+
+    def _sample(self, meth, opt, x0, u, sig, cost, iteration, workspace):
+        """phnn_<meth>_sample; sig: the method's extra input tensors (CEM's standard deviation)."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u, H = self._controls(u, B)
-        ws = self._mppi_buffers({} if workspace is None else workspace, B, H, samples)
-        opt, _keep = self._mppi_options(0, samples, 1.0, sigma, seed, epoch, problem_offset)
-        rc = self.lib.phnn_mppi_sample(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), C.byref(opt), int(iteration),
-                                       self._p(ws["mppi_v"]), self._p(ws["mppi_x0"]), self._stream())
+        self._assert_device_f32(*sig)
+        assert all(t.numel() == u.numel() for t in sig)
+        ws = self._sampling_buffers({} if workspace is None else workspace, meth, B, H, opt.samples)
+        rc = getattr(self.lib, f"phnn_{meth}_sample")(self.h, self._p(x0), self._p(u), *map(self._p, sig), B, H, C.byref(cost),
+                                                      C.byref(opt), int(iteration), self._p(ws[meth + "_v"]),
+                                                      self._p(ws[meth + "_x0"]), self._stream())
         _check(self.lib, self.h, rc)
-        return ws["mppi_v"], ws["mppi_x0"]
+        return ws[meth + "_v"], ws[meth + "_x0"]
+
+    def mppi_sample(self, x0, u, cost, samples, sigma, seed, iteration, epoch=0, problem_offset=0, workspace=None):
+        """k_sample with MPPI's sigma.  x0 (B,n), nominal u (B,H,m) -> (v (B*samples,H,m), x0 replicated (B*samples,n)):
+        sample b * samples + k is clamp(u_b + sigma o z), z standard normal from the Philox counter (seed, epoch, iteration,
+        problem_offset + b, k) and zero for k = 0.  The outputs are views of `workspace` (a dict reused across calls)."""
+        opt, _keep = self._mppi_options(0, samples, 1.0, sigma, seed, epoch, problem_offset)
+        return self._sample("mppi", opt, x0, u, (), cost, iteration, workspace)
+
+    def cem_sample(self, x0, u, sig, cost, samples, seed, iteration, epoch=0, problem_offset=0, workspace=None):
+        """k_sample with CEM's sigma: as mppi_sample with a standard deviation sig (B,H,m) per problem and element,
+        sample b * samples + k = clamp(u_b + sig_b o z)."""
+        opt, _keep = self._cem_options(0, samples, 1, 0.0, 0.0, 0.0, seed, epoch, problem_offset)
+        return self._sample("cem", opt, x0, u, (sig,), cost, iteration, workspace)
+
+    def _update(self, meth, options, u, sig, v, s, cost, costs_row, best_cost, best_u):
+        """phnn_<meth>_update; options(samples) -> the method's options struct, sig as in _sample."""
+        self._assert_device_f32(u, *sig, v, s, costs_row, best_cost, best_u)
+        B, H = u.shape[0], u.shape[1]
+        samples = s.numel() // max(B, 1)
+        assert v.numel() == B * samples * H * self.m and s.numel() == B * samples and all(t.numel() == u.numel() for t in sig)
+        opt, _keep = options(samples)
+        rc = getattr(self.lib, f"phnn_{meth}_update")(self.h, self._p(u), *map(self._p, sig), self._p(v), self._p(s), B, H,
+                                                      C.byref(cost), C.byref(opt), self._p(costs_row), self._p(best_cost),
+                                                      self._p(best_u), self._stream())
+        _check(self.lib, self.h, rc)
 
     def mppi_update(self, u, v, s, lam, cost, costs_row=None, best_cost=None, best_u=None):
         """k_mppi_update, in place on the nominal u (B,H,m): u_b = clamp(sum_k w_k v_{b,k} / sum_k w_k) with
         w_k = exp(-(s_{b,k} - min_k s_b) / lam) over the samples v (B*K,H,m) of costs s (B*K); the clamp is the cost's.  costs_row (B) receives
         s_{b,0}; best_cost (B) / best_u (B,H,m) the lowest-cost sample seen so far (strict '<', lowest k on ties)."""
-        for t in (u, v, s, costs_row, best_cost, best_u):
-            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device)
-        B, H = u.shape[0], u.shape[1]
-        samples = s.numel() // max(B, 1)
-        assert v.numel() == B * samples * H * self.m and s.numel() == B * samples
-        opt, _keep = self._mppi_options(0, samples, lam, 0.0, 0, 0, 0)
-        rc = self.lib.phnn_mppi_update(self.h, self._p(u), self._p(v), self._p(s), B, H, C.byref(cost), C.byref(opt),
-                                       self._p(costs_row),
-                                       self._p(best_cost), self._p(best_u), self._stream())
+        self._update("mppi", lambda K: self._mppi_options(0, K, lam, 0.0, 0, 0, 0), u, (), v, s, cost, costs_row, best_cost, best_u)
+
+    def cem_update(self, u, sig, v, s, elites, alpha, sigma_min, cost, costs_row=None, best_cost=None, best_u=None):
+        """k_cem_update, in place on the mean u and the standard deviation sig (B,H,m): both refitted to the `elites`
+        samples of lowest finite cost (cost, then sample index) among v (B*K,H,m) with costs s (B*K):
+        u = clamp(alpha u + (1 - alpha) mean), sig = max(sigma_min, sqrt(alpha sig^2 + (1 - alpha) var)); the clamp is
+        the cost's.  costs_row (B) receives s_{b,0}; best_cost (B) / best_u (B,H,m) the lowest-cost sample seen so far."""
+        self._update("cem", lambda K: self._cem_options(0, K, elites, alpha, 0.0, sigma_min, 0, 0, 0), u, (sig,), v, s, cost,
+                     costs_row, best_cost, best_u)
+
+    def _solve_sampling(self, meth, opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
+                        expanded_ref):
+        """phnn_solve_<meth> -> dict(u_last, [sigma_last (CEM),] costs, best_u, best_cost)."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u_init, H = self._controls(u_init, B)
+        integ = self._integ(integrator)
+        ws = self._sampling_buffers(self._roll_workspace(workspace, B, H, integ), meth, B, H, opt.samples)
+        f = dict(dtype=torch.float32, device=self.device)
+        u = u_init.detach().clone().contiguous()
+        costs = torch.empty(max(opt.iters, 0), B, **f) if record_costs else None
+        best_cost, best_u = torch.empty(B, **f), torch.empty(B, H, self.m, **f)
+        sig = (torch.empty(B, H, self.m, **f),) if meth == "cem" else ()
+        ref, _keep_ref = self._reference(x_ref if expanded_ref else self.mppi_reference(x_ref, B, opt.samples), ref_offset,
+                                         B * opt.samples)
+        rc = getattr(self.lib, "phnn_solve_" + meth)(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
+                                                     None if ref is None else C.byref(ref), integ, float(dt), C.byref(opt),
+                                                     self._p(ws[meth]), ws[meth].numel(), self._p(costs), self._p(best_cost),
+                                                     self._p(best_u), *map(self._p, sig), self._stream())
         _check(self.lib, self.h, rc)
+        return {"u_last": u, **({"sigma_last": sig[0]} if sig else {}), "costs": costs, "best_u": best_u, "best_cost": best_cost}
 
     def solve_mppi(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=4, samples=64, lam=1.0, sigma=1.0, seed=0,
                    epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0, expanded_ref=False):
         """phnn_solve_mppi: sampling MPC (MPPI) on B independent problems as ONE library call: the nominal is clamped,
-        then iters x (k_mppi_sample, K1 over B * samples rollouts, k_mppi_update); no gradient is taken anywhere.
+        then iters x (k_sample, K1 over B * samples rollouts, k_mppi_update); no gradient is taken anywhere.
         -> dict(u_last (B,H,m) last nominal (in bounds), costs (iters,B) the nominal's cost at every iteration or None,
         best_u (B,H,m) / best_cost (B) the best sample over all iterations), same results bit for bit as
         solver.mppi_solve.  sigma: noise standard deviation, one value or one per control component; lam: softmin
@@ -605,120 +677,24 @@ class RolloutEngine:
         (problem b's noise depends on problem_offset + b, not on the batch).  x_ref, ref_offset: as in rollout_cost; a
         per-problem reference is expanded to one row set per rollout (mppi_reference: samples times its bytes) once per
         call, unless expanded_ref says x_ref already is what mppi_reference returned (a closed loop expands it once)."""
-        x0 = self._t(x0, (-1, self.n))
-        B = x0.shape[0]
-        u_init, H = self._controls(u_init, B)
-        integ = self._integ(integrator)
-        ws = self._mppi_buffers(self._roll_workspace(workspace, B, H, integ), B, H, samples)
-        f = dict(dtype=torch.float32, device=self.device)
-        u = u_init.detach().clone().contiguous()
-        costs = torch.empty(max(int(iters), 0), B, **f) if record_costs else None
-        best_cost, best_u = torch.empty(B, **f), torch.empty(B, H, self.m, **f)
         opt, _keep = self._mppi_options(iters, samples, lam, sigma, seed, epoch, problem_offset)
-        ref, _keep_ref = self._reference(x_ref if expanded_ref else self.mppi_reference(x_ref, B, samples), ref_offset,
-                                         B * int(samples))
-        rc = self.lib.phnn_solve_mppi(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
-                                      None if ref is None else C.byref(ref), integ, float(dt), C.byref(opt),
-                                      self._p(ws["mppi"]), ws["mppi"].numel(), self._p(costs), self._p(best_cost),
-                                      self._p(best_u), self._stream())
-        _check(self.lib, self.h, rc)
-        return {"u_last": u, "costs": costs, "best_u": best_u, "best_cost": best_cost}
-
-    # ------------------------------------------------------------------ batched cross-entropy (CEM) solve (k_cem_sample, K1, k_cem_update)
-    def cem_workspace_bytes(self, B, H, samples):
-        return int(self.lib.phnn_cem_workspace_bytes(self.h, int(B), int(H), int(samples)))
-
-    def _cem_options(self, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch, problem_offset):
-        """-> (phnn_cem_options, what to keep alive).  sigma: the initial standard deviation, one value or one per control
-        component; the counter fields as in _mppi_options."""
-        mo, keep = self._mppi_options(iters, samples, 1.0, sigma, seed, epoch, problem_offset)
-        opt = _capi.CemOptions()
-        opt.iters, opt.samples, opt.elites = mo.iters, mo.samples, int(elites)
-        opt.alpha, opt.sigma_min = float(alpha), float(sigma_min)
-        for i in range(self.m):
-            opt.sigma_init[i] = mo.sigma[i]
-        opt.seed, opt.problem_offset, opt.epoch_dev, opt.epoch_host = mo.seed, mo.problem_offset, mo.epoch_dev, mo.epoch_host
-        return opt, keep
-
-    def _cem_buffers(self, ws, B, H, samples):
-        """The MPPI views (_mppi_buffers: sample tensor, replicated x0, K1 cost vector) and the sigma state (B, H, m) of a
-        CEM problem, as views of one phnn_cem_workspace_bytes buffer kept in the dict `ws` (phnn_solve_cem's layout)."""
-        key = (B, H, int(samples))
-        if ws.get("cem_key") != key:
-            ws["cem_key"] = key
-            nbytes = self.cem_workspace_bytes(B, H, samples)  # 0: arguments the library call itself will refuse
-            buf = ws["cem"] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-            R, N = (B * int(samples) if nbytes else 0), H * self.m
-            a256 = lambda x: (x + 255) & ~255
-            o_x0 = a256(4 * R * N)
-            o_s = a256(o_x0 + 4 * R * self.n)
-            o_sig = a256(o_s + 4 * R)
-            nb = B if nbytes else 0
-            ws["cem_v"] = buf[: 4 * R * N].view(torch.float32).view(R, H, self.m)
-            ws["cem_x0"] = buf[o_x0: o_x0 + 4 * R * self.n].view(torch.float32).view(R, self.n)
-            ws["cem_s"] = buf[o_s: o_s + 4 * R].view(torch.float32)
-            ws["cem_sig"] = buf[o_sig: o_sig + 4 * nb * N].view(torch.float32).view(nb, H, self.m)
-        return ws
-
-    def cem_sample(self, x0, u, sig, cost, samples, seed, iteration, epoch=0, problem_offset=0, workspace=None):
-        """k_cem_sample.  x0 (B,n), mean u (B,H,m), standard deviation sig (B,H,m) -> (v (B*samples,H,m), x0 replicated
-        (B*samples,n)): sample b * samples + k is clamp(u_b + sig_b o z), z standard normal from the Philox counter (seed,
-        epoch, iteration, problem_offset + b, k) and zero for k = 0.  The outputs are views of `workspace`."""
-        x0 = self._t(x0, (-1, self.n))
-        B = x0.shape[0]
-        u, H = self._controls(u, B)
-        assert sig.is_contiguous() and sig.dtype == torch.float32 and sig.device == self.device and sig.numel() == u.numel()
-        ws = self._cem_buffers({} if workspace is None else workspace, B, H, samples)
-        opt, _keep = self._cem_options(0, samples, 1, 0.0, 0.0, 0.0, seed, epoch, problem_offset)
-        rc = self.lib.phnn_cem_sample(self.h, self._p(x0), self._p(u), self._p(sig), B, H, C.byref(cost), C.byref(opt),
-                                      int(iteration), self._p(ws["cem_v"]), self._p(ws["cem_x0"]), self._stream())
-        _check(self.lib, self.h, rc)
-        return ws["cem_v"], ws["cem_x0"]
-
-    def cem_update(self, u, sig, v, s, elites, alpha, sigma_min, cost, costs_row=None, best_cost=None, best_u=None):
-        """k_cem_update, in place on the mean u and the standard deviation sig (B,H,m): both refitted to the `elites`
-        samples of lowest finite cost (cost, then sample index) among v (B*K,H,m) with costs s (B*K):
-        u = clamp(alpha u + (1 - alpha) mean), sig = max(sigma_min, sqrt(alpha sig^2 + (1 - alpha) var)); the clamp is
-        the cost's.  costs_row (B) receives s_{b,0}; best_cost (B) / best_u (B,H,m) the lowest-cost sample seen so far."""
-        for t in (u, sig, v, s, costs_row, best_cost, best_u):
-            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device)
-        B, H = u.shape[0], u.shape[1]
-        samples = s.numel() // max(B, 1)
-        assert v.numel() == B * samples * H * self.m and s.numel() == B * samples and sig.numel() == u.numel()
-        opt, _keep = self._cem_options(0, samples, elites, alpha, 0.0, sigma_min, 0, 0, 0)
-        rc = self.lib.phnn_cem_update(self.h, self._p(u), self._p(sig), self._p(v), self._p(s), B, H, C.byref(cost),
-                                      C.byref(opt), self._p(costs_row), self._p(best_cost), self._p(best_u), self._stream())
-        _check(self.lib, self.h, rc)
+        return self._solve_sampling("mppi", opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
+                                    expanded_ref)
 
     def solve_cem(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=4, samples=64, elites=8, alpha=0.25, sigma=1.0,
                   sigma_min=0.05, seed=0, epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None,
                   ref_offset=0, expanded_ref=False):
         """phnn_solve_cem: sampling MPC by the cross-entropy method on B independent problems as ONE library call: the
-        mean is clamped and the standard deviation set to sigma, then iters x (k_cem_sample, K1 over B * samples
+        mean is clamped and the standard deviation set to sigma, then iters x (k_sample, K1 over B * samples
         rollouts, k_cem_update); no gradient is taken anywhere.  -> dict(u_last (B,H,m) last mean (in bounds), sigma_last
         (B,H,m) last standard deviation, costs (iters,B) the mean's cost at every iteration or None, best_u (B,H,m) /
         best_cost (B) the best sample over all iterations), same results bit for bit as solver.cem_solve.  elites: how
         many of the lowest-cost samples mean and standard deviation are refitted to; alpha: smoothing in [0, 1);
         sigma: initial standard deviation, one value or one per control component; sigma_min: its floor.  seed, epoch,
         problem_offset, x_ref, ref_offset, expanded_ref: as in solve_mppi."""
-        x0 = self._t(x0, (-1, self.n))
-        B = x0.shape[0]
-        u_init, H = self._controls(u_init, B)
-        integ = self._integ(integrator)
-        ws = self._cem_buffers(self._roll_workspace(workspace, B, H, integ), B, H, samples)
-        f = dict(dtype=torch.float32, device=self.device)
-        u = u_init.detach().clone().contiguous()
-        costs = torch.empty(max(int(iters), 0), B, **f) if record_costs else None
-        best_cost, best_u, sig = torch.empty(B, **f), torch.empty(B, H, self.m, **f), torch.empty(B, H, self.m, **f)
         opt, _keep = self._cem_options(iters, samples, elites, alpha, sigma, sigma_min, seed, epoch, problem_offset)
-        ref, _keep_ref = self._reference(x_ref if expanded_ref else self.mppi_reference(x_ref, B, samples), ref_offset,
-                                         B * int(samples))
-        rc = self.lib.phnn_solve_cem(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
-                                     None if ref is None else C.byref(ref), integ, float(dt), C.byref(opt),
-                                     self._p(ws["cem"]), ws["cem"].numel(), self._p(costs), self._p(best_cost),
-                                     self._p(best_u), self._p(sig), self._stream())
-        _check(self.lib, self.h, rc)
-        return {"u_last": u, "sigma_last": sig, "costs": costs, "best_u": best_u, "best_cost": best_cost}
+        return self._solve_sampling("cem", opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
+                                    expanded_ref)
 
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,

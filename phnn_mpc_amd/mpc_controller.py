@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import cem_solver_for, lbfgs_solver_for, mppi_solver_for, solver_for
+from .solver import SAMPLING, lbfgs_solver_for, solver_for
 
 
 class MPCController:
@@ -136,10 +136,8 @@ class MPCController:
         epoch (MPPI, CrossEntropy): the noise counter of this solve; None: self.epoch, which then advances by one."""
         if self.optimizer_type == "LBFGS":
             return self._solve_batch_lbfgs(states, record_costs, x_ref, ref_offset)
-        if self.optimizer_type == "MPPI":
-            return self._solve_batch_mppi(states, record_costs, x_ref, ref_offset, epoch)
-        if self.optimizer_type == "CrossEntropy":
-            return self._solve_batch_cem(states, record_costs, x_ref, ref_offset, epoch)
+        if self.optimizer_type in SAMPLING:
+            return self._solve_batch_sampling(states, record_costs, x_ref, ref_offset, epoch)
         if self.optimizer_type != "Adam":
             raise ValueError(f"Unknown optimizer type: {self.optimizer_type}")
         eng = self.engine
@@ -185,34 +183,28 @@ class MPCController:
         self._epoch_dev.fill_(int(epoch))
         return self._epoch_dev
 
-    def _solve_batch_mppi(self, states, record_costs, x_ref, ref_offset, epoch):
-        """B independent sampling solves (cold start from zeros) in one batched device solve (engine.solve_mppi)."""
-        eng = self.engine
-        self._graphed_mppi = mppi_solver_for(eng, self.use_graph, getattr(self, "_graphed_mppi", None))
-        x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
-        u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
-        return self._graphed_mppi(eng, x0, u0, self._cost(), self.integrator, self.dt, epoch=self._mppi_epoch(eng, epoch),
-                                  record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **self.mppi_options())
-
     def cem_options(self):
         """solve_cem keyword arguments of this controller."""
         return dict(iters=self.max_iterations, samples=self.samples, elites=self.elites, alpha=self.alpha,
                     sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), sigma_min=self.sigma_min,
                     seed=self.seed)
 
-    def _solve_batch_cem(self, states, record_costs, x_ref, ref_offset, epoch):
-        """B independent cross-entropy solves (cold start from zeros) in one batched device solve (engine.solve_cem)."""
+    def _solve_batch_sampling(self, states, record_costs, x_ref, ref_offset, epoch):
+        """B independent sampling solves, MPPI or cross-entropy (cold start from zeros), in one batched device solve
+        (engine.solve_mppi / engine.solve_cem)."""
         eng = self.engine
-        self._graphed_cem = cem_solver_for(eng, self.use_graph, getattr(self, "_graphed_cem", None))
+        meth, graphed_or_eager = SAMPLING[self.optimizer_type]
+        solve = graphed_or_eager(eng, self.use_graph, getattr(self, "_graphed_" + meth, None))
+        setattr(self, "_graphed_" + meth, solve)
         x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
         u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
-        return self._graphed_cem(eng, x0, u0, self._cost(), self.integrator, self.dt, epoch=self._mppi_epoch(eng, epoch),
-                                 record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **self.cem_options())
+        return solve(eng, x0, u0, self._cost(), self.integrator, self.dt, epoch=self._mppi_epoch(eng, epoch),
+                     record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **getattr(self, meth + "_options")())
 
     def compute_control_batch(self, states, x_ref=None, ref_offset=0, epoch=None):
         """states (B,n) -> np.ndarray (B,1): first control of each plant's optimised sequence (x_ref, epoch:
         solve_batch)."""
-        kw = {"epoch": epoch} if self.optimizer_type in ("MPPI", "CrossEntropy") else {}
+        kw = {"epoch": epoch} if self.optimizer_type in SAMPLING else {}
         out = self.solve_batch(states, x_ref=x_ref, ref_offset=ref_offset, **kw)
         u0 = out["u_last"][:, 0, :]
         if self.u_min is not None and self.u_max is not None:

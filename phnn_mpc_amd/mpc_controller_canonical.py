@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import cem_solver_for, mppi_solver_for, solver_for
+from .solver import SAMPLING, solver_for
 
 
 class MPCControllerCanonical:
@@ -147,19 +147,20 @@ class MPCControllerCanonical:
             u0 = torch.zeros(B, self.horizon, self.input_dim, dtype=torch.float32, device=eng.device)
         else:
             u0 = torch.as_tensor(u_init, dtype=torch.float32).reshape(B, self.horizon, self.input_dim).to(eng.device)
-        if self.optimizer == "MPPI":
-            self._graphed_mppi = mppi_solver_for(eng, self.use_graph, getattr(self, "_graphed_mppi", None))
-            return self._graphed_mppi(eng, x0, u0, self._cost(), self.integrator, self.dt,
-                                      epoch=self._mppi_epoch(eng, epoch), record_costs=record_costs, x_ref=x_ref,
-                                      ref_offset=ref_offset, **self.mppi_options())
-        if self.optimizer == "CrossEntropy":
-            self._graphed_cem = cem_solver_for(eng, self.use_graph, getattr(self, "_graphed_cem", None))
-            return self._graphed_cem(eng, x0, u0, self._cost(), self.integrator, self.dt,
-                                     epoch=self._mppi_epoch(eng, epoch), record_costs=record_costs, x_ref=x_ref,
-                                     ref_offset=ref_offset, **self.cem_options())
+        if self.optimizer in SAMPLING:
+            return self._solve_batch_sampling(x0, u0, record_costs, x_ref, ref_offset, epoch)
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.learning_rate,
                                  self.optimizer_steps, track_best=True, u_min=self.u_min, u_max=self.u_max,
                                  record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset)
+
+    def _solve_batch_sampling(self, x0, u0, record_costs, x_ref, ref_offset, epoch):
+        """The MPPI or cross-entropy solve of optimize_control_batch (engine.solve_mppi / engine.solve_cem)."""
+        eng = self.engine
+        meth, graphed_or_eager = SAMPLING[self.optimizer]
+        solve = graphed_or_eager(eng, self.use_graph, getattr(self, "_graphed_" + meth, None))
+        setattr(self, "_graphed_" + meth, solve)
+        return solve(eng, x0, u0, self._cost(), self.integrator, self.dt, epoch=self._mppi_epoch(eng, epoch),
+                     record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **getattr(self, meth + "_options")())
 
     def control_batch(self, x_current, u_prev=None, x_ref=None, ref_offset=0, epoch=None):
         """x_current (B,n), u_prev (B,H,m) or None -> (u (B,m), u_sequence (B,H,m), best_cost (B)) numpy arrays.

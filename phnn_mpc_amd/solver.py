@@ -82,18 +82,12 @@ def _eager(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=False
                           record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, workspace=workspace)
 
 
-def mppi_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, sigma, seed, epoch=0, problem_offset=0,
-               record_costs=True, workspace=None, x_ref=None, ref_offset=0):
-    """Sampling MPC (MPPI) on B independent problems: x0 (B,n), u_init (B,H,m) -> dict(u_last, costs, best_u, best_cost).
-
-    The nominal u starts at clamp(u_init) (the cost's bounds); `iters` times: v = engine.mppi_sample (samples
-    perturbed copies per problem, sample 0 the nominal itself), S = engine.rollout_cost of all B * samples rollouts,
-    engine.mppi_update moves the nominal to sum_k w_k v_k / sum_k w_k with w_k = exp(-(S_k - min S) / lam).
-    u_last   : the last nominal (B,H,m), in bounds
-    costs    : (iters,B) cost of the nominal at every iteration (its sample 0), if record_costs
-    best_u   : the best sample seen over all iterations (strict '<', lowest sample index on ties), best_cost its cost
-    seed, epoch (int or device int32 tensor), problem_offset: the noise counter; problem b draws the noise of global
-    problem problem_offset + b whatever batch it is solved in.  x_ref, ref_offset: as in shooting_solve."""
+def _sampling_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, sample, update, record_costs, workspace, x_ref,
+                    ref_offset):
+    """The loop under mppi_solve and cem_solve -> dict(u_last, costs, best_u, best_cost).  The mean u starts at
+    clamp(u_init) (the cost's bounds); `iters` times: v, x0_rep = sample(u, i, ws) (samples perturbed copies per problem,
+    sample 0 u itself), S = engine.rollout_cost of all B * samples rollouts, update(u, v, S, costs_row=, best_cost=,
+    best_u=) moves u in place.  sample and update are the method's engine calls with its own arguments bound."""
     _need_reference(engine, x_ref)
     rkw = {}
     B = u_init.shape[0]
@@ -108,21 +102,29 @@ def mppi_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, si
     best_u = torch.zeros_like(u)
     ws = {} if workspace is None else workspace
     for i in range(iters):
-        v, x0_rep = engine.mppi_sample(x0, u, cost, samples, sigma, seed, i, epoch=epoch, problem_offset=problem_offset,
-                                       workspace=ws)
+        v, x0_rep = sample(u, i, ws)
         s = engine.rollout_cost(x0_rep, v, cost, integrator, dt, **rkw)
-        engine.mppi_update(u, v, s, lam, cost, costs_row=costs[i] if record_costs else None, best_cost=best_cost, best_u=best_u)
+        update(u, v, s, costs_row=costs[i] if record_costs else None, best_cost=best_cost, best_u=best_u)
     return {"u_last": u, "costs": costs, "best_u": best_u, "best_cost": best_cost}
 
 
-def _mppi_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, sigma, seed, epoch=0, problem_offset=0,
-                record_costs=True, workspace=None, x_ref=None, ref_offset=0):
-    """The MPPI solve without a captured graph: the library's own loop (engine.solve_mppi) where the engine has one, else
-    the Python loop over its primitives.  Same launches, same order: identical results."""
-    fn = engine.solve_mppi if hasattr(engine, "solve_mppi") else lambda *a, **k: mppi_solve(engine, *a, **k)
-    return fn(x0, u_init, cost, integrator, dt, iters=iters, samples=samples, lam=lam, sigma=sigma, seed=seed, epoch=epoch,
-              problem_offset=problem_offset, record_costs=record_costs, workspace=workspace, x_ref=x_ref,
-              ref_offset=ref_offset)
+def mppi_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, sigma, seed, epoch=0, problem_offset=0,
+               record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+    """Sampling MPC (MPPI) on B independent problems: x0 (B,n), u_init (B,H,m) -> dict(u_last, costs, best_u, best_cost).
+
+    The nominal u starts at clamp(u_init) (the cost's bounds); `iters` times: v = engine.mppi_sample (samples
+    perturbed copies per problem, sample 0 the nominal itself), S = engine.rollout_cost of all B * samples rollouts,
+    engine.mppi_update moves the nominal to sum_k w_k v_k / sum_k w_k with w_k = exp(-(S_k - min S) / lam).
+    u_last   : the last nominal (B,H,m), in bounds
+    costs    : (iters,B) cost of the nominal at every iteration (its sample 0), if record_costs
+    best_u   : the best sample seen over all iterations (strict '<', lowest sample index on ties), best_cost its cost
+    seed, epoch (int or device int32 tensor), problem_offset: the noise counter; problem b draws the noise of global
+    problem problem_offset + b whatever batch it is solved in.  x_ref, ref_offset: as in shooting_solve."""
+    return _sampling_solve(
+        engine, x0, u_init, cost, integrator, dt, iters, samples,
+        lambda u, i, ws: engine.mppi_sample(x0, u, cost, samples, sigma, seed, i, epoch=epoch, problem_offset=problem_offset,
+                                            workspace=ws),
+        lambda u, v, s, **out: engine.mppi_update(u, v, s, lam, cost, **out), record_costs, workspace, x_ref, ref_offset)
 
 
 def cem_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch=0,
@@ -135,46 +137,45 @@ def cem_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, 
     sample 0 the mean itself), S = engine.rollout_cost of all B * samples rollouts, engine.cem_update refits u and sig
     to the `elites` samples of lowest finite cost with smoothing alpha, sig floored at sigma_min.
     u_last   : the last mean (B,H,m), in bounds;  sigma_last: the last standard deviation (B,H,m)
-    costs    : (iters,B) cost of the mean at every iteration (its sample 0), if record_costs
-    best_u   : the best sample seen over all iterations (strict '<', lowest sample index on ties), best_cost its cost
-    seed, epoch, problem_offset, x_ref, ref_offset: as in mppi_solve."""
+    costs, best_u, best_cost, seed, epoch, problem_offset, x_ref, ref_offset: as in mppi_solve."""
     _need_reference(engine, x_ref)
-    rkw = {}
-    B = u_init.shape[0]
-    if x_ref is not None:
-        rkw = {"x_ref": engine.mppi_reference(x_ref, B, samples), "ref_offset": ref_offset}
-    u = u_init.detach().clone().contiguous()
-    if cost.has_u_bounds:
-        u = torch.clamp(u, float(cost.u_min), float(cost.u_max))
-    dev = u.device
-    m = u.shape[2]
+    m = u_init.shape[2]
     s0 = np.asarray(sigma, dtype=np.float64).reshape(-1)
     if s0.size not in (1, m):
         raise ValueError(f"sigma: one value or one per control component (m = {m}), got {sigma!r}")
     if not np.all((s0 >= 0) & np.isfinite(s0)):
         raise ValueError("sigma must be >= 0 and finite")
-    sig = torch.tensor(np.broadcast_to(s0, (m,)).copy(), dtype=torch.float32, device=dev).expand_as(u).contiguous()
-    costs = torch.empty(iters, B, dtype=torch.float32, device=dev) if record_costs else None
-    best_cost = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
-    best_u = torch.zeros_like(u)
-    ws = {} if workspace is None else workspace
-    for i in range(iters):
-        v, x0_rep = engine.cem_sample(x0, u, sig, cost, samples, seed, i, epoch=epoch, problem_offset=problem_offset,
-                                      workspace=ws)
-        s = engine.rollout_cost(x0_rep, v, cost, integrator, dt, **rkw)
-        engine.cem_update(u, sig, v, s, elites, alpha, sigma_min, cost, costs_row=costs[i] if record_costs else None,
-                          best_cost=best_cost, best_u=best_u)
-    return {"u_last": u, "sigma_last": sig, "costs": costs, "best_u": best_u, "best_cost": best_cost}
+    sig = torch.tensor(np.broadcast_to(s0, (m,)).copy(), dtype=torch.float32, device=u_init.device).expand_as(u_init).contiguous()
+    out = _sampling_solve(
+        engine, x0, u_init, cost, integrator, dt, iters, samples,
+        lambda u, i, ws: engine.cem_sample(x0, u, sig, cost, samples, seed, i, epoch=epoch, problem_offset=problem_offset,
+                                           workspace=ws),
+        lambda u, v, s, **out: engine.cem_update(u, sig, v, s, elites, alpha, sigma_min, cost, **out), record_costs, workspace,
+        x_ref, ref_offset)
+    return {"u_last": out.pop("u_last"), "sigma_last": sig, **out}
+
+
+def _library_or(engine, name, loop):
+    """-> the eager solve of a sampling method: the library's own loop (engine.<name>) where the engine has one, else the
+    Python loop over its primitives (`loop`, called with the engine first).  Same launches, same order: identical results."""
+    return getattr(engine, name) if hasattr(engine, name) else lambda *a, **k: loop(engine, *a, **k)
+
+
+def _mppi_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, sigma, seed, epoch=0, problem_offset=0,
+                record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+    """The MPPI solve without a captured graph (_library_or); called as mppi_solve is."""
+    return _library_or(engine, "solve_mppi", mppi_solve)(
+        x0, u_init, cost, integrator, dt, iters=iters, samples=samples, lam=lam, sigma=sigma, seed=seed, epoch=epoch,
+        problem_offset=problem_offset, record_costs=record_costs, workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
 
 
 def _cem_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch=0,
                problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
-    """The CEM solve without a captured graph: the library's own loop (engine.solve_cem) where the engine has one, else
-    the Python loop over its primitives.  Same launches, same order: identical results."""
-    fn = engine.solve_cem if hasattr(engine, "solve_cem") else lambda *a, **k: cem_solve(engine, *a, **k)
-    return fn(x0, u_init, cost, integrator, dt, iters=iters, samples=samples, elites=elites, alpha=alpha, sigma=sigma,
-              sigma_min=sigma_min, seed=seed, epoch=epoch, problem_offset=problem_offset, record_costs=record_costs,
-              workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
+    """The CEM solve without a captured graph (_library_or); called as cem_solve is."""
+    return _library_or(engine, "solve_cem", cem_solve)(
+        x0, u_init, cost, integrator, dt, iters=iters, samples=samples, elites=elites, alpha=alpha, sigma=sigma,
+        sigma_min=sigma_min, seed=seed, epoch=epoch, problem_offset=problem_offset, record_costs=record_costs,
+        workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
 
 
 def capture(device, fn):
@@ -276,18 +277,18 @@ class GraphedLBFGS(Graphed):
 
 
 class GraphedMPPI(Graphed):
-    """The MPPI solve (_mppi_eager) as a graph: the clamp and resets plus every iters x (k_mppi_sample, K1,
-    k_mppi_update) launch.  `epoch` is part of the graph's signature: an int re-captures when it changes, a device int32
-    tensor is read through its pointer at every replay (fill it in place between calls to draw fresh noise).  sigma
-    must be hashable (a float or a tuple).  A per-problem x_ref lives in the graph's static buffer as given and its
-    expansion to one row set per rollout is part of the replayed graph."""
+    """The MPPI solve (_mppi_eager) as a graph: the clamp and resets plus every iters x (k_sample, K1, k_mppi_update)
+    launch.  `epoch` is part of the graph's signature: an int re-captures when it changes, a device int32 tensor is read
+    through its pointer at every replay (fill it in place between calls to draw fresh noise).  sigma must be hashable (a
+    float or a tuple).  A per-problem x_ref lives in the graph's static buffer as given and its expansion to one row set
+    per rollout is part of the replayed graph."""
 
     def __init__(self, engine):
         super().__init__(engine, _mppi_eager)
 
 
 class GraphedCEM(Graphed):
-    """The CEM solve (_cem_eager) as a graph: the clamp and resets plus every iters x (k_cem_sample, K1, k_cem_update)
+    """The CEM solve (_cem_eager) as a graph: the clamp and resets plus every iters x (k_sample, K1, k_cem_update)
     launch.  `epoch`, sigma and x_ref behave as in GraphedMPPI."""
 
     def __init__(self, engine):
@@ -331,3 +332,7 @@ def cem_solver_for(engine, use_graph, previous=None):
     if not hasattr(engine, "cem_sample"):
         raise NotImplementedError(f"{type(engine).__name__} has no CEM kernels (RolloutEngine has)")
     return _graphed_or(_cem_eager, GraphedCEM, engine, use_graph, previous)
+
+
+# optimizer name of a sampling solve -> (its short name: engine.solve_<name>, controller.<name>_options(), solver_for)
+SAMPLING = {"MPPI": ("mppi", mppi_solver_for), "CrossEntropy": ("cem", cem_solver_for)}

@@ -1,7 +1,7 @@
-"""NumPy restatement of the CEM kernels (phnn_mpc_amd/csrc/phnn_cem.hip).  TEST INFRASTRUCTURE.
+"""NumPy restatement of the CEM kernels (phnn_mpc_amd/csrc/phnn_sampling.hip).  TEST INFRASTRUCTURE.
 
   sample          v = clamp(u + sig o z) with a standard deviation per problem and element, sample 0 with z = 0; the
-                  noise is mppi_model's (Philox4x32-10, the counter layout of phnn_mppi.h, Box-Muller)
+                  noise is mppi_model's (Philox4x32-10, the counter layout of phnn_sampling.h, Box-Muller)
   elite_order     the elite rule: among the finite costs the E lowest in the order (cost as floats with -0 == +0, then k
                   ascending), stated with a stable sort -- not with the kernel's key descent, which it is the check of
   update          em = mean of the elite rows, ev = mean of their squared deviations from em (two passes, k ascending),

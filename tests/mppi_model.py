@@ -1,7 +1,7 @@
-"""NumPy restatement of the MPPI kernels (phnn_mpc_amd/csrc/phnn_mppi.hip).  TEST INFRASTRUCTURE.
+"""NumPy restatement of the MPPI kernels (phnn_mpc_amd/csrc/phnn_sampling.hip).  TEST INFRASTRUCTURE.
 
   philox4x32_10   Philox4x32-10 in integer arithmetic (uint64 products split into high / low words)
-  counter / key   the counter layout of phnn_mppi.h: which (seed, epoch, iteration, problem, sample, float4) feeds a call
+  counter / key   the counter layout of phnn_sampling.h: which (seed, epoch, iteration, problem, sample, float4) feeds a call
   normals         Box-Muller on the four words of a call: uniforms ((x >> 8) + 0.5) * 2^-24
   sample          v = clamp(u + sigma o z), sample 0 with z = 0
   update          u = clamp(sum_k w_k v_k / sum_k w_k), w_k = exp(-(S_k - min S) / lambda), best-sample tracking
@@ -19,7 +19,7 @@ M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
 MASK = np.uint64(0xFFFFFFFF)
 LANES = 16
-# supported ranges of the counter fields (phnn_mppi.h)
+# supported ranges of the counter fields (phnn_sampling.h)
 MAX_ITERS, MAX_SAMPLES, MAX_PROBLEM, MAX_J = 1 << 16, 1 << 26, 1 << 48, 64
 
 

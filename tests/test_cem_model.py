@@ -278,8 +278,9 @@ def test_argument_errors():
 
 # ----------------------------------------------------------------------------- 5. static: the new code object
 def test_cem_kernels_are_in_the_library_without_scratch():
-    """k_cem_sample (both alignments) and k_cem_update (four widths x two alignments) are in libphnn_mpc.so and none of
-    them touches scratch memory: the check tests/test_mppi_model.py makes for the MPPI kernels."""
+    """k_sample, shared with MPPI (both sigma sources x both alignments), and k_cem_update (four widths x two
+    alignments) are in libphnn_mpc.so and none of them touches scratch memory: the check tests/test_mppi_model.py makes
+    for the MPPI kernels."""
     import test_static_isa as si
     if not os.path.exists(os.path.join(si.LLVM, "llvm-objdump")):
         pytest.skip("llvm-objdump not available")
@@ -294,11 +295,12 @@ def test_cem_kernels_are_in_the_library_without_scratch():
             open(f, "wb").write(img)
             txt = subprocess.run([os.path.join(si.LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", f], capture_output=True,
                                  text=True, check=True).stdout
-            for name, body in re.findall(r"^[0-9a-f]+ <([^>]*k_cem_[^>]*)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", txt, re.S | re.M):
+            for name, body in re.findall(r"^[0-9a-f]+ <([^>]*k_(?:cem_update|sample|clamp|sigma_init)[^>]*)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", txt, re.S | re.M):
                 found[name] = body
     upd = sorted(n for n in found if "k_cem_update" in n)
-    smp = sorted(n for n in found if "k_cem_sample" in n)
-    assert len(upd) == 8 and len(smp) == 2, (upd, smp)
+    smp = sorted(n for n in found if "k_sample" in n)
+    assert len(upd) == 8 and len(smp) == 4, (upd, smp)
+    assert any("k_clamp" in n for n in found) and any("k_sigma_init" in n for n in found)  # the small kernels, no scratch either
     for name, body in found.items():
         assert "scratch_" not in body, name
 

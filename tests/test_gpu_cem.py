@@ -1,10 +1,10 @@
-"""The CEM solve on the device (engine.cem_sample / cem_update / solve_cem, kernels k_cem_sample and k_cem_update).
+"""The CEM solve on the device (engine.cem_sample / cem_update / solve_cem, kernels k_sample and k_cem_update).
 
   update      k_cem_update has no transcendental: its mean, sigma, best sample and cost record must equal the float32
               form of tests/cem_model.py BIT FOR BIT -- on the device's own samples and K1 costs for every shape, and on
               the synthetic edge costs of tests/test_cem_model.py (ties across the elite boundary, -0 / +0, non-finite
               costs, fewer finite costs than E, none) uploaded as they are.
-  sample      k_cem_sample vs the float64 model with test_gpu_mppi's allowance (device log / sqrt / sincospi are not
+  sample      k_sample vs the float64 model with test_gpu_mppi's allowance (device log / sqrt / sincospi are not
               bit-specified): 8 x the float32 form's distance from the float64 form + one ulp.
   bitwise     solve_cem == solver.cem_solve over the primitives; repeat == first; B problems at once == each alone with
               its problem_offset (B = 37: split-tile K1, B = 300 x K = 30: 563 tiles, whole-tile K1); graph == eager;
@@ -139,7 +139,7 @@ def test_update_equals_the_float32_model_on_synthetic_costs(torch, K):
                 assert sorted(cm.elite_order(s[b], E)) == list(np.nonzero(r["elite"][b])[0])
 
 
-# ----------------------------------------------------------------------------- 2. k_cem_sample against the float64 model
+# ----------------------------------------------------------------------------- 2. k_sample against the float64 model
 @pytest.mark.parametrize("model, integ, B, K, H", CASES)
 def test_sample_against_the_float64_model(torch, model, integ, B, K, H):
     eng = engine(model)

@@ -1,4 +1,4 @@
-"""The MPPI solve on the device (engine.mppi_sample / mppi_update / solve_mppi, kernels k_mppi_sample and k_mppi_update).
+"""The MPPI solve on the device (engine.mppi_sample / mppi_update / solve_mppi, kernels k_sample and k_mppi_update).
 
   primitives  mppi_sample vs the float64 model (tests/mppi_model.py); mppi_update vs the float64 model fed the device's
               own samples and K1 costs.  Device log / sqrt / sincospi / exp are not bit-specified, so the allowance is

@@ -225,8 +225,9 @@ def test_argument_errors():
 
 # ----------------------------------------------------------------------------- 11. static: the new code object
 def test_mppi_kernels_are_in_the_library_without_scratch():
-    """k_mppi_sample (both alignments) and k_mppi_update (four widths x two alignments) are in libphnn_mpc.so; none of
-    them touches scratch memory, the aligned sampler stores 16 bytes at a time, and the update's row reductions are DPP."""
+    """k_sample, shared with CEM (both sigma sources x both alignments), and k_mppi_update (four widths x two alignments)
+    are in libphnn_mpc.so; none of them touches scratch memory, the aligned sampler stores 16 bytes at a time, and the
+    update's row reductions are DPP."""
     import test_static_isa as si
     if not os.path.exists(os.path.join(si.LLVM, "llvm-objdump")):
         pytest.skip("llvm-objdump not available")
@@ -241,15 +242,17 @@ def test_mppi_kernels_are_in_the_library_without_scratch():
             open(f, "wb").write(img)
             txt = subprocess.run([os.path.join(si.LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", f], capture_output=True,
                                  text=True, check=True).stdout
-            for name, body in re.findall(r"^[0-9a-f]+ <([^>]*k_mppi_[^>]*)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", txt, re.S | re.M):
+            for name, body in re.findall(r"^[0-9a-f]+ <([^>]*k_(?:mppi_update|sample|clamp|sigma_init)[^>]*)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", txt, re.S | re.M):
                 found[name] = body
     upd = sorted(n for n in found if "k_mppi_update" in n)
-    smp = sorted(n for n in found if "k_mppi_sample" in n)
-    assert len(upd) == 8 and len(smp) == 2, (upd, smp)
+    smp = sorted(n for n in found if "k_sample" in n)
+    assert len(upd) == 8 and len(smp) == 4, (upd, smp)
+    assert any("k_clamp" in n for n in found) and any("k_sigma_init" in n for n in found)  # the small kernels, no scratch either
+    assert {re.search(r"k_sampleI(Lb\dELb\d)E", n).group(1) for n in smp} == {"Lb0ELb0", "Lb0ELb1", "Lb1ELb0", "Lb1ELb1"}
     for name, body in found.items():
         assert "scratch_" not in body, name
     assert all("_dpp" in found[n] for n in upd)
-    assert any("global_store_dwordx4" in found[n] for n in smp)
+    assert all(("global_store_dwordx4" in found[n]) == ("ELb1EE" in n) for n in smp)
 
 
 # ----------------------------------------------------------------------------- 6. the saturated start

@@ -8,7 +8,7 @@ import sys
 csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "phnn_mpc_amd", "csrc")
 out = ""
 for src, extra in (("phnn_mpc.hip", []), ("phnn_grad.hip", []), ("phnn_wgrad.hip", []), ("phnn_split.hip", []),
-                   ("phnn_lbfgs.hip", []), ("phnn_mppi.hip", []), ("phnn_cem.hip", [])):  # as the Makefile
+                   ("phnn_lbfgs.hip", []), ("phnn_sampling.hip", [])):  # as the Makefile
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
            "--cuda-device-only", "-c", "-o", "/dev/null", src, "-Rpass-analysis=kernel-resource-usage"] + extra
