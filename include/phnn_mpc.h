@@ -507,6 +507,54 @@ int phnn_solve_cem(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B,
                    size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, float* sigma_out_dev,
                    void* stream);
 
+/* ---- time-correlated (shaped) sampling noise for the MPPI and CEM solves -----------------------------------------
+ * A noise shape is a matrix L with rows = H rows and cols = P columns, 1 <= P <= H: float32, row-major, on the device,
+ * shared by the whole batch, never written.  For problem b, sample k >= 1, control component c and step t
+ *   z[t, c] = sum_{s = 0 .. P-1} L[t, s] * eps[s, c]     float32: acc = 0, then acc = acc + L[t, s] * eps[s, c] for s
+ *                                                         ascending, the product rounded, then the sum (no fused
+ *                                                         multiply-add)
+ *   v[t, c] = clamp(u[t, c] + sigma[t, c] * z[t, c])      sigma: MPPI's table entry sigma[c], or CEM's tensor
+ * where eps[s, c] is the white normal the unshaped sampler draws for element s*m + c of a row of length P*m with the
+ * same (seed, epoch, iteration, gid = problem_offset + b, k): component (s*m + c) % 4 of the Philox call with counter
+ * word 3 = k << 6 | (s*m + c) / 4.  Each normal is drawn once per rollout.  Sample 0 stays the nominal / mean itself
+ * (z = 0; L is not read for it).  Shaping acts along time for each control component separately.
+ *   - rows = cols = H and L = I returns the values of the unshaped sampler.
+ *   - Problem b's samples depend on (seed, epoch, iteration, gid, L) only: not on B, on its position in the batch, on how
+ *     the batch is split over calls, or on graph vs eager.
+ *   - When L's rows have unit Euclidean norm every z[t, c] has unit variance, and sigma, CEM's refit of it and sigma_min
+ *     keep their meaning.  The library does NOT normalise (phnn_mpc_amd/noise.py's builders do).
+ * Buffers: L_dev holds exactly rows * cols floats and is only read; it is caller-owned and must stay alive and unchanged
+ * until the work enqueued with it has run (a captured graph reads it through this pointer at every replay).  Every
+ * other buffer is as documented for the unshaped entry point; the workspace sizes do not change
+ * (phnn_mppi_workspace_bytes / phnn_cem_workspace_bytes), and the update entry points are shared.
+ * The *_shaped entry points take the arguments of their unshaped counterparts plus `shape`.  shape == NULL is the
+ * unshaped call: same launches, same bits.  Else k_shaped_sample replaces k_sample (one group of 16, 32 or 64 lanes per
+ * rollout; L staged in LDS when rows * (cols | 1) * 4 bytes <= 48 KiB, read from global memory above that), K1 and the update kernels are
+ * launched exactly as in the unshaped solve; stream-ordered, capturable, epoch_dev read by every launch.
+ * Every check of the unshaped entry point runs in its order; then PHNN_ERR_INVALID_ARG, with nothing launched, for
+ * rows != H, cols < 1, cols > rows or L_dev == NULL (B > 0); PHNN_ERR_UNSUPPORTED for H*m > 256 stays the last check
+ * of the options.  DESIGN.md 15. */
+typedef struct {
+  const float* L_dev;   /* device, (rows, cols) row-major, never written */
+  int32_t rows;         /* must equal H */
+  int32_t cols;         /* P, 1 <= P <= rows */
+  int32_t reserved[4];  /* zero */
+} phnn_noise_shape;
+int phnn_mppi_sample_shaped(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                            const phnn_mppi_options* opt, int32_t iteration, const phnn_noise_shape* shape, float* samples_dev,
+                            float* x0_rep_dev, void* stream);
+int phnn_cem_sample_shaped(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* sigma_dev, int64_t B, int32_t H,
+                           const phnn_cost* cost, const phnn_cem_options* opt, int32_t iteration, const phnn_noise_shape* shape,
+                           float* samples_dev, float* x0_rep_dev, void* stream);
+int phnn_solve_mppi_shaped(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                           const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt,
+                           const phnn_noise_shape* shape, void* workspace, size_t workspace_size, float* costs_dev,
+                           float* best_cost_dev, float* best_u_dev, void* stream);
+int phnn_solve_cem_shaped(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                          const phnn_reference* ref, int32_t integrator, float dt, const phnn_cem_options* opt,
+                          const phnn_noise_shape* shape, void* workspace, size_t workspace_size, float* costs_dev,
+                          float* best_cost_dev, float* best_u_dev, float* sigma_out_dev, void* stream);
+
 /* ---- the plant on the other side of the path ------------------------------------------
  * Ground-truth cart-pole of src/cartpole_simulator.py:63-112: float64, explicit Euler, the standard cart-pole
  * equations in the reference's operation order; termination |x| > x_limit or |theta| > theta_limit.  Defaults of

@@ -34,6 +34,7 @@ EXPORTED = [
     "phnn_version", "phnn_rollout_fwd_ref", "phnn_rollout_grad_ref", "phnn_solve_ref", "phnn_lbfgs_workspace_bytes",
     "phnn_solve_lbfgs", "phnn_mppi_workspace_bytes", "phnn_mppi_sample", "phnn_mppi_update", "phnn_solve_mppi",
     "phnn_cem_workspace_bytes", "phnn_cem_sample", "phnn_cem_update", "phnn_solve_cem",
+    "phnn_mppi_sample_shaped", "phnn_cem_sample_shaped", "phnn_solve_mppi_shaped", "phnn_solve_cem_shaped",
 ]
 
 
@@ -88,6 +89,12 @@ class CemOptions(C.Structure):
                 ("sigma_init", C.c_float * PHNN_MAX_M), ("sigma_min", C.c_float), ("seed", C.c_uint64),
                 ("problem_offset", C.c_int64), ("epoch_dev", C.c_void_p), ("epoch_host", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
+
+
+class NoiseShape(C.Structure):
+    """phnn_noise_shape: the (rows = H, cols = P) float32 row-major device matrix L that turns the white normals of a
+    sampling solve into time-correlated ones, z[t, c] = sum_s L[t, s] eps[s, c] (phnn_mpc_amd/noise.py builds them)."""
+    _fields_ = [("L_dev", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class Plant(C.Structure):
@@ -265,6 +272,12 @@ def load_library():
     lib.phnn_solve_cem.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float,
                                    C.POINTER(CemOptions), vp, C.c_size_t, f32p, f32p, f32p, f32p, vp]
     lib.phnn_solve_cem.restype = C.c_int
+    # the *_shaped entry points: the unshaped argument lists with a phnn_noise_shape* after `iteration` / `opt`
+    shp = C.POINTER(NoiseShape)
+    for name, at in (("mppi_sample", 8), ("cem_sample", 9), ("solve_mppi", 10), ("solve_cem", 10)):
+        fn, base = getattr(lib, f"phnn_{name}_shaped"), getattr(lib, f"phnn_{name}")
+        fn.argtypes = base.argtypes[:at] + [shp] + base.argtypes[at:]
+        fn.restype = C.c_int
     lib.phnn_plant_step.argtypes = [vp, C.POINTER(Plant), vp, f32p, i64, i64, i32, C.c_float, C.c_float, f32p, vp, vp, i32,
                                     vp, f32p, vp]
     lib.phnn_plant_step.restype = C.c_int

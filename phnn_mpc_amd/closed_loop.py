@@ -12,6 +12,9 @@
   x_ref                  (all three drivers) per-plant reference trajectories broadcastable to (B, rows, 4): control
                          step s solves with the window starting at row s (past its end a reference holds its last
                          row) -- the loop index on the host, the device step counter in the device loop.
+  noise                  (all three drivers) an MPPI / CrossEntropy controller built with noise= (time-correlated sampling
+                         noise, phnn_mpc_amd/noise.py) solves with it at every step: it travels in the controller's
+                         mppi_options() / cem_options(), and a captured control step reads its device tensor in place.
   stability_report       the "stability achieved" criterion of scripts/run_cartpole_mpc.py:117-159 with the
                          tolerances of the `stability` config section, per plant.
 """

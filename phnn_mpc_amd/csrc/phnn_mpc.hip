@@ -1249,7 +1249,17 @@ static int check_width(phnn_handle* h, const SamplingCommon& c, int32_t H) {
   return PHNN_OK;
 }
 
-static int check_mppi(phnn_handle* h, const phnn_mppi_options* opt, int64_t B, int32_t H, int32_t iteration, SamplingCommon* c) {
+// the noise shape of a *_shaped entry point (NULL: none), checked after the method's options and before the width
+static int check_shape(phnn_handle* h, const phnn_noise_shape* shape, int64_t B, int32_t H) {
+  if (!shape) return PHNN_OK;
+  if (shape->rows != H) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_noise_shape: rows != H");
+  if (shape->cols < 1 || shape->cols > shape->rows) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_noise_shape: cols outside 1 .. rows");
+  if (!shape->L_dev && B > 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_noise_shape: L_dev is NULL");
+  return PHNN_OK;
+}
+
+static int check_mppi(phnn_handle* h, const phnn_mppi_options* opt, int64_t B, int32_t H, int32_t iteration, SamplingCommon* c,
+                      const phnn_noise_shape* shape = nullptr) {
   if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options is NULL");
   *c = {"phnn_mppi_options", "MPPI", opt->iters, opt->samples, opt->seed, opt->problem_offset, opt->epoch_dev, opt->epoch_host};
   if (int rc = check_sampling(h, *c, B, H, iteration)) return rc;
@@ -1258,10 +1268,12 @@ static int check_mppi(phnn_handle* h, const phnn_mppi_options* opt, int64_t B, i
   for (int i = 0; i < h->desc.m; ++i)
     if (!(opt->sigma[i] >= 0.f) || !std::isfinite(opt->sigma[i]))
       return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_options: sigma must be >= 0 and finite");
+  if (int rc = check_shape(h, shape, B, H)) return rc;
   return check_width(h, *c, H);
 }
 
-static int check_cem(phnn_handle* h, const phnn_cem_options* opt, int64_t B, int32_t H, int32_t iteration, SamplingCommon* c) {
+static int check_cem(phnn_handle* h, const phnn_cem_options* opt, int64_t B, int32_t H, int32_t iteration, SamplingCommon* c,
+                     const phnn_noise_shape* shape = nullptr) {
   if (!opt) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options is NULL");
   *c = {"phnn_cem_options", "CEM", opt->iters, opt->samples, opt->seed, opt->problem_offset, opt->epoch_dev, opt->epoch_host};
   if (int rc = check_sampling(h, *c, B, H, iteration)) return rc;
@@ -1274,6 +1286,7 @@ static int check_cem(phnn_handle* h, const phnn_cem_options* opt, int64_t B, int
       return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: sigma_init must be >= 0 and finite");
   if (!(opt->sigma_min >= 0.f) || !std::isfinite(opt->sigma_min))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_options: sigma_min must be >= 0 and finite");
+  if (int rc = check_shape(h, shape, B, H)) return rc;
   return check_width(h, *c, H);
 }
 
@@ -1290,11 +1303,11 @@ size_t phnn_cem_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int3
   return sampling_workspace_bytes(h, B, H, samples, true);
 }
 
-// One k_sample launch.  sigma_dev: the (B, N) standard deviations (CEM), or NULL: the table sigma[m] (MPPI).
-// `who`: the entry point, for the NULL-tensor message.
+// One k_sample launch (shape == NULL) or one k_shaped_sample launch.  sigma_dev: the (B, N) standard deviations (CEM),
+// or NULL: the table sigma[m] (MPPI).  `who`: the entry point, for the NULL-tensor message.
 static int sample(phnn_handle* h, const char* who, const SamplingCommon& c, const float* x0_dev, const float* u_dev,
                   const float* sigma_dev, const float* sigma, int64_t B, int32_t H, const phnn_cost* cost, int32_t iteration,
-                  float* samples_dev, float* x0_rep_dev, void* stream) {
+                  const phnn_noise_shape* shape, float* samples_dev, float* x0_rep_dev, void* stream) {
   if (int rc = check_cost(h, cost)) return rc;
   if (B == 0) return PHNN_OK;
   if (!u_dev || (!sigma && !sigma_dev) || !samples_dev || (x0_rep_dev && !x0_dev))
@@ -1322,26 +1335,56 @@ static int sample(phnn_handle* h, const char* who, const SamplingCommon& c, cons
   p.epoch_dev = c.epoch_dev;
   p.epoch_host = c.epoch_host;
   p.iteration = iteration;
+  if (shape) {
+    hipError_t e = sample_shaped_launch(p, shape->L_dev, shape->cols, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(h, e, "k_shaped_sample launch");
+    return PHNN_OK;
+  }
   hipError_t e = sample_launch(p, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(h, e, "k_sample launch");
   return PHNN_OK;
 }
 
-int phnn_mppi_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
-                     const phnn_mppi_options* opt, int32_t iteration, float* samples_dev, float* x0_rep_dev, void* stream) {
+static int mppi_sample(phnn_handle* h, const char* who, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                       const phnn_cost* cost, const phnn_mppi_options* opt, int32_t iteration, const phnn_noise_shape* shape,
+                       float* samples_dev, float* x0_rep_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
   SamplingCommon c;
-  if (int rc = check_mppi(h, opt, B, H, iteration, &c)) return rc;
-  return sample(h, "phnn_mppi_sample", c, x0_dev, u_dev, nullptr, opt->sigma, B, H, cost, iteration, samples_dev, x0_rep_dev, stream);
+  if (int rc = check_mppi(h, opt, B, H, iteration, &c, shape)) return rc;
+  return sample(h, who, c, x0_dev, u_dev, nullptr, opt->sigma, B, H, cost, iteration, shape, samples_dev, x0_rep_dev, stream);
+}
+
+int phnn_mppi_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                     const phnn_mppi_options* opt, int32_t iteration, float* samples_dev, float* x0_rep_dev, void* stream) {
+  return mppi_sample(h, "phnn_mppi_sample", x0_dev, u_dev, B, H, cost, opt, iteration, nullptr, samples_dev, x0_rep_dev, stream);
+}
+
+int phnn_mppi_sample_shaped(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                            const phnn_mppi_options* opt, int32_t iteration, const phnn_noise_shape* shape, float* samples_dev,
+                            float* x0_rep_dev, void* stream) {
+  return mppi_sample(h, "phnn_mppi_sample_shaped", x0_dev, u_dev, B, H, cost, opt, iteration, shape, samples_dev, x0_rep_dev, stream);
+}
+
+static int cem_sample(phnn_handle* h, const char* who, const float* x0_dev, const float* u_dev, const float* sigma_dev, int64_t B,
+                      int32_t H, const phnn_cost* cost, const phnn_cem_options* opt, int32_t iteration,
+                      const phnn_noise_shape* shape, float* samples_dev, float* x0_rep_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  SamplingCommon c;
+  if (int rc = check_cem(h, opt, B, H, iteration, &c, shape)) return rc;
+  return sample(h, who, c, x0_dev, u_dev, sigma_dev, nullptr, B, H, cost, iteration, shape, samples_dev, x0_rep_dev, stream);
 }
 
 int phnn_cem_sample(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* sigma_dev, int64_t B, int32_t H,
                     const phnn_cost* cost, const phnn_cem_options* opt, int32_t iteration, float* samples_dev,
                     float* x0_rep_dev, void* stream) {
-  if (!h) return PHNN_ERR_INVALID_ARG;
-  SamplingCommon c;
-  if (int rc = check_cem(h, opt, B, H, iteration, &c)) return rc;
-  return sample(h, "phnn_cem_sample", c, x0_dev, u_dev, sigma_dev, nullptr, B, H, cost, iteration, samples_dev, x0_rep_dev, stream);
+  return cem_sample(h, "phnn_cem_sample", x0_dev, u_dev, sigma_dev, B, H, cost, opt, iteration, nullptr, samples_dev, x0_rep_dev, stream);
+}
+
+int phnn_cem_sample_shaped(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* sigma_dev, int64_t B, int32_t H,
+                           const phnn_cost* cost, const phnn_cem_options* opt, int32_t iteration, const phnn_noise_shape* shape,
+                           float* samples_dev, float* x0_rep_dev, void* stream) {
+  return cem_sample(h, "phnn_cem_sample_shaped", x0_dev, u_dev, sigma_dev, B, H, cost, opt, iteration, shape, samples_dev,
+                    x0_rep_dev, stream);
 }
 
 int phnn_mppi_update(phnn_handle* h, float* u_dev, const float* samples_dev, const float* sample_cost_dev, int64_t B,
@@ -1464,18 +1507,54 @@ static int solve_sampling(phnn_handle* h, const char* who, const SamplingCommon&
 }
 }  // extern "C++"
 
+static int solve_mppi(phnn_handle* h, const char* who, const float* x0_dev, float* u_dev, int64_t B, int32_t H,
+                      const phnn_cost* cost, const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt,
+                      const phnn_noise_shape* shape, void* workspace, size_t workspace_size, float* costs_dev, float* best_cost_dev,
+                      float* best_u_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  SamplingCommon c;
+  if (int rc = check_mppi(h, opt, B, H, 0, &c, shape)) return rc;
+  return solve_sampling(
+      h, who, c, x0_dev, u_dev, B, H, cost, ref, integrator, dt, nullptr, workspace, workspace_size, costs_dev,
+      best_cost_dev, best_u_dev, nullptr, stream,
+      [&](int it, float*, float* v, float* x0_rep) {
+        return mppi_sample(h, who, x0_dev, u_dev, B, H, cost, opt, it, shape, v, x0_rep, stream);
+      },
+      [&](float*, const float* v, const float* s, float* costs_row) {
+        return phnn_mppi_update(h, u_dev, v, s, B, H, cost, opt, costs_row, best_cost_dev, best_u_dev, stream);
+      });
+}
+
 int phnn_solve_mppi(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
                     const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt, void* workspace,
                     size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, void* stream) {
+  return solve_mppi(h, "phnn_solve_mppi", x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, nullptr, workspace, workspace_size,
+                    costs_dev, best_cost_dev, best_u_dev, stream);
+}
+
+int phnn_solve_mppi_shaped(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                           const phnn_reference* ref, int32_t integrator, float dt, const phnn_mppi_options* opt,
+                           const phnn_noise_shape* shape, void* workspace, size_t workspace_size, float* costs_dev,
+                           float* best_cost_dev, float* best_u_dev, void* stream) {
+  return solve_mppi(h, "phnn_solve_mppi_shaped", x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, shape, workspace,
+                    workspace_size, costs_dev, best_cost_dev, best_u_dev, stream);
+}
+
+static int solve_cem(phnn_handle* h, const char* who, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                     const phnn_reference* ref, int32_t integrator, float dt, const phnn_cem_options* opt,
+                     const phnn_noise_shape* shape, void* workspace, size_t workspace_size, float* costs_dev, float* best_cost_dev,
+                     float* best_u_dev, float* sigma_out_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
   SamplingCommon c;
-  if (int rc = check_mppi(h, opt, B, H, 0, &c)) return rc;
+  if (int rc = check_cem(h, opt, B, H, 0, &c, shape)) return rc;
   return solve_sampling(
-      h, "phnn_solve_mppi", c, x0_dev, u_dev, B, H, cost, ref, integrator, dt, nullptr, workspace, workspace_size, costs_dev,
-      best_cost_dev, best_u_dev, nullptr, stream,
-      [&](int it, float*, float* v, float* x0_rep) { return phnn_mppi_sample(h, x0_dev, u_dev, B, H, cost, opt, it, v, x0_rep, stream); },
-      [&](float*, const float* v, const float* s, float* costs_row) {
-        return phnn_mppi_update(h, u_dev, v, s, B, H, cost, opt, costs_row, best_cost_dev, best_u_dev, stream);
+      h, who, c, x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt->sigma_init, workspace, workspace_size, costs_dev,
+      best_cost_dev, best_u_dev, sigma_out_dev, stream,
+      [&](int it, float* sig, float* v, float* x0_rep) {
+        return cem_sample(h, who, x0_dev, u_dev, sig, B, H, cost, opt, it, shape, v, x0_rep, stream);
+      },
+      [&](float* sig, const float* v, const float* s, float* costs_row) {
+        return phnn_cem_update(h, u_dev, sig, v, s, B, H, cost, opt, costs_row, best_cost_dev, best_u_dev, stream);
       });
 }
 
@@ -1483,18 +1562,16 @@ int phnn_solve_cem(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B,
                    const phnn_reference* ref, int32_t integrator, float dt, const phnn_cem_options* opt, void* workspace,
                    size_t workspace_size, float* costs_dev, float* best_cost_dev, float* best_u_dev, float* sigma_out_dev,
                    void* stream) {
-  if (!h) return PHNN_ERR_INVALID_ARG;
-  SamplingCommon c;
-  if (int rc = check_cem(h, opt, B, H, 0, &c)) return rc;
-  return solve_sampling(
-      h, "phnn_solve_cem", c, x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt->sigma_init, workspace, workspace_size, costs_dev,
-      best_cost_dev, best_u_dev, sigma_out_dev, stream,
-      [&](int it, float* sig, float* v, float* x0_rep) {
-        return phnn_cem_sample(h, x0_dev, u_dev, sig, B, H, cost, opt, it, v, x0_rep, stream);
-      },
-      [&](float* sig, const float* v, const float* s, float* costs_row) {
-        return phnn_cem_update(h, u_dev, sig, v, s, B, H, cost, opt, costs_row, best_cost_dev, best_u_dev, stream);
-      });
+  return solve_cem(h, "phnn_solve_cem", x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, nullptr, workspace, workspace_size,
+                   costs_dev, best_cost_dev, best_u_dev, sigma_out_dev, stream);
+}
+
+int phnn_solve_cem_shaped(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                          const phnn_reference* ref, int32_t integrator, float dt, const phnn_cem_options* opt,
+                          const phnn_noise_shape* shape, void* workspace, size_t workspace_size, float* costs_dev,
+                          float* best_cost_dev, float* best_u_dev, float* sigma_out_dev, void* stream) {
+  return solve_cem(h, "phnn_solve_cem_shaped", x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, shape, workspace,
+                   workspace_size, costs_dev, best_cost_dev, best_u_dev, sigma_out_dev, stream);
 }
 
 int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, const float* action_dev,

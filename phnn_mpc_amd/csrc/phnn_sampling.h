@@ -75,6 +75,12 @@ struct SamplingLayout {
 SamplingLayout sampling_layout(long long B, int N, int n, int K, bool sigma_state);
 
 hipError_t sample_launch(const SampleParams& p, hipStream_t st);
+// k_shaped_sample: sample_launch with a noise shape L (H = N / m rows, P columns, row-major, device, read-only):
+// z[t, c] = sum_{s < P} L[t, s] * eps[s, c], eps the white normals of a row of length P * m.
+hipError_t sample_shaped_launch(const SampleParams& p, const float* L, int P, hipStream_t st);
+// Bytes of LDS k_shaped_sample stages an (H, P) shape in (row stride P | 1 floats), or 0: too large, L is read from
+// global memory.  Introspection for tests and tools.
+size_t sample_shaped_lds_bytes(int H, int P);
 hipError_t mppi_update_launch(const MppiUpdateParams& p, hipStream_t st);
 hipError_t cem_update_launch(const CemUpdateParams& p, hipStream_t st);
 // u <- clamp(u) in place (count floats): the entry of both solves

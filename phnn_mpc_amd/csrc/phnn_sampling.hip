@@ -13,6 +13,8 @@
 // One Philox call gives the four normals of one float4: two Box-Muller pairs, uniforms (x >> 8 + 0.5) * 2^-24.
 // The standard deviation is the only thing the two methods' samples differ in: MPPI's is a table per control
 // component in the kernel arguments, CEM's a (B, N) tensor, and k_sample is instantiated for either source.
+// k_shaped_sample is k_sample with time-correlated noise, z = L eps along the horizon (the *_shaped entry points,
+// DESIGN.md section 15); k_sample itself, the update kernels and K1 are the same with and without it.
 //
 // The update kernels have k_lbfgs's geometry: 16 lanes (one DPP row) per problem, lane l owns float4 l + 16e of the row.
 // Reductions over the K samples: lane l takes k = l, l + 16, ... in order, then a DPP butterfly inside the row; every
@@ -117,6 +119,111 @@ __global__ __launch_bounds__(kBlock) void k_sigma_init(float* sig, long long cou
   if (i >= count) return;
   const int c = (int)(i % m);
   sig[i] = c == 0 ? init.s[0] : c == 1 ? init.s[1] : c == 2 ? init.s[2] : init.s[3];
+}
+
+// ---------------------------------------------------------------------------------------------- k_shaped_sample
+// k_sample with time-correlated noise: z[t, c] = sum_{s < P} L[t, s] * eps[s, c], eps the white
+// normals k_sample would draw for a row of length P*m (element s*m + c), summed s ascending from 0 as
+// acc = acc + L * eps (a rounded product, then a rounded sum; the unit is built with -ffp-contract=off).
+// One group of G lanes per rollout r = b * K + k, G = 16, 32 or 64: the smallest that has a lane per float4 of the row
+// (a wave for N > 128; four rollouts to a wave for N <= 64, so that a short row does not leave most of a wave idle).
+// The 256 / G groups of a block take rows base + group, base striding over the grid, so a block stages L once for all
+// the rows it serves.  Per row, lane l of its group:
+//   1. makes the one Philox call of float4 l of the eps row (at most 64 calls) and leaves it in LDS;
+//   2. forms z of elements e = l, l + G, l + 2G, l + 3G (t = e / m, c = e % m) and leaves them in LDS: the lanes of one
+//      read walk consecutive rows t of L at one s -- the LDS row stride is odd, so they fall on distinct banks (m lanes,
+//      and the groups of a wave, share a word: a broadcast) -- and one word eps[s, c] per component (the rows' eps slots
+//      are 4G + 1 floats apart, so the groups of a wave read theirs from different banks);
+//   3. takes float4 l of z and writes float4 l of the sample row exactly as k_sample does.
+// Sample 0 skips 1 and 2 (z = 0): it reads neither L nor eps.  STAGED: L sits in LDS (dynamic, H rows of stride
+// ld = P | 1 floats), else it is read in place from global memory (shared by every rollout: it stays in L2).
+constexpr int kShapedMaxBlocks = 2048;
+constexpr size_t kShapedStageBytes = 48 * 1024;  // L (padded) at most this large is staged in LDS
+
+template <bool TENSOR, bool ALIGNED, bool STAGED, int G>
+__global__ __launch_bounds__(kBlock) void k_shaped_sample(SampleParams p, const float* __restrict__ Lg, int P) {
+  constexpr int kShapedRows = kBlock / G;  // rollouts (lane groups) per block and pass
+  constexpr int kSlot = 4 * G;             // floats of a row's eps / z: G float4, 4 * G >= 4 * ceil(N / 4)
+  extern __shared__ float Ls[];            // STAGED: (H, ld)
+  __shared__ float eps_s[kShapedRows * (kSlot + 1)];
+  __shared__ __attribute__((aligned(16))) float z_s[kShapedRows * (kSlot + 4)];
+  const int lane = threadIdx.x & (G - 1), wave = threadIdx.x / G;  // `wave`: the lane group's index in the block
+  const int N = p.N, m = p.m, H = N / m;
+  const int nv4 = (N + 3) / 4, nvp4 = (P * m + 3) / 4;
+  const int ld = STAGED ? (P | 1) : P;
+  if (STAGED) {
+    for (int i = threadIdx.x; i < H * P; i += kBlock) Ls[(i / P) * ld + (i % P)] = Lg[i];
+  }
+  const float* L = STAGED ? Ls : Lg;
+  const long long rows = p.B * p.K;
+  float* eps = eps_s + wave * (kSlot + 1);
+  float* zz = z_s + wave * (kSlot + 4);
+  for (long long base = (long long)blockIdx.x * kShapedRows; base < rows; base += (long long)gridDim.x * kShapedRows) {
+    const long long r = base + wave;
+    const bool live = r < rows;  // whole groups; every group keeps to the block's barriers
+    const long long b = live ? r / p.K : 0;
+    const int k = live ? (int)(r - b * p.K) : 0;
+    if (live && k != 0 && lane < nvp4) {
+      const unsigned long long gid = (unsigned long long)(p.problem_offset + b);
+      const int epoch = p.epoch_dev ? *p.epoch_dev : p.epoch_host;
+      U4 c;
+      c.x = (unsigned)gid;
+      c.y = (unsigned)(gid >> 32) | ((unsigned)p.iteration << 16);
+      c.z = (unsigned)epoch;
+      c.w = ((unsigned)k << 6) | (unsigned)lane;
+      const U4 o = philox4x32_10(c, p.key0, p.key1);
+      float e0, e1, e2, e3;
+      box_muller(o.x, o.y, e0, e1);
+      box_muller(o.z, o.w, e2, e3);
+      eps[4 * lane + 0] = e0, eps[4 * lane + 1] = e1, eps[4 * lane + 2] = e2, eps[4 * lane + 3] = e3;
+    }
+    __syncthreads();  // eps rows (and, first pass, L) are in LDS
+    if (live) {
+      for (int e = lane; e < 4 * nv4; e += G) {
+        float acc = 0.f;
+        if (k != 0 && e < N) {
+          const int t = e / m, c = e - t * m;
+          const float* Lrow = L + (size_t)t * ld;
+#pragma unroll 4  // the loads of four steps in flight; the sum stays in order
+          for (int s = 0; s < P; ++s) acc = acc + Lrow[s] * eps[s * m + c];
+        }
+        zz[e] = acc;
+      }
+    }
+    __syncthreads();  // z rows are in LDS
+    if (live && lane < nv4) {
+      const int j = lane, e = 4 * j;
+      const float z[4] = {zz[e], zz[e + 1], zz[e + 2], zz[e + 3]};
+      const float* urow = p.u + (size_t)b * N;
+      const float* srow = TENSOR ? p.sig + (size_t)b * N : nullptr;
+      float* vrow = p.v + (size_t)r * N;
+      if (ALIGNED) {  // as k_sample
+        const float4 u4 = reinterpret_cast<const float4*>(urow)[j];
+        const float un[4] = {u4.x, u4.y, u4.z, u4.w};
+        float sn[4], o[4];
+        if (TENSOR) {
+          const float4 s4 = reinterpret_cast<const float4*>(srow)[j];
+          sn[0] = s4.x, sn[1] = s4.y, sn[2] = s4.z, sn[3] = s4.w;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) sn[i] = p.sigma[(e + i) % m];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = clampf(un[i] + sn[i] * z[i], p.u_min, p.u_max, p.has_u_bounds);
+        reinterpret_cast<float4*>(vrow)[j] = make_float4(o[0], o[1], o[2], o[3]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (e + i < N) {
+            const float sg = TENSOR ? srow[e + i] : p.sigma[(e + i) % m];
+            vrow[e + i] = clampf(urow[e + i] + sg * z[i], p.u_min, p.u_max, p.has_u_bounds);
+          }
+      }
+      if (j == 0 && p.x0_rep) {
+        for (int i = 0; i < p.n; ++i) p.x0_rep[(size_t)r * p.n + i] = p.x0[(size_t)b * p.n + i];
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------- k_mppi_update
@@ -400,6 +507,39 @@ hipError_t sample_launch(const SampleParams& p, hipStream_t st) {
   const bool al = p.N % 4 == 0 && aligned16(p.u) && aligned16(p.sig) && aligned16(p.v);
   if (p.sig) hipLaunchKernelGGL((al ? k_sample<true, true> : k_sample<true, false>), grid, block, 0, st, p);
   else hipLaunchKernelGGL((al ? k_sample<false, true> : k_sample<false, false>), grid, block, 0, st, p);
+  return hipGetLastError();
+}
+
+size_t sample_shaped_lds_bytes(int H, int P) {
+  const size_t bytes = (size_t)H * (size_t)(P | 1) * sizeof(float);
+  return bytes <= kShapedStageBytes ? bytes : 0;
+}
+
+// the shaped sample kernel of the sigma source and the row's alignment; lds: the bytes of L to stage, 0 = L stays in global memory
+template <bool TENSOR, bool ALIGNED, int G>
+static void sample_shaped_pick_g(const SampleParams& p, const float* L, int P, size_t lds, hipStream_t st) {
+  const long long want = (p.B * p.K + kBlock / G - 1) / (kBlock / G);
+  const dim3 grid((unsigned)(want < kShapedMaxBlocks ? want : kShapedMaxBlocks));
+  if (lds) hipLaunchKernelGGL((k_shaped_sample<TENSOR, ALIGNED, true, G>), grid, dim3(kBlock), lds, st, p, L, P);
+  else hipLaunchKernelGGL((k_shaped_sample<TENSOR, ALIGNED, false, G>), grid, dim3(kBlock), 0, st, p, L, P);
+}
+
+// G: the smallest lane group with a lane per float4 of the sample row (P <= H: the eps row is no longer)
+template <bool TENSOR, bool ALIGNED>
+static void sample_shaped_pick(const SampleParams& p, const float* L, int P, size_t lds, hipStream_t st) {
+  const int nv4 = (p.N + 3) / 4;
+  if (nv4 <= 16) sample_shaped_pick_g<TENSOR, ALIGNED, 16>(p, L, P, lds, st);
+  else if (nv4 <= 32) sample_shaped_pick_g<TENSOR, ALIGNED, 32>(p, L, P, lds, st);
+  else sample_shaped_pick_g<TENSOR, ALIGNED, 64>(p, L, P, lds, st);
+}
+
+hipError_t sample_shaped_launch(const SampleParams& p, const float* L, int P, hipStream_t st) {
+  const long long rows = p.B * p.K;
+  if (rows < 1 || !L || p.m < 1 || p.N % p.m || P < 1 || P > p.N / p.m || p.N > kSamplingMaxN) return hipErrorInvalidValue;
+  const size_t lds = sample_shaped_lds_bytes(p.N / p.m, P);
+  const bool al = p.N % 4 == 0 && aligned16(p.u) && aligned16(p.sig) && aligned16(p.v);
+  if (p.sig) al ? sample_shaped_pick<true, true>(p, L, P, lds, st) : sample_shaped_pick<true, false>(p, L, P, lds, st);
+  else al ? sample_shaped_pick<false, true>(p, L, P, lds, st) : sample_shaped_pick<false, false>(p, L, P, lds, st);
   return hipGetLastError();
 }
 

@@ -591,32 +591,44 @@ class RolloutEngine:
         for t in tensors:
             assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device)
 
-    def _sample(self, meth, opt, x0, u, sig, cost, iteration, workspace):
-        """phnn_<meth>_sample; sig: the method's extra input tensors (CEM's standard deviation)."""
+    def _noise_shape(self, noise):
+        """noise (noise.Noise, or an (H, P) array wrapped here) -> (phnn_noise_shape on this device, what to keep alive)."""
+        from .noise import Noise
+        noise = noise if isinstance(noise, Noise) else Noise(noise.detach().cpu().numpy() if isinstance(noise, torch.Tensor) else noise)
+        return noise.struct(self.device), noise
+
+    def _sample(self, meth, opt, x0, u, sig, cost, iteration, workspace, noise=None):
+        """phnn_<meth>_sample (noise None) or phnn_<meth>_sample_shaped; sig: the method's extra input tensors (CEM's
+        standard deviation)."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u, H = self._controls(u, B)
         self._assert_device_f32(*sig)
         assert all(t.numel() == u.numel() for t in sig)
         ws = self._sampling_buffers({} if workspace is None else workspace, meth, B, H, opt.samples)
-        rc = getattr(self.lib, f"phnn_{meth}_sample")(self.h, self._p(x0), self._p(u), *map(self._p, sig), B, H, C.byref(cost),
-                                                      C.byref(opt), int(iteration), self._p(ws[meth + "_v"]),
-                                                      self._p(ws[meth + "_x0"]), self._stream())
+        head = (self.h, self._p(x0), self._p(u), *map(self._p, sig), B, H, C.byref(cost), C.byref(opt), int(iteration))
+        tail = (self._p(ws[meth + "_v"]), self._p(ws[meth + "_x0"]), self._stream())
+        if noise is None:
+            rc = getattr(self.lib, f"phnn_{meth}_sample")(*head, *tail)
+        else:
+            shape, _keep = self._noise_shape(noise)
+            rc = getattr(self.lib, f"phnn_{meth}_sample_shaped")(*head, C.byref(shape), *tail)
         _check(self.lib, self.h, rc)
         return ws[meth + "_v"], ws[meth + "_x0"]
 
-    def mppi_sample(self, x0, u, cost, samples, sigma, seed, iteration, epoch=0, problem_offset=0, workspace=None):
+    def mppi_sample(self, x0, u, cost, samples, sigma, seed, iteration, epoch=0, problem_offset=0, workspace=None, noise=None):
         """k_sample with MPPI's sigma.  x0 (B,n), nominal u (B,H,m) -> (v (B*samples,H,m), x0 replicated (B*samples,n)):
         sample b * samples + k is clamp(u_b + sigma o z), z standard normal from the Philox counter (seed, epoch, iteration,
-        problem_offset + b, k) and zero for k = 0.  The outputs are views of `workspace` (a dict reused across calls)."""
+        problem_offset + b, k) and zero for k = 0.  The outputs are views of `workspace` (a dict reused across calls).
+        noise: None = white; a noise.Noise (or an (H, P) array) = k_shaped_sample, z[t, c] = sum_s L[t, s] eps[s, c]."""
         opt, _keep = self._mppi_options(0, samples, 1.0, sigma, seed, epoch, problem_offset)
-        return self._sample("mppi", opt, x0, u, (), cost, iteration, workspace)
+        return self._sample("mppi", opt, x0, u, (), cost, iteration, workspace, noise)
 
-    def cem_sample(self, x0, u, sig, cost, samples, seed, iteration, epoch=0, problem_offset=0, workspace=None):
+    def cem_sample(self, x0, u, sig, cost, samples, seed, iteration, epoch=0, problem_offset=0, workspace=None, noise=None):
         """k_sample with CEM's sigma: as mppi_sample with a standard deviation sig (B,H,m) per problem and element,
-        sample b * samples + k = clamp(u_b + sig_b o z)."""
+        sample b * samples + k = clamp(u_b + sig_b o z).  noise: as in mppi_sample."""
         opt, _keep = self._cem_options(0, samples, 1, 0.0, 0.0, 0.0, seed, epoch, problem_offset)
-        return self._sample("cem", opt, x0, u, (sig,), cost, iteration, workspace)
+        return self._sample("cem", opt, x0, u, (sig,), cost, iteration, workspace, noise)
 
     def _update(self, meth, options, u, sig, v, s, cost, costs_row, best_cost, best_u):
         """phnn_<meth>_update; options(samples) -> the method's options struct, sig as in _sample."""
@@ -645,8 +657,9 @@ class RolloutEngine:
                      costs_row, best_cost, best_u)
 
     def _solve_sampling(self, meth, opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
-                        expanded_ref):
-        """phnn_solve_<meth> -> dict(u_last, [sigma_last (CEM),] costs, best_u, best_cost)."""
+                        expanded_ref, noise=None):
+        """phnn_solve_<meth> (noise None) or phnn_solve_<meth>_shaped -> dict(u_last, [sigma_last (CEM),] costs, best_u,
+        best_cost)."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u_init, H = self._controls(u_init, B)
@@ -659,15 +672,21 @@ class RolloutEngine:
         sig = (torch.empty(B, H, self.m, **f),) if meth == "cem" else ()
         ref, _keep_ref = self._reference(x_ref if expanded_ref else self.mppi_reference(x_ref, B, opt.samples), ref_offset,
                                          B * opt.samples)
-        rc = getattr(self.lib, "phnn_solve_" + meth)(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
-                                                     None if ref is None else C.byref(ref), integ, float(dt), C.byref(opt),
-                                                     self._p(ws[meth]), ws[meth].numel(), self._p(costs), self._p(best_cost),
-                                                     self._p(best_u), *map(self._p, sig), self._stream())
+        head = (self.h, self._p(x0), self._p(u), B, H, C.byref(cost), None if ref is None else C.byref(ref), integ, float(dt),
+                C.byref(opt))
+        tail = (self._p(ws[meth]), ws[meth].numel(), self._p(costs), self._p(best_cost), self._p(best_u), *map(self._p, sig),
+                self._stream())
+        if noise is None:
+            rc = getattr(self.lib, "phnn_solve_" + meth)(*head, *tail)
+        else:
+            shape, _keep_noise = self._noise_shape(noise)
+            rc = getattr(self.lib, f"phnn_solve_{meth}_shaped")(*head, C.byref(shape), *tail)
         _check(self.lib, self.h, rc)
         return {"u_last": u, **({"sigma_last": sig[0]} if sig else {}), "costs": costs, "best_u": best_u, "best_cost": best_cost}
 
     def solve_mppi(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=4, samples=64, lam=1.0, sigma=1.0, seed=0,
-                   epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0, expanded_ref=False):
+                   epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0, expanded_ref=False,
+                   noise=None):
         """phnn_solve_mppi: sampling MPC (MPPI) on B independent problems as ONE library call: the nominal is clamped,
         then iters x (k_sample, K1 over B * samples rollouts, k_mppi_update); no gradient is taken anywhere.
         -> dict(u_last (B,H,m) last nominal (in bounds), costs (iters,B) the nominal's cost at every iteration or None,
@@ -676,14 +695,16 @@ class RolloutEngine:
         temperature in units of the cost; seed, epoch (int or device int32 tensor), problem_offset: the noise counter
         (problem b's noise depends on problem_offset + b, not on the batch).  x_ref, ref_offset: as in rollout_cost; a
         per-problem reference is expanded to one row set per rollout (mppi_reference: samples times its bytes) once per
-        call, unless expanded_ref says x_ref already is what mppi_reference returned (a closed loop expands it once)."""
+        call, unless expanded_ref says x_ref already is what mppi_reference returned (a closed loop expands it once).
+        noise: None = white noise; a noise.Noise (or an (H, P) array) = time-correlated noise (phnn_solve_mppi_shaped:
+        k_shaped_sample in k_sample's place, everything else as it is); a captured graph reads its device tensor in place."""
         opt, _keep = self._mppi_options(iters, samples, lam, sigma, seed, epoch, problem_offset)
         return self._solve_sampling("mppi", opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
-                                    expanded_ref)
+                                    expanded_ref, noise)
 
     def solve_cem(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=4, samples=64, elites=8, alpha=0.25, sigma=1.0,
                   sigma_min=0.05, seed=0, epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None,
-                  ref_offset=0, expanded_ref=False):
+                  ref_offset=0, expanded_ref=False, noise=None):
         """phnn_solve_cem: sampling MPC by the cross-entropy method on B independent problems as ONE library call: the
         mean is clamped and the standard deviation set to sigma, then iters x (k_sample, K1 over B * samples
         rollouts, k_cem_update); no gradient is taken anywhere.  -> dict(u_last (B,H,m) last mean (in bounds), sigma_last
@@ -691,10 +712,10 @@ class RolloutEngine:
         best_cost (B) the best sample over all iterations), same results bit for bit as solver.cem_solve.  elites: how
         many of the lowest-cost samples mean and standard deviation are refitted to; alpha: smoothing in [0, 1);
         sigma: initial standard deviation, one value or one per control component; sigma_min: its floor.  seed, epoch,
-        problem_offset, x_ref, ref_offset, expanded_ref: as in solve_mppi."""
+        problem_offset, x_ref, ref_offset, expanded_ref, noise (phnn_solve_cem_shaped): as in solve_mppi."""
         opt, _keep = self._cem_options(iters, samples, elites, alpha, sigma, sigma_min, seed, epoch, problem_offset)
         return self._solve_sampling("cem", opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
-                                    expanded_ref)
+                                    expanded_ref, noise)
 
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,

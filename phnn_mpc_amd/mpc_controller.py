@@ -20,13 +20,14 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import SAMPLING, lbfgs_solver_for, solver_for
+from .noise import resolve as resolve_noise
+from .solver import SAMPLING, _noise_kw, lbfgs_solver_for, solver_for
 
 
 class MPCController:
     def __init__(self, phnn_model, horizon, dt, Q, R, target_state=None, u_min=None, u_max=None, x_min=None, x_max=None,
                  optimizer_type="Adam", lr=0.1, max_iterations=50, samples=64, lam=1.0, sigma=1.0, seed=0, elites=8,
-                 alpha=0.25, sigma_min=0.05):
+                 alpha=0.25, sigma_min=0.05, noise=None):
         self.model = phnn_model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -47,6 +48,9 @@ class MPCController:
         # optimizer_type='CrossEntropy': samples, sigma (the initial standard deviation), seed and epoch as above; elites:
         # how many lowest-cost samples the distribution is refitted to, smoothing alpha in [0, 1), floor of sigma
         self.elites, self.alpha, self.sigma_min = elites, alpha, sigma_min
+        # MPPI and CrossEntropy: the time correlation of the sampling noise (noise.resolve: None = white, a noise.Noise,
+        # {"type": "ar1" | "colored" | "knots", ...} or an (H, P) array); ValueError for an unknown type or another horizon
+        self.noise = resolve_noise(noise, horizon)
         self.integrator = "euler"  # src/mpc_controller.py:137-138
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -169,7 +173,8 @@ class MPCController:
     def mppi_options(self):
         """solve_mppi keyword arguments of this controller."""
         return dict(iters=self.max_iterations, samples=self.samples, lam=self.lam,
-                    sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), seed=self.seed)
+                    sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), seed=self.seed,
+                    **_noise_kw(self.noise))
 
     def _mppi_epoch(self, eng, epoch):
         """The epoch argument of one solve: `epoch` (None: the controller's own counter, advanced here); with use_graph
@@ -187,7 +192,7 @@ class MPCController:
         """solve_cem keyword arguments of this controller."""
         return dict(iters=self.max_iterations, samples=self.samples, elites=self.elites, alpha=self.alpha,
                     sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), sigma_min=self.sigma_min,
-                    seed=self.seed)
+                    seed=self.seed, **_noise_kw(self.noise))
 
     def _solve_batch_sampling(self, states, record_costs, x_ref, ref_offset, epoch):
         """B independent sampling solves, MPPI or cross-entropy (cold start from zeros), in one batched device solve
@@ -214,8 +219,8 @@ class MPCController:
 
 def _mppi_keys(mpc):
     """The sampling-solver keywords present in the `mpc` config section (optimizer: MPPI or CrossEntropy): samples, lam,
-    sigma, seed, elites, alpha, sigma_min."""
-    return {k: mpc[k] for k in ("samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min") if k in mpc}
+    sigma, seed, elites, alpha, sigma_min, noise."""
+    return {k: mpc[k] for k in ("samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise") if k in mpc}
 
 
 def create_mpc_from_config(phnn_model, config):

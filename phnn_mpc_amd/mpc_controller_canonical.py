@@ -18,13 +18,14 @@ import numpy as np
 import torch
 
 from . import _capi
-from .solver import SAMPLING, solver_for
+from .noise import resolve as resolve_noise
+from .solver import SAMPLING, _noise_kw, solver_for
 
 
 class MPCControllerCanonical:
     def __init__(self, model, horizon=20, dt=0.02, Q=None, R=None, x_target=None, u_min=-10.0, u_max=10.0,
                  optimizer_steps=50, learning_rate=0.1, verbose=False, optimizer="Adam", samples=64, lam=1.0, sigma=1.0,
-                 seed=0, elites=8, alpha=0.25, sigma_min=0.05):
+                 seed=0, elites=8, alpha=0.25, sigma_min=0.05, noise=None):
         self.model = model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -48,6 +49,9 @@ class MPCControllerCanonical:
         # optimizer='CrossEntropy': samples, sigma (the initial standard deviation), seed and epoch as above; elites: how
         # many lowest-cost samples the distribution is refitted to, smoothing alpha in [0, 1), floor of sigma
         self.elites, self.alpha, self.sigma_min = elites, alpha, sigma_min
+        # MPPI and CrossEntropy: the time correlation of the sampling noise (noise.resolve: None = white, a noise.Noise,
+        # {"type": "ar1" | "colored" | "knots", ...} or an (H, P) array); ValueError for an unknown type or another horizon
+        self.noise = resolve_noise(noise, horizon)
         self.integrator = "euler"
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -115,13 +119,14 @@ class MPCControllerCanonical:
     def mppi_options(self):
         """solve_mppi keyword arguments of this controller."""
         return dict(iters=self.optimizer_steps, samples=self.samples, lam=self.lam,
-                    sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), seed=self.seed)
+                    sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), seed=self.seed,
+                    **_noise_kw(self.noise))
 
     def cem_options(self):
         """solve_cem keyword arguments of this controller."""
         return dict(iters=self.optimizer_steps, samples=self.samples, elites=self.elites, alpha=self.alpha,
                     sigma=tuple(np.asarray(self.sigma, dtype=np.float64).reshape(-1).tolist()), sigma_min=self.sigma_min,
-                    seed=self.seed)
+                    seed=self.seed, **_noise_kw(self.noise))
 
     def _mppi_epoch(self, eng, epoch):
         """The epoch argument of one solve: `epoch` (None: the controller's own counter, advanced here); with use_graph
@@ -184,4 +189,5 @@ def create_mpc_controller(model, config):
         x_target=np.array(mpc.get("x_target", [0.0, 0.0, 0.0, 0.0])), u_min=mpc.get("u_min", -10.0),
         u_max=mpc.get("u_max", 10.0), optimizer_steps=mpc.get("optimizer_steps", 50),
         learning_rate=mpc.get("learning_rate", 0.1), verbose=mpc.get("verbose", False),
-        **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min") if k in mpc})
+        **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise")
+           if k in mpc})

@@ -108,8 +108,14 @@ def _sampling_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, sa
     return {"u_last": u, "costs": costs, "best_u": best_u, "best_cost": best_cost}
 
 
+def _noise_kw(noise):
+    """The `noise` keyword of an engine call: passed only when there is a noise shape, so that an engine written before
+    shaped noise existed is called exactly as it always was."""
+    return {} if noise is None else {"noise": noise}
+
+
 def mppi_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, sigma, seed, epoch=0, problem_offset=0,
-               record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+               record_costs=True, workspace=None, x_ref=None, ref_offset=0, noise=None):
     """Sampling MPC (MPPI) on B independent problems: x0 (B,n), u_init (B,H,m) -> dict(u_last, costs, best_u, best_cost).
 
     The nominal u starts at clamp(u_init) (the cost's bounds); `iters` times: v = engine.mppi_sample (samples
@@ -119,16 +125,17 @@ def mppi_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, si
     costs    : (iters,B) cost of the nominal at every iteration (its sample 0), if record_costs
     best_u   : the best sample seen over all iterations (strict '<', lowest sample index on ties), best_cost its cost
     seed, epoch (int or device int32 tensor), problem_offset: the noise counter; problem b draws the noise of global
-    problem problem_offset + b whatever batch it is solved in.  x_ref, ref_offset: as in shooting_solve."""
+    problem problem_offset + b whatever batch it is solved in.  x_ref, ref_offset: as in shooting_solve.
+    noise: None = white noise; a noise.Noise = time-correlated noise of that shape (engine.mppi_sample(noise=))."""
     return _sampling_solve(
         engine, x0, u_init, cost, integrator, dt, iters, samples,
         lambda u, i, ws: engine.mppi_sample(x0, u, cost, samples, sigma, seed, i, epoch=epoch, problem_offset=problem_offset,
-                                            workspace=ws),
+                                            workspace=ws, **_noise_kw(noise)),
         lambda u, v, s, **out: engine.mppi_update(u, v, s, lam, cost, **out), record_costs, workspace, x_ref, ref_offset)
 
 
 def cem_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch=0,
-              problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+              problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0, noise=None):
     """Sampling MPC by the cross-entropy method on B independent problems: x0 (B,n), u_init (B,H,m) ->
     dict(u_last, sigma_last, costs, best_u, best_cost).
 
@@ -137,7 +144,7 @@ def cem_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, 
     sample 0 the mean itself), S = engine.rollout_cost of all B * samples rollouts, engine.cem_update refits u and sig
     to the `elites` samples of lowest finite cost with smoothing alpha, sig floored at sigma_min.
     u_last   : the last mean (B,H,m), in bounds;  sigma_last: the last standard deviation (B,H,m)
-    costs, best_u, best_cost, seed, epoch, problem_offset, x_ref, ref_offset: as in mppi_solve."""
+    costs, best_u, best_cost, seed, epoch, problem_offset, x_ref, ref_offset, noise: as in mppi_solve."""
     _need_reference(engine, x_ref)
     m = u_init.shape[2]
     s0 = np.asarray(sigma, dtype=np.float64).reshape(-1)
@@ -149,7 +156,7 @@ def cem_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, 
     out = _sampling_solve(
         engine, x0, u_init, cost, integrator, dt, iters, samples,
         lambda u, i, ws: engine.cem_sample(x0, u, sig, cost, samples, seed, i, epoch=epoch, problem_offset=problem_offset,
-                                           workspace=ws),
+                                           workspace=ws, **_noise_kw(noise)),
         lambda u, v, s, **out: engine.cem_update(u, sig, v, s, elites, alpha, sigma_min, cost, **out), record_costs, workspace,
         x_ref, ref_offset)
     return {"u_last": out.pop("u_last"), "sigma_last": sig, **out}
@@ -162,20 +169,21 @@ def _library_or(engine, name, loop):
 
 
 def _mppi_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, lam, sigma, seed, epoch=0, problem_offset=0,
-                record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+                record_costs=True, workspace=None, x_ref=None, ref_offset=0, noise=None):
     """The MPPI solve without a captured graph (_library_or); called as mppi_solve is."""
     return _library_or(engine, "solve_mppi", mppi_solve)(
         x0, u_init, cost, integrator, dt, iters=iters, samples=samples, lam=lam, sigma=sigma, seed=seed, epoch=epoch,
-        problem_offset=problem_offset, record_costs=record_costs, workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
+        problem_offset=problem_offset, record_costs=record_costs, workspace=workspace, x_ref=x_ref, ref_offset=ref_offset,
+        **_noise_kw(noise))
 
 
 def _cem_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, elites, alpha, sigma, sigma_min, seed, epoch=0,
-               problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+               problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0, noise=None):
     """The CEM solve without a captured graph (_library_or); called as cem_solve is."""
     return _library_or(engine, "solve_cem", cem_solve)(
         x0, u_init, cost, integrator, dt, iters=iters, samples=samples, elites=elites, alpha=alpha, sigma=sigma,
         sigma_min=sigma_min, seed=seed, epoch=epoch, problem_offset=problem_offset, record_costs=record_costs,
-        workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
+        workspace=workspace, x_ref=x_ref, ref_offset=ref_offset, **_noise_kw(noise))
 
 
 def capture(device, fn):
@@ -281,7 +289,8 @@ class GraphedMPPI(Graphed):
     launch.  `epoch` is part of the graph's signature: an int re-captures when it changes, a device int32 tensor is read
     through its pointer at every replay (fill it in place between calls to draw fresh noise).  sigma must be hashable (a
     float or a tuple).  A per-problem x_ref lives in the graph's static buffer as given and its expansion to one row set
-    per rollout is part of the replayed graph."""
+    per rollout is part of the replayed graph.  noise: None or a noise.Noise -- it keys the graph by identity and its
+    device tensor is the graph's static buffer: keep the object, another one re-captures."""
 
     def __init__(self, engine):
         super().__init__(engine, _mppi_eager)

@@ -5,6 +5,7 @@ inside an iteration against a plain K1 of the same batch, and the single-plant /
 
   python tools/sampling_probe.py --method mppi|cem --shape 1024x64 [--H 50] [--elites 8] [--reps 20]   one JSON line per measurement
   python tools/sampling_probe.py --method cem --shape 1024x64 --loop   also: one plant graphed, 4096 plants x 100 closed-loop steps
+  python tools/sampling_probe.py --method mppi --shape 4096x256 --noise ar1:0.9|colored:2|knots:8   shaped noise
   rocprofv3 --kernel-trace --stats -d profiles/mppi_1024x64 -- python tools/sampling_probe.py --method mppi --shape 1024x64 --reps 5
 
 Times are device events around `reps` back-to-back launches of one phase (median of 5 such groups), after a warm-up.
@@ -44,6 +45,7 @@ def main():
     ap.add_argument("--H", type=int, default=50)
     ap.add_argument("--elites", type=int, default=8, help="cem only")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--noise", default=None, help="shaped noise: ar1:RHO | colored:BETA | knots:COUNT (default: white)")
     ap.add_argument("--loop", action="store_true", help="also: one plant H=20 K=64 iters=4 graphed, 4096 plants x 100 steps")
     a = ap.parse_args()
     import torch
@@ -59,22 +61,29 @@ def main():
     u = torch.zeros(B, H, 1, device="cuda")
     ws = {}
     R, N, n = B * K, H * eng.m, eng.n
+    nkw = {}  # the `noise` keyword of the sample and solve calls
+    if a.noise:
+        from phnn_mpc_amd import noise as nz
+        kind, _, arg = a.noise.partition(":")
+        L = {"ar1": lambda: nz.ar1(H, float(arg)), "colored": lambda: nz.colored(H, float(arg)),
+             "knots": lambda: nz.knots(H, int(arg))}[kind]()
+        nkw = {"noise": nz.Noise(L)}
     # per method: the three calls, the closed-loop config, and the algorithmic bytes of sample and update
     if M == "mppi":
-        sample = lambda: eng.mppi_sample(x0, u, cost, K, 2.0, 1, 0, workspace=ws)
+        sample = lambda: eng.mppi_sample(x0, u, cost, K, 2.0, 1, 0, workspace=ws, **nkw)
         update = lambda: eng.mppi_update(u, v, s, 50.0, cost, best_cost=bc, best_u=bu)
         solve = lambda: eng.solve_mppi(x0, u, cost, "euler", 0.02, iters=4, samples=K, lam=50.0, sigma=2.0, seed=1,
-                                       record_costs=False, workspace=ws)
+                                       record_costs=False, workspace=ws, **nkw)
         config = dict(optimizer="MPPI", samples=64, lam=50.0, sigma=3.0, seed=1, optimizer_steps=4)
         by_s = 4 * (R * N + B * N + R * n + B * n)          # samples written, nominal read, x0 replicated
         by_u = 4 * (R * N + 2 * R + 2 * B * N + 2 * B)      # samples read, costs read twice (L2), nominal + best written
     else:
         sig = torch.full((B, H, 1), 2.0, device="cuda")
         u2, sig2 = u.clone(), sig.clone()  # the update works in place: alpha = 0.25 keeps both in range over the repetitions
-        sample = lambda: eng.cem_sample(x0, u, sig, cost, K, 1, 0, workspace=ws)
+        sample = lambda: eng.cem_sample(x0, u, sig, cost, K, 1, 0, workspace=ws, **nkw)
         update = lambda: eng.cem_update(u2, sig2, v, s, E, 0.25, 0.05, cost, best_cost=bc, best_u=bu)
         solve = lambda: eng.solve_cem(x0, u, cost, "euler", 0.02, iters=4, samples=K, elites=E, alpha=0.25, sigma=2.0,
-                                      sigma_min=0.05, seed=1, record_costs=False, workspace=ws)
+                                      sigma_min=0.05, seed=1, record_costs=False, workspace=ws, **nkw)
         config = dict(optimizer="CrossEntropy", samples=64, elites=8, alpha=0.25, sigma=3.0, sigma_min=0.05, seed=1,
                       optimizer_steps=4)
         by_s = 4 * (R * N + 2 * B * N + R * n + B * n)          # samples written, mean + sigma read, x0 replicated
@@ -82,7 +91,8 @@ def main():
     v, x0r = sample()
     s = eng.rollout_cost(x0r, v, cost, "euler", 0.02)
     bc, bu = torch.full((B,), float("inf"), device="cuda"), torch.zeros_like(u)
-    res = {"shape": a.shape, "H": H, **({"elites": E} if M == "cem" else {}), "rollouts": R, "variant": eng.variant}
+    res = {"shape": a.shape, "H": H, **({"elites": E} if M == "cem" else {}), "rollouts": R, "variant": eng.variant,
+           "noise": a.noise or "white", **({"P": nkw["noise"].P} if nkw else {})}
     t_s = timed(torch, sample, a.reps)
     t_u = timed(torch, update, a.reps)
     # K1 on the sample tensor (what an iteration launches) and on an ordinary (R, H, m) batch, alternating
@@ -109,6 +119,9 @@ def main():
         cfgp = os.path.join(ROOT, "configs", "cartpole_mpc.yaml")
         cfg = yaml.safe_load(open(cfgp))
         cfg["mpc"].update(config)
+        if nkw:
+            kind, _, arg = a.noise.partition(":")
+            cfg["mpc"]["noise"] = {"type": kind, {"ar1": "rho", "colored": "beta", "knots": "count"}[kind]: float(arg) if kind != "knots" else int(arg)}
         m = pHNN(cfgp)
         m.load_state_dict({k: torch.tensor(w) for k, w in ol.load_weights("phnn_cartpole").items()})
         c = create_mpc_from_config(m, cfg)
