@@ -145,7 +145,9 @@ typedef struct {
  * (src/mpc_controller.py:75-114 with Q = diag, R = scalar*I; src/mpc_controller_canonical.py:91-120 with
  * full Q, R).  Controls are clamped to [u_min,u_max] before use when has_u_bounds, and the returned
  * gradient is w.r.t. the UNclamped controls (torch.clamp backward: pass-through on u_min<=u<=u_max,
- * src/mpc_controller.py:180-181). */
+ * src/mpc_controller.py:180-181).  Every clamp of the library -- here, in the sampling kernels and updates, in
+ * phnn_adam_step's best_u and in phnn_plant_step -- passes a NaN on as torch.clamp does (it never becomes u_min), and
+ * CEM's floor max(sigma_min, .) passes a NaN deviation on as numpy.maximum does: a diverged problem shows as NaN. */
 typedef struct {
   float Q[PHNN_MAX_N * PHNN_MAX_N]; /* row-major n x n (leading n*n entries used) */
   float R[PHNN_MAX_M * PHNN_MAX_M]; /* row-major m x m */
@@ -566,7 +568,8 @@ typedef struct {
 /* One plant step for B plants, everything resident on the device (no host round trip in a closed loop):
  *   state_dev (B,4) float64, updated in place;  action: action_dev[b * action_stride] (float32 force; the first
  *   control of rollout b's sequence when action_stride = H*m), clamped to [u_min,u_max] first when has_u_bounds
- *   (src/mpc_controller.py:203-209 returns clamp(u_seq[0])).
+ *   (src/mpc_controller.py:203-209 returns clamp(u_seq[0])); a NaN force is not clamped: it reaches the state, its
+ *   float32 copy and both logs as NaN, and a NaN state never terminates (done_step stays as it is).
  * Optional outputs (NULL = skip): state_f32_dev (B,4) = float32 of the new state (what the next solve consumes:
  * torch.tensor(state, dtype=float32) in scripts/run_cartpole_mpc.py:129); done_step_dev (B) int32, set to the step
  * index the first time a plant terminates (initialise to -1); log_states_dev (T+1,B,4) float64 and

@@ -22,9 +22,11 @@ import numpy as np
 
 
 class BatchedCartPole:
-    def __init__(self, dt=0.02):
+    def __init__(self, dt=0.02, gravity=9.8, masscart=1.0, masspole=0.1, length=0.5, x_limit=10.0, theta_limit=0.5):
+        """The defaults are the reference's plant; the other arguments are the fields of phnn_plant (_capi.Plant)."""
         self.dt = dt
-        self.gravity, self.masscart, self.masspole, self.length = 9.8, 1.0, 0.1, 0.5
+        self.gravity, self.masscart, self.masspole, self.length = gravity, masscart, masspole, length
+        self.x_limit, self.theta_limit = x_limit, theta_limit
         self.polemass_length = self.masspole * self.length
         self.total_mass = self.masspole + self.masscart
         self.state = None
@@ -44,7 +46,7 @@ class BatchedCartPole:
         xacc = temp - self.polemass_length * thetaacc * costheta / self.total_mass
         self.state = np.stack([x + self.dt * x_dot, theta + self.dt * theta_dot, x_dot + self.dt * xacc,
                                theta_dot + self.dt * thetaacc], axis=1)
-        done = (np.abs(self.state[:, 0]) > 10.0) | (np.abs(self.state[:, 1]) > 0.5)
+        done = (np.abs(self.state[:, 0]) > self.x_limit) | (np.abs(self.state[:, 1]) > self.theta_limit)
         return self.state.copy(), done
 
     def get_state(self):

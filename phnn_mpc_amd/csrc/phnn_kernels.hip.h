@@ -3011,7 +3011,21 @@ DEV void store_state(float* p, f32x4 x) {
   }
 }
 
-DEV float clamp_u(const phnn_cost& c, float u) { return c.has_u_bounds ? fminf(fmaxf(u, c.u_min), c.u_max) : u; }
+// A NaN control stays NaN, as in torch.clamp (fminf / fmaxf alone would turn it into u_min).  Where nothing is to be
+// clamped (no bounds, or `on` false: the cost-free marches) the clamp runs against -inf / +inf, which returns every
+// non-NaN u as it is: the only per-lane decision is the NaN select, and the uniform conditions pick two scalars outside
+// the time-step loop instead of standing in it, where the compiler turned `no_cost ? u : (has_u_bounds && u == u ? ..)`
+// into branches that made K2 wait for the control load at the head of every step (1.3 % of K2).
+DEV float clamp_u(const phnn_cost& c, float u, bool on = true) {
+  const bool b = on && c.has_u_bounds;
+  const float lo = b ? c.u_min : -INFINITY, hi = b ? c.u_max : INFINITY;
+  const float r = fminf(fmaxf(u, lo), hi);
+  return u == u ? r : u;
+}
+// The same clamp as a select on `has_u_bounds && u == u`, for K1's control load: there the compiler keeps it a select,
+// and this form measured inside the parent's run-to-run spread where the one above cost K1 0.5 % (same instruction
+// count, another placement).  Same value for every input.
+DEV float clamp_u_k1(const phnn_cost& c, float u) { return c.has_u_bounds && u == u ? fminf(fmaxf(u, c.u_min), c.u_max) : u; }
 
 // controls of one step: (B,H,MI) row-major, up = this rollout's (H,MI) block
 template <int MI>
@@ -3022,9 +3036,9 @@ DEV f32x4 load_u(const float* up, int t) {
   return u;
 }
 template <int MI>
-DEV f32x4 clamp_u4(const phnn_cost& c, f32x4 u) {
+DEV f32x4 clamp_u4(const phnn_cost& c, f32x4 u, bool on = true) {
 #pragma unroll
-  for (int k = 0; k < MI; ++k) u[k] = clamp_u(c, u[k]);
+  for (int k = 0; k < MI; ++k) u[k] = clamp_u(c, u[k], on);
   return u;
 }
 // u^T R u in the order of ((u @ R) * u).sum() (src/mpc_controller_canonical.py:116-118); m = 1: (u R) u
@@ -3153,7 +3167,9 @@ DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
   for (int t = 0; t < p.H; ++t) {
     f32x4 tgt;
     if constexpr (REF) tgt = rr.row(t + 1);
-    f32x4 u = clamp_u4<MI>(p.c, load_u<MI>(up, t));
+    f32x4 u = load_u<MI>(up, t);
+#pragma unroll
+    for (int k = 0; k < MI; ++k) u[k] = clamp_u_k1(p.c, u[k]);
     if (MI == 1) cost = __builtin_fmaf(u[0] * p.c.R[0], u[0], cost);
     else cost += control_cost<MI>(p.c, u);
     float* sl = STASH ? p.stash + (tile * p.H + t) * (long long)SS::FLOATS : nullptr;
@@ -3230,7 +3246,7 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
     f32x4 tgt;
     if constexpr (REF && INTEG == PHNN_INTEG_EULER) tgt = rr.row(t);
     f32x4 uraw = load_u<MI>(up, t);
-    f32x4 u = p.no_cost ? uraw : clamp_u4<MI>(p.c, uraw);
+    f32x4 u = clamp_u4<MI>(p.c, uraw, !p.no_cost);
     f32x4 dxb = splat4(0.f);
     if (INTEG == PHNN_INTEG_EULER && db) dxb = load_state<N>(db + (long long)t * N) * live;
     f32x4 xb, ub, utot;
@@ -3273,7 +3289,7 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
         f32x4 y;
         if constexpr (STASH) y = s == 0 ? load_state<N>(tr + (long long)t * N) : load_stage(sl + s * SLOT + SS::TAPE, ln);
         else y = s == 0 ? load_state<N>(tr + (long long)t * N) : (s == 1 ? y2 : (s == 2 ? y3 : y4));
-        const f32x4 us = p.no_cost ? load_u<MI>(up, t) : clamp_u4<MI>(p.c, load_u<MI>(up, t));
+        const f32x4 us = clamp_u4<MI>(p.c, load_u<MI>(up, t), !p.no_cost);
         // cotangent on k_s: dt/6 (1,2,2,1) lam + the next stage's state cotangent times its step factor
         f32x4 in = ((s == 0 || s == 3) ? p.sixth_dt : 2.0f * p.sixth_dt) * lam;
         if (s != 3) in = in + (s == 2 ? p.dt : p.half_dt) * ybn;
@@ -3289,7 +3305,7 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
       x = load_state<N>(tr + (long long)t * N);
       if constexpr (REF) tgt = rr.row(t);
       uraw = load_u<MI>(up, t);
-      u = p.no_cost ? uraw : clamp_u4<MI>(p.c, uraw);
+      u = clamp_u4<MI>(p.c, uraw, !p.no_cost);
     }
     if constexpr (REF) lam = lam + cb * state_cost_grad<N>(p.c, p.Qs, x, tgt);
     else lam = lam + cb * state_cost_grad<N>(p.c, p.Qs, x, p.c.x_target);
@@ -3957,7 +3973,8 @@ __global__ void k_best_cost(const float* cost, float* best_cost, long long B) {
 }
 
 // Plant: the reference's ground-truth cart-pole (src/cartpole_simulator.py:63-112), float64, one thread per plant.
-// Operation order as in the reference (compiled with -ffp-contract=off: no fused multiply-adds).
+// Operation order as in the reference (compiled with -ffp-contract=off: no fused multiply-adds).  The force is clamped
+// as torch.clamp clamps: a NaN command stays NaN (it is not u_min), so a diverged solve shows in the state and the logs.
 struct PlantParams {
   phnn_plant pl;
   double* state;        // (B,4) in/out
@@ -3978,7 +3995,7 @@ __global__ void k_plant_step(PlantParams p) {
   if (b >= p.B) return;
   const int step = p.step_dev ? *p.step_dev : p.step_host;
   float uf = p.action[b * p.stride];
-  if (p.has_u_bounds) uf = fminf(fmaxf(uf, p.u_min), p.u_max);
+  if (p.has_u_bounds && uf == uf) uf = fminf(fmaxf(uf, p.u_min), p.u_max);  // a NaN command stays NaN: state and logs show it
   const double force = (double)uf;
   const double polemass_length = p.pl.masspole * p.pl.length, total_mass = p.pl.masspole + p.pl.masscart;
   double x = p.state[4 * b + 0], theta = p.state[4 * b + 1], x_dot = p.state[4 * b + 2], theta_dot = p.state[4 * b + 3];

@@ -46,7 +46,8 @@ __device__ __forceinline__ void box_muller(unsigned a, unsigned b, float& z0, fl
   z1 = r * s;
 }
 
-__device__ __forceinline__ float clampf(float v, float lo, float hi, int on) { return on ? fminf(fmaxf(v, lo), hi) : v; }
+// a NaN stays NaN, as in torch.clamp (fminf / fmaxf alone would turn it into lo)
+__device__ __forceinline__ float clampf(float v, float lo, float hi, int on) { return on && v == v ? fminf(fmaxf(v, lo), hi) : v; }
 
 // ---------------------------------------------------------------------------------------------- one DPP row
 template <int CTRL>

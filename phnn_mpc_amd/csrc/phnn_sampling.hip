@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleParams p) {
 
 __global__ __launch_bounds__(kBlock) void k_clamp(float* u, long long count, float lo, float hi) {
   const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-  if (i < count) u[i] = fminf(fmaxf(u[i], lo), hi);
+  if (i < count) u[i] = clampf(u[i], lo, hi, 1);
 }
 
 struct SigmaInit {
@@ -330,7 +330,8 @@ __device__ __forceinline__ float refit_mean(float u, float em, const CemUpdatePa
 }
 
 __device__ __forceinline__ float refit_sigma(float sg, float ev, const CemUpdateParams& p, float oma) {
-  return fmaxf(p.sigma_min, sqrtf(p.alpha * (sg * sg) + oma * ev));
+  const float r = sqrtf(p.alpha * (sg * sg) + oma * ev);
+  return r == r ? fmaxf(p.sigma_min, r) : r;  // np.maximum: a NaN deviation stays NaN
 }
 
 template <int E4, bool ALIGNED>

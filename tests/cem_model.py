@@ -75,7 +75,7 @@ def update(u, sig, v, s, E, alpha, sigma_min, dtype=np.float64, u_min=None, u_ma
         d = v[:, k] - em
         acc = np.where(elite[:, k, None], acc + d * d, acc)
     ev = acc / Ef
-    assert np.all(ev >= 0)
+    assert not np.any(ev < 0)  # a NaN sample or mean gives a NaN variance, never a negative one
     mean = a * u0 + oma * em
     if u_min is not None:
         mean = np.minimum(np.maximum(mean, dtype(np.float32(u_min))), dtype(np.float32(u_max)))

@@ -9,7 +9,7 @@ Three groups:
      row_scales: k_b = 5 ((7 b mod 17) - 8), -40 .. 40, mixed inside every 16-rollout tile, rollouts 3 and 20 scaled
      by exactly 0) and whole-cost scales 2^k on Q, R and barrier_weight (COST_EXPONENTS, scale_cost).
   B  isolation: a clean batch and a copy in which the rollouts POISONED carry a non-finite or extreme state or control
-     (POISONS, poison_rollout, poison_point).
+     (POISONS, poison_rollout, poison_point); a NaN control with and without the control bounds.
   C  the state-magnitude ladder (ladder, ladder_states, DROPPED): the census states times 10^j, one component at 6.0e4 / 7.0e4,
      and for the canonical model the angle at 30, 300 and 2900.
 """
@@ -96,7 +96,7 @@ def batch(sid, s, nb=B, horizon=H):
 
 # ----------------------------------------------------------------------------- B: poisoned rollouts
 POISONED = (0, 9, 15, 16, 36)  # first and last lane of a tile, a tile boundary, the last rollout of the ragged tile
-POISONS = ("nan_state", "inf_state", "state_1e30", "state_7e4", "nan_control", "inf_control_clamped")
+POISONS = ("nan_state", "inf_state", "state_1e30", "state_7e4", "nan_control", "nan_control_clamped", "inf_control_clamped")
 _STATE_VALUE = {"nan_state": np.nan, "inf_state": np.inf, "state_1e30": 1e30, "state_7e4": 7e4}
 
 
@@ -108,9 +108,9 @@ def unbounded(cost):
 
 def poison_rollout(kind, x0, U, cost, rows=POISONED):
     """-> (x0', U', cost'): copies with the rollouts `rows` poisoned; cost' is also the cost of the clean run
-    (nan_control runs without control bounds, so that the NaN is not clamped away).  The poisoned state component
-    rotates with the rollout (component b mod n); controls are poisoned at step 1 (NaN) or at steps 0 and 2 (+inf,
-    -inf)."""
+    (nan_control runs without control bounds, nan_control_clamped keeps them: the clamp passes a NaN on, as torch.clamp
+    does, so both give a NaN cost).  The poisoned state component rotates with the rollout (component b mod n);
+    controls are poisoned at step 1 (NaN, component b mod m) or at steps 0 and 2 (+inf, -inf)."""
     x0, U = np.array(x0, np.float32), np.array(U, np.float32)
     n = x0.shape[1]
     rows = [b for b in rows if b < len(x0)]
@@ -118,10 +118,10 @@ def poison_rollout(kind, x0, U, cost, rows=POISONED):
         for b in rows:
             x0[b, b % n] = _STATE_VALUE[kind]
         return x0, U, cost
-    if kind == "nan_control":
+    if kind in ("nan_control", "nan_control_clamped"):
         for b in rows:
             U[b, 1, b % U.shape[2]] = np.nan
-        return x0, U, unbounded(cost)
+        return x0, U, unbounded(cost) if kind == "nan_control" else cost
     assert kind == "inf_control_clamped"
     for b in rows:
         U[b, 0, :] = np.inf
@@ -137,7 +137,7 @@ def poison_point(kind, x, u, rows=POISONED):
     for b in rows:
         if kind in _STATE_VALUE:
             x[b, b % n] = _STATE_VALUE[kind]
-        elif kind == "nan_control":
+        elif kind in ("nan_control", "nan_control_clamped"):
             u[b, b % u.shape[1]] = np.nan
         else:
             u[b, :] = np.inf if b % 2 == 0 else -np.inf

@@ -64,8 +64,10 @@ def on_device(torch, a, misalign=False):
     return t
 
 
-def check_update(torch, eng, cost, u, sig, v, s, E, alpha, smin, misalign=False, lim=10.0, tag=""):
-    """One k_cem_update launch on numpy inputs against the float32 model, everything as bits."""
+def check_update(torch, eng, cost, u, sig, v, s, E, alpha, smin, misalign=False, lim=10.0, tag="", bits=bits):
+    """One k_cem_update launch on numpy inputs against the float32 model, everything as bits (`bits`: float32 array ->
+    uint32; a caller that feeds NaN inputs passes one that gives every NaN one pattern, a NaN's sign and payload being no
+    part of the model)."""
     B, N = u.shape
     H = N // eng.m
     K = s.size // B

@@ -7,7 +7,9 @@ A  Power-of-two homogeneity, bit for bit, every spec of the census (tests/test_h
    through rollout_cost_grad, stash and recompute (A2); at the same scales the gradients of one spec per family against
    the float64 oracle (A3), so that a consistently wrong kernel does not pass.
 B  Isolation, bit for bit: rollouts {0, 9, 15, 16, 36} carry a NaN / +inf / 1e30 / 7e4 state, a NaN control without
-   bounds or +-inf controls under the clamp; every output row of every other rollout equals the clean batch's.  The
+   and with bounds (the clamp passes a NaN on, as torch.clamp does: cost, trajectory from x_2 on and gradients are
+   non-finite where the float64 oracle's are) or +-inf controls under the clamp; every output row of every other
+   rollout equals the clean batch's.  The
    same for one problem of a solve, Adam, L-BFGS, MPPI and CEM.
 C  The state-magnitude ladder against the float64 oracle: on every admitted rung (heterogeneous.DROPPED) the device is
    within the stated tolerance or non-finite, never finite and outside it; f32 and bf16x3 kernels are within tolerance
@@ -208,6 +210,24 @@ def test_isolation(torch, sid, kind):
                 for name in ("K1 cost", "K2 cost stash=True", "K2 cost stash=False"):
                     rep.true(f"{name} {t}: finite where the float64 oracle's cost is not",
                              not np.isfinite(dirty[name][bad]).any())
+                if kind == "nan_control_clamped":  # the clamp passes the NaN on (torch.clamp): it first reaches x_2
+                    rep.true(f"oracle's cost non-finite on exactly the poisoned rollouts {t}", bool(bad[rows].all()))
+                    rep.same(f"K1 traj rows 0..1 of the poisoned rollouts {t}", dirty["K1 traj"][rows][:, :2],
+                             clean["K1 traj"][rows][:, :2])
+                    rep.true(f"oracle's traj non-finite from row 2 on {t}",
+                             bool((~np.isfinite(ref["traj"][rows][:, 2:])).any(axis=2).all()))
+                    rep.true(f"K1 traj rows >= 2 non-finite where the float64 oracle's are {t}",
+                             bool((~np.isfinite(dirty["K1 traj"][rows][:, 2:])).any(axis=2).all())
+                             and not np.isfinite(dirty["K1 traj"][rows][:, 2:][~np.isfinite(ref["traj"][rows][:, 2:])]).any())
+                    at_nan = np.isnan(Up[rows])  # the mask of the clamp zeroes the gradient entry at the NaN itself
+                    for stash in (True, False):
+                        for q in ("grad_u", "grad_x0"):
+                            nf = ~np.isfinite(ref[q][rows])
+                            if q == "grad_u":
+                                nf &= ~at_nan
+                            rep.true(f"oracle's {q} is non-finite somewhere {t}", bool(nf.any()))
+                            rep.true(f"K2 {q} stash={stash} {t}: finite where the float64 oracle's is not",
+                                     not np.isfinite(dirty[f"K2 {q} stash={stash}"][rows][nf]).any())
                 if kind == "inf_control_clamped":  # the clamp makes them finite: the whole batch against the oracle
                     rep.true(f"oracle finite {t}", not bad.any())
                     rep.le(f"clamped cost {t}", vc.err_cost(dirty["K1 cost"], ref["cost"]), vc.COST_RTOL * s["tol"])

@@ -128,7 +128,7 @@ def test_poison_builders():
 @pytest.mark.parametrize("kind", het.POISONS)
 def test_float64_oracle_on_the_poisoned_rollouts(kind):
     """What the GPU test expects of the poisoned rollouts themselves: a NaN or infinite state or an unclamped NaN control
-    makes the float64 oracle's cost non-finite; clamped infinite controls and the finite extreme states leave it finite."""
+    (or one under the clamp, which passes a NaN on) makes the float64 oracle's cost non-finite; clamped infinite controls and the finite extreme states leave it finite."""
     sid = het.FAMILIES[0]
     s = vc.ALL_SPECS[sid][1]
     d = het.batch(sid, s)
@@ -137,10 +137,36 @@ def test_float64_oracle_on_the_poisoned_rollouts(kind):
     c = m64.rollout(x0, U, cost, "euler", d["dt"], grad=False, traj=False)["cost"]
     rows = list(het.POISONED)
     assert np.isfinite(c[het.others(het.B)]).all()
-    if kind in ("nan_state", "inf_state", "nan_control"):
+    if kind in ("nan_state", "inf_state", "nan_control", "nan_control_clamped"):
         assert not np.isfinite(c[rows]).any()
     else:
         assert np.isfinite(c[rows]).all()
+
+
+@pytest.mark.parametrize("sid", het.ISOLATION_SPECS)
+def test_float64_oracle_passes_a_nan_control_through_the_clamp(sid):
+    """nan_control_clamped on the oracle alone, at every shape the GPU test runs: the cost is non-finite on exactly
+    POISONED, the trajectory is the clean one up to x_1 and non-finite from x_2 on, and both gradients are non-finite
+    somewhere besides the entry of the NaN itself -- so what the GPU test asks of the kernels there is not vacuous."""
+    s = vc.ALL_SPECS[sid][1]
+    m64 = ol.OracleModel(vc.build_state_dict(sid, s), "f64", activation=s["act"])
+    for nb in (het.B,) + (het.SPLIT_BATCHES[1:] if s["split"] else ()):
+        d = het.batch(sid, s, nb)
+        x0, U, cost = het.poison_rollout("nan_control_clamped", d["x0"], d["U"], d["cost"])
+        assert cost.has_u_bounds == 1 and het.same_bits(x0, d["x0"])
+        keep = het.others(nb)
+        rows = np.flatnonzero(~keep)
+        assert np.isnan(U).sum() == len(rows) and np.isnan(U[rows, 1]).any(axis=1).all()
+        for integ in het.INTEGRATORS:
+            r = m64.rollout(x0, U, cost, integ, d["dt"], nthreads=8)
+            c = m64.rollout(d["x0"], d["U"], cost, integ, d["dt"], nthreads=8)
+            assert not np.isfinite(r["cost"][rows]).any() and np.isfinite(r["cost"][keep]).all(), (sid, nb, integ)
+            assert np.array_equal(r["traj"][rows][:, :2], c["traj"][rows][:, :2]), (sid, nb, integ)
+            assert (~np.isfinite(r["traj"][rows][:, 2:])).any(axis=2).all(), (sid, nb, integ)
+            assert (~np.isfinite(r["grad_u"][rows]) & ~np.isnan(U[rows])).any(axis=(1, 2)).all(), (sid, nb, integ)
+            assert (~np.isfinite(r["grad_x0"][rows])).any(axis=1).all(), (sid, nb, integ)
+            for q in ("cost", "traj", "grad_u", "grad_x0"):
+                assert np.array_equal(r[q][keep], c[q][keep]), (sid, nb, integ, q)
 
 
 @pytest.mark.parametrize("sid", het.LADDER_SPECS)

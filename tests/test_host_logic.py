@@ -307,6 +307,47 @@ def test_batched_plant_matches_reference_simulator_g11(ctl):
     assert ctl["plant_done"][-1, 2] and not ctl["plant_done"][0].any()
 
 
+def test_parametrised_plant_with_default_arguments_is_the_old_one(ctl):
+    """BatchedCartPole's optional constants default to the reference's: with them spelled out (and with none given) the
+    G11 run is bit-identical to the plant with the constants written into the step, restated here; another constant
+    changes it; the limits are strict and only move `done`."""
+    from phnn_mpc_amd.closed_loop import BatchedCartPole
+
+    def old_step(s, force, dt=0.02):
+        x, theta, x_dot, theta_dot = s.T
+        costheta, sintheta = np.cos(theta), np.sin(theta)
+        temp = (force + (0.1 * 0.5) * theta_dot ** 2 * sintheta) / (0.1 + 1.0)
+        thetaacc = (9.8 * sintheta - costheta * temp) / (0.5 * (4.0 / 3.0 - 0.1 * costheta ** 2 / (0.1 + 1.0)))
+        xacc = temp - (0.1 * 0.5) * thetaacc * costheta / (0.1 + 1.0)
+        s = np.stack([x + dt * x_dot, theta + dt * theta_dot, x_dot + dt * xacc, theta_dot + dt * thetaacc], axis=1)
+        return s, (np.abs(s[:, 0]) > 10.0) | (np.abs(s[:, 1]) > 0.5)
+
+    sims = [BatchedCartPole(0.02), BatchedCartPole(dt=0.02, gravity=9.8, masscart=1.0, masspole=0.1, length=0.5, x_limit=10.0,
+                                                   theta_limit=0.5)]
+    other = [BatchedCartPole(0.02, **{k: v}) for k, v in dict(gravity=9.81, masscart=1.5, masspole=0.2, length=0.6).items()]
+    tight = BatchedCartPole(0.02, x_limit=0.05, theta_limit=0.01)
+    for s in sims + other + [tight]:
+        s.reset(ctl["plant_init"])
+    want = np.array(ctl["plant_init"], np.float64).reshape(-1, 4)
+    tight_done = np.zeros(len(want), bool)
+    for t in range(60):
+        f = np.asarray(ctl["plant_forces"][t], np.float64).reshape(-1)
+        want, done = old_step(want, f)
+        for s in sims:
+            x, d = s.step(ctl["plant_forces"][t])
+            assert np.array_equal(x.view(np.uint64), want.view(np.uint64)) and np.array_equal(d, done)
+        x, d = tight.step(ctl["plant_forces"][t])
+        assert np.array_equal(x.view(np.uint64), want.view(np.uint64))
+        assert np.array_equal(d, (np.abs(want[:, 0]) > 0.05) | (np.abs(want[:, 1]) > 0.01))
+        tight_done |= d
+        for s in other:
+            s.step(ctl["plant_forces"][t])
+    assert tight_done.any() and all(not np.array_equal(s.get_state(), want) for s in other)
+    edge = BatchedCartPole(0.5, x_limit=2.0, theta_limit=0.25)
+    edge.reset([[2.0, 0, 0, 0], [np.nextafter(2.0, np.inf), 0, 0, 0], [0, 0.25, 0, 0], [0, -np.nextafter(0.25, np.inf), 0, 0]])
+    assert edge.step(np.zeros(4))[1].tolist() == [False, True, False, True]
+
+
 def test_batched_closed_loop_equals_per_plant_loops():
     """run_mpc_batch (one batched solve per control step) == B separate reference-style loops."""
     from phnn_mpc_amd.closed_loop import BatchedCartPole, run_mpc_batch, stability_report
