@@ -39,6 +39,7 @@ constexpr int kTileB = 16;       // rollouts per wave
 #define PHNN_KMAXWAVES 8
 #endif
 constexpr int kMaxWaves = PHNN_KMAXWAVES;  // waves per workgroup (8 = 2 per SIMD; 12 = 3 per SIMD is an experiment: DESIGN.md section 9)
+constexpr size_t kMaxLdsBytes = 160 << 10;  // the 160 KiB of LDS one workgroup may take: image + kMaxWaves x per-wave scratch
 constexpr int kScrFloats = 16 * 20;  // per-wave LDS scratch: 16 rollouts x (16 + 4 pad) floats
 
 struct Lane {
@@ -1720,7 +1721,7 @@ struct PhnnModel {
   // the 160 KiB of LDS next to the image and eight waves' scratch: the 128-wide learned-G variants (146 + 10 KiB
   // already) have no room and keep q1 in their tape.
   static constexpr bool CURV = MM == MM_F16X2 && ACT == ACT_TANH &&
-                               4 * (oP + CurvImg<HID>::FLOATS + kMaxWaves * SCR) <= 160 * 1024;
+                               sizeof(float) * (oP + CurvImg<HID>::FLOATS + kMaxWaves * SCR) <= kMaxLdsBytes;
   static constexpr int IMG = oP + (CURV ? CurvImg<HID>::FLOATS : 0);
   // per-pair epilogue sites (kFuseEpi) the kernels of this model have the registers for, by tools/resource_usage.py: a
   // fused product keeps a second set of operand fragments live, and G_net's hidden vector or further control columns

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -22,16 +23,6 @@
 namespace {
 
 thread_local std::string g_create_error;
-
-struct KernelSet {
-  RollTable fwd, grad;  // K1, K2: [ref][stash][integrator] (phnn_variants.h)
-  int stash_floats[2];  // per wave (16 rollouts) per step: Euler, RK4
-  int scr_floats;       // per-wave LDS scratch
-  void (*mfwd)(PointParams);
-  void (*mvjp)(PointParams);
-  int img_floats;
-  const char* name;
-};
 
 template <class M>
 KernelSet make_set(const char* name) {
@@ -418,29 +409,38 @@ bool pad_source_map(const phnn_desc* d, std::vector<int>* map) {
 
 }  // namespace
 
+// Owns what it points to: built by phnn_create_ex, deleted by phnn_destroy or by any error return of the former.
 struct phnn_handle {
-  phnn_desc desc;    // as given by the caller
-  phnn_desc pdesc;   // zero-padded to a kernel width
-  phnn_options opt;
-  int device;
-  int variant;
-  KernelSet ks;
-  WgradSet wg;       // weight-gradient kernels (has_wgrad)
-  bool has_wgrad;
-  SplitSet sp;       // split-tile kernels for small batches (has_split)
-  bool has_split;
-  int* d_unpad;      // index map original blob -> padded blob (k_wgrad_finish)
-  int* d_padsrc;     // index map padded blob -> original blob, -1 = padding (phnn_update_weights_dev)
-  float* d_pblob;    // scratch of the device-side packer: the padded blob
-  int n_pad;         // floats of the padded blob
-  int n_params;      // floats of the original blob
-  float* d_img;
-  float* h_img;      // pinned staging copy of the image (phnn_update_weights uploads from it asynchronously)
-  hipEvent_t up_done;  // recorded behind the last asynchronous upload from h_img (null until the first one)
-  size_t img_floats;
-  int n_cu;
-  int max_waves;
+  phnn_desc desc{};    // as given by the caller
+  phnn_desc pdesc{};   // zero-padded to a kernel width
+  phnn_options opt{};
+  int device = 0;
+  int variant = V_NONE;
+  KernelSet ks{};
+  WgradSet wg{};       // weight-gradient kernels (has_wgrad)
+  bool has_wgrad = false;
+  SplitSet sp{};       // split-tile kernels for small batches (has_split)
+  bool has_split = false;
+  int* d_unpad = nullptr;   // index map original blob -> padded blob (k_wgrad_finish)
+  int* d_padsrc = nullptr;  // index map padded blob -> original blob, -1 = padding (phnn_update_weights_dev)
+  float* d_pblob = nullptr;  // scratch of the device-side packer: the padded blob
+  int n_pad = 0;             // floats of the padded blob
+  int n_params = 0;          // floats of the original blob
+  float* d_img = nullptr;
+  float* h_img = nullptr;  // pinned staging copy of the image (phnn_update_weights uploads from it asynchronously)
+  hipEvent_t up_done = nullptr;  // recorded behind the last asynchronous upload from h_img (null until the first one)
+  int n_cu = 0;
+  int max_waves = 0;
   std::string err;
+
+  phnn_handle() = default;
+  phnn_handle(const phnn_handle&) = delete;
+  ~phnn_handle() {
+    for (void* dev : {(void*)d_img, (void*)d_unpad, (void*)d_padsrc, (void*)d_pblob})
+      if (dev) (void)hipFree(dev);
+    if (h_img) (void)hipHostFree(h_img);
+    if (up_done) (void)hipEventDestroy(up_done);
+  }
 };
 
 namespace {
@@ -463,19 +463,29 @@ int pick_waves(long long tiles, int n_cu, int max_waves) {
   return w;
 }
 
+// The one launch path: the status of a *_launch, of a runtime call or of the kernel launched here as the entry point's return value.
+int checked(phnn_handle* h, hipError_t e, const char* what) { return e == hipSuccess ? PHNN_OK : hip_fail(h, e, what); }
+template <class... P, class... A>
+int checked(phnn_handle* h, const char* what, void (*kern)(P...), dim3 grid, dim3 block, size_t shmem, hipStream_t st,
+            const A&... args) {
+  hipLaunchKernelGGL(kern, grid, block, shmem, st, args...);
+  return checked(h, hipGetLastError(), what);
+}
+
+// the element-wise kernels: one thread per element
+constexpr int kFlatThreads = 256;
+dim3 flat_grid(long long count) { return dim3((unsigned)((count + kFlatThreads - 1) / kFlatThreads)); }
+
+long long tiles_of(int64_t B) { return (B + kTileB - 1) / kTileB; }  // 16-rollout tiles of a batch
+
 template <class P>
 int launch(phnn_handle* h, void (*kern)(P), const P& p, long long tiles, bool grid_stride, hipStream_t st) {
   int waves = pick_waves(tiles, h->n_cu, h->max_waves);
   long long grid = (tiles + waves - 1) / waves;
   if (grid_stride && grid > 4LL * h->n_cu) grid = 4LL * h->n_cu;
   if (grid < 1) grid = 1;
-  size_t shmem = sizeof(float) * ((size_t)h->ks.img_floats + (size_t)waves * h->ks.scr_floats);
-  if (shmem > 160 * 1024) return fail(h, PHNN_ERR_UNSUPPORTED, "weight image does not fit the 160 KiB of LDS");
-  // (hipFuncAttributeMaxDynamicSharedMemorySize was raised once per kernel in phnn_create_ex: allow_big_lds)
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * waves), shmem, st, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
-  return PHNN_OK;
+  // the LDS fits and is allowed: phnn_create_ex checked lds_bytes(kMaxWaves) <= kMaxLdsBytes and raised the kernels' limit
+  return checked(h, "kernel launch", kern, dim3((unsigned)grid), dim3(64 * waves), h->ks.lds_bytes(waves), st, p);
 }
 
 // Small batches: with at most two 16-rollout tiles per CU the whole-tile kernels run one wave per SIMD at best (one
@@ -496,10 +506,8 @@ int launch_roll(phnn_handle* h, bool grad, bool ref, bool stash, int integrator,
     return launch(h, whole, p, tiles, false, st);
   }
   RollKernel kern = train_tape ? h->sp.fwd_t[integrator] : (grad ? h->sp.grad : h->sp.fwd)[ref][stash][integrator];
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), sizeof(float) * (size_t)h->sp.lds_floats, st, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(h, e, "kernel launch (split-tile)");
-  return PHNN_OK;
+  return checked(h, "kernel launch (split-tile)", kern, dim3((unsigned)tiles), dim3(256), sizeof(float) * (size_t)h->sp.lds_floats,
+                 st, p);
 }
 
 // Makes the handle's device current for the duration of one C-ABI call and restores the caller's device after it.
@@ -523,17 +531,40 @@ struct DeviceGuard {
   DeviceGuard guard_((h), (h)->device); \
   if (guard_.rc) return guard_.rc
 
-// dynamic LDS above 64 KiB has to be allowed per kernel once; done for every kernel of the set at create time
-template <class P>
-hipError_t allow_big_lds(void (*kern)(P)) {
-  if (!kern) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+phnn_cost neutral_cost() { return phnn_cost{}; }  // of the cost-free marches (no_cost): all zero, no bounds
+
+// the empty batch of the weight-gradient entry points: a gradient that is not accumulated into is all zeros
+int zero_grad_theta_if_fresh(phnn_handle* h, float* grad_theta_dev, int accumulate, hipStream_t st) {
+  if (accumulate) return PHNN_OK;
+  return checked(h, hipMemsetAsync(grad_theta_dev, 0, sizeof(float) * (size_t)h->n_params, st), "hipMemsetAsync");
 }
 
 int check_cost(phnn_handle* h, const phnn_cost* c) {
   if (!c) return fail(h, PHNN_ERR_INVALID_ARG, "cost is NULL");
   if (c->has_u_bounds && !(c->u_min <= c->u_max)) return fail(h, PHNN_ERR_INVALID_ARG, "u_min > u_max");
   return PHNN_OK;
+}
+
+template <class T>
+hipError_t upload(T** dst, const std::vector<T>& src) {  // hipMalloc + blocking copy
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), sizeof(T) * src.size());
+  return e != hipSuccess ? e : hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice);
+}
+
+// What phnn_create_ex allocates behind d_img: the pinned image (copied to d_img), the index maps, the packer's scratch.
+// After a failure the handle's destructor frees what was allocated before it.
+hipError_t upload_image(phnn_handle* h, const std::vector<float>& img) {
+  const size_t bytes = sizeof(float) * img.size();
+  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&h->h_img), bytes, hipHostMallocDefault);
+  if (e != hipSuccess) return e;
+  memcpy(h->h_img, img.data(), bytes);
+  e = hipMemcpy(h->d_img, h->h_img, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && h->has_wgrad) e = upload(&h->d_unpad, unpad_map(&h->desc, &h->pdesc));
+  std::vector<int> src;
+  if (e != hipSuccess || !pad_source_map(&h->desc, &src)) return e;
+  h->n_pad = (int)src.size();
+  e = upload(&h->d_padsrc, src);
+  return e != hipSuccess ? e : hipMalloc(reinterpret_cast<void**>(&h->d_pblob), sizeof(float) * src.size());
 }
 
 }  // namespace
@@ -578,8 +609,7 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
                    const phnn_options* opt_in, phnn_handle** out) {
   if (!desc || !weights_host || !out) return fail(nullptr, PHNN_ERR_INVALID_ARG, "NULL argument");
   *out = nullptr;
-  phnn_options opt;
-  memset(&opt, 0, sizeof opt);
+  phnn_options opt{};
   if (opt_in) opt = *opt_in;
   if (opt.matmul_mode < PHNN_MATMUL_DEFAULT || opt.matmul_mode > PHNN_MATMUL_F16X2 || opt.max_waves < 0 ||
       opt.max_waves > kMaxWaves || opt.split_tiles < 0 || opt.split_tiles > 2)
@@ -596,20 +626,13 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
   if (device < 0 || device >= ndev) return fail(nullptr, PHNN_ERR_INVALID_ARG, "device index out of range");
   DeviceGuard guard(nullptr, device);
   if (guard.rc) return guard.rc;
-  phnn_handle* h = new phnn_handle();
+  auto h = std::make_unique<phnn_handle>();  // an error return below deletes it with what it holds by then
   h->desc = *desc;
   h->pdesc = pdesc;
   h->opt = opt;
   h->device = device;
   h->variant = v;
   h->max_waves = opt.max_waves > 0 ? opt.max_waves : kMaxWaves;
-  h->d_img = nullptr;
-  h->h_img = nullptr;
-  h->up_done = nullptr;
-  h->d_unpad = nullptr;
-  h->d_padsrc = nullptr;
-  h->d_pblob = nullptr;
-  h->n_pad = 0;
   h->n_params = (int)n_floats;
   kernel_set(v, &h->ks);
   h->has_wgrad = phnn_wgrad_kernels(v, &h->wg);
@@ -617,73 +640,23 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
   hipDeviceProp_t prop;
   e = hipGetDeviceProperties(&prop, device);
   h->n_cu = (e == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  h->img_floats = img.size();
-  if (sizeof(float) * (img.size() + (size_t)kMaxWaves * h->ks.scr_floats) > 160 * 1024) {
-    delete h;
+  if (h->ks.lds_bytes(kMaxWaves) > kMaxLdsBytes)  // img.size() == ks.img_floats: both the variant's M::IMG
     return fail(nullptr, PHNN_ERR_UNSUPPORTED, "weight image does not fit the 160 KiB of LDS");
-  }
+  // dynamic LDS above 64 KiB has to be allowed per kernel, once: here, for every kernel the handle can launch with it
   e = hipSuccess;
-  RollKernel* tables[] = {&h->ks.fwd[0][0][0], &h->ks.grad[0][0][0], h->has_split ? &h->sp.fwd[0][0][0] : nullptr,
-                          h->has_split ? &h->sp.grad[0][0][0] : nullptr};
-  for (RollKernel* t : tables)
-    for (int i = 0; t && i < 8; ++i)
-      if (e == hipSuccess) e = allow_big_lds(t[i]);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.mfwd);
-  if (e == hipSuccess) e = allow_big_lds(h->ks.mvjp);
-  if (h->has_wgrad) {
-    if (e == hipSuccess) e = allow_big_lds(h->wg.grad[0]);
-    if (e == hipSuccess) e = allow_big_lds(h->wg.grad[1]);
-    if (e == hipSuccess) e = allow_big_lds(h->wg.mvjp);
-    if (e == hipSuccess) e = allow_big_lds(h->wg.reduce);
-    if (e == hipSuccess) e = allow_big_lds(h->wg.grad_t[0]);
-    if (e == hipSuccess) e = allow_big_lds(h->wg.grad_t[1]);
-    if (e == hipSuccess) e = allow_big_lds(h->wg.reduce_t);
-    if (e == hipSuccess) e = allow_big_lds(h->wg.fwd_t[0]);
-    if (e == hipSuccess) e = allow_big_lds(h->wg.fwd_t[1]);
-  }
-  if (h->has_split) {
-    if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_t[0]);
-    if (e == hipSuccess) e = allow_big_lds(h->sp.fwd_t[1]);
-  }
-  if (h->has_split && (size_t)h->sp.lds_floats * sizeof(float) > 160 * 1024) h->has_split = false;
-  if (e != hipSuccess) {
-    delete h;
-    return hip_fail(nullptr, e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-  }
+  auto allow_big_lds = [&e](const void* kern) {
+    if (kern && e == hipSuccess) e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
+  };
+  h->ks.each_kernel(allow_big_lds);  // (the first call on a unit's kernel loads the unit's code object: this order)
+  if (h->has_split) h->sp.each_kernel(allow_big_lds);
+  if (h->has_wgrad) h->wg.each_kernel(allow_big_lds);
+  if (h->has_split && (size_t)h->sp.lds_floats * sizeof(float) > kMaxLdsBytes) h->has_split = false;
+  if (e != hipSuccess) return hip_fail(nullptr, e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
   e = hipMalloc(reinterpret_cast<void**>(&h->d_img), sizeof(float) * img.size());
-  if (e != hipSuccess) {
-    delete h;
-    return hip_fail(nullptr, e, "hipMalloc(weights image)");
-  }
-  e = hipHostMalloc(reinterpret_cast<void**>(&h->h_img), sizeof(float) * img.size(), hipHostMallocDefault);
-  if (e == hipSuccess) {
-    memcpy(h->h_img, img.data(), sizeof(float) * img.size());
-    e = hipMemcpy(h->d_img, h->h_img, sizeof(float) * img.size(), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && h->has_wgrad) {
-    std::vector<int> map = unpad_map(desc, &pdesc);
-    e = hipMalloc(reinterpret_cast<void**>(&h->d_unpad), sizeof(int) * map.size());
-    if (e == hipSuccess) e = hipMemcpy(h->d_unpad, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) {
-    std::vector<int> src;
-    if (pad_source_map(desc, &src)) {
-      h->n_pad = (int)src.size();
-      e = hipMalloc(reinterpret_cast<void**>(&h->d_padsrc), sizeof(int) * src.size());
-      if (e == hipSuccess) e = hipMemcpy(h->d_padsrc, src.data(), sizeof(int) * src.size(), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_pblob), sizeof(float) * src.size());
-    }
-  }
-  if (e != hipSuccess) {
-    if (h->h_img) (void)hipHostFree(h->h_img);
-    if (h->d_unpad) (void)hipFree(h->d_unpad);
-    if (h->d_padsrc) (void)hipFree(h->d_padsrc);
-    if (h->d_pblob) (void)hipFree(h->d_pblob);
-    (void)hipFree(h->d_img);
-    delete h;
-    return hip_fail(nullptr, e, "upload of the weights image");
-  }
-  *out = h;
+  if (e != hipSuccess) return hip_fail(nullptr, e, "hipMalloc(weights image)");
+  e = upload_image(h.get(), img);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "upload of the weights image");
+  *out = h.release();
   return PHNN_OK;
 }
 
@@ -695,7 +668,7 @@ int phnn_update_weights(phnn_handle* h, const float* weights_host, size_t n_floa
   std::vector<float> img;
   int v = V_NONE, code = PHNN_OK;
   if (build_image(&h->desc, weights_host, n_floats, h->opt, &pdesc, &v, &img, &why, &code)) return fail(h, code, why);
-  if (v != h->variant || img.size() != h->img_floats) return fail(h, PHNN_ERR_INVALID_ARG, "weights select another kernel variant");
+  if (v != h->variant || img.size() != (size_t)h->ks.img_floats) return fail(h, PHNN_ERR_INVALID_ARG, "weights select another kernel variant");
   PHNN_ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -703,20 +676,13 @@ int phnn_update_weights(phnn_handle* h, const float* weights_host, size_t n_floa
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_update_weights packs on the host and cannot be captured into a graph");
   // the pinned staging buffer may still feed the PREVIOUS asynchronous upload (on whatever stream that one used):
   // wait for the event recorded behind it -- not for the caller's stream, which may be another one and busy
-  hipError_t e;
-  if (h->up_done) {
-    e = hipEventSynchronize(h->up_done);
-    if (e != hipSuccess) return hip_fail(h, e, "hipEventSynchronize(previous weight upload)");
-  } else {
-    e = hipEventCreateWithFlags(&h->up_done, hipEventDisableTiming);
-    if (e != hipSuccess) return hip_fail(h, e, "hipEventCreate");
-  }
+  if (int rc = h->up_done ? checked(h, hipEventSynchronize(h->up_done), "hipEventSynchronize(previous weight upload)")
+                          : checked(h, hipEventCreateWithFlags(&h->up_done, hipEventDisableTiming), "hipEventCreate"))
+    return rc;
   memcpy(h->h_img, img.data(), sizeof(float) * img.size());
-  e = hipMemcpyAsync(h->d_img, h->h_img, sizeof(float) * img.size(), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(h->d_img, h->h_img, sizeof(float) * img.size(), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return hip_fail(h, e, "hipMemcpyAsync(weights image)");
-  e = hipEventRecord(h->up_done, st);
-  if (e != hipSuccess) return hip_fail(h, e, "hipEventRecord");
-  return PHNN_OK;
+  return checked(h, hipEventRecord(h->up_done, st), "hipEventRecord");
 }
 
 int phnn_update_weights_dev(phnn_handle* h, const float* weights_dev, size_t n_floats, void* stream) {
@@ -729,28 +695,14 @@ int phnn_update_weights_dev(phnn_handle* h, const float* weights_dev, size_t n_f
   }
   if (!h->d_padsrc || !h->d_pblob) return fail(h, PHNN_ERR_UNSUPPORTED, "no device-side packer for this handle");
   PHNN_ON_DEVICE(h);
-  PackParams p;
-  p.orig = weights_dev;
-  p.pad_src = h->d_padsrc;
-  p.n_pad = h->n_pad;
-  p.pblob = h->d_pblob;
-  p.img = h->d_img;
-  p.pdesc = h->pdesc;
+  const PackParams p{weights_dev, h->d_padsrc, h->n_pad, h->d_pblob, h->d_img, h->pdesc};
   const int rc = phnn_pack_launch(h->variant, p, (hipStream_t)stream);
   if (rc < 0) return fail(h, PHNN_ERR_UNSUPPORTED, "no device-side packer for this kernel variant");
-  if (rc != (int)hipSuccess) return hip_fail(h, (hipError_t)rc, "kernel launch (weight packing)");
-  return PHNN_OK;
+  return checked(h, (hipError_t)rc, "kernel launch (weight packing)");
 }
 
 int phnn_destroy(phnn_handle* h) {
-  if (!h) return PHNN_OK;
-  if (h->d_img) (void)hipFree(h->d_img);
-  if (h->h_img) (void)hipHostFree(h->h_img);
-  if (h->up_done) (void)hipEventDestroy(h->up_done);
-  if (h->d_unpad) (void)hipFree(h->d_unpad);
-  if (h->d_padsrc) (void)hipFree(h->d_padsrc);
-  if (h->d_pblob) (void)hipFree(h->d_pblob);
-  delete h;
+  delete h;  // ~phnn_handle frees on whatever device is current, as hipFree allows; NULL is fine
   return PHNN_OK;
 }
 
@@ -761,7 +713,7 @@ int phnn_model_forward(phnn_handle* h, const float* x_dev, const float* u_dev, i
   if (!x_dev || !u_dev || !dx_dev || B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "NULL tensor or negative batch");
   PHNN_ON_DEVICE(h);
   PointParams p{h->d_img, x_dev, u_dev, nullptr, dx_dev, H_dev, (long long)B, nullptr, nullptr};
-  return launch(h, h->ks.mfwd, p, (B + kTileB - 1) / kTileB, true, (hipStream_t)stream);
+  return launch(h, h->ks.mfwd, p, tiles_of(B), true, (hipStream_t)stream);
 }
 
 int phnn_model_vjp(phnn_handle* h, const float* x_dev, const float* u_dev, const float* lam_dev, int64_t B,
@@ -772,7 +724,7 @@ int phnn_model_vjp(phnn_handle* h, const float* x_dev, const float* u_dev, const
     return fail(h, PHNN_ERR_INVALID_ARG, "NULL tensor or negative batch");
   PHNN_ON_DEVICE(h);
   PointParams p{h->d_img, x_dev, u_dev, lam_dev, xbar_dev, ubar_dev, (long long)B, nullptr, nullptr};
-  return launch(h, h->ks.mvjp, p, (B + kTileB - 1) / kTileB, true, (hipStream_t)stream);
+  return launch(h, h->ks.mvjp, p, tiles_of(B), true, (hipStream_t)stream);
 }
 
 static int fill_roll(phnn_handle* h, RollParams* p, const float* x0, const float* u, int64_t B, int32_t H,
@@ -802,8 +754,7 @@ static int fill_roll(phnn_handle* h, RollParams* p, const float* x0, const float
 
 size_t phnn_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t integrator) {
   if (!h || B <= 0 || H < 1 || (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4)) return 0;
-  size_t tiles = (size_t)((B + kTileB - 1) / kTileB);
-  return tiles * (size_t)H * (size_t)h->ks.stash_floats[integrator] * sizeof(float);
+  return (size_t)tiles_of(B) * (size_t)H * (size_t)h->ks.stash_floats[integrator] * sizeof(float);
 }
 
 // phnn_reference -> RollParams (the *_ref entry points); ref == NULL leaves the tracking fields zero
@@ -835,9 +786,8 @@ static int rollout_fwd(phnn_handle* h, const float* x0_dev, const float* u_dev, 
   PHNN_ON_DEVICE(h);
   p.cost = cost_dev;
   p.traj = traj_dev;
-  const long long tiles = (B + kTileB - 1) / kTileB;
   p.stash = (float*)workspace_dev;
-  return launch_roll(h, false, ref != nullptr, workspace_dev != nullptr, integrator, p, tiles, (hipStream_t)stream);
+  return launch_roll(h, false, ref != nullptr, workspace_dev != nullptr, integrator, p, tiles_of(B), (hipStream_t)stream);
 }
 
 int phnn_rollout_fwd(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
@@ -870,9 +820,8 @@ static int rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, 
   p.cost_bar = cost_bar_dev;
   p.grad_u = grad_u_dev;
   p.grad_x0 = grad_x0_dev;
-  const long long tiles = (B + kTileB - 1) / kTileB;
   p.stash = (float*)workspace_dev;
-  return launch_roll(h, true, ref != nullptr, workspace_dev != nullptr, integrator, p, tiles, (hipStream_t)stream);
+  return launch_roll(h, true, ref != nullptr, workspace_dev != nullptr, integrator, p, tiles_of(B), (hipStream_t)stream);
 }
 
 int phnn_rollout_grad(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
@@ -902,7 +851,7 @@ int phnn_rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, in
 
 // ---- training side --------------------------------------------------------------------------
 static long long wgrad_records(int64_t B, int32_t H, int32_t integrator) {
-  long long tiles = (B + kTileB - 1) / kTileB;
+  long long tiles = tiles_of(B);
   if (H <= 0) return tiles;  // point mode
   return tiles * (long long)H * (integrator == PHNN_INTEG_RK4 ? 4 : 1);
 }
@@ -933,13 +882,11 @@ static int wgrad_reduce(phnn_handle* h, void* workspace_dev, long long n_rec, fl
   const int rows = wgrad_rows(h, n_rec);
   WgradParams wp{h->d_img, rec, n_rec, slab, h->wg.blob_floats, tape_floats ? rec + wgrad_tape_offset(h, n_rec) : nullptr,
                  tape_floats};
-  hipLaunchKernelGGL(tape_floats ? h->wg.reduce_t : h->wg.reduce, dim3((unsigned)rows), dim3(64 * h->wg.reduce_waves),
-                     (size_t)h->wg.reduce_lds_bytes, st, wp);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(h, e, "wgrad reduce launch");
-  e = phnn_wgrad_finish(slab, rows, h->wg.blob_floats, h->d_unpad, h->n_params, grad_theta_dev, accumulate, st);
-  if (e != hipSuccess) return hip_fail(h, e, "wgrad finish launch");
-  return PHNN_OK;
+  if (int rc = checked(h, "wgrad reduce launch", tape_floats ? h->wg.reduce_t : h->wg.reduce, dim3((unsigned)rows),
+                       dim3(64 * h->wg.reduce_waves), (size_t)h->wg.reduce_lds_bytes, st, wp))
+    return rc;
+  return checked(h, phnn_wgrad_finish(slab, rows, h->wg.blob_floats, h->d_unpad, h->n_params, grad_theta_dev, accumulate, st),
+                 "wgrad finish launch");
 }
 
 int phnn_wgrad_record_info(const phnn_handle* h, int32_t* record_floats, int32_t* small_offset, int32_t* small_stride) {
@@ -961,8 +908,7 @@ int phnn_rollout_trajectory_ws(phnn_handle* h, const float* x0_dev, const float*
   if (!h) return PHNN_ERR_INVALID_ARG;
   if (wgrad_workspace_dev && !h->has_wgrad)
     return fail(h, PHNN_ERR_UNSUPPORTED, "no weight-gradient kernels for this model variant: pass a NULL workspace");
-  phnn_cost neutral;
-  memset(&neutral, 0, sizeof neutral);
+  const phnn_cost neutral = neutral_cost();
   RollParams p;
   if (int rc = fill_roll(h, &p, x0_dev, u_dev, B, H, &neutral, integrator, dt)) return rc;
   if (B == 0) return PHNN_OK;
@@ -971,10 +917,9 @@ int phnn_rollout_trajectory_ws(phnn_handle* h, const float* x0_dev, const float*
   p.traj = traj_dev;
   p.dx_out = dx_dev;
   p.no_cost = 1;
-  const long long tiles = (B + kTileB - 1) / kTileB;
   const bool tapes = wgrad_workspace_dev != nullptr;
   if (tapes) p.stash = (float*)wgrad_workspace_dev + wgrad_tape_offset(h, wgrad_records(B, H, integrator));
-  return launch_roll(h, false, false, tapes, integrator, p, tiles, (hipStream_t)stream, tapes);
+  return launch_roll(h, false, false, tapes, integrator, p, tiles_of(B), (hipStream_t)stream, tapes);
 }
 
 int phnn_rollout_wgrad(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, int32_t integrator,
@@ -986,20 +931,13 @@ int phnn_rollout_wgrad(phnn_handle* h, const float* x0_dev, const float* u_dev, 
   const bool tapes = (flags & PHNN_WGRAD_TAPES) != 0;
   if (!h->has_wgrad)
     return fail(h, PHNN_ERR_UNSUPPORTED, "no weight-gradient kernels for this model variant (pHNN and canonical pHNN have them)");
-  phnn_cost neutral;
-  memset(&neutral, 0, sizeof neutral);
+  const phnn_cost neutral = neutral_cost();
   RollParams p;
   if (int rc = fill_roll(h, &p, x0_dev, u_dev, B, H, &neutral, integrator, dt)) return rc;
   if (!grad_theta_dev) return fail(h, PHNN_ERR_INVALID_ARG, "grad_theta_dev is NULL");
   PHNN_ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
-  if (B == 0) {
-    if (!accumulate) {
-      hipError_t e = hipMemsetAsync(grad_theta_dev, 0, sizeof(float) * (size_t)h->n_params, st);
-      if (e != hipSuccess) return hip_fail(h, e, "hipMemsetAsync");
-    }
-    return PHNN_OK;
-  }
+  if (B == 0) return zero_grad_theta_if_fresh(h, grad_theta_dev, accumulate, st);
   if (!traj_dev || !workspace_dev) return fail(h, PHNN_ERR_INVALID_ARG, "traj_dev / workspace_dev is NULL");
   p.traj_in = traj_dev;
   p.traj_bar = traj_bar_dev;
@@ -1010,7 +948,7 @@ int phnn_rollout_wgrad(phnn_handle* h, const float* x0_dev, const float* u_dev, 
   p.wrec = (float*)workspace_dev;
   const long long n_rec = wgrad_records(B, H, integrator);
   if (tapes) p.stash = (float*)workspace_dev + wgrad_tape_offset(h, n_rec);
-  if (int rc = launch(h, tapes ? h->wg.grad_t[integrator] : h->wg.grad[integrator], p, (B + kTileB - 1) / kTileB, false, st))
+  if (int rc = launch(h, tapes ? h->wg.grad_t[integrator] : h->wg.grad[integrator], p, tiles_of(B), false, st))
     return rc;
   return wgrad_reduce(h, workspace_dev, n_rec, grad_theta_dev, accumulate, st, tapes ? h->wg.tape_floats[integrator] : 0);
 }
@@ -1024,17 +962,11 @@ int phnn_model_wgrad(phnn_handle* h, const float* x_dev, const float* u_dev, con
   if (N < 0 || !grad_theta_dev) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or grad_theta_dev is NULL");
   PHNN_ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
-  if (N == 0) {
-    if (!accumulate) {
-      hipError_t e = hipMemsetAsync(grad_theta_dev, 0, sizeof(float) * (size_t)h->n_params, st);
-      if (e != hipSuccess) return hip_fail(h, e, "hipMemsetAsync");
-    }
-    return PHNN_OK;
-  }
+  if (N == 0) return zero_grad_theta_if_fresh(h, grad_theta_dev, accumulate, st);
   if (!x_dev || !u_dev || !lam_dev || !workspace_dev || !xbar_dev || !ubar_dev)
     return fail(h, PHNN_ERR_INVALID_ARG, "NULL tensor");
   PointParams p{h->d_img, x_dev, u_dev, lam_dev, xbar_dev, ubar_dev, (long long)N, Hbar_dev, (float*)workspace_dev};
-  if (int rc = launch(h, h->wg.mvjp, p, (N + kTileB - 1) / kTileB, true, st)) return rc;
+  if (int rc = launch(h, h->wg.mvjp, p, tiles_of(N), true, st)) return rc;
   return wgrad_reduce(h, workspace_dev, wgrad_records(N, 0, 0), grad_theta_dev, accumulate, st);
 }
 
@@ -1049,8 +981,7 @@ int phnn_adam_step(phnn_handle* h, float* u_dev, const float* grad_dev, float* e
     return fail(h, PHNN_ERR_INVALID_ARG, "best-iterate tracking needs cost_dev, best_u_dev and per | count");
   if (count == 0) return PHNN_OK;
   PHNN_ON_DEVICE(h);
-  AdamParams p;
-  memset(&p, 0, sizeof p);
+  AdamParams p{};
   p.u = u_dev;
   p.g = grad_dev;
   p.m = exp_avg_dev;
@@ -1073,16 +1004,10 @@ int phnn_adam_step(phnn_handle* h, float* u_dev, const float* grad_dev, float* e
   p.u_max = u_max;
   p.has_u_bounds = has_u_bounds;
   hipStream_t st = (hipStream_t)stream;
-  const int threads = 256;
-  hipLaunchKernelGGL(k_adam, dim3((unsigned)((count + threads - 1) / threads)), dim3(threads), 0, st, p);
-  if (best_cost_dev) {
-    long long B = count / p.per;
-    hipLaunchKernelGGL(k_best_cost, dim3((unsigned)((B + threads - 1) / threads)), dim3(threads), 0, st, cost_dev,
-                       best_cost_dev, B);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(h, e, "adam launch");
-  return PHNN_OK;
+  const long long B = count / p.per;
+  hipLaunchKernelGGL(k_adam, flat_grid(count), dim3(kFlatThreads), 0, st, p);
+  if (best_cost_dev) hipLaunchKernelGGL(k_best_cost, flat_grid(B), dim3(kFlatThreads), 0, st, cost_dev, best_cost_dev, B);
+  return checked(h, hipGetLastError(), "adam launch");  // read once, behind both launches
 }
 
 static int solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
@@ -1179,8 +1104,7 @@ int phnn_solve_lbfgs(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t 
   if (e == hipSuccess && n_iter_dev) e = hipMemsetAsync(n_iter_dev, 0, sizeof(int32_t) * (size_t)B, st);
   if (e == hipSuccess && func_evals_dev) e = hipMemsetAsync(func_evals_dev, 0, sizeof(int32_t) * (size_t)B, st);
   if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_lbfgs: state reset");
-  LbfgsParams lp;
-  memset(&lp, 0, sizeof lp);
+  LbfgsParams lp{};
   lp.u = u_dev;
   lp.cost = cost_dev;
   lp.grad = grad_dev;
@@ -1213,8 +1137,7 @@ int phnn_solve_lbfgs(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t 
         return rc;
       lp.slot = slot;
       lp.costs_out = (slot == 0 && costs_dev) ? costs_dev + (size_t)k * B : nullptr;
-      e = lbfgs_launch(lp, st);
-      if (e != hipSuccess) return hip_fail(h, e, "k_lbfgs launch");
+      if (int rc = checked(h, lbfgs_launch(lp, st), "k_lbfgs launch")) return rc;
     }
   }
   return PHNN_OK;
@@ -1313,8 +1236,7 @@ static int sample(phnn_handle* h, const char* who, const SamplingCommon& c, cons
   if (!u_dev || (!sigma && !sigma_dev) || !samples_dev || (x0_rep_dev && !x0_dev))
     return fail(h, PHNN_ERR_INVALID_ARG, std::string(who) + ": NULL tensor");
   PHNN_ON_DEVICE(h);
-  SampleParams p;
-  memset(&p, 0, sizeof p);
+  SampleParams p{};
   p.u = u_dev;
   p.sig = sigma_dev;
   p.x0 = x0_dev;
@@ -1335,14 +1257,8 @@ static int sample(phnn_handle* h, const char* who, const SamplingCommon& c, cons
   p.epoch_dev = c.epoch_dev;
   p.epoch_host = c.epoch_host;
   p.iteration = iteration;
-  if (shape) {
-    hipError_t e = sample_shaped_launch(p, shape->L_dev, shape->cols, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(h, e, "k_shaped_sample launch");
-    return PHNN_OK;
-  }
-  hipError_t e = sample_launch(p, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "k_sample launch");
-  return PHNN_OK;
+  if (shape) return checked(h, sample_shaped_launch(p, shape->L_dev, shape->cols, (hipStream_t)stream), "k_shaped_sample launch");
+  return checked(h, sample_launch(p, (hipStream_t)stream), "k_sample launch");
 }
 
 static int mppi_sample(phnn_handle* h, const char* who, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
@@ -1399,8 +1315,7 @@ int phnn_mppi_update(phnn_handle* h, float* u_dev, const float* samples_dev, con
   if ((best_cost_dev != nullptr) != (best_u_dev != nullptr))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_mppi_update: best_cost_dev and best_u_dev go together");
   PHNN_ON_DEVICE(h);
-  MppiUpdateParams p;
-  memset(&p, 0, sizeof p);
+  MppiUpdateParams p{};
   p.u = u_dev;
   p.v = samples_dev;
   p.s = sample_cost_dev;
@@ -1414,9 +1329,7 @@ int phnn_mppi_update(phnn_handle* h, float* u_dev, const float* samples_dev, con
   p.u_min = cost->u_min;
   p.u_max = cost->u_max;
   p.has_u_bounds = cost->has_u_bounds;
-  hipError_t e = mppi_update_launch(p, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "k_mppi_update launch");
-  return PHNN_OK;
+  return checked(h, mppi_update_launch(p, (hipStream_t)stream), "k_mppi_update launch");
 }
 
 int phnn_cem_update(phnn_handle* h, float* u_dev, float* sigma_dev, const float* samples_dev, const float* sample_cost_dev,
@@ -1432,8 +1345,7 @@ int phnn_cem_update(phnn_handle* h, float* u_dev, float* sigma_dev, const float*
   if ((best_cost_dev != nullptr) != (best_u_dev != nullptr))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_cem_update: best_cost_dev and best_u_dev go together");
   PHNN_ON_DEVICE(h);
-  CemUpdateParams p;
-  memset(&p, 0, sizeof p);
+  CemUpdateParams p{};
   p.u = u_dev;
   p.sig = sigma_dev;
   p.v = samples_dev;
@@ -1450,9 +1362,7 @@ int phnn_cem_update(phnn_handle* h, float* u_dev, float* sigma_dev, const float*
   p.u_min = cost->u_min;
   p.u_max = cost->u_max;
   p.has_u_bounds = cost->has_u_bounds;
-  hipError_t e = cem_update_launch(p, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "k_cem_update launch");
-  return PHNN_OK;
+  return checked(h, cem_update_launch(p, (hipStream_t)stream), "k_cem_update launch");
 }
 
 // The solve of both methods, after the method's argument check: the entry state (best = (+inf, 0), u in bounds, and
@@ -1586,8 +1496,7 @@ int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, 
   if ((log_states_dev || log_controls_dev) && !step_dev && step_host < 0)
     return fail(h, PHNN_ERR_INVALID_ARG, "negative step index");
   PHNN_ON_DEVICE(h);
-  PlantParams p;
-  memset(&p, 0, sizeof p);
+  PlantParams p{};
   p.pl = *plant;
   p.state = state_dev;
   p.action = action_dev;
@@ -1602,11 +1511,7 @@ int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, 
   p.step_host = step_host;
   p.log_states = log_states_dev;
   p.log_controls = log_controls_dev;
-  const int threads = 256;
-  hipLaunchKernelGGL(k_plant_step, dim3((unsigned)((B + threads - 1) / threads)), dim3(threads), 0, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(h, e, "plant step launch");
-  return PHNN_OK;
+  return checked(h, "plant step launch", k_plant_step, flat_grid(B), dim3(kFlatThreads), 0, (hipStream_t)stream, p);
 }
 
 int phnn_shift_controls(phnn_handle* h, const float* src_dev, float* dst_dev, int64_t B, int32_t H, int32_t m,
@@ -1620,34 +1525,28 @@ int phnn_shift_controls(phnn_handle* h, const float* src_dev, float* dst_dev, in
     return fail(h, PHNN_ERR_INVALID_ARG, "overlapping control tensors (the shift is not in place)");
   if (B == 0 && !step_dev) return PHNN_OK;  // B == 0 with a counter: only advance the step
   PHNN_ON_DEVICE(h);
-  const int threads = 256;
-  long long count = (long long)B * H * m;
-  if (count < 1) count = 1;
-  hipLaunchKernelGGL(k_shift_controls, dim3((unsigned)((count + threads - 1) / threads)), dim3(threads), 0,
-                     (hipStream_t)stream, src_dev, dst_dev, (long long)B, (int)H, (int)m, step_dev);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(h, e, "shift launch");
-  return PHNN_OK;
+  const long long count = std::max<long long>((long long)B * H * m, 1);
+  return checked(h, "shift launch", k_shift_controls, flat_grid(count), dim3(kFlatThreads), 0, (hipStream_t)stream, src_dev,
+                 dst_dev, (long long)B, (int)H, (int)m, step_dev);
 }
 
 int phnn_read_image(phnn_handle* h, float* image_host, size_t n_floats, size_t* image_floats, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (image_floats) *image_floats = h->img_floats;
+  if (image_floats) *image_floats = (size_t)h->ks.img_floats;
   if (!image_host) return PHNN_OK;
-  if (n_floats < h->img_floats) return fail(h, PHNN_ERR_INVALID_ARG, "image_host is smaller than the image");
+  if (n_floats < (size_t)h->ks.img_floats) return fail(h, PHNN_ERR_INVALID_ARG, "image_host is smaller than the image");
   PHNN_ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(image_host, h->d_img, sizeof(float) * h->img_floats, hipMemcpyDeviceToHost, st);
+  hipError_t e = hipMemcpyAsync(image_host, h->d_img, sizeof(float) * (size_t)h->ks.img_floats, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail(h, e, "hipMemcpyAsync(read image)");
-  return PHNN_OK;
+  return checked(h, e, "hipMemcpyAsync(read image)");
 }
 
 int phnn_kernel_info(const phnn_handle* h, int32_t integrator, int32_t* rollouts_per_wg, int32_t* lds_bytes,
                      int32_t* n_workgroups_for_B, int64_t B) {
   if (!h) return PHNN_ERR_INVALID_ARG;
   (void)integrator;
-  long long tiles = (B + kTileB - 1) / kTileB;
+  long long tiles = tiles_of(B);
   if (use_split(h, tiles)) {  // four waves per tile
     if (rollouts_per_wg) *rollouts_per_wg = kTileB;
     if (lds_bytes) *lds_bytes = (int32_t)(sizeof(float) * (size_t)h->sp.lds_floats);
@@ -1656,7 +1555,7 @@ int phnn_kernel_info(const phnn_handle* h, int32_t integrator, int32_t* rollouts
   }
   int waves = pick_waves(tiles, h->n_cu, h->max_waves);
   if (rollouts_per_wg) *rollouts_per_wg = waves * kTileB;
-  if (lds_bytes) *lds_bytes = (int32_t)(sizeof(float) * ((size_t)h->ks.img_floats + (size_t)waves * h->ks.scr_floats));
+  if (lds_bytes) *lds_bytes = (int32_t)h->ks.lds_bytes(waves);
   if (n_workgroups_for_B) *n_workgroups_for_B = (int32_t)((tiles + waves - 1) / waves);
   return PHNN_OK;
 }

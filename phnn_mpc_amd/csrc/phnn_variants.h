@@ -115,6 +115,21 @@ using M_ODE_4_128_GELU = OdeModel<4, 128, MM_F32, ACT_GELU>;
 using RollKernel = void (*)(RollParams);
 using RollTable = RollKernel[2][2][2];
 
+// Each kernel set below visits its own kernel pointers (each_kernel: as const void*, null ones included), so that what
+// is done once per kernel -- phnn_create_ex raises the dynamic-LDS limit -- keeps no list of its own.  The static_assert
+// next to a visitor counts the struct's fields: a kernel pointer added without the visitor does not compile.
+template <class K>
+const void* kernel_ptr(K* kern) { return reinterpret_cast<const void*>(kern); }
+template <class F>
+void each_roll(const RollTable& t, F& f) {
+  for (int ref = 0; ref < 2; ++ref)
+    for (int stash = 0; stash < 2; ++stash)
+      for (int integ = 0; integ < 2; ++integ) f(kernel_ptr(t[ref][stash][integ]));
+}
+constexpr size_t set_bytes(size_t pointers, size_t ints) {  // sizeof a struct of that many pointers, then ints
+  return (pointers * sizeof(void*) + ints * sizeof(int) + sizeof(void*) - 1) / sizeof(void*) * sizeof(void*);
+}
+
 template <class M>
 void fill_fwd(RollTable t) {
   t[0][0][0] = k_rollout_fwd<M, PHNN_INTEG_EULER, TAPE_NONE>;
@@ -158,6 +173,27 @@ struct GradSet {
 // defined in phnn_grad.hip
 bool phnn_grad_kernels(int variant, GradSet* g);
 
+// The whole-tile kernels of one variant: K1 here (phnn_mpc.hip, make_set), K2 and the VJP from the GradSet.
+struct KernelSet {
+  RollTable fwd, grad;  // K1, K2
+  void (*mfwd)(PointParams);
+  void (*mvjp)(PointParams);
+  const char* name;
+  int stash_floats[2];  // per wave (16 rollouts) per step: Euler, RK4
+  int scr_floats;       // per-wave LDS scratch
+  int img_floats;
+  // dynamic LDS of a launch with that many waves per workgroup: the image and one scratch area per wave
+  size_t lds_bytes(int waves) const { return sizeof(float) * ((size_t)img_floats + (size_t)waves * scr_floats); }
+  template <class F>
+  void each_kernel(F f) const {
+    each_roll(fwd, f);
+    each_roll(grad, f);
+    f(kernel_ptr(mfwd));
+    f(kernel_ptr(mvjp));
+  }
+};
+static_assert(sizeof(KernelSet) == set_bytes(8 + 8 + 2 + /* name */ 1, 4), "KernelSet::each_kernel visits every kernel?");
+
 // Split-tile kernels (small batches: four waves share one 16-rollout tile; phnn_kernels.hip.h "Split-tile models"),
 // defined in phnn_split.hip for the 128-wide f16x2 pHNN (fixed G) and canonical variants.  Bitwise the same results
 // and the same tape formats as the whole-tile kernels.
@@ -165,7 +201,14 @@ struct SplitSet {
   RollTable fwd, grad;
   RollKernel fwd_t[2];  // K1 keeping the training tape: Euler, RK4
   int lds_floats;  // image + 4 x per-wave scratch + exchange area
+  template <class F>
+  void each_kernel(F f) const {
+    each_roll(fwd, f);
+    each_roll(grad, f);
+    for (RollKernel k : fwd_t) f(kernel_ptr(k));
+  }
 };
+static_assert(sizeof(SplitSet) == set_bytes(8 + 8 + 2, 1), "SplitSet::each_kernel visits every kernel?");
 bool phnn_split_kernels(int variant, SplitSet* g);  // false: no split-tile kernels for this variant
 
 // Weight-gradient kernels (training side), defined in phnn_wgrad.hip for the pHNN and canonical
@@ -182,7 +225,19 @@ struct WgradSet {
   int blob_floats;    // floats per slab row = size of the (width-padded) weight blob
   int reduce_waves;   // waves per workgroup of the reduce kernel (= hidden width / 16)
   int reduce_lds_bytes;
+  template <class F>
+  void each_kernel(F f) const {
+    for (int i = 0; i < 2; ++i) {
+      f(kernel_ptr(grad[i]));
+      f(kernel_ptr(grad_t[i]));
+      f(kernel_ptr(fwd_t[i]));
+    }
+    f(kernel_ptr(mvjp));
+    f(kernel_ptr(reduce));
+    f(kernel_ptr(reduce_t));
+  }
 };
+static_assert(sizeof(WgradSet) == set_bytes(2 + 2 + 2 + 3, 2 + 4), "WgradSet::each_kernel visits every kernel?");
 bool phnn_wgrad_kernels(int variant, WgradSet* g);  // false: no weight-gradient kernels for this variant
 // launches k_wgrad_finish (phnn_wgrad.hip); returns the launch status
 hipError_t phnn_wgrad_finish(const float* slab, int rows, int PP, const int* map, int P, float* out, int accumulate,
