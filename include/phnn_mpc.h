@@ -28,7 +28,8 @@
  *     _vjp, phnn_rollout_trajectory_ws before phnn_rollout_wgrad with PHNN_WGRAD_TAPES).  The exceptions accumulate, so
  *     their contents on entry are data: grad_theta_dev with PHNN_WGRAD_ACCUMULATE / accumulate = 1; best_cost_dev and
  *     best_u_dev of phnn_adam_step, phnn_mppi_update and phnn_cem_update (the solves reset them first); done_step_dev of
- *     phnn_plant_step (initialise to -1); log_states_dev / log_controls_dev, of which a call writes one row; and the
+ *     phnn_plant_step (initialise to -1); log_states_dev / log_controls_dev, of which a call writes one row (and of
+ *     phnn_plant_step_ex: disturbance_log_dev likewise, cost_acc_dev / run_dev / best_run_dev of its metrics); and the
  *     documented in-place states (u_dev of the solves and updates, sigma_dev, exp_avg / exp_avg_sq of phnn_adam_step,
  *     state_dev, *step_dev);
  *   - alignment: float32 / int32 tensors need 4-byte and float64 tensors 8-byte alignment, with two exceptions.
@@ -579,6 +580,68 @@ int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, 
                     int64_t action_stride, int64_t B, int32_t has_u_bounds, float u_min, float u_max,
                     float* state_f32_dev, int32_t* done_step_dev, const int32_t* step_dev, int32_t step_host,
                     double* log_states_dev, float* log_controls_dev, void* stream);
+
+/* ---- plant scenarios: per-plant parameters, disturbances, freeze at termination, metrics ------
+ * phnn_plant_step_ex is phnn_plant_step with two optional structs; ex == NULL && metrics == NULL IS phnn_plant_step
+ * (same kernel, same bits), and a zero-initialised ex with metrics == NULL gives its bits too.  Everything is float64
+ * unless stated, without fused multiply-adds.  Per plant b, gid = plant_offset + b:
+ *   1. step index, force uf and its clamp: as phnn_plant_step (a NaN command stays NaN; log_controls holds uf).
+ *   2. disturbance w, float32: w = force_bias_dev ? force_bias_dev[b] : 0; if force_sigma > 0, w = w + force_sigma * z0
+ *      (the product rounded, then the sum).  force = (double)uf + (double)w; with neither a bias nor a sigma nothing is
+ *      added at all, force = (double)uf (a -0.0 command stays -0.0).  disturbance_log_dev row `step` receives w.
+ *   3. noise: the library's sampling generator (Philox4x32-10, Box-Muller; key = seed).  z0 is component 0 of the call
+ *      with counter (gid & 0xffffffff, gid >> 32, step, 1 << 6 | 0), the four measurement normals z_0..z_3 are the four
+ *      components of the call with last word 1 << 6 | 1.  CONTRACT: these are the values the white sampler
+ *      (phnn_mppi_sample, sigma 1, u 0, no bounds) draws for elements 0 and 4..7 of sample 1 of problem gid at (seed,
+ *      epoch = step, iteration = 0).  The noise of plant gid at step s depends on (seed, gid, s) only: not on B, on the
+ *      position in the batch, on how a batch is split over calls, or on graph replay vs eager launches.  Use a seed
+ *      other than the controller's sampling seed, or the disturbance equals one of the controller's own perturbations.
+ *      A call is made only where its sigma is non-zero.
+ *   4. parameters: params_dev[4b .. 4b+3] = gravity, masscart, masspole, length when given, else the phnn_plant's; dt
+ *      and the limits are always the phnn_plant's.  The dynamics are phnn_plant_step's, operation for operation.
+ *   5. freeze_done: a plant whose done_step_dev[b] >= 0 ON ENTRY is not stepped: state_dev keeps its bits, the log_states
+ *      row repeats them, log_controls and disturbance_log are still written (the computed w is logged, not applied),
+ *      state_f32 is the measurement (6) of the kept state, done_step and the metrics are not touched.
+ *   6. measurement: state_f32[i] = (float)x_i, and for every i with meas_sigma[i] > 0 additionally + meas_sigma[i] * z_i
+ *      in float32 (product rounded, then the sum).  State, logs and the termination test never see this noise.
+ *   7. termination: on the true new state, strict, written once; a NaN state never terminates.
+ *   8. metrics (metrics != NULL, plant stepped): e_i = x_i - target[i] on the new state;
+ *      c = sum_i sum_j (e_i * Q[4i+j]) * e_j + ((double)uf * R) * (double)uf, i outer, j inner, ascending, added one
+ *      by one to an accumulator that starts at 0; cost_acc[b] += c; ok = all_i |e_i| <= tol[i] (false for a NaN);
+ *      run[b] = ok ? run[b] + 1 : 0; best_run[b] = max(best_run[b], run[b]).  To count the initial state as
+ *      closed_loop.stability_report does, initialise run / best_run to 1 where it is in the band, else 0.
+ * Buffer contract as at the top of this file: params_dev, force_bias_dev and action_dev are inputs and are never
+ * written; cost_acc_dev, run_dev, best_run_dev accumulate (their contents on entry are data, the caller initialises
+ * them), disturbance_log_dev receives one row per call like the other logs.  Stream-ordered and capturable; *step_dev
+ * is read by the launch, so a replayed graph draws fresh noise at every control step.
+ * PHNN_ERR_INVALID_ARG, nothing launched: what phnn_plant_step refuses, in its order; then a negative or non-finite
+ * force_sigma / meas_sigma; plant_offset < 0 or plant_offset + B > 2^48; freeze_done without done_step_dev;
+ * disturbance_log_dev with neither step_dev nor step_host >= 0; non-zero reserved; metrics with a NULL array or a
+ * negative or NaN tol. */
+typedef struct {
+  const double* params_dev;     /* (B,4) float64 per plant: gravity, masscart, masspole, length; NULL = the phnn_plant's.
+                                   dt, x_limit, theta_limit stay shared */
+  const float*  force_bias_dev; /* (B) constant force offset per plant, or NULL */
+  float   force_sigma;          /* std of additive Gaussian force noise, >= 0, finite */
+  float   meas_sigma[4];        /* std of Gaussian noise on state_f32 only (what the controller sees), >= 0, finite */
+  uint64_t seed;                /* noise key; use a seed other than the controller's sampling seed */
+  int64_t plant_offset;         /* global id of plant 0: gid = plant_offset + b, 0 <= .., plant_offset + B <= 2^48 */
+  int32_t freeze_done;          /* 1: a plant whose done_step is >= 0 ON ENTRY is not stepped any more */
+  float*  disturbance_log_dev;  /* (T,B) float32, row `step` receives w_b, or NULL */
+  int32_t reserved[4];          /* zero */
+} phnn_plant_ex;
+
+typedef struct {
+  double Q[16], R, target[4], tol[4]; /* closed-loop stage cost and the stability band, float64 */
+  double*  cost_acc_dev;  /* (B) += cost of this step            (caller zeroes)            */
+  int32_t* run_dev;       /* (B) current in-band run length      (caller initialises)       */
+  int32_t* best_run_dev;  /* (B) longest in-band run so far      (caller initialises)       */
+} phnn_plant_metrics;
+
+int phnn_plant_step_ex(phnn_handle* h, const phnn_plant* plant, const phnn_plant_ex* ex, const phnn_plant_metrics* metrics,
+                       double* state_dev, const float* action_dev, int64_t action_stride, int64_t B, int32_t has_u_bounds,
+                       float u_min, float u_max, float* state_f32_dev, int32_t* done_step_dev, const int32_t* step_dev,
+                       int32_t step_host, double* log_states_dev, float* log_controls_dev, void* stream);
 
 /* Warm start of the next solve, src/mpc_controller_canonical.py:252-255: dst[b,t] = src[b,t+1] for t < H-1,
  * dst[b,H-1] = 0 (u (B,H,m), shift by one step).  Also advances *step_dev by one when step_dev != NULL; B == 0 with a

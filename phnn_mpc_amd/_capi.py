@@ -35,6 +35,7 @@ EXPORTED = [
     "phnn_solve_lbfgs", "phnn_mppi_workspace_bytes", "phnn_mppi_sample", "phnn_mppi_update", "phnn_solve_mppi",
     "phnn_cem_workspace_bytes", "phnn_cem_sample", "phnn_cem_update", "phnn_solve_cem",
     "phnn_mppi_sample_shaped", "phnn_cem_sample_shaped", "phnn_solve_mppi_shaped", "phnn_solve_cem_shaped",
+    "phnn_plant_step_ex",
 ]
 
 
@@ -105,6 +106,21 @@ class Plant(C.Structure):
     @classmethod
     def default(cls, dt=0.02):
         return cls(9.8, 1.0, 0.1, 0.5, float(dt), 10.0, 0.5)
+
+
+class PlantEx(C.Structure):
+    """phnn_plant_ex: per-plant parameters (B,4) float64, force bias (B) float32, force / measurement noise, the noise
+    counter fields seed / plant_offset, freeze at termination, and the disturbance log (T,B) float32."""
+    _fields_ = [("params_dev", C.c_void_p), ("force_bias_dev", C.c_void_p), ("force_sigma", C.c_float),
+                ("meas_sigma", C.c_float * 4), ("seed", C.c_uint64), ("plant_offset", C.c_int64), ("freeze_done", C.c_int32),
+                ("disturbance_log_dev", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class PlantMetrics(C.Structure):
+    """phnn_plant_metrics: the closed-loop stage cost (Q row-major, R), the stability band (target, tol) and the three
+    accumulating device arrays: cost (B) float64, current and longest in-band run (B) int32."""
+    _fields_ = [("Q", C.c_double * 16), ("R", C.c_double), ("target", C.c_double * 4), ("tol", C.c_double * 4),
+                ("cost_acc_dev", C.c_void_p), ("run_dev", C.c_void_p), ("best_run_dev", C.c_void_p)]
 
 
 class Options(C.Structure):
@@ -281,6 +297,10 @@ def load_library():
     lib.phnn_plant_step.argtypes = [vp, C.POINTER(Plant), vp, f32p, i64, i64, i32, C.c_float, C.c_float, f32p, vp, vp, i32,
                                     vp, f32p, vp]
     lib.phnn_plant_step.restype = C.c_int
+    # the arguments of phnn_plant_step with a phnn_plant_ex* and a phnn_plant_metrics* after the plant
+    lib.phnn_plant_step_ex.argtypes = (lib.phnn_plant_step.argtypes[:2] + [C.POINTER(PlantEx), C.POINTER(PlantMetrics)] +
+                                       lib.phnn_plant_step.argtypes[2:])
+    lib.phnn_plant_step_ex.restype = C.c_int
     lib.phnn_shift_controls.argtypes = [vp, f32p, f32p, i64, i32, i32, vp, vp]
     lib.phnn_shift_controls.restype = C.c_int
     lib.phnn_kernel_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i64]

@@ -17,45 +17,183 @@
                          mppi_options() / cem_options(), and a captured control step reads its device tensor in place.
   stability_report       the "stability achieved" criterion of scripts/run_cartpole_mpc.py:117-159 with the
                          tolerances of the `stability` config section, per plant.
+  PlantScenario          (all three drivers, scenario=) what makes the plants differ from the model and from each other:
+                         per-plant gravity / masses / length, a constant force bias, Gaussian force and measurement
+                         noise, and a freeze at termination (include/phnn_mpc.h: phnn_plant_step_ex).
+                         The device loop can also keep per-plant metrics (metrics=) and drop the logs (log=False).
 """
 import numpy as np
 
+PARAMS = ("gravity", "masscart", "masspole", "length")  # the columns of a (B,4) per-plant parameter array
+PLANT_DEFAULTS = dict(gravity=9.8, masscart=1.0, masspole=0.1, length=0.5)
+STABILITY_DEFAULTS = dict(tolerance=[0.5, 0.1, 0.5, 0.5], min_duration=1.0)
+
+
+class PlantScenario:
+    """How the B plants of a closed loop differ from the nominal one (the fields of phnn_plant_ex).
+
+    params      (B,4) array of gravity, masscart, masspole, length per plant, or a dict of those names to (B,) arrays or
+                scalars (a missing name keeps the plant's shared value); None: the shared plant
+    force_bias  (B,) constant force offset per plant (float32), or None
+    force_sigma standard deviation of additive Gaussian force noise, drawn afresh at every control step
+    meas_sigma  standard deviation of Gaussian noise on the float32 state the controller is handed, one value or four;
+                the true state, the logs and the termination test never see it
+    seed        key of the noise; plant gid at step s draws from (seed, gid, s) alone.  Use a seed other than the
+                controller's sampling seed (MPPI / CEM): the draws share the sampler's counter space
+    plant_offset  global id of plant 0 (a batch split over calls or devices draws what the whole batch would)
+    freeze_done a plant that has terminated is not stepped any more: its state stays, its metrics stop"""
+
+    def __init__(self, params=None, force_bias=None, force_sigma=0.0, meas_sigma=0.0, seed=0x706C616E74, plant_offset=0,
+                 freeze_done=False):
+        self.params, self.force_bias = params, force_bias
+        self.force_sigma = float(np.float32(force_sigma))
+        ms = np.broadcast_to(np.asarray(meas_sigma, dtype=np.float32).reshape(-1), (4,)).copy()
+        self.meas_sigma = ms
+        if not (self.force_sigma >= 0 and np.isfinite(self.force_sigma) and np.all(ms >= 0) and np.all(np.isfinite(ms))):
+            raise ValueError("force_sigma and meas_sigma must be >= 0 and finite")
+        self.seed, self.plant_offset, self.freeze_done = int(seed), int(plant_offset), bool(freeze_done)
+        if not 0 <= self.seed < 1 << 64 or self.plant_offset < 0:
+            raise ValueError("seed must fit 64 bits and plant_offset be >= 0")
+
+    @staticmethod
+    def spread(B, rel, rng):
+        """(B,4) parameters spread uniformly within +-rel about the defaults: rel one value for all four columns, four
+        values (gravity, masscart, masspole, length) or a dict of names (a missing name: no spread); rng a
+        numpy Generator.  Every entry lies in [default * (1 - rel), default * (1 + rel)]."""
+        if isinstance(rel, dict):
+            unknown = set(rel) - set(PARAMS)
+            if unknown:
+                raise ValueError(f"spread: unknown parameter(s) {sorted(unknown)}")
+            rel = [rel.get(k, 0.0) for k in PARAMS]
+        rel = np.broadcast_to(np.asarray(rel, dtype=np.float64).reshape(-1), (4,))
+        if np.any(rel < 0) or np.any(rel >= 1):
+            raise ValueError("spread: 0 <= rel < 1")
+        base = np.array([PLANT_DEFAULTS[k] for k in PARAMS])
+        lo, hi = base * (1.0 - rel), base * (1.0 + rel)
+        return np.clip(base * (1.0 + rel * rng.uniform(-1.0, 1.0, size=(int(B), 4))), lo, hi)
+
+    def params_array(self, B, shared):
+        """-> (B,4) float64, or None when the scenario has no per-plant parameters.  shared: the four shared values."""
+        if self.params is None:
+            return None
+        if isinstance(self.params, dict):
+            unknown = set(self.params) - set(PARAMS)
+            if unknown:
+                raise ValueError(f"PlantScenario: unknown parameter(s) {sorted(unknown)}")
+            cols = [np.broadcast_to(np.asarray(self.params.get(k, shared[i]), dtype=np.float64).reshape(-1), (B,))
+                    for i, k in enumerate(PARAMS)]
+            return np.ascontiguousarray(np.stack(cols, axis=1))
+        p = np.ascontiguousarray(self.params, dtype=np.float64)
+        if p.shape != (B, 4):
+            raise ValueError(f"PlantScenario: params must be ({B},4), got {p.shape}")
+        return p
+
+    def bias_array(self, B):
+        """-> (B,) float32 or None"""
+        if self.force_bias is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(self.force_bias, dtype=np.float32).reshape(-1), (B,)))
+
+    @property
+    def measured(self):
+        return bool(np.any(self.meas_sigma > 0))
+
 
 class BatchedCartPole:
-    def __init__(self, dt=0.02, gravity=9.8, masscart=1.0, masspole=0.1, length=0.5, x_limit=10.0, theta_limit=0.5):
-        """The defaults are the reference's plant; the other arguments are the fields of phnn_plant (_capi.Plant)."""
+    def __init__(self, dt=0.02, gravity=9.8, masscart=1.0, masspole=0.1, length=0.5, x_limit=10.0, theta_limit=0.5,
+                 scenario=None, replay=None):
+        """The defaults are the reference's plant; the other arguments are the fields of phnn_plant (_capi.Plant).
+        scenario: a PlantScenario -- per-plant parameters, force bias and noise, measurement noise, freeze; the noise is
+        the device plant's, drawn in float64 (noise.plant_normals).  replay: a (T,B) float32 disturbance log (the device
+        loop's `disturbance`): step t applies row t instead of computing bias + noise."""
         self.dt = dt
         self.gravity, self.masscart, self.masspole, self.length = gravity, masscart, masspole, length
         self.x_limit, self.theta_limit = x_limit, theta_limit
         self.polemass_length = self.masspole * self.length
         self.total_mass = self.masspole + self.masscart
         self.state = None
+        self.scenario = scenario
+        self.replay = None if replay is None else np.asarray(replay, dtype=np.float32)
+        self.t = 0
+        self.disturbance = None  # (B,) float32: what the last step added to the force (with a scenario or a replay)
 
     def reset(self, initial_states):
         self.state = np.array(initial_states, dtype=np.float64).reshape(-1, 4)
+        self.t = 0
+        B = self.state.shape[0]
+        self._terminated = np.zeros(B, dtype=bool)
+        self._bias = None
+        sc = self.scenario
+        if sc is not None:
+            p = sc.params_array(B, (self.gravity, self.masscart, self.masspole, self.length))
+            if p is not None:
+                self.gravity, self.masscart, self.masspole, self.length = p.T.copy()
+                self.polemass_length = self.masspole * self.length
+                self.total_mass = self.masspole + self.masscart
+            self._bias = sc.bias_array(B)
         return self.state.copy()
+
+    def _disturbance(self, B):
+        """-> (B,) float32 added to the force at this step, or None: nothing is added."""
+        sc = self.scenario
+        if self.replay is not None:
+            return self.replay[self.t].reshape(B)
+        if sc is None or (self._bias is None and not sc.force_sigma > 0):
+            return None
+        w = np.zeros(B, np.float32) if self._bias is None else self._bias.copy()
+        if sc.force_sigma > 0:
+            from .noise import plant_normals
+            z0 = plant_normals(sc.seed, self.t, sc.plant_offset + np.arange(B), 0)[:, 0].astype(np.float32)
+            w = w + np.float32(sc.force_sigma) * z0
+        return w
 
     def step(self, action):
         """action (B,) or (B,1) forces -> (states (B,4), done (B,) bool)"""
         force = np.asarray(action, dtype=np.float64).reshape(-1)
+        self.disturbance = self._disturbance(self.state.shape[0])
+        if self.disturbance is not None:
+            force = force + self.disturbance.astype(np.float64)
         x, theta, x_dot, theta_dot = self.state.T
         costheta, sintheta = np.cos(theta), np.sin(theta)
         temp = (force + self.polemass_length * theta_dot ** 2 * sintheta) / self.total_mass
         thetaacc = (self.gravity * sintheta - costheta * temp) / (
             self.length * (4.0 / 3.0 - self.masspole * costheta ** 2 / self.total_mass))
         xacc = temp - self.polemass_length * thetaacc * costheta / self.total_mass
-        self.state = np.stack([x + self.dt * x_dot, theta + self.dt * theta_dot, x_dot + self.dt * xacc,
-                               theta_dot + self.dt * thetaacc], axis=1)
+        new = np.stack([x + self.dt * x_dot, theta + self.dt * theta_dot, x_dot + self.dt * xacc,
+                        theta_dot + self.dt * thetaacc], axis=1)
+        if self.scenario is not None and self.scenario.freeze_done:  # terminated on entry: not stepped
+            new = np.where(self._terminated[:, None], self.state, new)
+        self.state = new
         done = (np.abs(self.state[:, 0]) > self.x_limit) | (np.abs(self.state[:, 1]) > self.theta_limit)
+        self._terminated |= done
+        self.t += 1
         return self.state.copy(), done
+
+    def measurement(self):
+        """The float32 state the controller is handed: float32(state), plus the scenario's measurement noise of the step
+        that produced it (none on the initial state)."""
+        x32 = self.state.astype(np.float32)
+        sc = self.scenario
+        if sc is None or not sc.measured or self.t == 0:
+            return x32
+        from .noise import plant_normals
+        z = plant_normals(sc.seed, self.t - 1, sc.plant_offset + np.arange(x32.shape[0]), 1).astype(np.float32)
+        on = sc.meas_sigma > 0
+        x32[:, on] = x32[:, on] + sc.meas_sigma[on] * z[:, on]
+        return x32
 
     def get_state(self):
         return self.state.copy()
 
 
-def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None):
+def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, scenario=None):
     """-> dict(states (T+1,B,4), controls (T,B,1), done_step (B,) first step a plant terminated at, or -1).
-    x_ref: reference trajectories broadcastable to (B, rows, 4); control step s tracks them from row s."""
+    x_ref: reference trajectories broadcastable to (B, rows, 4); control step s tracks them from row s.
+    scenario: a PlantScenario for the simulator (a BatchedCartPole built with scenario= / replay= has its own); the
+    result then also holds disturbance (T,B) float32, what each step added to the commanded force."""
+    if scenario is not None:
+        simulator.scenario = scenario
+    measured = hasattr(simulator, "measurement")
     x = simulator.reset(initial_states)
     B = x.shape[0]
     states, controls = [x.copy()], []
@@ -64,20 +202,27 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None):
     u_prev = None
     from .solver import SAMPLING
     sampling = getattr(controller, "optimizer", getattr(controller, "optimizer_type", None)) in SAMPLING
+    dist = []
     for step in range(num_steps):
         rkw = {"epoch": step} if sampling else {}  # the noise counter of an MPPI / CrossEntropy solve: the control step
         if x_ref is not None:
             rkw.update(x_ref=x_ref, ref_offset=step)
+        x32 = simulator.measurement() if measured else x.astype(np.float32)
         if canonical:
-            u, u_prev, _ = controller.control_batch(x.astype(np.float32), u_prev, **rkw)
+            u, u_prev, _ = controller.control_batch(x32, u_prev, **rkw)
         else:
-            u = controller.compute_control_batch(x.astype(np.float32), **rkw)
+            u = controller.compute_control_batch(x32, **rkw)
         x, done = simulator.step(u)
         newly = done & (done_step < 0)
         done_step[newly] = step
         states.append(x.copy())
         controls.append(np.asarray(u, dtype=np.float64).reshape(B, -1))
-    return {"states": np.stack(states), "controls": np.stack(controls), "done_step": done_step}
+        if getattr(simulator, "disturbance", None) is not None:
+            dist.append(simulator.disturbance.copy())
+    out = {"states": np.stack(states), "controls": np.stack(controls), "done_step": done_step}
+    if dist:
+        out["disturbance"] = np.stack(dist)
+    return out
 
 
 class DeviceClosedLoop:
@@ -98,9 +243,19 @@ class DeviceClosedLoop:
     step moves one row along.  The graph reads the reference through a pointer taken here: a float32 tensor on the
     engine's device with a contiguous last dimension is read in place (keep it alive and in place -- the loop holds a
     view of it; values changed in place between runs are seen), anything else is copied once, here.
+
+    scenario: a PlantScenario; the plant step is then k_plant_step_ex (phnn_plant_step_ex), with the step counter as the
+    noise step, so eager and replayed runs draw the same noise, and the result holds disturbance (T,B) float32 (what
+    each step added to the force; hand it to BatchedCartPole(replay=) to repeat the run on the host).  metrics: True or
+    the config's `stability` section (tolerance, min_duration): the plant step also accumulates, per plant, the
+    closed-loop cost sum_t e_t^T Q e_t + R u_t^2 (the controller's Q, R and target, float64, on the true states 1..T) and
+    the longest run inside the stability band; the result gains cost (B,), longest_run_s (B,) and stable (B,), the
+    latter two equal to stability_report over states 0..T.  log=False: the (T+1,B,4) and (T,B) logs are neither
+    allocated nor written; states, controls (and disturbance) are None.  With none of the three the loop is what it was.
     """
 
-    def __init__(self, controller, initial_states, num_steps, use_graph=True, dt=None, x_ref=None):
+    def __init__(self, controller, initial_states, num_steps, use_graph=True, dt=None, x_ref=None, scenario=None,
+                 metrics=False, log=True):
         import torch
         from . import _capi
         self.torch, self.ctl = torch, controller
@@ -113,9 +268,11 @@ class DeviceClosedLoop:
         self.plant = _capi.Plant.default(controller.dt if dt is None else dt)
         self.state = torch.tensor(x, dtype=torch.float64, device=dev)
         self.x32 = self.state.to(torch.float32)  # what the reference hands the controller (float32 of the state)
-        self.log_states = torch.empty(self.T + 1, B, 4, dtype=torch.float64, device=dev)
-        self.log_states[0].copy_(self.state)
-        self.log_controls = torch.empty(self.T, B, dtype=torch.float32, device=dev)
+        self.log_states = self.log_controls = None
+        if log:
+            self.log_states = torch.empty(self.T + 1, B, 4, dtype=torch.float64, device=dev)
+            self.log_states[0].copy_(self.state)
+            self.log_controls = torch.empty(self.T, B, dtype=torch.float32, device=dev)
         self.done_step = torch.full((B,), -1, dtype=torch.int32, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.u_init = torch.zeros(B, H, m, dtype=torch.float32, device=dev)
@@ -141,11 +298,65 @@ class DeviceClosedLoop:
             raise NotImplementedError(f"{type(eng).__name__} has no batched L-BFGS solve (RolloutEngine has)")
         self.graph = None
         self.use_graph = use_graph and dev.type == "cuda"
+        self.ex = self.metrics = None
+        self._keep = {}  # the device tensors the two structs point at
+        if scenario is not None:
+            self._scenario(scenario, log)
+        if metrics:
+            self._metrics(STABILITY_DEFAULTS if metrics is True else metrics, x)
+
+    def _scenario(self, sc, log):
+        """Fills self.ex (phnn_plant_ex) from a PlantScenario."""
+        torch, dev, B, pl = self.torch, self.eng.device, self.B, self.plant
+        from . import _capi
+        ex, k = _capi.PlantEx(), self._keep
+        params = sc.params_array(B, (pl.gravity, pl.masscart, pl.masspole, pl.length))
+        if params is not None:
+            k["params"] = torch.tensor(params, dtype=torch.float64, device=dev)
+            ex.params_dev = k["params"].data_ptr()
+        bias = sc.bias_array(B)
+        if bias is not None:
+            k["bias"] = torch.tensor(bias, dtype=torch.float32, device=dev)
+            ex.force_bias_dev = k["bias"].data_ptr()
+        ex.force_sigma = sc.force_sigma
+        for i in range(4):
+            ex.meas_sigma[i] = float(sc.meas_sigma[i])
+        ex.seed, ex.plant_offset, ex.freeze_done = sc.seed, sc.plant_offset, int(sc.freeze_done)
+        if log:
+            k["disturbance"] = torch.zeros(self.T, B, dtype=torch.float32, device=dev)
+            ex.disturbance_log_dev = k["disturbance"].data_ptr()
+        self.ex = ex
+
+    def _metrics(self, stab, x0):
+        """Fills self.metrics (phnn_plant_metrics) from the controller's cost and a `stability` section; the run counters
+        start from the initial state, as stability_report counts it."""
+        torch, dev, B = self.torch, self.eng.device, self.B
+        from . import _capi
+        if self.eng.n != 4 or self.eng.m != 1:
+            raise ValueError("closed-loop metrics are the cart-pole's: a 4-state, 1-input model")
+        mt, k, cost = _capi.PlantMetrics(), self._keep, self.cost
+        for i in range(4):
+            for j in range(4):
+                mt.Q[4 * i + j] = float(cost.Q[4 * i + j])
+            mt.target[i] = float(cost.x_target[i])
+        mt.R = float(cost.R[0])
+        tol = np.broadcast_to(np.asarray(stab.get("tolerance", STABILITY_DEFAULTS["tolerance"]), dtype=np.float64).reshape(-1), (4,))
+        for i in range(4):
+            mt.tol[i] = float(tol[i])
+        self.need = max(int(np.ceil(stab.get("min_duration", STABILITY_DEFAULTS["min_duration"]) / self.plant.dt)), 1)
+        ok0 = np.all(np.abs(x0 - np.array(list(mt.target))) <= tol, axis=1).astype(np.int32)
+        k["cost"] = torch.zeros(B, dtype=torch.float64, device=dev)
+        k["run"] = torch.tensor(ok0, dtype=torch.int32, device=dev)
+        k["best_run"] = k["run"].clone()
+        mt.cost_acc_dev, mt.run_dev, mt.best_run_dev = k["cost"].data_ptr(), k["run"].data_ptr(), k["best_run"].data_ptr()
+        self.metrics = mt
 
     def _control_step(self):
         eng, c = self.eng, self.ctl
         log = dict(state_f32=self.x32, done_step=self.done_step, step_dev=self.step_dev, log_states=self.log_states,
                    log_controls=self.log_controls)
+        if self.ex is not None or self.metrics is not None:
+            log.update(ex=self.ex, metrics=self.metrics)
         H = self.u_init.shape[1] * self.u_init.shape[2]
         if self.sampling:
             out = self._solve_sampling()
@@ -183,13 +394,24 @@ class DeviceClosedLoop:
             for _ in range(self.T):
                 self._control_step()
         torch.cuda.synchronize(dev)
-        return {"states": self.log_states.cpu().numpy(), "controls": self.log_controls.cpu().numpy()[:, :, None].astype(np.float64),
-                "done_step": self.done_step.cpu().numpy().astype(np.int64)}
+        logged = self.log_states is not None
+        out = {"states": self.log_states.cpu().numpy() if logged else None,
+               "controls": self.log_controls.cpu().numpy()[:, :, None].astype(np.float64) if logged else None,
+               "done_step": self.done_step.cpu().numpy().astype(np.int64)}
+        if self.ex is not None:
+            out["disturbance"] = self._keep["disturbance"].cpu().numpy() if logged else None
+        if self.metrics is not None:
+            best = self._keep["best_run"].cpu().numpy().astype(np.int64)
+            out.update(cost=self._keep["cost"].cpu().numpy(), longest_run_s=best * self.plant.dt, stable=best >= self.need)
+        return out
 
 
-def run_mpc_batch_device(controller, initial_states, num_steps, use_graph=True, x_ref=None):
-    """Device-resident version of run_mpc_batch: same return dict, one host synchronisation at the end."""
-    return DeviceClosedLoop(controller, initial_states, num_steps, use_graph=use_graph, x_ref=x_ref).run()
+def run_mpc_batch_device(controller, initial_states, num_steps, use_graph=True, x_ref=None, scenario=None, metrics=False,
+                         log=True):
+    """Device-resident version of run_mpc_batch: same return dict, one host synchronisation at the end.  scenario,
+    metrics, log: as in DeviceClosedLoop."""
+    return DeviceClosedLoop(controller, initial_states, num_steps, use_graph=use_graph, x_ref=x_ref, scenario=scenario,
+                            metrics=metrics, log=log).run()
 
 
 def stability_report(states, target, tolerance, min_duration, dt):

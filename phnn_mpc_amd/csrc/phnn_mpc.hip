@@ -1514,6 +1514,76 @@ int phnn_plant_step(phnn_handle* h, const phnn_plant* plant, double* state_dev, 
   return checked(h, "plant step launch", k_plant_step, flat_grid(B), dim3(kFlatThreads), 0, (hipStream_t)stream, p);
 }
 
+int phnn_plant_step_ex(phnn_handle* h, const phnn_plant* plant, const phnn_plant_ex* ex, const phnn_plant_metrics* metrics,
+                       double* state_dev, const float* action_dev, int64_t action_stride, int64_t B, int32_t has_u_bounds,
+                       float u_min, float u_max, float* state_f32_dev, int32_t* done_step_dev, const int32_t* step_dev,
+                       int32_t step_host, double* log_states_dev, float* log_controls_dev, void* stream) {
+  if (!ex && !metrics)  // nothing extended: the old entry point, the old kernel
+    return phnn_plant_step(h, plant, state_dev, action_dev, action_stride, B, has_u_bounds, u_min, u_max, state_f32_dev,
+                           done_step_dev, step_dev, step_host, log_states_dev, log_controls_dev, stream);
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B == 0) return PHNN_OK;
+  if (!plant || !state_dev || !action_dev || B < 0 || action_stride < 0)
+    return fail(h, PHNN_ERR_INVALID_ARG, "NULL plant / state / action, or negative batch / stride");
+  if (has_u_bounds && !(u_min <= u_max)) return fail(h, PHNN_ERR_INVALID_ARG, "u_min > u_max");
+  if ((log_states_dev || log_controls_dev) && !step_dev && step_host < 0)
+    return fail(h, PHNN_ERR_INVALID_ARG, "negative step index");
+  const auto sigma_ok = [](float s) { return s >= 0.f && std::isfinite(s); };
+  PlantExParams p{};
+  if (ex) {
+    if (!sigma_ok(ex->force_sigma) || !sigma_ok(ex->meas_sigma[0]) || !sigma_ok(ex->meas_sigma[1]) ||
+        !sigma_ok(ex->meas_sigma[2]) || !sigma_ok(ex->meas_sigma[3]))
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_plant_step_ex: negative or non-finite force_sigma / meas_sigma");
+    if (ex->plant_offset < 0 || ex->plant_offset > kSamplingMaxProblem || B > kSamplingMaxProblem - ex->plant_offset)
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_plant_step_ex: plant_offset < 0 or plant_offset + B > 2^48");
+    if (ex->freeze_done && !done_step_dev)
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_plant_step_ex: freeze_done needs done_step_dev");
+    if (ex->disturbance_log_dev && !step_dev && step_host < 0)
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_plant_step_ex: disturbance_log_dev with a negative step index");
+    for (int i = 0; i < 4; ++i)
+      if (ex->reserved[i]) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_plant_step_ex: reserved fields must be zero");
+    p.params = ex->params_dev;
+    p.force_bias = ex->force_bias_dev;
+    p.force_sigma = ex->force_sigma;
+    for (int i = 0; i < 4; ++i) p.meas_sigma[i] = ex->meas_sigma[i];
+    p.key0 = (unsigned)(ex->seed & 0xffffffffu);
+    p.key1 = (unsigned)(ex->seed >> 32);
+    p.plant_offset = ex->plant_offset;
+    p.freeze_done = ex->freeze_done != 0;
+    p.disturbance_log = ex->disturbance_log_dev;
+  }
+  if (metrics) {
+    if (!metrics->cost_acc_dev || !metrics->run_dev || !metrics->best_run_dev)
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_plant_step_ex: metrics with a NULL array");
+    for (int i = 0; i < 4; ++i)
+      if (!(metrics->tol[i] >= 0.0)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_plant_step_ex: negative or NaN tol");
+    p.has_metrics = 1;
+    for (int i = 0; i < 16; ++i) p.Q[i] = metrics->Q[i];
+    p.R = metrics->R;
+    for (int i = 0; i < 4; ++i) p.target[i] = metrics->target[i], p.tol[i] = metrics->tol[i];
+    p.cost_acc = metrics->cost_acc_dev;
+    p.run = metrics->run_dev;
+    p.best_run = metrics->best_run_dev;
+  }
+  PHNN_ON_DEVICE(h);
+  p.gravity = plant->gravity, p.masscart = plant->masscart, p.masspole = plant->masspole, p.length = plant->length;
+  p.dt = plant->dt, p.x_limit = plant->x_limit, p.theta_limit = plant->theta_limit;
+  p.state = state_dev;
+  p.action = action_dev;
+  p.stride = action_stride;
+  p.B = B;
+  p.has_u_bounds = has_u_bounds;
+  p.u_min = u_min;
+  p.u_max = u_max;
+  p.state_f32 = state_f32_dev;
+  p.done_step = done_step_dev;
+  p.step_dev = step_dev;
+  p.step_host = step_host;
+  p.log_states = log_states_dev;
+  p.log_controls = log_controls_dev;
+  return checked(h, plant_step_ex_launch(p, (hipStream_t)stream), "extended plant step launch");
+}
+
 int phnn_shift_controls(phnn_handle* h, const float* src_dev, float* dst_dev, int64_t B, int32_t H, int32_t m,
                         int32_t* step_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;

@@ -87,3 +87,36 @@ hipError_t cem_update_launch(const CemUpdateParams& p, hipStream_t st);
 hipError_t clamp_launch(float* u, long long count, float u_min, float u_max, hipStream_t st);
 // sig[b, t, c] = sigma_init[c] (count = B * N floats, m components): the entry of phnn_solve_cem
 hipError_t sigma_init_launch(float* sig, long long count, int m, const float* sigma_init, hipStream_t st);
+
+// k_plant_step_ex (phnn_plant_step_ex): k_plant_step with per-plant parameters, a force
+// disturbance, measurement noise, a freeze at termination and running metrics.  It lives in this unit because the noise
+// is the sampler's: z0 and the four measurement normals of plant gid at step s are the normals of float4 0 and float4 1
+// of sample 1 of problem gid at (seed, epoch = s, iteration = 0), i.e. counter words (gid, gid >> 32, s, 1 << 6 | 0 / 1).
+struct PlantExParams {
+  double gravity, masscart, masspole, length, dt, x_limit, theta_limit;  // the phnn_plant
+  double* state;        // (B,4) in/out
+  const float* action;  // action[b * stride]
+  long long stride, B;
+  int has_u_bounds;
+  float u_min, u_max;
+  float* state_f32;
+  int* done_step;
+  const int* step_dev;
+  int step_host;
+  double* log_states;    // (T+1,B,4)
+  float* log_controls;   // (T,B)
+  const double* params;  // (B,4) gravity, masscart, masspole, length per plant, or NULL: the shared ones above
+  const float* force_bias;  // (B) or NULL
+  float force_sigma;
+  float meas_sigma[4];
+  unsigned key0, key1;     // seed
+  long long plant_offset;  // gid = plant_offset + b
+  int freeze_done;
+  float* disturbance_log;  // (T,B) or NULL
+  int has_metrics;
+  double Q[16], R, target[4], tol[4];
+  double* cost_acc;  // (B)
+  int* run;          // (B)
+  int* best_run;     // (B)
+};
+hipError_t plant_step_ex_launch(const PlantExParams& p, hipStream_t st);

@@ -28,6 +28,9 @@
 // below T, or equals T while fewer than E - #{key < T} such rows have been taken.  The 16 lanes of a problem walk k
 // together, so that running count is the same in all of them.  Only elite rows are loaded.  No transcendental anywhere
 // in k_cem_update: it is pinned bit for bit against a float32 model (tests/cem_model.py).
+//
+// k_plant_step_ex, the extended plant step of the device closed loop (phnn_plant_step_ex), is here
+// as well: its disturbance and measurement noise are draws of this unit's generator at the sampler's counters.
 #include "phnn_sampling.h"
 
 #include <math.h>
@@ -470,6 +473,103 @@ __global__ __launch_bounds__(kBlock) void k_cem_update(CemUpdateParams p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- k_plant_step_ex
+// k_plant_step (phnn_kernels.hip.h) restated with the extensions of phnn_plant_step_ex: one thread per plant, float64
+// dynamics in k_plant_step's operation order (tests pin the two bit for bit), no LDS, no atomics.  At most two Philox
+// calls per plant, and only those whose sigma is non-zero.
+__device__ __forceinline__ U4 plant_noise(const PlantExParams& p, long long b, int step, unsigned j) {
+  const unsigned long long gid = (unsigned long long)(p.plant_offset + b);
+  U4 c;
+  c.x = (unsigned)gid;
+  c.y = (unsigned)(gid >> 32);  // iteration 0
+  c.z = (unsigned)step;
+  c.w = (1u << 6) | j;  // sample 1, float4 j
+  return philox4x32_10(c, p.key0, p.key1);
+}
+
+__global__ __launch_bounds__(kBlock) void k_plant_step_ex(PlantExParams p) {
+  const long long b = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (b >= p.B) return;
+  const int step = p.step_dev ? *p.step_dev : p.step_host;
+  float uf = p.action[b * p.stride];
+  if (p.has_u_bounds && uf == uf) uf = fminf(fmaxf(uf, p.u_min), p.u_max);  // a NaN command stays NaN
+  double force = (double)uf;
+  const bool disturbed = p.force_bias || p.force_sigma > 0.f;
+  float w = p.force_bias ? p.force_bias[b] : 0.f;
+  if (p.force_sigma > 0.f) {
+    const U4 o = plant_noise(p, b, step, 0u);
+    float z0, z1;
+    box_muller(o.x, o.y, z0, z1);
+    w = w + p.force_sigma * z0;
+  }
+  if (disturbed) force = (double)uf + (double)w;  // else nothing is added: a -0.0 command stays -0.0
+  const bool frozen = p.freeze_done && p.done_step[b] >= 0;
+
+  double x = p.state[4 * b + 0], theta = p.state[4 * b + 1], x_dot = p.state[4 * b + 2], theta_dot = p.state[4 * b + 3];
+  if (!frozen) {
+    double gravity = p.gravity, masscart = p.masscart, masspole = p.masspole, length = p.length;
+    if (p.params) gravity = p.params[4 * b + 0], masscart = p.params[4 * b + 1], masspole = p.params[4 * b + 2], length = p.params[4 * b + 3];
+    const double polemass_length = masspole * length, total_mass = masspole + masscart;
+    const double costheta = cos(theta), sintheta = sin(theta);
+    const double temp = (force + polemass_length * (theta_dot * theta_dot) * sintheta) / total_mass;
+    const double thetaacc = (gravity * sintheta - costheta * temp) / (length * (4.0 / 3.0 - masspole * (costheta * costheta) / total_mass));
+    const double xacc = temp - polemass_length * thetaacc * costheta / total_mass;
+    x = x + p.dt * x_dot;
+    theta = theta + p.dt * theta_dot;
+    x_dot = x_dot + p.dt * xacc;
+    theta_dot = theta_dot + p.dt * thetaacc;
+    p.state[4 * b + 0] = x;
+    p.state[4 * b + 1] = theta;
+    p.state[4 * b + 2] = x_dot;
+    p.state[4 * b + 3] = theta_dot;
+  }
+  if (p.state_f32) {
+    float m[4] = {(float)x, (float)theta, (float)x_dot, (float)theta_dot};
+    if (p.meas_sigma[0] > 0.f || p.meas_sigma[1] > 0.f || p.meas_sigma[2] > 0.f || p.meas_sigma[3] > 0.f) {
+      const U4 o = plant_noise(p, b, step, 1u);
+      float z[4];
+      box_muller(o.x, o.y, z[0], z[1]);
+      box_muller(o.z, o.w, z[2], z[3]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (p.meas_sigma[i] > 0.f) m[i] = m[i] + p.meas_sigma[i] * z[i];
+    }
+    p.state_f32[4 * b + 0] = m[0];
+    p.state_f32[4 * b + 1] = m[1];
+    p.state_f32[4 * b + 2] = m[2];
+    p.state_f32[4 * b + 3] = m[3];
+  }
+  if (!frozen) {
+    const bool done = fabs(x) > p.x_limit || fabs(theta) > p.theta_limit;
+    if (p.done_step && done && p.done_step[b] < 0) p.done_step[b] = step;
+  }
+  if (p.log_states) {
+    double* row = p.log_states + ((long long)(step + 1) * p.B + b) * 4;
+    row[0] = x;
+    row[1] = theta;
+    row[2] = x_dot;
+    row[3] = theta_dot;
+  }
+  if (p.log_controls) p.log_controls[(long long)step * p.B + b] = uf;
+  if (p.disturbance_log) p.disturbance_log[(long long)step * p.B + b] = w;
+  if (p.has_metrics && !frozen) {
+    const double e[4] = {x - p.target[0], theta - p.target[1], x_dot - p.target[2], theta_dot - p.target[3]};
+    double c = 0.0;
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c = c + (e[i] * p.Q[4 * i + j]) * e[j];
+      ok = ok && fabs(e[i]) <= p.tol[i];  // false for a NaN
+    }
+    c = c + ((double)uf * p.R) * (double)uf;
+    p.cost_acc[b] = p.cost_acc[b] + c;
+    const int run = ok ? p.run[b] + 1 : 0;
+    p.run[b] = run;
+    if (run > p.best_run[b]) p.best_run[b] = run;
+  }
+}
+
 // the update kernel of the row width: table[ALIGNED][E4 - 1], E4 = float4 per lane
 template <class P>
 hipError_t update_launch(void (*const table[2][4])(P), const P& p, bool aligned, hipStream_t st) {
@@ -557,6 +657,13 @@ hipError_t cem_update_launch(const CemUpdateParams& p, hipStream_t st) {
 hipError_t clamp_launch(float* u, long long count, float u_min, float u_max, hipStream_t st) {
   if (count < 1) return hipSuccess;
   hipLaunchKernelGGL(k_clamp, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, u, count, u_min, u_max);
+  return hipGetLastError();
+}
+
+hipError_t plant_step_ex_launch(const PlantExParams& p, hipStream_t st) {
+  const long long blocks = (p.B + kBlock - 1) / kBlock;
+  if (blocks < 1 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_plant_step_ex, dim3((unsigned)blocks), dim3(kBlock), 0, st, p);
   return hipGetLastError();
 }
 

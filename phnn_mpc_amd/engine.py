@@ -719,17 +719,23 @@ class RolloutEngine:
 
     # ------------------------------------------------------------------ the plant, on the device
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
-                   step=0, step_dev=None, log_states=None, log_controls=None):
+                   step=0, step_dev=None, log_states=None, log_controls=None, ex=None, metrics=None):
         """One float64 Euler step of the reference cart-pole for B plants, in place on `state` (B,4) float64.
-        action: float32 tensor, plant b takes action.view(-1)[b * action_stride].  See include/phnn_mpc.h."""
+        action: float32 tensor, plant b takes action.view(-1)[b * action_stride].  See include/phnn_mpc.h.
+        ex (_capi.PlantEx) / metrics (_capi.PlantMetrics): phnn_plant_step_ex -- per-plant parameters, disturbances,
+        freeze at termination, running metrics; the structs hold device pointers, the caller keeps the tensors alive."""
         assert state.dtype == torch.float64 and state.is_contiguous() and state.device == self.device
         assert action.dtype == torch.float32 and action.is_contiguous() and action.device == self.device
         B = state.shape[0]
         has_b = u_min is not None and u_max is not None
-        rc = self.lib.phnn_plant_step(self.h, C.byref(plant), self._p(state), self._p(action), int(action_stride), B,
-                                      int(has_b), float(u_min) if has_b else 0.0, float(u_max) if has_b else 0.0,
-                                      self._p(state_f32), self._p(done_step), self._p(step_dev), int(step),
-                                      self._p(log_states), self._p(log_controls), self._stream())
+        rest = (self._p(state), self._p(action), int(action_stride), B, int(has_b), float(u_min) if has_b else 0.0,
+                float(u_max) if has_b else 0.0, self._p(state_f32), self._p(done_step), self._p(step_dev), int(step),
+                self._p(log_states), self._p(log_controls), self._stream())
+        if ex is None and metrics is None:
+            rc = self.lib.phnn_plant_step(self.h, C.byref(plant), *rest)
+        else:
+            rc = self.lib.phnn_plant_step_ex(self.h, C.byref(plant), C.byref(ex) if ex is not None else None,
+                                             C.byref(metrics) if metrics is not None else None, *rest)
         _check(self.lib, self.h, rc)
 
     def shift_controls(self, src, dst, step_dev=None):

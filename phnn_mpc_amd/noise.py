@@ -17,6 +17,10 @@ Noise is the holder the engine, the solvers and the controllers pass around: the
 hashes by identity, so a captured graph (solver.GraphedMPPI / GraphedCEM) keys on the object and reads its device tensor
 through the pointer it was captured with -- keep the object, and change the tensor in place if at all.
 resolve() turns what a controller or a config gives (None, a Noise, {"type": ...}, an array) into an array for a horizon.
+
+The last section restates the library's generator (csrc/phnn_rows.hip.h: Philox4x32-10, Box-Muller) in numpy float64 at
+the counters of the extended plant step (include/phnn_mpc.h: phnn_plant_step_ex): plant_normals() gives the host plant
+closed_loop.BatchedCartPole the force and measurement normals the device plant draws, up to float32 rounding.
 """
 import numpy as np
 
@@ -174,3 +178,49 @@ def resolve(spec, H):
     if noise.H != int(H):
         raise ValueError(f"the noise shape has {noise.H} rows, the horizon is {H}")
     return noise
+
+
+# ----------------------------------------------------------------------------- the library's generator, in float64
+_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_MASK = np.uint64(0xFFFFFFFF)
+_32 = np.uint64(32)
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10: ctr (..., 4), key (2,) unsigned 32-bit values -> (..., 4) uint32."""
+    c = [np.asarray(ctr)[..., i].astype(np.uint64) & _MASK for i in range(4)]
+    k = [np.uint64(int(key[i]) & 0xFFFFFFFF) for i in range(2)]
+    for _ in range(10):
+        p0, p1 = np.uint64(_M0) * c[0], np.uint64(_M1) * c[2]
+        c = [(p1 >> _32) ^ c[1] ^ k[0], p1 & _MASK, (p0 >> _32) ^ c[3] ^ k[1], p0 & _MASK]
+        k = [(k[0] + np.uint64(_W0)) & _MASK, (k[1] + np.uint64(_W1)) & _MASK]
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def _unit(x):
+    """top 24 bits -> (0, 1]: (n + 0.5) * 2^-24"""
+    return ((x >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+
+
+def _box_muller(a, b):
+    r = np.sqrt(-2.0 * np.log(_unit(a)))
+    ang = np.pi * (2.0 * _unit(b))
+    return r * np.cos(ang), r * np.sin(ang)
+
+
+def plant_normals(seed, step, gids, j):
+    """The four float64 normals of float4 j (0: component 0 is the force normal z0; 1: the measurement normals) of the
+    plants with global ids `gids` at control step `step`: one Philox call each, key = seed, counter (gid & 0xffffffff,
+    gid >> 32, step, 1 << 6 | j) -- sample 1 of problem gid at (epoch = step, iteration = 0) in the sampler's layout
+    (csrc/phnn_sampling.h).  -> (len(gids), 4)."""
+    g = np.asarray(gids, dtype=np.int64).reshape(-1)
+    if np.any(g < 0) or np.any(g >= 1 << 48) or j not in (0, 1):
+        raise ValueError("plant_normals: 0 <= gid < 2^48, j in (0, 1)")
+    g = g.astype(np.uint64)
+    step = np.uint64(int(step) & 0xFFFFFFFF)  # the int32 step's bit pattern
+    ctr = np.stack([g & _MASK, g >> _32, np.full_like(g, step), np.full_like(g, (1 << 6) | j)], axis=-1)
+    o = philox4x32_10(ctr, (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF))
+    z = np.empty(o.shape, np.float64)
+    z[:, 0], z[:, 1] = _box_muller(o[:, 0], o[:, 1])
+    z[:, 2], z[:, 3] = _box_muller(o[:, 2], o[:, 3])
+    return z
