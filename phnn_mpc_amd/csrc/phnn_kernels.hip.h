@@ -47,6 +47,15 @@ struct Lane {
   int w;        // split-tile kernels: which quarter of every hidden vector this wave owns (tiles 2w, 2w+1); else 0
   float* xch;   // split-tile kernels: LDS exchange area of the workgroup; else null
 };
+DEV Lane make_lane(int wave_in_tile = 0) {  // of this thread; xch: the split-tile set-up (tile_ctx) points it
+  Lane ln;
+  ln.lane = threadIdx.x & 63;
+  ln.i = ln.lane & 15;
+  ln.q = ln.lane >> 4;
+  ln.w = wave_in_tile;
+  ln.xch = nullptr;
+  return ln;
+}
 
 template <int T>
 struct Act {
@@ -1398,6 +1407,21 @@ DEV void hnet_tape_load(const float* stash, int oC, Lane ln, HTape<HID>& tp, Cur
   else load_act<T>(stash + T * 256, ln, tp.q1);
 }
 
+// Power-of-two normalisation of the operand of a linear chain that runs on f16x2 products: e with mx * 2^-e in [0.5, 1),
+// so that scaling by 2^-e and undoing it by 2^e at the end are both exact; e = 0 (no scaling) for mx = 0, inf or NaN.
+DEV int pow2_exponent(float mx) {
+  int e = 0;
+  (void)__builtin_frexpf(mx, &e);
+  return (mx > 0.f && mx < 3.0e38f) ? e : 0;
+}
+DEV f32x4 pow2_normalise(f32x4 v, float& unscale) {  // max|v_i| into [0.5, 1); unscale = the power of two that undoes it
+  float mx = fmaxf(fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])));
+  const int e = pow2_exponent(mx);
+  v = v * __builtin_ldexpf(1.0f, -e);
+  unscale = __builtin_ldexpf(1.0f, e);
+  return v;
+}
+
 // Hv = (d^2 H / dz^2) v : forward-over-reverse through the kept tape (a1, a2, q1).  Consumes the tape
 // (q1 is overwritten) to keep the live register set at five activation vectors.
 // cv != null (f16x2 Tanh, no weight-gradient record): the q1 term comes as the curvature block, tp.q1 is not touched;
@@ -1412,14 +1436,7 @@ DEV f32x4 hnet_hvp(const float* L, Lane ln, HTape<HID>& tp, f32x4 v, float* rec 
   using Y = LayH2<HID, MM>;
   constexpr int T = Y::T;
   float unscale = 1.0f;
-  if (MM == MM_F16X2) {  // Hv is linear in v: bring max|v_i| into [0.5,1) by a power of two (exact), undo at the end
-    float mx = fmaxf(fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])));
-    int e = 0;
-    (void)__builtin_frexpf(mx, &e);
-    e = (mx > 0.f && mx < 3.0e38f) ? e : 0;
-    v = v * __builtin_ldexpf(1.0f, -e);
-    unscale = __builtin_ldexpf(1.0f, e);
-  }
+  if (MM == MM_F16X2) v = pow2_normalise(v, unscale);  // Hv is linear in v: normalise (exact), undo at the end
   Act<T> ad1, w;
   zero_act<T>(ad1);
   in_layer_mm<T, MM, SITE>(ad1, L, Y::oW1f, Y::oW1h, ln, v);
@@ -1545,9 +1562,7 @@ DEV void h1_bwd_operands(const float* L, Lane ln, const float (&obar)[16], f16x8
   float mx = 0.f;
 #pragma unroll
   for (int k = 0; k < 16; ++k) mx = fmaxf(mx, __builtin_fabsf(obar[k]));
-  int e = 0;
-  (void)__builtin_frexpf(mx, &e);
-  e = (mx > 0.f && mx < 3.0e38f) ? e : 0;
+  const int e = pow2_exponent(mx);
   const float sc = __builtin_ldexpf(1.0f, -e);
   unscale = __builtin_ldexpf(1.0f, e) * L[Y::oSc];
   const bool second = (ln.q & 1) != 0, lo_half = ln.q >= 2;
@@ -1835,7 +1850,7 @@ struct PhnnModel {
       } else {
         h1_fwd<HID, MM, INH & kInHNet1Adj, ACT>(L + oR, scr, ln, x, hR, rf);
       }
-      sym_from_rf<N>(rf, S);
+      sym_from_rf<N>(rf, S);  // (down to rbar_from: as in PhnnSplit::vjp; a shared helper changes kernels at their register limit)
 #pragma unroll
       for (int k = 0; k < N; ++k) {
         float a = 0.f, c = 0.f;
@@ -1878,7 +1893,7 @@ struct PhnnModel {
         }
       xb += h1_bwd<HID, MM, WG && RECHB, ACT>(L + oGn, ln, hG, gbar, WG && RECHB ? rec + 5 * Rec::VEC : nullptr);
     }
-    // v = A^T lam, A = Jeff - S S^T
+    // v = A^T lam, A = Jeff - S S^T  (the same lines as in PhnnSplit::vjp)
     f32x4 v = splat4(0.f);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -1891,7 +1906,7 @@ struct PhnnModel {
     }
     if (WG && ln.q == 0) {
       f32x4* sm = reinterpret_cast<f32x4*>(rec + Rec::oSmall + ln.i * kRecSmall);
-      sm[0] = x;
+      sm[0] = x;  // (rows 0-3, 8, 9: as in the two branches of CanonModel::vjp)
       sm[1] = v;
       sm[2] = lam;
       sm[3] = dH;
@@ -2038,6 +2053,29 @@ struct CanonModel {
   // f16x2 Tanh (CURV): compact MPC tape a2 (T x 256), dH (64), C (256), as PhnnModel's without rf
   static constexpr int oTapeC = T * 256 + 64, TAPE_C = oTapeC + 256;
 
+  // Forward algebra of the cart-pole mass matrix M(q) = [[a, b cos q1], [b cos q1, c]] around the H-net; CanonSplit calls it too
+  struct CartZ { float a, b, c, sn, bc; f32x4 z; };  // z = (q, M(q) qdot), and what f's tail and the adjoint reuse
+  DEV static CartZ cart_z(const float* L, f32x4 y) {
+    CartZ r;
+    r.a = L[oC + 0], r.b = L[oC + 1], r.c = L[oC + 2];
+    float cs;
+    sincos_dev(y[1], r.sn, cs);
+    r.bc = r.b * cs;
+    r.z = f32x4{y[0], y[1], r.a * y[2] + r.bc * y[3], r.bc * y[2] + r.c * y[3]};
+    return r;
+  }
+  // f = (M^-1 p, dp) from dH; the determinant carries the reference's 1e-6
+  DEV static f32x4 cart_f_tail(const float* L, const CartZ& cz, f32x4 dH, f32x4 u) {
+    const float a = cz.a, c = cz.c, bc = cz.bc;
+    const f32x4 z = cz.z;
+    float dp0 = (-dH[0] - L[oC + 6] * dH[2]) + Base_Gu(L, 2, u);
+    float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
+    float det = (a * c - bc * bc) + 1e-6f;
+    float mi00 = c / det, mi01 = -bc / det, mi11 = a / det;
+    return f32x4{mi00 * z[2] + mi01 * z[3], mi01 * z[2] + mi11 * z[3], mi00 * dp0 + mi01 * dp1,
+                 mi01 * dp0 + mi11 * dp1};
+  }
+
   template <bool WANT_H, int TK = TAPE_NONE, int FE = 0>  // FE: per-pair epilogue sites (kFuse*)
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, float& Hval, float* stash = nullptr) {
     constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC && CURV;
@@ -2054,20 +2092,11 @@ struct CanonModel {
       float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
       return f32x4{w[0] * z[2] + w[1] * z[3], w[1] * z[2] + w[2] * z[3], w[0] * dp0 + w[1] * dp1, w[1] * dp0 + w[2] * dp1};
     }
-    float a = L[oC + 0], b = L[oC + 1], c = L[oC + 2];
-    float sn, cs;
-    sincos_dev(y[1], sn, cs);
-    float bc = b * cs;
-    f32x4 z = {y[0], y[1], a * y[2] + bc * y[3], bc * y[2] + c * y[3]};
+    const CartZ cz = cart_z(L, y);
     HTape<HID> tp;
-    f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT, FE>(L + oH, ln, z, tp, Hval);
+    f32x4 dH = hnet_grad<HID, WANT_H, MM, kInHFwd, ACT, FE>(L + oH, ln, cz.z, tp, Hval);
     if (ST) hnet_tape_store<HID, CT>(stash, oTapeC, L + oP, ln, tp, dH);
-    float dp0 = (-dH[0] - L[oC + 6] * dH[2]) + Base_Gu(L, 2, u);
-    float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
-    float det = (a * c - bc * bc) + 1e-6f;
-    float mi00 = c / det, mi01 = -bc / det, mi11 = a / det;
-    return f32x4{mi00 * z[2] + mi01 * z[3], mi01 * z[2] + mi11 * z[3], mi00 * dp0 + mi01 * dp1,
-                 mi01 * dp0 + mi11 * dp1};
+    return cart_f_tail(L, cz, dH, u);
   }
 
   static constexpr int NBIG = 4;
@@ -2092,7 +2121,7 @@ struct CanonModel {
       HTape<HID> tp;
       float Hdummy;
       f32x4 dH;
-      if (ST) {
+      if (ST) {  // (H-net state for the adjoint, tape or recompute: the same lines as in the cart-pole branch below)
         dH = tape_load_dH<T, CQ>(stash, ln);  // needed first: requested first
         hnet_tape_load<HID, CQ>(stash, oTapeC, ln, tp, cv);
         hnet_layer1<HID, MM, ACT>(L + oH, ln, z, tp.a1);
@@ -2114,7 +2143,7 @@ struct CanonModel {
         }
         if (ln.q == 0) {
           f32x4* sm = reinterpret_cast<f32x4*>(rec + Rec::oSmall + ln.i * kRecSmall);
-          sm[0] = z;
+          sm[0] = z;  // (rows 0-3, 8, 9: as in the cart-pole branch below and in PhnnModel::vjp)
           sm[1] = v;
           sm[2] = lam;
           sm[3] = dH;
@@ -2154,6 +2183,7 @@ struct CanonModel {
       }
       return;
     }
+    // (z as cart_z, the rest as CanonSplit::vjp: helpers shared with it change kernels at their register limit, some spill)
     float a = L[oC + 0], b = L[oC + 1], c = L[oC + 2];
     float sn, cs;
     sincos_dev(y[1], sn, cs);
@@ -2162,7 +2192,7 @@ struct CanonModel {
     HTape<HID> tp;
     float Hdummy;
     f32x4 dH;
-    if (ST) {
+    if (ST) {  // (H-net state for the adjoint, tape or recompute: the same lines as in the MassMatrixNetwork branch above)
       dH = tape_load_dH<T, CQ>(stash, ln);  // needed first: requested first
       hnet_tape_load<HID, CQ>(stash, oTapeC, ln, tp, cv);
       hnet_layer1<HID, MM, ACT>(L + oH, ln, z, tp.a1);
@@ -2190,7 +2220,7 @@ struct CanonModel {
       }
       if (ln.q == 0) {
         f32x4* sm = reinterpret_cast<f32x4*>(rec + Rec::oSmall + ln.i * kRecSmall);
-        sm[0] = z;
+        sm[0] = z;  // (rows 0-3, 8, 9: as in the MassMatrixNetwork branch above and in PhnnModel::vjp)
         sm[1] = v;
         sm[2] = lam;
         sm[3] = dH;
@@ -2389,13 +2419,8 @@ DEV f32x4 hnet_grad_w(const float* L, Lane ln, f32x4 z, HTapeW& tp, PreBarrier p
 DEV f32x4 hnet_hvp_w(const float* L, Lane ln, HTapeW& tp, f32x4 v, float& scale, float& unscale, f32x4& vn) {
   using Y = LayH2<128, MM_F16X2>;
   const int t0 = 2 * ln.w;
-  float mx = fmaxf(fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])));
-  int e = 0;
-  (void)__builtin_frexpf(mx, &e);
-  e = (mx > 0.f && mx < 3.0e38f) ? e : 0;
-  v = v * __builtin_ldexpf(1.0f, -e);
+  v = pow2_normalise(v, unscale);
   vn = v;
-  unscale = __builtin_ldexpf(1.0f, e);
   ActW ad1, w;
   zero_act<2>(ad1);
   in_layer_mm<2, MM_F16X2, kInHHvp>(ad1, L, Y::oW1f, Y::oW1h, ln, v, t0);
@@ -2487,7 +2512,7 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     if (CT) curv_put_w(L + Base::oP, ln, tp);
     float rf[16];
     rnet_out(L, scr, ln, rf, ST ? stash + (CT ? Base::oTapeRf : Base::oStashRf) : nullptr);
-    if (ST) {
+    if (ST) {  // (tape write of a split f: the same lines as in CanonSplit::f)
       store_act<2>(stash + 2 * ln.w * 256, ln, tp.a2);
       if (!CT) store_act<2>(stash + T * 256 + 2 * ln.w * 256, ln, tp.q1);
     }
@@ -2532,7 +2557,7 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
       dH = xch_sum_partials(ln.xch + kXP0, ln);
       spread_curv(curv_get_w(L + Base::oP, ln), ln, cv);
     }
-    float S[N][N], Stl[N], StdH[N];
+    float S[N][N], Stl[N], StdH[N];  // (down to rbar_from: as in PhnnModel::vjp)
     sym_from_rf<N>(rf, S);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -2570,7 +2595,7 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     ubar = splat4(0.f);
 #pragma unroll
     for (int i = 0; i < N; ++i) ubar[0] = __builtin_fmaf(L[oG + i], lam[i], ubar[0]);
-    f32x4 v = splat4(0.f);
+    f32x4 v = splat4(0.f);  // v = A^T lam: the same lines as in PhnnModel::vjp
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       float acc = 0.f;
@@ -2599,24 +2624,19 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
   static constexpr bool SPLIT = true;
   static constexpr int SCR = 0, IMG = Base::IMG, STASH = Base::STASH, TAPE_C = Base::TAPE_C, oH = Base::oH, oC = Base::oC, MI = 1;
   static constexpr bool CURV = true;
-  DEV static float Base_Gu(const float* L, int row, f32x4 u) { return Base::Base_Gu(L, row, u); }
-  DEV static f32x4 Base_Gt(const float* L, float dpb0, float dpb1) { return Base::Base_Gt(L, dpb0, dpb1); }
+  using CartZ = typename Base::CartZ;  // the per-rollout algebra is the whole-tile model's (Base::cart_*)
 
   template <bool WANT_H, int TK = TAPE_NONE, int FE = 0>  // FE: unused (the marches pass it to every model)
   DEV static f32x4 f(const float* L, float* scr, Lane ln, f32x4 y, f32x4 u, float& Hval, float* stash = nullptr) {
     static_assert(!WANT_H, "the split-tile kernels are rollout kernels");
     constexpr bool ST = TK != TAPE_NONE, CT = TK == TAPE_MPC;  // tape formats: CanonModel
     keep_lds_reads_local();
-    float a = L[oC + 0], b = L[oC + 1], c = L[oC + 2];
-    float sn, cs;
-    sincos_dev(y[1], sn, cs);
-    float bc = b * cs;
-    f32x4 z = {y[0], y[1], a * y[2] + bc * y[3], bc * y[2] + c * y[3]};
+    const CartZ cz = Base::cart_z(L, y);
     HTapeW tp;
-    f32x4 P = hnet_grad_w(L + oH, ln, z, tp, []() {});
+    f32x4 P = hnet_grad_w(L + oH, ln, cz.z, tp, []() {});
     xch_put_partial(ln.xch + kXP0, ln, P);
     if (CT) curv_put_w(L + Base::oP, ln, tp);
-    if (ST) {
+    if (ST) {  // (tape write of a split f: the same lines as in PhnnSplit::f)
       store_act<2>(stash + 2 * ln.w * 256, ln, tp.a2);
       if (!CT) store_act<2>(stash + T * 256 + 2 * ln.w * 256, ln, tp.q1);
     }
@@ -2624,12 +2644,7 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
     f32x4 dH = xch_sum_partials(ln.xch + kXP0, ln);
     if (ST && ln.q == 0 && ln.w == 0) PHNN_NT_STORE(dH, reinterpret_cast<f32x4*>(stash + (CT ? 1 : 2) * T * 256) + ln.i);
     if (CT) store_rf(stash + Base::oTapeC, ln, curv_get_w(L + Base::oP, ln));  // wave 0 writes
-    float dp0 = (-dH[0] - L[oC + 6] * dH[2]) + Base_Gu(L, 2, u);
-    float dp1 = (-dH[1] - L[oC + 7] * dH[3]) + Base_Gu(L, 3, u);
-    float det = (a * c - bc * bc) + 1e-6f;
-    float mi00 = c / det, mi01 = -bc / det, mi11 = a / det;
-    return f32x4{mi00 * z[2] + mi01 * z[3], mi01 * z[2] + mi11 * z[3], mi00 * dp0 + mi01 * dp1,
-                 mi01 * dp0 + mi11 * dp1};
+    return Base::cart_f_tail(L, cz, dH, u);
   }
 
   template <bool ST = false, bool WG = false, int INH = -1, int FE = 0>  // INH: mask on the f16 input-layer sites (in_layer_mm); FE: as f
@@ -2638,11 +2653,9 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
     static_assert(!WG, "weight-gradient records come from the whole-tile kernels");
     keep_lds_reads_local();
     const int t0 = 2 * ln.w;
-    float a = L[oC + 0], b = L[oC + 1], c = L[oC + 2];
-    float sn, cs;
-    sincos_dev(y[1], sn, cs);
-    float bc = b * cs;
-    f32x4 z = {y[0], y[1], a * y[2] + bc * y[3], bc * y[2] + c * y[3]};
+    const CartZ cz = Base::cart_z(L, y);
+    const float a = cz.a, b = cz.b, c = cz.c, sn = cz.sn, bc = cz.bc;
+    const f32x4 z = cz.z;
     HTapeW tp;
     Curv cv;
     f32x4 dH;
@@ -2662,9 +2675,9 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
       dH = xch_sum_partials(ln.xch + kXP0, ln);
       spread_curv(curv_get_w(L + Base::oP, ln), ln, cv);
     }
-    float Rd2 = L[oC + 6], Rd3 = L[oC + 7];
-    float dp0 = (-dH[0] - Rd2 * dH[2]) + Base_Gu(L, 2, u);
-    float dp1 = (-dH[1] - Rd3 * dH[3]) + Base_Gu(L, 3, u);
+    float Rd2 = L[oC + 6], Rd3 = L[oC + 7];  // (from here, but for the H-net call: as the cart-pole branch of CanonModel::vjp)
+    float dp0 = (-dH[0] - Rd2 * dH[2]) + Base::Base_Gu(L, 2, u);
+    float dp1 = (-dH[1] - Rd3 * dH[3]) + Base::Base_Gu(L, 3, u);
     float det = (a * c - bc * bc) + 1e-6f;
     float rdet = 1.0f / det;
     float mi00 = c * rdet, mi01 = -bc * rdet, mi11 = a * rdet;
@@ -2674,7 +2687,7 @@ struct CanonSplit {  // CanonModel<128, f16x2> with the tile split over four wav
     float mb01 = lam[0] * z[3] + lam[1] * z[2] + lam[2] * dp1 + lam[3] * dp0;
     float mb11 = lam[1] * z[3] + lam[3] * dp1;
     f32x4 v = {-dpb0, -dpb1, -Rd2 * dpb0, -Rd3 * dpb1};
-    ubar = Base_Gt(L, dpb0, dpb1);
+    ubar = Base::Base_Gt(L, dpb0, dpb1);
     float scaleH, unscaleH;
     f32x4 vn;
     f32x4 PH = hnet_hvp_w(L + oH, ln, tp, v, scaleH, unscaleH, vn);
@@ -2829,14 +2842,7 @@ struct OdeModel {
       (void)fwd(L, ln, x, u, tp);
     }
     float unscale = 1.0f;
-    if (MM == MM_F16X2) {  // the backward chain is linear in lam: normalise by a power of two (exact)
-      float mx = fmaxf(fmaxf(__builtin_fabsf(lam[0]), __builtin_fabsf(lam[1])), fmaxf(__builtin_fabsf(lam[2]), __builtin_fabsf(lam[3])));
-      int e = 0;
-      (void)__builtin_frexpf(mx, &e);
-      e = (mx > 0.f && mx < 3.0e38f) ? e : 0;
-      lam = lam * __builtin_ldexpf(1.0f, -e);
-      unscale = __builtin_ldexpf(1.0f, e);
-    }
+    if (MM == MM_F16X2) lam = pow2_normalise(lam, unscale);  // the backward chain is linear in lam: normalise (exact)
     Act<T> d, e;
     zero_act<T>(d);
     in_layer<T>(d, L + oW4f, ln, sel4(lam, ln.q));
@@ -3085,10 +3091,7 @@ template <class M>
 DEV bool tile_ctx(TileCtx& c, float* lds, long long B) {  // false: no tile for this wave
   const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   static_prio(wave);
-  c.ln.lane = threadIdx.x & 63;
-  c.ln.i = c.ln.lane & 15;
-  c.ln.q = c.ln.lane >> 4;
-  c.ln.w = M::SPLIT ? wave : 0;
+  c.ln = make_lane(M::SPLIT ? wave : 0);
   c.ln.xch = M::SPLIT ? lds + M::IMG + nwaves * M::SCR : nullptr;
   c.scr = lds + M::IMG + wave * M::SCR;
   c.tile = M::SPLIT ? (long long)blockIdx.x : (long long)blockIdx.x * nwaves + wave;
@@ -3350,14 +3353,9 @@ __global__ __launch_bounds__(64 * kMaxWaves) void k_model_forward(PointParams p)
   constexpr int N = M::N;
   stage_image<M::IMG>(lds, p.img);
   const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  Lane ln;
-  ln.lane = threadIdx.x & 63;
-  ln.i = ln.lane & 15;
-  ln.q = ln.lane >> 4;
-  ln.w = 0;
-  ln.xch = nullptr;
+  const Lane ln = make_lane();
   float* scr = lds + M::IMG + wave * M::SCR;
-  const long long ntiles = (p.B + kTileB - 1) / kTileB;
+  const long long ntiles = (p.B + kTileB - 1) / kTileB;  // (the loop head below: the same in both point kernels)
   for (long long tile = (long long)blockIdx.x * nwaves + wave; tile < ntiles; tile += (long long)gridDim.x * nwaves) {
     long long b = tile * kTileB + ln.i;
     const bool valid = b < p.B;
@@ -3378,14 +3376,9 @@ __global__ __launch_bounds__(64 * kMaxWaves) void k_model_vjp(PointParams p) {
   constexpr int N = M::N;
   stage_image<M::IMG>(lds, p.img);
   const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  Lane ln;
-  ln.lane = threadIdx.x & 63;
-  ln.i = ln.lane & 15;
-  ln.q = ln.lane >> 4;
-  ln.w = 0;
-  ln.xch = nullptr;
+  const Lane ln = make_lane();
   float* scr = lds + M::IMG + wave * M::SCR;
-  const long long ntiles = (p.B + kTileB - 1) / kTileB;
+  const long long ntiles = (p.B + kTileB - 1) / kTileB;  // (the loop head below: the same in both point kernels)
   for (long long tile = (long long)blockIdx.x * nwaves + wave; tile < ntiles; tile += (long long)gridDim.x * nwaves) {
     long long b = tile * kTileB + ln.i;
     const bool valid = b < p.B;
@@ -3645,12 +3638,7 @@ __global__ __launch_bounds__(64 * M::T) void k_wgrad_reduce(WgradParams p) {
   const float* LR = lds + GE::HN - GE::R0;             // LR[LayH1::o...] valid for the staged R_net range
   const float* LG = lds + GE::HN + GE::RN - GE::R0;    // G_net
   const int w = threadIdx.x >> 6;
-  Lane ln;
-  ln.lane = threadIdx.x & 63;
-  ln.i = ln.lane & 15;
-  ln.q = ln.lane >> 4;
-  ln.w = 0;
-  ln.xch = nullptr;
+  const Lane ln = make_lane();
   // Exchange buffers (x2, ping-pong).  The matrix-shaped gradient W2bar = sum_points gdot2* (x) a1 + g2 (x) adot1 is a
   // GEMM with K = points; per record K = 32 (16 rollouts x 2 terms), one v_mfma_f32_16x16x32_bf16 k-depth.  The
   // factors go through LDS as three bf16 pieces each (x = hi + mid + lo to 2^-24; bf16 keeps the f32 exponent range,

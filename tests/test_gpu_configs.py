@@ -333,44 +333,56 @@ def test_full_size_bitwise_repeatable(torch, name):
     eng.use_stash = True
 
 
-@pytest.mark.parametrize("name", ["phnn_cartpole", "canonical_cartpole"])
+SPLIT_N2 = "phnn<n=2,hid=128,fixedG,f16x2>"  # PhnnSplit<2>: no fixture of its own, seeded weights from the census builder
+
+
+@pytest.mark.parametrize("name", ["phnn_cartpole", "canonical_cartpole", SPLIT_N2])
 def test_split_tile_kernels_bitwise_equal_whole_tile(torch, name):
     """Small batches run on the split-tile kernels (four waves per 16-rollout tile).  They keep every
     summation order of the whole-tile kernels, so costs, trajectories and gradients must be BITWISE identical --
     Euler with and without the activation stash, RK4, ragged batch sizes; and the automatic choice must pick them
-    for small batches only."""
+    for small batches only.  The n = 2 model runs B = 1 (one lane) and B = 17 (a full tile and one ragged lane), H = 3."""
     from phnn_mpc_amd.engine import RolloutEngine
-    g, w = ol.load_golden("phnn_cartpole"), ol.load_weights(name)
-    whole, split, auto = RolloutEngine(w, split="never"), RolloutEngine(w, split="always"), RolloutEngine(w)
+    rng = np.random.default_rng(33)
+    if name == SPLIT_N2:
+        import variant_census as vc
+        s = vc.CENSUS[name]
+        w, kw, dt, cost = vc.build_state_dict(name, s), vc.engine_kwargs(s), vc.dt_of(s), vc.cost_of(s, rng)
+        shapes = ((1, 3), (17, 3))
+    else:
+        w, kw, dt, cost = ol.load_weights(name), {}, 0.02, ol.cost_from_golden(ol.load_golden("phnn_cartpole"))
+        shapes = ((1, 20), (17, 25), (300, 31))
+    whole, split, auto = RolloutEngine(w, split="never", **kw), RolloutEngine(w, split="always", **kw), RolloutEngine(w, **kw)
     assert auto.kernel_info(4096)["rollouts_per_workgroup"] == 16 and auto.kernel_info(65536)["rollouts_per_workgroup"] == 128
     assert whole.kernel_info(4096)["rollouts_per_workgroup"] > 0 and split.kernel_info(64)["rollouts_per_workgroup"] == 16
-    rng = np.random.default_rng(33)
-    cost = ol.cost_from_golden(g)
-    for B, H in ((1, 20), (17, 25), (300, 31)):
-        x0 = (rng.uniform(-1, 1, size=(B, 4)) * [1.0, 0.3, 0.5, 0.5]).astype(np.float32)
-        U = rng.uniform(-17, 17, size=(B, H, 1)).astype(np.float32)
+    for B, H in shapes:
+        if name == SPLIT_N2:
+            x0, U = vc.states(rng, s["n"], B), vc.controls(rng, B, H, s["m"])
+        else:
+            x0 = (rng.uniform(-1, 1, size=(B, 4)) * [1.0, 0.3, 0.5, 0.5]).astype(np.float32)
+            U = rng.uniform(-17, 17, size=(B, H, 1)).astype(np.float32)
         for integ in ("euler", "rk4"):
             for stash in (True, False):
                 res = []
                 for eng in (whole, split):
                     eng.use_stash = stash
-                    c, gu, gx = eng.rollout_cost_grad(x0, U, cost, integ, 0.02, want_grad_x0=True)
-                    _, tr = eng.rollout_cost(x0, U, cost, integ, 0.02, want_traj=True)
-                    traj, dX = eng.rollout_trajectory(x0, U, integ, 0.02, want_dx=True)
+                    c, gu, gx = eng.rollout_cost_grad(x0, U, cost, integ, dt, want_grad_x0=True)
+                    _, tr = eng.rollout_cost(x0, U, cost, integ, dt, want_traj=True)
+                    traj, dX = eng.rollout_trajectory(x0, U, integ, dt, want_dx=True)
                     res.append([t.clone() for t in (c, gu, gx, tr, traj, dX)])
                     eng.use_stash = True
                 for a, b, what in zip(res[0], res[1], ("cost", "grad_u", "grad_x0", "traj", "train traj", "dX")):
                     assert torch.equal(a, b), (name, B, H, integ, stash, what, float((a - b).abs().max()))
-    # mixed: K1 by one kernel family, K2 by the other, through the shared stash format
+    # mixed: K1 by one kernel family, K2 by the other, through the shared stash format (the last shape of the loop above)
     import ctypes as C
-    B, H = 300, 31
+    (B, H), n = shapes[-1], x0.shape[1]
     x0t, Ut = torch.tensor(x0, device="cuda"), torch.tensor(U, device="cuda")
     out = {}
     for k1, k2 in ((whole, split), (split, whole), (whole, whole)):
-        traj = torch.empty(B, H + 1, 4, device="cuda"); cst = torch.empty(B, device="cuda"); gu = torch.empty(B, H, 1, device="cuda")
+        traj = torch.empty(B, H + 1, n, device="cuda"); cst = torch.empty(B, device="cuda"); gu = torch.empty(B, H, 1, device="cuda")
         st = torch.empty(k1.workspace_bytes(B, H, 0), dtype=torch.uint8, device="cuda")
-        k1.lib.phnn_rollout_fwd(k1.h, k1._p(x0t), k1._p(Ut), B, H, C.byref(cost), 0, 0.02, k1._p(cst), k1._p(traj), k1._p(st), k1._stream())
-        k2.lib.phnn_rollout_grad(k2.h, k2._p(x0t), k2._p(Ut), B, H, C.byref(cost), 0, 0.02, k2._p(traj), k2._p(st), k2._p(gu), None, k2._stream())
+        k1.lib.phnn_rollout_fwd(k1.h, k1._p(x0t), k1._p(Ut), B, H, C.byref(cost), 0, dt, k1._p(cst), k1._p(traj), k1._p(st), k1._stream())
+        k2.lib.phnn_rollout_grad(k2.h, k2._p(x0t), k2._p(Ut), B, H, C.byref(cost), 0, dt, k2._p(traj), k2._p(st), k2._p(gu), None, k2._stream())
         out[(k1 is split, k2 is split)] = gu.clone()
     assert torch.equal(out[(False, True)], out[(False, False)]) and torch.equal(out[(True, False)], out[(False, False)])
 

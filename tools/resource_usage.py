@@ -7,11 +7,12 @@ import sys
 
 csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "phnn_mpc_amd", "csrc")
 out = ""
-for src, extra in (("phnn_mpc.hip", []), ("phnn_grad.hip", []), ("phnn_wgrad.hip", []), ("phnn_split.hip", []),
-                   ("phnn_lbfgs.hip", []), ("phnn_sampling.hip", [])):  # as the Makefile
+# every translation unit of the Makefile's link rule, with the Makefile's flags
+rule = re.search(r"^libphnn_mpc\.so:(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M)
+for src in [w[:-2] + ".hip" for w in rule.group(1).split() if w.endswith(".o")]:
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
-           "--cuda-device-only", "-c", "-o", "/dev/null", src, "-Rpass-analysis=kernel-resource-usage"] + extra
+           "--cuda-device-only", "-c", "-o", "/dev/null", src, "-Rpass-analysis=kernel-resource-usage"]
     cmd += sys.argv[1:]
     out += subprocess.run(cmd, cwd=csrc, capture_output=True, text=True).stderr
 rows, cur = [], {}
