@@ -650,6 +650,52 @@ int phnn_plant_step_ex(phnn_handle* h, const phnn_plant* plant, const phnn_plant
 int phnn_shift_controls(phnn_handle* h, const float* src_dev, float* dst_dev, int64_t B, int32_t H, int32_t m,
                         int32_t* step_dev, void* stream);
 
+/* ---- linearisation and time-varying LQR gains ----------------------------------------------------
+ * The local model  delta x_{t+1} = A_t delta x_t + B_t delta u_t  of a rollout, and the LQ backward pass on it.
+ * All three calls are stream-ordered and capturable, allocate nothing and do not synchronise; B == 0 returns PHNN_OK
+ * with nothing launched; H >= 1.  PHNN_ERR_INVALID_ARG, nothing launched and no output touched: NULL required buffers,
+ * B < 0, H < 1, an unknown integrator, a non-finite dt, u_min > u_max with has_u_bounds, a negative or non-finite mu, a
+ * non-zero reserved.  Buffer contract as at the top of this file: sizes are exact, inputs are never written, outputs
+ * are fully written for b < B and nothing else is touched.  For n = 4, A_dev and traj_dev (and x_dev of the point
+ * Jacobian) are tensors of state rows and must be 16-byte aligned; Bm_dev, u_dev and the float64 tensors are accessed
+ * by element.
+ *
+ * Point Jacobian: x_dev (B,n), u_dev (B,m) -> A[b,i,j] = d f_i / d x_j, Bm[b,i,k] = d f_i / d u_k at (x_b, u_b).
+ * Row i is, bit for bit, what the single-call VJP above returns for the cotangent e_i (one launch instead of n, the
+ * inputs not replicated). */
+int phnn_model_jacobian(phnn_handle* h, const float* x_dev, const float* u_dev, int64_t B,
+                        float* A_dev /* (B,n,n) */, float* Bm_dev /* (B,n,m) */, void* stream);
+
+/* A[b,t] = d x_{t+1} / d x_t, Bm[b,t] = d x_{t+1} / d u_t (unclamped u) of the integrator step K1 takes at
+ * (traj[b,t], u[b,t]).  cost: read for has_u_bounds / u_min / u_max only; NULL = no clamp.  With bounds, column k of
+ * Bm[b,t] is 0 where u[b,t,k] lies outside [u_min, u_max] or is NaN (the adjoint's mask).
+ * traj_dev: the states K1 wrote, (B,H+1,n) (rows 0 .. H-1 are read).  u_dev (B,H,m).
+ * Row i is, bit for bit, grad_x0 / grad_u of the general reverse pass above on the one-step rollout from traj[b,t] with
+ * traj_bar = (0, e_i) and cost_bar = 0 (the step adjoint of K2 in recompute mode, operation for operation). */
+int phnn_rollout_linearize(phnn_handle* h, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                           int32_t integrator, float dt, const float* traj_dev,
+                           float* A_dev /* (B,H,n,n) */, float* Bm_dev /* (B,H,n,m) */, void* stream);
+
+/* LQ backward pass (Riccati recursion) per problem, float64 without fused multiply-adds, for the stage cost x^T Q x
+ * (also at t = H) + u^T R u of `cost` (Q, R only; target, bounds and barrier do not enter):
+ *   Lxx = Q + Q^T, Luu = R + R^T (widened first), P_H = Lxx; for t = H-1 .. 0:  S = P A_t, T = P B_t,
+ *   Qxx = Lxx + A^T S, Qux = B^T S, Quu = Luu + B^T T + mu I (lower triangle read), Quu = L D L^T without square roots,
+ *   X = Quu^-1 Qux, K_t = -X, P_t = Qxx - Qux^T X, symmetrised as 0.5 (P + P^T).
+ * Every inner product runs with its index ascending from an accumulator 0, each product rounded, then added;
+ * tests/tvlqr_model.py states the remaining order and the kernel equals it bit for bit.  The feedback law is
+ * delta u_t = K_t delta x_t.
+ * Failure: a pivot d with !(d > 0) or d = +inf.  On the first failure, going backwards, at step t: K_s and P_s for every
+ * s <= t (P0 included) are quiet NaN, status[b] = t + 1, the steps after t keep their values; else status[b] = 0.  A NaN
+ * in A_t or B_t reaches a pivot one step further down (B_t: the same step) and is reported this way; a NaN in A_0 can
+ * only show as NaN in K_0 and P0.  A diverged problem is NaN plus a status, never a finite wrong gain.
+ * A_dev (B,H,n,n), Bm_dev (B,H,n,m) float32 -> K_dev (B,H,m,n), P0_dev (B,n,n), status_dev (B) int32 and, when not
+ * NULL, P_all_dev (B,H+1,n,n) = P_0 .. P_H. */
+typedef struct { double mu; int32_t reserved[4]; } phnn_tvlqr_options;   /* mu >= 0, finite; NULL = {0} */
+int phnn_tvlqr(phnn_handle* h, const float* A_dev, const float* Bm_dev, int64_t B, int32_t H,
+               const phnn_cost* cost, const phnn_tvlqr_options* opt,
+               double* K_dev /* (B,H,m,n) */, double* P0_dev /* (B,n,n) */,
+               double* P_all_dev /* (B,H+1,n,n) or NULL */, int32_t* status_dev /* (B) */, void* stream);
+
 /* Introspection for tests: copies the packed weight image the kernels stage into LDS (phnn_kernels.hip.h layouts; a
  * device-resident private format) to image_host after the work queued on `stream`, and waits for the copy.
  * *image_floats (may be NULL) receives its size; image_host == NULL only queries the size. */

@@ -35,7 +35,7 @@ EXPORTED = [
     "phnn_solve_lbfgs", "phnn_mppi_workspace_bytes", "phnn_mppi_sample", "phnn_mppi_update", "phnn_solve_mppi",
     "phnn_cem_workspace_bytes", "phnn_cem_sample", "phnn_cem_update", "phnn_solve_cem",
     "phnn_mppi_sample_shaped", "phnn_cem_sample_shaped", "phnn_solve_mppi_shaped", "phnn_solve_cem_shaped",
-    "phnn_plant_step_ex",
+    "phnn_plant_step_ex", "phnn_model_jacobian", "phnn_rollout_linearize", "phnn_tvlqr",
 ]
 
 
@@ -96,6 +96,11 @@ class NoiseShape(C.Structure):
     """phnn_noise_shape: the (rows = H, cols = P) float32 row-major device matrix L that turns the white normals of a
     sampling solve into time-correlated ones, z[t, c] = sum_s L[t, s] eps[s, c] (phnn_mpc_amd/noise.py builds them)."""
     _fields_ = [("L_dev", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class TvlqrOptions(C.Structure):
+    """phnn_tvlqr_options: mu >= 0 is added to the diagonal of Quu (a Levenberg-Marquardt style regularisation)."""
+    _fields_ = [("mu", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
 class Plant(C.Structure):
@@ -225,6 +230,12 @@ def load_library():
     lib.phnn_model_forward.restype = C.c_int
     lib.phnn_model_vjp.argtypes = [vp, f32p, f32p, f32p, i64, f32p, f32p, vp]
     lib.phnn_model_vjp.restype = C.c_int
+    lib.phnn_model_jacobian.argtypes = [vp, f32p, f32p, i64, f32p, f32p, vp]
+    lib.phnn_model_jacobian.restype = C.c_int
+    lib.phnn_rollout_linearize.argtypes = [vp, f32p, i64, i32, C.POINTER(Cost), i32, C.c_float, f32p, f32p, f32p, vp]
+    lib.phnn_rollout_linearize.restype = C.c_int
+    lib.phnn_tvlqr.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(TvlqrOptions), vp, vp, vp, vp, vp]
+    lib.phnn_tvlqr.restype = C.c_int
     lib.phnn_rollout_fwd.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), i32, C.c_float, f32p, f32p, vp, vp]
     lib.phnn_rollout_fwd.restype = C.c_int
     lib.phnn_workspace_bytes.argtypes = [vp, i64, i32, i32]

@@ -3405,6 +3405,313 @@ __global__ __launch_bounds__(64 * kMaxWaves) void k_model_vjp(PointParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Linearisation: the local model delta x+ = A delta x + B delta u of the dynamics at points
+// (k_model_jacobian) and of the integrator step along a stored trajectory (k_rollout_linearize), row by row from unit
+// cotangents through M::vjp -- the arithmetic of k_model_vjp and of grad_march in recompute mode, operation for
+// operation, so that row i is bit for bit what those kernels return for the cotangent e_i.  Point kernels: 16 points
+// per wave, the tile loop of k_model_vjp, padding lanes clamped to the last point and never written.  Instantiated in
+// phnn_lin.hip.
+// ------------------------------------------------------------------------------------------------
+struct LinParams {
+  const float* img;
+  const float* x;   // jacobian: (P,N) points; linearize: traj (B,H+1,N), point p = b*H + t reads row b*(H+1) + t
+  const float* u;   // (P,MI)
+  float* A;         // (P,N,N)
+  float* Bm;        // (P,N,MI)
+  long long P;      // points (linearize: B*H)
+  int H;            // linearize: steps per rollout
+  float dt, half_dt, sixth_dt;
+  phnn_cost c;      // linearize: has_u_bounds / u_min / u_max
+};
+
+template <int N>
+DEV f32x4 unit_cotangent(int i) {
+  f32x4 e = splat4(0.f);
+#pragma unroll
+  for (int r = 0; r < N; ++r) e[r] = r == i ? 1.0f : 0.0f;
+  return e;
+}
+
+template <class M>
+__global__ __launch_bounds__(64 * kMaxWaves) void k_model_jacobian(LinParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int N = M::N, MI = M::MI;
+  stage_image<M::IMG>(lds, p.img);
+  const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const Lane ln = make_lane();
+  float* scr = lds + M::IMG + wave * M::SCR;
+  const long long ntiles = (p.P + kTileB - 1) / kTileB;
+  for (long long tile = (long long)blockIdx.x * nwaves + wave; tile < ntiles; tile += (long long)gridDim.x * nwaves) {
+    long long b = tile * kTileB + ln.i;
+    const bool valid = b < p.P;
+    if (!valid) b = p.P - 1;
+#pragma unroll 1
+    for (int i = 0; i < N; ++i) {
+      // (x and u are re-read per row -- L2 hits -- instead of riding through vjp, where registers are full)
+      const f32x4 x = load_state<N>(p.x + b * N);
+      const f32x4 u = load_u<MI>(p.u + b * MI, 0);
+      f32x4 xb, ub;
+      M::template vjp<false, false, 0>(lds, scr, ln, x, u, unit_cotangent<N>(i), xb, ub);  // f32 input layers, as k_model_vjp
+      if (valid && ln.q == 0) {
+        store_state<N>(p.A + (b * N + i) * N, xb);
+#pragma unroll
+        for (int k = 0; k < MI; ++k) p.Bm[(b * N + i) * MI + k] = ub[k];
+      }
+    }
+  }
+}
+
+template <class M, int INTEG>
+__global__ __launch_bounds__(64 * kMaxWaves) void k_rollout_linearize(LinParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int N = M::N, MI = M::MI;
+  stage_image<M::IMG>(lds, p.img);
+  const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const Lane ln = make_lane();
+  float* scr = lds + M::IMG + wave * M::SCR;
+  const float* L = lds;
+  const long long ntiles = (p.P + kTileB - 1) / kTileB;
+  for (long long tile = (long long)blockIdx.x * nwaves + wave; tile < ntiles; tile += (long long)gridDim.x * nwaves) {
+    long long pt = tile * kTileB + ln.i;
+    const bool valid = pt < p.P;
+    if (!valid) pt = p.P - 1;
+    const long long b = pt / p.H;
+    const float* xr = p.x + (pt + b) * N;  // row b*(H+1) + t, t = pt - b*H
+    const float* up = p.u + pt * MI;
+    [[maybe_unused]] f32x4 y2, y3, y4;
+    if constexpr (INTEG != PHNN_INTEG_EULER) {  // the stage states of grad_march's recompute mode: the same for every row
+      const f32x4 x = load_state<N>(xr);
+      const f32x4 u = clamp_u4<MI>(p.c, load_u<MI>(up, 0));
+      y2 = x, y3 = x, y4 = x;
+      f32x4 y = x;
+      float Hd;
+#pragma unroll 1
+      for (int s = 0; s < 3; ++s) {
+        const f32x4 k = M::template f<false>(L, scr, ln, y, u, Hd);
+        y = x + (s == 2 ? p.dt : p.half_dt) * k;
+        y2 = s == 0 ? y : y2;
+        y3 = s == 1 ? y : y3;
+        y4 = s == 2 ? y : y4;
+      }
+    }
+#pragma unroll 1
+    for (int i = 0; i < N; ++i) {
+      const f32x4 lam = unit_cotangent<N>(i);  // the cotangent on x_{t+1}
+      f32x4 row, utot, ub;
+      if constexpr (INTEG == PHNN_INTEG_EULER) {
+        const f32x4 x = load_state<N>(xr);
+        const f32x4 u = clamp_u4<MI>(p.c, load_u<MI>(up, 0));
+        f32x4 xb;
+        M::template vjp<false, false, -1, kFuseEpi<M, INTEG, false, false, kFuseK2Act | kFuseK2Red>>(
+            L, scr, ln, x, u, p.dt * lam + splat4(0.f), xb, ub, nullptr);
+        row = lam + xb;
+        utot = ub;
+      } else {
+        f32x4 ysum = splat4(0.f), ybn = ysum;
+        utot = splat4(0.f);
+#pragma unroll 1
+        for (int s = 3; s >= 0; --s) {
+          const f32x4 y = s == 0 ? load_state<N>(xr) : (s == 1 ? y2 : (s == 2 ? y3 : y4));
+          const f32x4 us = clamp_u4<MI>(p.c, load_u<MI>(up, 0));
+          f32x4 in = ((s == 0 || s == 3) ? p.sixth_dt : 2.0f * p.sixth_dt) * lam;
+          if (s != 3) in = in + (s == 2 ? p.dt : p.half_dt) * ybn;
+          f32x4 yb;
+          M::template vjp<false>(L, scr, ln, y, us, in, yb, ub, nullptr);
+          utot = s == 3 ? ub : utot + ub;
+          ybn = yb;
+          ysum = s == 3 ? yb : ysum + yb;  // ((yb4 + yb3) + yb2) + yb1
+        }
+        row = lam + ysum;
+      }
+      if (valid && ln.q == 0) {
+        store_state<N>(p.A + (pt * N + i) * N, row);
+        const f32x4 uraw = load_u<MI>(up, 0);
+#pragma unroll
+        for (int k = 0; k < MI; ++k) {
+          float g = utot[k];
+          if (p.c.has_u_bounds && !(uraw[k] >= p.c.u_min && uraw[k] <= p.c.u_max)) g = 0.f;  // the adjoint's mask: NaN -> 0
+          p.Bm[(pt * N + i) * MI + k] = g;
+        }
+      }
+    }
+  }
+}
+
+// TV-LQR backward pass (tests/tvlqr_model.py states the operation order): one thread per problem,
+// float64 in registers, every product rounded before it is added (the units are built with -ffp-contract=off).
+struct TvlqrParams {
+  const float* A;   // (B,H,N,N)
+  const float* Bm;  // (B,H,N,MI)
+  double* K;        // (B,H,MI,N)
+  double* P0;       // (B,N,N)
+  double* P_all;    // (B,H+1,N,N) or null
+  int* status;      // (B)
+  long long B;
+  int H;
+  double mu;
+  double Lxx[16], Luu[16];  // Q + Q^T (N x N), R + R^T (MI x MI), row-major, formed on the host in float64
+};
+
+template <int N, int MI>
+__global__ __launch_bounds__(64) void k_tvlqr(TvlqrParams p) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= p.B) return;
+  const float* Ab = p.A + b * p.H * (N * N);
+  const float* Bb = p.Bm + b * p.H * (N * MI);
+  double* Kb = p.K + b * p.H * (MI * N);
+  double* Pa = p.P_all ? p.P_all + b * (p.H + 1) * (N * N) : nullptr;
+  double P[N][N];
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      P[i][j] = p.Lxx[i * N + j];
+      if (Pa) Pa[(long long)p.H * (N * N) + i * N + j] = P[i][j];
+    }
+  int t = p.H - 1;
+  for (; t >= 0; --t) {
+    double A[N][N], Bt[N][MI];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) A[i][j] = (double)Ab[(long long)t * (N * N) + i * N + j];
+#pragma unroll
+      for (int j = 0; j < MI; ++j) Bt[i][j] = (double)Bb[(long long)t * (N * MI) + i * MI + j];
+    }
+    double S[N][N], T[N][MI];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) a = a + P[i][k] * A[k][j];
+        S[i][j] = a;
+      }
+#pragma unroll
+      for (int j = 0; j < MI; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) a = a + P[i][k] * Bt[k][j];
+        T[i][j] = a;
+      }
+    }
+    double Qxx[N][N], Qux[MI][N], Quu[MI][MI];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) a = a + A[k][i] * S[k][j];
+        Qxx[i][j] = p.Lxx[i * N + j] + a;
+      }
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) a = a + Bt[k][i] * S[k][j];
+        Qux[i][j] = a;
+      }
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {  // lower triangle only
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) a = a + Bt[k][i] * T[k][j];
+        double q = p.Luu[i * MI + j] + a;
+        if (i == j) q = q + p.mu;
+        Quu[i][j] = q;
+      }
+    }
+    // Quu = L D L^T, no square roots
+    double Lf[MI][MI], D[MI];
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < MI; ++j) {
+      double w[MI];
+      double d = Quu[j][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) {
+        w[k] = Lf[j][k] * D[k];
+        d = d - Lf[j][k] * w[k];
+      }
+      D[j] = d;
+      if (!(d > 0.0) || d == __builtin_inf()) bad = true;
+#pragma unroll
+      for (int i = j + 1; i < MI; ++i) {
+        double s = Quu[i][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) s = s - Lf[i][k] * w[k];
+        Lf[i][j] = s / d;
+      }
+    }
+    if (bad) break;
+    double X[MI][N];
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      double y[MI];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        double s = Qux[i][c];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = s - Lf[i][k] * y[k];
+        y[i] = s;
+      }
+#pragma unroll
+      for (int i = 0; i < MI; ++i) y[i] = y[i] / D[i];
+#pragma unroll
+      for (int i = MI - 1; i >= 0; --i) {
+        double s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < MI; ++k) s = s - Lf[k][i] * X[k][c];
+        X[i][c] = s;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < N; ++j) Kb[(long long)t * (MI * N) + i * N + j] = -X[i][j];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < MI; ++k) a = a + Qux[k][i] * X[k][j];
+        S[i][j] = Qxx[i][j] - a;
+      }
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int j = i; j < N; ++j) {
+        const double s = 0.5 * (S[i][j] + S[j][i]);
+        P[i][j] = s;
+        P[j][i] = s;
+      }
+    if (Pa) {
+#pragma unroll
+      for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j < N; ++j) Pa[(long long)t * (N * N) + i * N + j] = P[i][j];
+    }
+  }
+  // the first failure, going backwards, at step t: K_s, P_s for s <= t are quiet NaN, status = t + 1 (0: none)
+  p.status[b] = t + 1;
+  const double qnan = __builtin_nan("");
+  for (int s = t; s >= 0; --s) {
+    for (int e = 0; e < MI * N; ++e) Kb[(long long)s * (MI * N) + e] = qnan;
+    if (Pa)
+      for (int e = 0; e < N * N; ++e) Pa[(long long)s * (N * N) + e] = qnan;
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) p.P0[b * (N * N) + i * N + j] = t >= 0 ? qnan : P[i][j];
+}
+
+// ------------------------------------------------------------------------------------------------
 // Weight-gradient reduction (training side): records -> d loss / d theta.
 //
 // Each gradient is a sum over evaluation points of outer products of per-point vectors (oracle/phnn_oracle.c

@@ -421,6 +421,7 @@ struct phnn_handle {
   bool has_wgrad = false;
   SplitSet sp{};       // split-tile kernels for small batches (has_split)
   bool has_split = false;
+  LinSet lin{};        // linearisation kernels (every variant has them)
   int* d_unpad = nullptr;   // index map original blob -> padded blob (k_wgrad_finish)
   int* d_padsrc = nullptr;  // index map padded blob -> original blob, -1 = padding (phnn_update_weights_dev)
   float* d_pblob = nullptr;  // scratch of the device-side packer: the padded blob
@@ -571,7 +572,7 @@ hipError_t upload_image(phnn_handle* h, const std::vector<float>& img) {
 
 extern "C" {
 
-int phnn_version(void) { return 260; }
+int phnn_version(void) { return 270; }
 
 const char* phnn_variant_name(const phnn_handle* h) { return h ? h->ks.name : ""; }
 
@@ -637,6 +638,7 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
   kernel_set(v, &h->ks);
   h->has_wgrad = phnn_wgrad_kernels(v, &h->wg);
   h->has_split = phnn_split_kernels(v, &h->sp);
+  if (!phnn_lin_kernels(v, &h->lin)) return fail(nullptr, PHNN_ERR_UNSUPPORTED, "no linearisation kernels for this kernel variant");
   hipDeviceProp_t prop;
   e = hipGetDeviceProperties(&prop, device);
   h->n_cu = (e == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
@@ -650,6 +652,7 @@ int phnn_create_ex(const phnn_desc* desc, const float* weights_host, size_t n_fl
   h->ks.each_kernel(allow_big_lds);  // (the first call on a unit's kernel loads the unit's code object: this order)
   if (h->has_split) h->sp.each_kernel(allow_big_lds);
   if (h->has_wgrad) h->wg.each_kernel(allow_big_lds);
+  h->lin.each_kernel(allow_big_lds);
   if (h->has_split && (size_t)h->sp.lds_floats * sizeof(float) > kMaxLdsBytes) h->has_split = false;
   if (e != hipSuccess) return hip_fail(nullptr, e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
   e = hipMalloc(reinterpret_cast<void**>(&h->d_img), sizeof(float) * img.size());
@@ -1598,6 +1601,91 @@ int phnn_shift_controls(phnn_handle* h, const float* src_dev, float* dst_dev, in
   const long long count = std::max<long long>((long long)B * H * m, 1);
   return checked(h, "shift launch", k_shift_controls, flat_grid(count), dim3(kFlatThreads), 0, (hipStream_t)stream, src_dev,
                  dst_dev, (long long)B, (int)H, (int)m, step_dev);
+}
+
+// ---- linearisation and TV-LQR gains ---------------------------------------------------------------
+int phnn_model_jacobian(phnn_handle* h, const float* x_dev, const float* u_dev, int64_t B, float* A_dev, float* Bm_dev,
+                        void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
+  if (B == 0) return PHNN_OK;
+  if (!x_dev || !u_dev || !A_dev || !Bm_dev) return fail(h, PHNN_ERR_INVALID_ARG, "NULL tensor");
+  PHNN_ON_DEVICE(h);
+  LinParams p{};
+  p.img = h->d_img;
+  p.x = x_dev;
+  p.u = u_dev;
+  p.A = A_dev;
+  p.Bm = Bm_dev;
+  p.P = (long long)B;
+  p.H = 1;
+  return launch(h, h->lin.jac, p, tiles_of(B), true, (hipStream_t)stream);
+}
+
+int phnn_rollout_linearize(phnn_handle* h, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                           int32_t integrator, float dt, const float* traj_dev, float* A_dev, float* Bm_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
+  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
+  if (cost)
+    if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!u_dev || !traj_dev || !A_dev || !Bm_dev) return fail(h, PHNN_ERR_INVALID_ARG, "NULL tensor");
+  PHNN_ON_DEVICE(h);
+  LinParams p{};
+  p.img = h->d_img;
+  p.x = traj_dev;
+  p.u = u_dev;
+  p.A = A_dev;
+  p.Bm = Bm_dev;
+  p.P = (long long)B * H;
+  p.H = H;
+  const double dtd = (double)dt;  // as fill_roll forms them
+  p.dt = dt;
+  p.half_dt = (float)(dtd / 2);
+  p.sixth_dt = (float)(dtd / 6.0);
+  if (cost) {  // the clamp only
+    p.c.has_u_bounds = cost->has_u_bounds;
+    p.c.u_min = cost->u_min;
+    p.c.u_max = cost->u_max;
+  }
+  return launch(h, h->lin.lin[integrator], p, tiles_of(p.P), true, (hipStream_t)stream);
+}
+
+int phnn_tvlqr(phnn_handle* h, const float* A_dev, const float* Bm_dev, int64_t B, int32_t H, const phnn_cost* cost,
+               const phnn_tvlqr_options* opt, double* K_dev, double* P0_dev, double* P_all_dev, int32_t* status_dev,
+               void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (!cost) return fail(h, PHNN_ERR_INVALID_ARG, "cost is NULL");
+  phnn_tvlqr_options o{};
+  if (opt) o = *opt;
+  if (!(o.mu >= 0.0) || !std::isfinite(o.mu)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_tvlqr_options: mu is negative or not finite");
+  for (int r : o.reserved)
+    if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_tvlqr_options: reserved must be zero");
+  if (B == 0) return PHNN_OK;
+  if (!A_dev || !Bm_dev || !K_dev || !P0_dev || !status_dev) return fail(h, PHNN_ERR_INVALID_ARG, "NULL tensor");
+  PHNN_ON_DEVICE(h);
+  const int n = h->desc.n, m = h->desc.m;
+  TvlqrParams p{};
+  p.A = A_dev;
+  p.Bm = Bm_dev;
+  p.K = K_dev;
+  p.P0 = P0_dev;
+  p.P_all = P_all_dev;
+  p.status = status_dev;
+  p.B = (long long)B;
+  p.H = H;
+  p.mu = o.mu;
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) p.Lxx[i * n + j] = (double)cost->Q[i * n + j] + (double)cost->Q[j * n + i];
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) p.Luu[i * m + j] = (double)cost->R[i * m + j] + (double)cost->R[j * m + i];
+  const hipError_t e = phnn_tvlqr_launch(n, m, p, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue && (n < 2 || n > 4 || m < 1 || m > 4))
+    return fail(h, PHNN_ERR_UNSUPPORTED, "no TV-LQR kernel for this (n, m)");
+  return checked(h, e, "kernel launch (tvlqr)");
 }
 
 int phnn_read_image(phnn_handle* h, float* image_host, size_t n_floats, size_t* image_floats, void* stream) {

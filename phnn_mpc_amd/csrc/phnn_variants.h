@@ -243,7 +243,24 @@ bool phnn_wgrad_kernels(int variant, WgradSet* g);  // false: no weight-gradient
 hipError_t phnn_wgrad_finish(const float* slab, int rows, int PP, const int* map, int P, float* out, int accumulate,
                              hipStream_t stream);
 
-#define PHNN_FOR_EACH_VARIANT(X)                                                                                       \
+// Linearisation kernels, defined in phnn_lin.hip for every variant: the point Jacobian and the
+// step Jacobians along a trajectory (Euler, RK4).
+using LinKernel = void (*)(LinParams);
+struct LinSet {
+  LinKernel jac;
+  LinKernel lin[2];
+  template <class F>
+  void each_kernel(F f) const {
+    f(kernel_ptr(jac));
+    for (LinKernel k : lin) f(kernel_ptr(k));
+  }
+};
+static_assert(sizeof(LinSet) == set_bytes(1 + 2, 0), "LinSet::each_kernel visits every kernel?");
+bool phnn_lin_kernels(int variant, LinSet* g);
+// launches k_tvlqr<n, m> (phnn_lin.hip), one thread per problem; hipErrorInvalidValue: no kernel for (n, m)
+hipError_t phnn_tvlqr_launch(int n, int m, const TvlqrParams& p, hipStream_t stream);
+
+#define PHNN_FOR_EACH_VARIANT(X)                                                                                      \
   X(V_PHNN_4_128_FIX, M_PHNN_4_128_FIX, "phnn<n=4,hid=128,fixedG>") \
   X(V_PHNN_4_64_FIX, M_PHNN_4_64_FIX, "phnn<n=4,hid=64,fixedG>") \
   X(V_PHNN_2_64_GNET, M_PHNN_2_64_GNET, "phnn<n=2,hid=64,Gnet>") \

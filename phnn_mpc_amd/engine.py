@@ -303,6 +303,60 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return gu, gx
 
+    # ------------------------------------------------------------------ linearisation, TV-LQR gains
+    def jacobian(self, x, u):
+        """Point Jacobians of the dynamics: x (B,n), u (B,m) -> A (B,n,n) = df/dx, Bm (B,n,m) = df/du, one launch.
+        Row i equals vjp(x, u, e_i) bit for bit."""
+        x = self._t(x, (-1, self.n))
+        u = self._t(u, (-1, self.m))
+        B = x.shape[0]
+        A = torch.empty(B, self.n, self.n, dtype=torch.float32, device=self.device)
+        Bm = torch.empty(B, self.n, self.m, dtype=torch.float32, device=self.device)
+        _check(self.lib, self.h, self.lib.phnn_model_jacobian(self.h, self._p(x), self._p(u), B, self._p(A), self._p(Bm),
+                                                              self._stream()))
+        return A, Bm
+
+    def rollout_linearize(self, x0, u, cost, integrator="euler", dt=0.02, traj=None):
+        """The local model of a rollout: A (B,H,n,n) = d x_{t+1} / d x_t and Bm (B,H,n,m) = d x_{t+1} / d u_t (unclamped
+        u; a column is 0 where the cost's bounds clamp that control) of the integrator step at (traj[b,t], u[b,t]).
+        traj (B,H+1,n): the states K1 wrote for (x0, u); None runs K1 here.  cost None: no clamp (needs traj).
+        -> (A, Bm, traj)."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u, H = self._controls(u, B)
+        integ = self._integ(integrator)
+        if traj is None:
+            if cost is None:
+                raise ValueError("rollout_linearize: without a cost the trajectory must be given")
+            _, traj = self.rollout_cost(x0, u, cost, integ, dt, want_traj=True)
+        else:
+            traj = self._t(traj, (B, H + 1, self.n))
+        A = torch.empty(B, H, self.n, self.n, dtype=torch.float32, device=self.device)
+        Bm = torch.empty(B, H, self.n, self.m, dtype=torch.float32, device=self.device)
+        rc = self.lib.phnn_rollout_linearize(self.h, self._p(u), B, H, C.byref(cost) if cost is not None else None, integ,
+                                             float(dt), self._p(traj), self._p(A), self._p(Bm), self._stream())
+        _check(self.lib, self.h, rc)
+        return A, Bm, traj
+
+    def tvlqr(self, A, Bm, cost, mu=0.0, want_P=False):
+        """LQ backward pass on (A (B,H,n,n), Bm (B,H,n,m)) with the cost's Q and R, float64: -> dict(K (B,H,m,n) with
+        delta u_t = K_t delta x_t, P0 (B,n,n) the cost-to-go at t = 0, P (B,H+1,n,n) or None, status (B) int32: 0, or
+        t + 1 where the recursion failed at step t (K_s, P_s for s <= t are NaN then))."""
+        A = self._t(A)
+        B, H = A.shape[0], A.shape[1]
+        A = A.reshape(B, H, self.n, self.n)
+        Bm = self._t(Bm, (B, H, self.n, self.m))
+        d = dict(dtype=torch.float64, device=self.device)
+        K, P0 = torch.empty(B, H, self.m, self.n, **d), torch.empty(B, self.n, self.n, **d)
+        P = torch.empty(B, H + 1, self.n, self.n, **d) if want_P else None
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        opt = _capi.TvlqrOptions()
+        opt.mu = float(mu)
+        rc = self.lib.phnn_tvlqr(self.h, self._p(A), self._p(Bm), B, H, C.byref(cost), C.byref(opt), self._p(K), self._p(P0),
+                                 self._p(P), self._p(status), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(K=K, P0=P0, P=P, status=status)
+
     # ------------------------------------------------------------------ training side: parameter gradients (row f4)
     @property
     def has_wgrad(self):

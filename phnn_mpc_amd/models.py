@@ -243,6 +243,12 @@ class _EngineBacked(nn.Module):
         self.refresh_engine()
         return r
 
+    def jacobian(self, x, u):
+        """Jacobians of the dynamics at points, on the engine: x (B,n), u (B,m) -> (A (B,n,n) = df/dx, Bm (B,n,m) =
+        df/du) in one launch (RolloutEngine.jacobian).  No autograd graph is recorded."""
+        with torch.no_grad():
+            return self.engine.jacobian(self._flatten(x), self._flatten(u))
+
     def _check_supported(self):
         for name, mod in self.named_modules():
             if isinstance(mod, MassMatrixNetwork) and mod.activation_name != "Tanh":

@@ -85,6 +85,22 @@ class MPCController:
         _, traj = eng.rollout_cost(x0d, ud, self._cost_noclamp(), self.integrator, self.dt, want_traj=True)
         return traj[0].cpu()
 
+    def feedback_gains(self, x0, u_seq, mu=0.0):
+        """Time-varying LQR gains around the planned trajectory: x0 (B,n) or (n,), u_seq (B,H,1) or (H,1) -> dict(K
+        (B,H,1,n), P0 (B,n,n), P (B,H+1,n,n), status (B), traj (B,H+1,n), A, Bm), all on the engine's device.  The
+        nominal trajectory x^nominal = traj is this controller's rollout of u_seq (its cost, integrator and dt), and the
+        law is  delta u_t = K_t (x_t - x_t^nominal),  to be added to u_seq[t] before the clamp.  Three launches: K1 ->
+        linearise -> tvlqr.  status[b] != 0: the recursion failed for problem b (its early gains are NaN); mu > 0
+        regularises Quu."""
+        eng = self.engine
+        x0 = torch.as_tensor(x0, dtype=torch.float32).reshape(-1, self.state_dim)
+        u = torch.as_tensor(u_seq, dtype=torch.float32).reshape(x0.shape[0], -1, 1)
+        cost = self._cost()
+        A, Bm, traj = eng.rollout_linearize(x0, u, cost, self.integrator, self.dt)
+        out = eng.tvlqr(A, Bm, cost, mu=mu, want_P=True)
+        out.update(traj=traj, A=A, Bm=Bm)
+        return out
+
     def compute_cost(self, states, controls):
         """Quadratic cost (+ barrier) of a given trajectory (src/mpc_controller.py:75-114); host arithmetic on
         (H+1,n)/(H,1) tensors -- the kernels fuse the same sum into the march."""

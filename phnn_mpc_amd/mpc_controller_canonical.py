@@ -89,6 +89,22 @@ class MPCControllerCanonical:
         _, traj = eng.rollout_cost(x0d, ud, self._cost(clamp=False), self.integrator, self.dt, want_traj=True)
         return traj[0].cpu()
 
+    def feedback_gains(self, x0, u_seq, mu=0.0):
+        """Time-varying LQR gains around the planned trajectory: x0 (B,n) or (n,), u_seq (B,H,m) or (H,m) -> dict(K
+        (B,H,m,n), P0 (B,n,n), P (B,H+1,n,n), status (B), traj (B,H+1,n), A, Bm), all on the engine's device.  The
+        nominal trajectory x^nominal = traj is this controller's rollout of u_seq (its cost, integrator and dt), and the
+        law is  delta u_t = K_t (x_t - x_t^nominal),  to be added to u_seq[t] before the clamp.  Three launches: K1 ->
+        linearise -> tvlqr.  status[b] != 0: the recursion failed for problem b (its early gains are NaN); mu > 0
+        regularises Quu."""
+        eng = self.engine
+        x0 = torch.as_tensor(x0, dtype=torch.float32).reshape(-1, self.state_dim)
+        u = torch.as_tensor(u_seq, dtype=torch.float32).reshape(x0.shape[0], -1, self.input_dim)
+        cost = self._cost()
+        A, Bm, traj = eng.rollout_linearize(x0, u, cost, self.integrator, self.dt)
+        out = eng.tvlqr(A, Bm, cost, mu=mu, want_P=True)
+        out.update(traj=traj, A=A, Bm=Bm)
+        return out
+
     def optimize_control(self, x0, u_init=None):
         """x0 (n,), u_init (H,m) or None -> (u_opt (H,m) tensor, info)   (src/mpc_controller_canonical.py:163-228)"""
         x0 = torch.as_tensor(x0, dtype=torch.float32).reshape(1, -1)
