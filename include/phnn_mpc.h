@@ -696,6 +696,86 @@ int phnn_tvlqr(phnn_handle* h, const float* A_dev, const float* Bm_dev, int64_t 
                double* K_dev /* (B,H,m,n) */, double* P0_dev /* (B,n,n) */,
                double* P_all_dev /* (B,H+1,n,n) or NULL */, int32_t* status_dev /* (B) */, void* stream);
 
+/* ---- batched Gauss-Newton solve on the linearisation and the LQ pass --------------------------------
+ * Projected Gauss-Newton shooting with Levenberg-Marquardt regularisation and a parallel backtracking line search, per
+ * problem b of B independent ones.  State: the iterate u_b (H,m), kept inside the cost's bounds, its cost_b and
+ * trajectory traj_b (H+1,n), and mu_b (float64).  Set-up: u <- clamp(u) when has_u_bounds (a NaN stays NaN),
+ * mu_b <- mu_init, accepts_b <- 0, one K1 gives cost_b and traj_b.  Then `iters` times, five launches:
+ *   1 linearise   phnn_rollout_linearize(u, traj) -> A (B,H,n,n), Bm (B,H,n,m), with the cost's bounds
+ *   2 direction   k_gn_direction<n,m>: float64, no fused multiply-adds, one thread per problem, (n, m) in {2,3,4} x
+ *                 {1,2,3,4}.  With e_t = x_t - r_t (r: x_target or the reference row) and act_t,i = 1 where the barrier
+ *                 of component i is active at x_t (x_min_i - x > 0 or x - x_max_i > 0):
+ *                   Lxx_t = (Q+Q^T) + diag(2 w act_t),  lx_t = (Q+Q^T) e_t - 2w (x_min - x) [below] + 2w (x - x_max) [above],
+ *                   lu_t = (R+R^T) u_t,  Luu = R+R^T;   P_H = Lxx_H, p_H = lx_H;  for t = H-1 .. 0:
+ *                   S, T, Qxx (with Lxx_t), Qux, Quu = Luu + B^T T + mu_b I and its L D L^T exactly as phnn_tvlqr forms them,
+ *                   qx = lx_t + A^T p, qu = lu_t + B^T p, X = Quu^-1 Qux, d = Quu^-1 qu (the same factors), K_t = -X,
+ *                   k_t = -d, P_t as in phnn_tvlqr (symmetrised), p_t = qx - Qux^T d, dV_b += qu^T d;
+ *                 then forward on the linear model: dx_0 = 0, du_t = k_t + K_t dx_t, dx_{t+1} = A_t dx_t + B_t du_t.
+ *                 -> du (B,H,m) float32 (the float64 value rounded once), dV (B) float64 (>= 0 in exact arithmetic; the
+ *                 predicted change of the cost at step length 1 is -dV/2 and its slope at 0 is -dV), status (B) int32
+ *                 with phnn_tvlqr's rule: t + 1 at the first pivot with !(d > 0) or +inf, else 0.  Where status != 0, or
+ *                 dV_b or an element of du_b is not finite, du_b is all zeros and dV_b quiet NaN: never a finite wrong
+ *                 step.  u is read as given (the solve keeps it in bounds).  tests/gn_model.py states the order.
+ *   3 candidates  k_gn_candidates: v_{b,j} = clamp(u_b + alpha_j du_b), alpha_j = 2^-j, j = 0 .. L-1 (float32, the product
+ *                 rounded, then the sum; the library's NaN-preserving clamp) -> cand (B*L,H,m), row b*L + j; and x0
+ *                 replicated -> x0_rep (B*L,n)
+ *   4 evaluate    ONE K1 launch over the B*L candidates with their trajectories (no K2, no stash)
+ *   5 select      k_gn_select: j* = the lowest finite candidate cost (as floats, lowest j on ties).  Accept iff
+ *                 status_b == 0 and S_{b,j*} < cost_b (strict): u_b, traj_b, cost_b take candidate j*'s row, trajectory
+ *                 and cost, mu_b <- max(mu_min, mu_b mu_down), accepts_b += 1.  Else u_b, traj_b, cost_b keep their bits
+ *                 and mu_b <- min(mu_max, mu_b mu_up).  costs_row[b] = cost_b BEFORE the update, alpha_row[b] =
+ *                 alpha_{j*} or 0 on reject.
+ * cost_b is therefore non-increasing bit for bit; a diverged problem shows as NaN or status plus rejections.  Not part
+ * of this solve: a closed-loop forward pass inside K1 (true iLQR), a box-QP at the bounds (a control on a bound that is
+ * pushed outwards loses that component to the clamp and the line search decides), early termination per problem.
+ * All calls are stream-ordered and capturable, allocate nothing and do not synchronise; inputs are never written. */
+typedef struct {
+  int32_t iters;      /* >= 0 */
+  int32_t line_steps; /* L, 1 .. 32 */
+  double mu_init;     /* the mu fields: >= 0 and finite, mu_min <= mu_max */
+  double mu_min;
+  double mu_max;
+  double mu_up;       /* >= 1, finite */
+  double mu_down;     /* in (0, 1] */
+  int32_t reserved[4]; /* zero */
+} phnn_gn_options;
+/* Bytes of the workspace of phnn_solve_gn: A, Bm, traj_b, du, dV, status, the direction's scratch, the candidates,
+ * their x0, costs and trajectories, each region 256-byte aligned.  0 for invalid arguments (B < 0, H < 1, L outside
+ * 1 .. 32, a model without a direction kernel); non-decreasing in B, H and line_steps. */
+size_t phnn_gn_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t line_steps);
+/* The three kernels, as phnn_mppi_sample / phnn_mppi_update stand next to their solve.  B == 0: PHNN_OK, nothing
+ * launched.  ref: NULL = the cost's x_target, else problem b's reference (batch_stride indexes PROBLEMS here).
+ * scratch_dev: B*H*(m*n + m) float64, private layout.  mu_dev (B) float64 is read only. */
+int phnn_gn_direction(phnn_handle* h, const float* A_dev, const float* Bm_dev, const float* traj_dev, const float* u_dev,
+                      int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref, const double* mu_dev,
+                      float* du_dev /* (B,H,m) */, double* dV_dev /* (B) */, int32_t* status_dev /* (B) */,
+                      double* scratch_dev, void* stream);
+int phnn_gn_candidates(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* du_dev, int64_t B, int32_t H,
+                       const phnn_cost* cost, int32_t line_steps, float* cand_dev /* (B*L,H,m) */,
+                       float* x0_rep_dev /* (B*L,n) or NULL */, void* stream);
+/* In place on u_dev (B,H,m), traj_dev (B,H+1,n), cost_dev (B), mu_dev (B) float64, accepts_dev (B) int32 from the
+ * candidates cand_dev (B*L,H,m), their K1 costs cand_cost_dev (B*L) and trajectories cand_traj_dev (B*L,H+1,n) and the
+ * direction's status_dev (B); costs_row_dev (B) / alpha_row_dev (B) float32 or NULL.  opt: line_steps and the mu fields
+ * are read (iters and mu_init are checked like the rest). */
+int phnn_gn_select(phnn_handle* h, float* u_dev, float* traj_dev, float* cost_dev, double* mu_dev, int32_t* accepts_dev,
+                   const float* cand_dev, const float* cand_cost_dev, const float* cand_traj_dev, const int32_t* status_dev,
+                   int64_t B, int32_t H, const phnn_gn_options* opt, float* costs_row_dev, float* alpha_row_dev, void* stream);
+/* The whole solve.  u_dev (B,H,m): in = initial iterate, out = the last one (in bounds).  cost_out (B) float32: its
+ * cost; mu_out (B) float64: the last mu; accepts_dev (B) int32: accepted iterations -- all three required, they are the
+ * solve's state and are defined after the set-up also when iters == 0.  costs_dev (iters,B) or NULL: the cost of the
+ * iterate at the START of every iteration; alpha_hist_dev (iters,B) float32 or NULL: the accepted step length, 0 on
+ * reject.  workspace: workspace_size >= phnn_gn_workspace_bytes, required when B > 0.  ref: as in phnn_solve_mppi -- its
+ * batch_stride indexes the B*L ROLLOUTS (rollout b*L + j belongs to problem b); the set-up K1 and the direction address
+ * problem b as rollout b*L, i.e. with stride batch_stride * L; offset_dev is read by every launch, the direction
+ * included.  B == 0: PHNN_OK, nothing launched.  PHNN_ERR_INVALID_ARG, nothing launched: NULL required buffers, a too
+ * small workspace, line_steps outside 1 .. 32, iters < 0, a non-finite or negative mu field, mu_min > mu_max, mu_up < 1,
+ * mu_down outside (0, 1], non-zero reserved, B < 0, H < 1, the reference checks of phnn_solve_mppi;
+ * PHNN_ERR_UNSUPPORTED: no direction kernel for the model's (n, m). */
+int phnn_solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                  const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
+                  size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
+                  float* alpha_hist_dev, void* stream);
+
 /* Introspection for tests: copies the packed weight image the kernels stage into LDS (phnn_kernels.hip.h layouts; a
  * device-resident private format) to image_host after the work queued on `stream`, and waits for the copy.
  * *image_floats (may be NULL) receives its size; image_host == NULL only queries the size. */

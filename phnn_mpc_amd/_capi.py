@@ -36,6 +36,7 @@ EXPORTED = [
     "phnn_cem_workspace_bytes", "phnn_cem_sample", "phnn_cem_update", "phnn_solve_cem",
     "phnn_mppi_sample_shaped", "phnn_cem_sample_shaped", "phnn_solve_mppi_shaped", "phnn_solve_cem_shaped",
     "phnn_plant_step_ex", "phnn_model_jacobian", "phnn_rollout_linearize", "phnn_tvlqr",
+    "phnn_gn_workspace_bytes", "phnn_gn_direction", "phnn_gn_candidates", "phnn_gn_select", "phnn_solve_gn",
 ]
 
 
@@ -101,6 +102,14 @@ class NoiseShape(C.Structure):
 class TvlqrOptions(C.Structure):
     """phnn_tvlqr_options: mu >= 0 is added to the diagonal of Quu (a Levenberg-Marquardt style regularisation)."""
     _fields_ = [("mu", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class GnOptions(C.Structure):
+    """phnn_gn_options: iters Gauss-Newton iterations with line_steps = L candidates u + 2^-j du each; mu is the
+    Levenberg-Marquardt term on Quu: started at mu_init, times mu_down (floor mu_min) after an accepted iteration, times
+    mu_up (cap mu_max) after a rejected one."""
+    _fields_ = [("iters", C.c_int32), ("line_steps", C.c_int32), ("mu_init", C.c_double), ("mu_min", C.c_double),
+                ("mu_max", C.c_double), ("mu_up", C.c_double), ("mu_down", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
 class Plant(C.Structure):
@@ -314,6 +323,19 @@ def load_library():
     lib.phnn_plant_step_ex.restype = C.c_int
     lib.phnn_shift_controls.argtypes = [vp, f32p, f32p, i64, i32, i32, vp, vp]
     lib.phnn_shift_controls.restype = C.c_int
+    gno = C.POINTER(GnOptions)
+    lib.phnn_gn_workspace_bytes.argtypes = [vp, i64, i32, i32]
+    lib.phnn_gn_workspace_bytes.restype = C.c_size_t
+    lib.phnn_gn_direction.argtypes = [vp, f32p, f32p, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), vp, f32p, vp,
+                                      vp, vp, vp]
+    lib.phnn_gn_direction.restype = C.c_int
+    lib.phnn_gn_candidates.argtypes = [vp, f32p, f32p, f32p, i64, i32, C.POINTER(Cost), i32, f32p, f32p, vp]
+    lib.phnn_gn_candidates.restype = C.c_int
+    lib.phnn_gn_select.argtypes = [vp, f32p, f32p, f32p, vp, vp, f32p, f32p, f32p, vp, i64, i32, gno, f32p, f32p, vp]
+    lib.phnn_gn_select.restype = C.c_int
+    lib.phnn_solve_gn.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float, gno, vp,
+                                  C.c_size_t, f32p, f32p, vp, vp, f32p, vp]
+    lib.phnn_solve_gn.restype = C.c_int
     lib.phnn_kernel_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i64]
     lib.phnn_kernel_info.restype = C.c_int
     lib.phnn_variant_name.argtypes = [vp]

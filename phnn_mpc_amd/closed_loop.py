@@ -236,7 +236,9 @@ class DeviceClosedLoop:
     run_mpc_batch (same kernels, same order); the plant differs from the numpy one only by the device's
     double-precision sin/cos.  An MPPI controller (optimizer_type / optimizer 'MPPI'): engine.solve_mppi -- the clamp
     and resets, iters x (k_sample, K1, k_mppi_update) -- with step_dev as the noise epoch, so every replay draws the
-    noise run_mpc_batch draws at that step.  A 'CrossEntropy' controller: engine.solve_cem in the same way.
+    noise run_mpc_batch draws at that step.  A 'CrossEntropy' controller: engine.solve_cem in the same way.  A
+    'GaussNewton' controller: engine.solve_gn -- the clamp, the state reset and the set-up K1, then iters x
+    (k_rollout_linearize, k_gn_direction, k_gn_candidates, K1, k_gn_select) -- in a workspace kept across the steps.
 
     x_ref: reference trajectories broadcastable to (B, rows, 4) (engine.reference_view); every solve tracks them from
     row step_dev, the device counter the plant step logs with and the shift advances, so each replay of the captured
@@ -289,10 +291,15 @@ class DeviceClosedLoop:
             raise NotImplementedError(f"{type(eng).__name__} has no batched {self.sampling.upper()} solve (RolloutEngine has)")
         if self.sampling and x_ref is not None:  # one row set per rollout, expanded once, here (samples x the bytes)
             self.x_ref = eng.mppi_reference(self.x_ref, B, controller.samples)
+        self.gn = (controller.optimizer if self.canonical else controller.optimizer_type) == "GaussNewton"
+        if self.gn and not hasattr(eng, "solve_gn"):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched Gauss-Newton solve (RolloutEngine has)")
+        if self.gn and x_ref is not None:  # one row set per candidate rollout, expanded once, here
+            self.x_ref = eng.mppi_reference(self.x_ref, B, controller.gn_line_steps)
         self.iters = controller.optimizer_steps if self.canonical else controller.max_iterations
         self.lr = controller.learning_rate if self.canonical else controller.lr
         self.lbfgs = not self.canonical and controller.optimizer_type == "LBFGS"
-        if not self.canonical and controller.optimizer_type not in ("Adam", "LBFGS", "MPPI", "CrossEntropy"):
+        if not self.canonical and controller.optimizer_type not in ("Adam", "LBFGS", "MPPI", "CrossEntropy", "GaussNewton"):
             raise ValueError(f"Unknown optimizer type: {controller.optimizer_type}")
         if self.lbfgs and not hasattr(eng, "solve_lbfgs"):
             raise NotImplementedError(f"{type(eng).__name__} has no batched L-BFGS solve (RolloutEngine has)")
@@ -360,6 +367,10 @@ class DeviceClosedLoop:
         H = self.u_init.shape[1] * self.u_init.shape[2]
         if self.sampling:
             out = self._solve_sampling()
+        elif self.gn:  # self.x_ref is already one row set per candidate rollout (or shared)
+            out = eng.solve_gn(self.x32, self.u_init, self.cost, c.integrator, c.dt, record_costs=False, workspace=self.ws,
+                               x_ref=self.x_ref, ref_offset=self.step_dev, expanded_ref=True, **c.gn_options())
+            out["best_u"] = out["u_last"]  # the cost of a problem never rises: the last iterate is the best one
         elif self.lbfgs:  # the reference's L-BFGS solve
             out = eng.solve_lbfgs(self.x32, self.u_init, self.cost, integrator=c.integrator, dt=c.dt, record_costs=False,
                                   workspace=self.ws, x_ref=self.x_ref, ref_offset=self.step_dev, **c.lbfgs_options())

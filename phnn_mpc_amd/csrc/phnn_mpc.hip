@@ -18,6 +18,7 @@
 #define PHNN_PREFETCH_BF
 #include "phnn_lbfgs.h"
 #include "phnn_sampling.h"
+#include "phnn_gn.h"
 #include "phnn_pack.h"
 
 namespace {
@@ -572,7 +573,7 @@ hipError_t upload_image(phnn_handle* h, const std::vector<float>& img) {
 
 extern "C" {
 
-int phnn_version(void) { return 270; }
+int phnn_version(void) { return 280; }
 
 const char* phnn_variant_name(const phnn_handle* h) { return h ? h->ks.name : ""; }
 
@@ -1686,6 +1687,191 @@ int phnn_tvlqr(phnn_handle* h, const float* A_dev, const float* Bm_dev, int64_t 
   if (e == hipErrorInvalidValue && (n < 2 || n > 4 || m < 1 || m > 4))
     return fail(h, PHNN_ERR_UNSUPPORTED, "no TV-LQR kernel for this (n, m)");
   return checked(h, e, "kernel launch (tvlqr)");
+}
+
+// ---- batched Gauss-Newton solve: kernels in phnn_gn.hip -------------------------------------------
+static bool gn_supported(const phnn_handle* h) {
+  return h->desc.n >= 2 && h->desc.n <= 4 && h->desc.m >= 1 && h->desc.m <= 4;
+}
+
+static int check_gn(phnn_handle* h, const phnn_gn_options* o, int64_t B, int32_t H) {
+  if (!o) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_options is NULL");
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (o->line_steps < 1 || o->line_steps > kGnMaxLineSteps)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_options: line_steps outside 1 .. 32");
+  if (o->iters < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_options: iters < 0");
+  for (double v : {o->mu_init, o->mu_min, o->mu_max, o->mu_up, o->mu_down})
+    if (!(v >= 0.0) || !std::isfinite(v))
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_options: a mu field is negative or not finite");
+  if (o->mu_min > o->mu_max) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_options: mu_min > mu_max");
+  if (o->mu_up < 1.0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_options: mu_up < 1");
+  if (!(o->mu_down > 0.0) || o->mu_down > 1.0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_options: mu_down outside (0, 1]");
+  for (int r : o->reserved)
+    if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_options: reserved must be zero");
+  return PHNN_OK;
+}
+
+size_t phnn_gn_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t line_steps) {
+  if (!h || B < 0 || H < 1 || line_steps < 1 || line_steps > kGnMaxLineSteps || !gn_supported(h)) return 0;
+  return std::max<size_t>(gn_layout(B, H, h->desc.n, h->desc.m, line_steps).total, 256);
+}
+
+int phnn_gn_direction(phnn_handle* h, const float* A_dev, const float* Bm_dev, const float* traj_dev, const float* u_dev,
+                      int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref, const double* mu_dev,
+                      float* du_dev, double* dV_dev, int32_t* status_dev, double* scratch_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (int rc = check_cost(h, cost)) return rc;
+  RollParams rp{};  // the reference checks, and its fields, are K1's
+  if (int rc = fill_ref(h, &rp, ref, B)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!A_dev || !Bm_dev || !traj_dev || !u_dev || !mu_dev || !du_dev || !dV_dev || !status_dev || !scratch_dev)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_direction: NULL tensor");
+  if (!gn_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no Gauss-Newton direction kernel for this (n, m)");
+  PHNN_ON_DEVICE(h);
+  const int n = h->desc.n, m = h->desc.m;
+  GnDirectionParams p{};
+  p.A = A_dev;
+  p.Bm = Bm_dev;
+  p.traj = traj_dev;
+  p.u = u_dev;
+  p.mu = mu_dev;
+  p.du = du_dev;
+  p.dV = dV_dev;
+  p.status = status_dev;
+  p.scratch = scratch_dev;
+  p.B = (long long)B;
+  p.H = H;
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) p.Lxx[i * n + j] = (double)cost->Q[i * n + j] + (double)cost->Q[j * n + i];
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) p.Luu[i * m + j] = (double)cost->R[i * m + j] + (double)cost->R[j * m + i];
+  for (int i = 0; i < n; ++i) p.x_target[i] = cost->x_target[i], p.x_min[i] = cost->x_min[i], p.x_max[i] = cost->x_max[i];
+  p.has_x_min = cost->has_x_min;
+  p.has_x_max = cost->has_x_max;
+  p.w2 = 2.0 * (double)cost->barrier_weight;
+  p.x_ref = rp.x_ref;
+  p.ref_bs = rp.ref_bs;
+  p.ref_ts = rp.ref_ts;
+  p.ref_rows = ref ? rp.ref_rows : 1;
+  p.ref_off_dev = rp.ref_off_dev;
+  p.ref_off_host = rp.ref_off_host;
+  return checked(h, gn_direction_launch(n, m, p, (hipStream_t)stream), "k_gn_direction launch");
+}
+
+int phnn_gn_candidates(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* du_dev, int64_t B, int32_t H,
+                       const phnn_cost* cost, int32_t line_steps, float* cand_dev, float* x0_rep_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (line_steps < 1 || line_steps > kGnMaxLineSteps) return fail(h, PHNN_ERR_INVALID_ARG, "line_steps outside 1 .. 32");
+  if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!u_dev || !du_dev || !cand_dev || (x0_rep_dev && !x0_dev)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_candidates: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  GnCandidatesParams p{};
+  p.u = u_dev;
+  p.du = du_dev;
+  p.x0 = x0_dev;
+  p.cand = cand_dev;
+  p.x0_rep = x0_rep_dev;
+  p.B = (long long)B;
+  p.L = line_steps;
+  p.N = H * h->desc.m;
+  p.n = h->desc.n;
+  p.u_min = cost->u_min;
+  p.u_max = cost->u_max;
+  p.has_u_bounds = cost->has_u_bounds;
+  return checked(h, gn_candidates_launch(p, (hipStream_t)stream), "k_gn_candidates launch");
+}
+
+int phnn_gn_select(phnn_handle* h, float* u_dev, float* traj_dev, float* cost_dev, double* mu_dev, int32_t* accepts_dev,
+                   const float* cand_dev, const float* cand_cost_dev, const float* cand_traj_dev, const int32_t* status_dev,
+                   int64_t B, int32_t H, const phnn_gn_options* opt, float* costs_row_dev, float* alpha_row_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_gn(h, opt, B, H)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!u_dev || !traj_dev || !cost_dev || !mu_dev || !accepts_dev || !cand_dev || !cand_cost_dev || !cand_traj_dev || !status_dev)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_select: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  GnSelectParams p{};
+  p.u = u_dev;
+  p.traj = traj_dev;
+  p.cost = cost_dev;
+  p.mu = mu_dev;
+  p.accepts = accepts_dev;
+  p.cand = cand_dev;
+  p.cand_cost = cand_cost_dev;
+  p.cand_traj = cand_traj_dev;
+  p.status = status_dev;
+  p.costs_row = costs_row_dev;
+  p.alpha_row = alpha_row_dev;
+  p.B = (long long)B;
+  p.L = opt->line_steps;
+  p.N = H * h->desc.m;
+  p.T = (H + 1) * h->desc.n;
+  p.mu_min = opt->mu_min;
+  p.mu_max = opt->mu_max;
+  p.mu_up = opt->mu_up;
+  p.mu_down = opt->mu_down;
+  return checked(h, gn_select_launch(p, (hipStream_t)stream), "k_gn_select launch");
+}
+
+int phnn_solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                  const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
+                  size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
+                  float* alpha_hist_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_gn(h, opt, B, H)) return rc;
+  RollParams rp;
+  if (int rc = fill_roll(h, &rp, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
+  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
+  if (int rc = fill_ref(h, &rp, ref, B)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!cost_out || !mu_out || !accepts_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn: cost_out, mu_out and accepts_dev are required");
+  if (!gn_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no Gauss-Newton direction kernel for this (n, m)");
+  const int n = h->desc.n, m = h->desc.m, L = opt->line_steps;
+  const GnLayout lay = gn_layout(B, H, n, m, L);
+  if (!workspace || workspace_size < lay.total) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn: workspace is NULL or too small");
+  // problem b is rollout b * L of the reference
+  phnn_reference pref{};
+  if (ref) {
+    pref = *ref;
+    pref.batch_stride = ref->batch_stride * L;
+  }
+  const phnn_reference* prefp = ref ? &pref : nullptr;
+  char* ws = (char*)workspace;
+  float* A = (float*)(ws + lay.A);
+  float* Bm = (float*)(ws + lay.Bm);
+  float* traj = (float*)(ws + lay.traj);
+  float* du = (float*)(ws + lay.du);
+  double* dV = (double*)(ws + lay.dV);
+  int32_t* status = (int32_t*)(ws + lay.status);
+  double* scratch = (double*)(ws + lay.scratch);
+  float* cand = (float*)(ws + lay.cand);
+  float* x0_rep = (float*)(ws + lay.x0_rep);
+  float* cand_cost = (float*)(ws + lay.cand_cost);
+  float* cand_traj = (float*)(ws + lay.cand_traj);
+  {
+    PHNN_ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    if (cost->has_u_bounds) e = clamp_launch(u_dev, (long long)B * H * m, cost->u_min, cost->u_max, st);
+    if (e == hipSuccess) e = gn_state_launch(mu_out, accepts_dev, (long long)B, opt->mu_init, st);
+    if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_gn: state reset");
+  }
+  if (int rc = rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, cost_out, traj, nullptr, prefp, stream)) return rc;
+  const int64_t rollouts = B * (int64_t)L;
+  for (int it = 0; it < opt->iters; ++it) {
+    if (int rc = phnn_rollout_linearize(h, u_dev, B, H, cost, integrator, dt, traj, A, Bm, stream)) return rc;
+    if (int rc = phnn_gn_direction(h, A, Bm, traj, u_dev, B, H, cost, prefp, mu_out, du, dV, status, scratch, stream)) return rc;
+    if (int rc = phnn_gn_candidates(h, x0_dev, u_dev, du, B, H, cost, L, cand, it == 0 ? x0_rep : nullptr, stream)) return rc;
+    if (int rc = rollout_fwd(h, x0_rep, cand, rollouts, H, cost, integrator, dt, cand_cost, cand_traj, nullptr, ref, stream)) return rc;
+    if (int rc = phnn_gn_select(h, u_dev, traj, cost_out, mu_out, accepts_dev, cand, cand_cost, cand_traj, status, B, H, opt,
+                                costs_dev ? costs_dev + (size_t)it * B : nullptr,
+                                alpha_hist_dev ? alpha_hist_dev + (size_t)it * B : nullptr, stream))
+      return rc;
+  }
+  return PHNN_OK;
 }
 
 int phnn_read_image(phnn_handle* h, float* image_host, size_t n_floats, size_t* image_floats, void* stream) {

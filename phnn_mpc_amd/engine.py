@@ -771,6 +771,116 @@ class RolloutEngine:
         return self._solve_sampling("cem", opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
                                     expanded_ref, noise)
 
+    # ------------------------------------------------------------------ batched Gauss-Newton solve
+    def gn_workspace_bytes(self, B, H, line_steps):
+        return int(self.lib.phnn_gn_workspace_bytes(self.h, int(B), int(H), int(line_steps)))
+
+    @staticmethod
+    def _gn_options(iters, line_steps, mu_init, mu_min, mu_max, mu_up, mu_down):
+        opt = _capi.GnOptions()
+        opt.iters, opt.line_steps = int(iters), int(line_steps)
+        opt.mu_init, opt.mu_min, opt.mu_max = float(mu_init), float(mu_min), float(mu_max)
+        opt.mu_up, opt.mu_down = float(mu_up), float(mu_down)
+        return opt
+
+    def _mu(self, mu, B):
+        """(B,) float64 on the device from a tensor of that shape or one value."""
+        if isinstance(mu, torch.Tensor):
+            return mu.to(device=self.device, dtype=torch.float64).reshape(B).contiguous()
+        return torch.full((B,), float(mu), dtype=torch.float64, device=self.device)
+
+    def gn_direction(self, A, Bm, traj, u, cost, mu, x_ref=None, ref_offset=0):
+        """k_gn_direction: the Gauss-Newton step of every problem on its local model.  A (B,H,n,n), Bm (B,H,n,m) from
+        rollout_linearize, traj (B,H+1,n), u (B,H,m), mu (B) float64 or one value; x_ref / ref_offset: problem b's
+        reference as in rollout_cost.  -> dict(du (B,H,m) float32, dV (B) float64 -- the cost's slope along du is -dV,
+        the predicted change at the full step -dV/2 --, status (B) int32 as tvlqr's).  A failed problem has du = 0 and
+        dV = NaN."""
+        A = self._t(A)
+        B, H = A.shape[0], A.shape[1]
+        A = A.reshape(B, H, self.n, self.n)
+        Bm, traj, u = self._t(Bm, (B, H, self.n, self.m)), self._t(traj, (B, H + 1, self.n)), self._t(u, (B, H, self.m))
+        mu = self._mu(mu, B)
+        du = torch.empty(B, H, self.m, dtype=torch.float32, device=self.device)
+        dV = torch.empty(B, dtype=torch.float64, device=self.device)
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        scratch = torch.empty(B * H * (self.m * self.n + self.m), dtype=torch.float64, device=self.device)
+        ref, _keep = self._reference(x_ref, ref_offset, B)
+        rc = self.lib.phnn_gn_direction(self.h, self._p(A), self._p(Bm), self._p(traj), self._p(u), B, H, C.byref(cost),
+                                        None if ref is None else C.byref(ref), self._p(mu), self._p(du), self._p(dV),
+                                        self._p(status), self._p(scratch), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(du=du, dV=dV, status=status)
+
+    def gn_candidates(self, x0, u, du, cost, line_steps):
+        """k_gn_candidates: -> (cand (B*L,H,m), x0 replicated (B*L,n)); row b*L + j = clamp(u_b + 2^-j du_b), the clamp
+        the cost's."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u, H = self._controls(u, B)
+        du = self._t(du, (B, H, self.m))
+        L = int(line_steps)
+        rows = B * L if 1 <= L <= 32 else 0  # the library call refuses another L
+        cand = torch.empty(rows, H, self.m, dtype=torch.float32, device=self.device)
+        x0_rep = torch.empty(rows, self.n, dtype=torch.float32, device=self.device)
+        rc = self.lib.phnn_gn_candidates(self.h, self._p(x0), self._p(u), self._p(du), B, H, C.byref(cost), L, self._p(cand),
+                                         self._p(x0_rep), self._stream())
+        _check(self.lib, self.h, rc)
+        return cand, x0_rep
+
+    def gn_select(self, u, traj, cost_b, mu, accepts, cand, cand_cost, cand_traj, status, line_steps, mu_min, mu_max, mu_up,
+                  mu_down, costs_row=None, alpha_row=None):
+        """k_gn_select, in place on u (B,H,m), traj (B,H+1,n), cost_b (B), mu (B) float64 and accepts (B) int32: problem
+        b takes its lowest-cost finite candidate (lowest j on ties) iff status_b == 0 and that cost is < cost_b; mu
+        shrinks by mu_down (floor mu_min) then, else grows by mu_up (cap mu_max).  costs_row (B) receives cost_b as it
+        was, alpha_row (B) the accepted step length or 0."""
+        self._assert_device_f32(u, traj, cost_b, cand, cand_cost, cand_traj, costs_row, alpha_row)
+        assert mu.dtype == torch.float64 and accepts.dtype == torch.int32 and status.dtype == torch.int32
+        assert all(t.is_contiguous() and t.device == self.device for t in (mu, accepts, status))
+        B, H = u.shape[0], u.shape[1]
+        L = int(line_steps)
+        assert cand.numel() == B * L * H * self.m and cand_cost.numel() == B * L and cand_traj.numel() == B * L * (H + 1) * self.n
+        opt = self._gn_options(0, L, 0.0, mu_min, mu_max, mu_up, mu_down)
+        rc = self.lib.phnn_gn_select(self.h, self._p(u), self._p(traj), self._p(cost_b), self._p(mu), self._p(accepts),
+                                     self._p(cand), self._p(cand_cost), self._p(cand_traj), self._p(status), B, H,
+                                     C.byref(opt), self._p(costs_row), self._p(alpha_row), self._stream())
+        _check(self.lib, self.h, rc)
+
+    def solve_gn(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=10, line_steps=8, mu_init=1e-6, mu_min=1e-9,
+                 mu_max=1e6, mu_up=10.0, mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0,
+                 expanded_ref=False):
+        """phnn_solve_gn: projected Gauss-Newton shooting on B independent problems as ONE library call: the iterate is
+        clamped and costed, then iters x (k_rollout_linearize, k_gn_direction, k_gn_candidates, K1 over B * line_steps
+        candidates, k_gn_select).  -> dict(u_last (B,H,m) in bounds, cost (B) its cost, costs (iters,B) the cost at the
+        start of every iteration or None, mu (B) float64, accepts (B) int32, alpha_hist (iters,B) the accepted step
+        lengths, 0 where rejected, or None), same results bit for bit as solver.gn_solve.  The cost of a problem never
+        rises.  x_ref, ref_offset, expanded_ref: as in solve_mppi, with line_steps rollouts per problem.  The workspace
+        (a dict reused across calls) keeps the device buffer of phnn_gn_workspace_bytes."""
+        x0 = self._t(x0, (-1, self.n))
+        B = x0.shape[0]
+        u_init, H = self._controls(u_init, B)
+        integ = self._integ(integrator)
+        opt = self._gn_options(iters, line_steps, mu_init, mu_min, mu_max, mu_up, mu_down)
+        ws = {} if workspace is None else workspace
+        key = (B, H, opt.line_steps)
+        if ws.get("gn_key") != key:
+            ws["gn_key"] = key
+            ws["gn"] = torch.empty(max(self.gn_workspace_bytes(B, H, opt.line_steps), 256), dtype=torch.uint8, device=self.device)
+        f = dict(dtype=torch.float32, device=self.device)
+        u = u_init.detach().clone().contiguous()
+        rows = max(opt.iters, 0)
+        costs = torch.empty(rows, B, **f) if record_costs else None
+        alpha = torch.empty(rows, B, **f) if record_costs else None
+        cost_b = torch.empty(B, **f)
+        mu = torch.empty(B, dtype=torch.float64, device=self.device)
+        accepts = torch.empty(B, dtype=torch.int32, device=self.device)
+        ref, _keep = self._reference(x_ref if expanded_ref else self.mppi_reference(x_ref, B, opt.line_steps), ref_offset,
+                                     B * max(opt.line_steps, 1))
+        rc = self.lib.phnn_solve_gn(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), None if ref is None else C.byref(ref),
+                                    integ, float(dt), C.byref(opt), self._p(ws["gn"]), ws["gn"].numel(), self._p(cost_b),
+                                    self._p(costs), self._p(mu), self._p(accepts), self._p(alpha), self._stream())
+        _check(self.lib, self.h, rc)
+        return {"u_last": u, "cost": cost_b, "costs": costs, "mu": mu, "accepts": accepts, "alpha_hist": alpha}
+
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
                    step=0, step_dev=None, log_states=None, log_controls=None, ex=None, metrics=None):

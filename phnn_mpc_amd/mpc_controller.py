@@ -13,6 +13,10 @@ cold-starts the nominal from zeros, runs max_iterations iterations of `samples` 
 clamp(u_0) of the last nominal.  lr is not used.
 optimizer_type='CrossEntropy' (not in the reference): the cross-entropy sampling solve (engine.solve_cem), called as
 the MPPI one is; returns clamp(u_0) of the last mean.  (The name is not 'CEM': that string stays an unknown optimizer.)
+optimizer_type='GaussNewton' (not in the reference): projected Gauss-Newton shooting on the rollout's linearisation
+(engine.solve_gn): every call cold-starts from zeros, runs max_iterations iterations (linearise, LQ direction with
+Levenberg-Marquardt term mu, gn_line_steps candidates u + 2^-j du in one K1 launch, select) and returns clamp(u_0) of the
+last iterate, whose cost never rises from one iteration to the next.  lr is not used.
 """
 import os
 
@@ -21,13 +25,14 @@ import torch
 
 from . import _capi
 from .noise import resolve as resolve_noise
-from .solver import SAMPLING, _noise_kw, lbfgs_solver_for, solver_for
+from .solver import SAMPLING, _noise_kw, gn_solver_for, lbfgs_solver_for, solver_for
 
 
 class MPCController:
     def __init__(self, phnn_model, horizon, dt, Q, R, target_state=None, u_min=None, u_max=None, x_min=None, x_max=None,
                  optimizer_type="Adam", lr=0.1, max_iterations=50, samples=64, lam=1.0, sigma=1.0, seed=0, elites=8,
-                 alpha=0.25, sigma_min=0.05, noise=None):
+                 alpha=0.25, sigma_min=0.05, noise=None, gn_line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
+                 mu_down=0.1):
         self.model = phnn_model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -51,6 +56,9 @@ class MPCController:
         # MPPI and CrossEntropy: the time correlation of the sampling noise (noise.resolve: None = white, a noise.Noise,
         # {"type": "ar1" | "colored" | "knots", ...} or an (H, P) array); ValueError for an unknown type or another horizon
         self.noise = resolve_noise(noise, horizon)
+        # optimizer_type='GaussNewton': candidates per line search, and the Levenberg-Marquardt term's start, range and factors
+        self.gn_line_steps, self.mu_init, self.mu_min, self.mu_max = gn_line_steps, mu_init, mu_min, mu_max
+        self.mu_up, self.mu_down = mu_up, mu_down
         self.integrator = "euler"  # src/mpc_controller.py:137-138
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -158,6 +166,8 @@ class MPCController:
             return self._solve_batch_lbfgs(states, record_costs, x_ref, ref_offset)
         if self.optimizer_type in SAMPLING:
             return self._solve_batch_sampling(states, record_costs, x_ref, ref_offset, epoch)
+        if self.optimizer_type == "GaussNewton":
+            return self._solve_batch_gn(states, record_costs, x_ref, ref_offset)
         if self.optimizer_type != "Adam":
             raise ValueError(f"Unknown optimizer type: {self.optimizer_type}")
         eng = self.engine
@@ -185,6 +195,23 @@ class MPCController:
         u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
         return self._graphed_lbfgs(x0, u0, self._cost(), integrator=self.integrator, dt=self.dt, record_costs=record_costs,
                                    x_ref=x_ref, ref_offset=ref_offset, **self.lbfgs_options())
+
+    def gn_options(self):
+        """solve_gn keyword arguments of this controller."""
+        return dict(iters=self.max_iterations, line_steps=self.gn_line_steps, mu_init=self.mu_init, mu_min=self.mu_min,
+                    mu_max=self.mu_max, mu_up=self.mu_up, mu_down=self.mu_down)
+
+    def _solve_batch_gn(self, states, record_costs, x_ref, ref_offset):
+        """B independent Gauss-Newton solves (cold start from zeros) in one batched device solve (engine.solve_gn); the
+        workspace stays with the controller."""
+        eng = self.engine
+        self._graphed_gn = gn_solver_for(eng, self.use_graph, getattr(self, "_graphed_gn", None))
+        if getattr(self, "_gn_ws", None) is None:
+            self._gn_ws = {}
+        x0 = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
+        u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
+        return self._graphed_gn(eng, x0, u0, self._cost(), self.integrator, self.dt, record_costs=record_costs,
+                                workspace=self._gn_ws, x_ref=x_ref, ref_offset=ref_offset, **self.gn_options())
 
     def mppi_options(self):
         """solve_mppi keyword arguments of this controller."""
@@ -234,9 +261,11 @@ class MPCController:
 
 
 def _mppi_keys(mpc):
-    """The sampling-solver keywords present in the `mpc` config section (optimizer: MPPI or CrossEntropy): samples, lam,
-    sigma, seed, elites, alpha, sigma_min, noise."""
-    return {k: mpc[k] for k in ("samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise") if k in mpc}
+    """The solver keywords present in the `mpc` config section: samples, lam, sigma, seed, elites, alpha, sigma_min, noise
+    (optimizer: MPPI or CrossEntropy) and gn_line_steps, mu_init, mu_min, mu_max, mu_up, mu_down (GaussNewton)."""
+    keys = ("samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise", "gn_line_steps", "mu_init", "mu_min",
+            "mu_max", "mu_up", "mu_down")
+    return {k: mpc[k] for k in keys if k in mpc}
 
 
 def create_mpc_from_config(phnn_model, config):

@@ -10,6 +10,9 @@ optimizer_steps iterations of `samples` perturbed rollouts per plant; the sequen
 'costs' the nominal's cost at every iteration; learning_rate is not used.
 optimizer='CrossEntropy' (not in the reference): the cross-entropy sampling solve (engine.solve_cem), called and
 returning as the MPPI one does.  (The name is not 'CEM': that string stays an unknown optimizer.)
+optimizer='GaussNewton' (not in the reference): projected Gauss-Newton shooting on the rollout's linearisation
+(engine.solve_gn), optimizer_steps iterations; a problem's cost never rises, so the sequence returned (best_u) is the
+last iterate and best_cost its cost; 'costs' is the cost at the start of every iteration; learning_rate is not used.
 """
 import os
 import time
@@ -19,13 +22,14 @@ import torch
 
 from . import _capi
 from .noise import resolve as resolve_noise
-from .solver import SAMPLING, _noise_kw, solver_for
+from .solver import SAMPLING, _noise_kw, gn_solver_for, solver_for
 
 
 class MPCControllerCanonical:
     def __init__(self, model, horizon=20, dt=0.02, Q=None, R=None, x_target=None, u_min=-10.0, u_max=10.0,
                  optimizer_steps=50, learning_rate=0.1, verbose=False, optimizer="Adam", samples=64, lam=1.0, sigma=1.0,
-                 seed=0, elites=8, alpha=0.25, sigma_min=0.05, noise=None):
+                 seed=0, elites=8, alpha=0.25, sigma_min=0.05, noise=None, gn_line_steps=8, mu_init=1e-6, mu_min=1e-9,
+                 mu_max=1e6, mu_up=10.0, mu_down=0.1):
         self.model = model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -41,7 +45,7 @@ class MPCControllerCanonical:
             x_target = np.zeros(self.state_dim)
         self.x_target = torch.tensor(x_target, dtype=torch.float32)
         self.u_min, self.u_max = u_min, u_max
-        if optimizer not in ("Adam", "MPPI", "CrossEntropy"):
+        if optimizer not in ("Adam", "MPPI", "CrossEntropy", "GaussNewton"):
             raise ValueError(f"Unknown optimizer type: {optimizer}")
         # optimizer='MPPI': samples per plant and iteration, softmin temperature (units of the cost), noise standard
         # deviation (one value or one per input), noise seed; `epoch` numbers the solves that are not given one
@@ -52,6 +56,9 @@ class MPCControllerCanonical:
         # MPPI and CrossEntropy: the time correlation of the sampling noise (noise.resolve: None = white, a noise.Noise,
         # {"type": "ar1" | "colored" | "knots", ...} or an (H, P) array); ValueError for an unknown type or another horizon
         self.noise = resolve_noise(noise, horizon)
+        # optimizer='GaussNewton': candidates per line search, and the Levenberg-Marquardt term's start, range and factors
+        self.gn_line_steps, self.mu_init, self.mu_min, self.mu_max = gn_line_steps, mu_init, mu_min, mu_max
+        self.mu_up, self.mu_down = mu_up, mu_down
         self.integrator = "euler"
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -170,6 +177,8 @@ class MPCControllerCanonical:
             u0 = torch.as_tensor(u_init, dtype=torch.float32).reshape(B, self.horizon, self.input_dim).to(eng.device)
         if self.optimizer in SAMPLING:
             return self._solve_batch_sampling(x0, u0, record_costs, x_ref, ref_offset, epoch)
+        if self.optimizer == "GaussNewton":
+            return self._solve_batch_gn(x0, u0, record_costs, x_ref, ref_offset)
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.learning_rate,
                                  self.optimizer_steps, track_best=True, u_min=self.u_min, u_max=self.u_max,
                                  record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset)
@@ -182,6 +191,22 @@ class MPCControllerCanonical:
         setattr(self, "_graphed_" + meth, solve)
         return solve(eng, x0, u0, self._cost(), self.integrator, self.dt, epoch=self._mppi_epoch(eng, epoch),
                      record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **getattr(self, meth + "_options")())
+
+    def gn_options(self):
+        """solve_gn keyword arguments of this controller."""
+        return dict(iters=self.optimizer_steps, line_steps=self.gn_line_steps, mu_init=self.mu_init, mu_min=self.mu_min,
+                    mu_max=self.mu_max, mu_up=self.mu_up, mu_down=self.mu_down)
+
+    def _solve_batch_gn(self, x0, u0, record_costs, x_ref, ref_offset):
+        """The Gauss-Newton solve of optimize_control_batch (engine.solve_gn); the workspace stays with the controller.
+        best_u / best_cost are the last iterate and its cost (the cost of a problem never rises)."""
+        eng = self.engine
+        self._graphed_gn = gn_solver_for(eng, self.use_graph, getattr(self, "_graphed_gn", None))
+        if getattr(self, "_gn_ws", None) is None:
+            self._gn_ws = {}
+        out = self._graphed_gn(eng, x0, u0, self._cost(), self.integrator, self.dt, record_costs=record_costs,
+                               workspace=self._gn_ws, x_ref=x_ref, ref_offset=ref_offset, **self.gn_options())
+        return {**out, "best_u": out["u_last"], "best_cost": out["cost"]}
 
     def control_batch(self, x_current, u_prev=None, x_ref=None, ref_offset=0, epoch=None):
         """x_current (B,n), u_prev (B,H,m) or None -> (u (B,m), u_sequence (B,H,m), best_cost (B)) numpy arrays.
@@ -205,5 +230,6 @@ def create_mpc_controller(model, config):
         x_target=np.array(mpc.get("x_target", [0.0, 0.0, 0.0, 0.0])), u_min=mpc.get("u_min", -10.0),
         u_max=mpc.get("u_max", 10.0), optimizer_steps=mpc.get("optimizer_steps", 50),
         learning_rate=mpc.get("learning_rate", 0.1), verbose=mpc.get("verbose", False),
-        **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise")
+        **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise",
+                                   "gn_line_steps", "mu_init", "mu_min", "mu_max", "mu_up", "mu_down")
            if k in mpc})

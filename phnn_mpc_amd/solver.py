@@ -17,6 +17,9 @@ engine.rollout_cost and engine.mppi_update that engine.solve_mppi (phnn_solve_mp
 cem_solve is the cross-entropy solver of the same shape (a mean and a standard deviation per problem and element, both
 refitted to the lowest-cost samples): the Python loop over engine.cem_sample, engine.rollout_cost and engine.cem_update
 that engine.solve_cem (phnn_solve_cem) is pinned to bit for bit.
+gn_solve is the curvature-based one: projected Gauss-Newton shooting on the rollout's linearisation with a parallel
+backtracking line search, the Python loop over engine.rollout_linearize, engine.gn_direction, engine.gn_candidates,
+engine.rollout_cost and engine.gn_select that engine.solve_gn (phnn_solve_gn) is pinned to bit for bit.
 """
 import ctypes
 import inspect
@@ -186,6 +189,54 @@ def _cem_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, elites,
         workspace=workspace, x_ref=x_ref, ref_offset=ref_offset, **_noise_kw(noise))
 
 
+def gn_solve(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
+             mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+    """Projected Gauss-Newton shooting with Levenberg-Marquardt regularisation and a parallel backtracking line search on
+    B independent problems: x0 (B,n), u_init (B,H,m) -> dict(u_last, cost, costs, mu, accepts, alpha_hist).
+
+    The iterate u starts at clamp(u_init) (the cost's bounds) with cost and trajectory from engine.rollout_cost and
+    mu = mu_init; `iters` times: engine.rollout_linearize at (u, traj), engine.gn_direction (the LQ step du on that
+    model with the stage cost's gradients, Quu + mu I), engine.gn_candidates (clamp(u + 2^-j du), j < line_steps),
+    engine.rollout_cost of all B * line_steps candidates, engine.gn_select (the best finite candidate replaces the
+    iterate iff it is strictly cheaper; mu shrinks after an accepted iteration and grows after a rejected one).
+    u_last    : the last iterate (B,H,m), in bounds;  cost: its cost (B) -- never higher than an earlier one
+    costs     : (iters,B) cost of the iterate at the START of every iteration, if record_costs
+    mu        : (B) float64, accepts: (B) int32 accepted iterations, alpha_hist: (iters,B) accepted step length or 0
+    x_ref, ref_offset: as in shooting_solve (one reference per problem; the candidates of a problem share it).
+    The Python loop that engine.solve_gn (phnn_solve_gn) is pinned to bit for bit."""
+    _need_reference(engine, x_ref)
+    B, L = u_init.shape[0], int(line_steps)
+    rkw_b, rkw_r = {}, {}
+    if x_ref is not None:
+        rkw_b = {"x_ref": x_ref, "ref_offset": ref_offset}
+        rkw_r = {"x_ref": engine.mppi_reference(x_ref, B, L), "ref_offset": ref_offset}
+    u = u_init.detach().clone().contiguous()
+    if cost.has_u_bounds:
+        u = torch.clamp(u, float(cost.u_min), float(cost.u_max))
+    dev = u.device
+    costs = torch.empty(iters, B, dtype=torch.float32, device=dev) if record_costs else None
+    alpha = torch.empty(iters, B, dtype=torch.float32, device=dev) if record_costs else None
+    mu = torch.full((B,), float(mu_init), dtype=torch.float64, device=dev)
+    accepts = torch.zeros(B, dtype=torch.int32, device=dev)
+    c, traj = engine.rollout_cost(x0, u, cost, integrator, dt, want_traj=True, **rkw_b)
+    for it in range(iters):
+        A, Bm, _ = engine.rollout_linearize(x0, u, cost, integrator, dt, traj=traj)
+        d = engine.gn_direction(A, Bm, traj, u, cost, mu, **rkw_b)
+        cand, x0_rep = engine.gn_candidates(x0, u, d["du"], cost, L)
+        s, ctraj = engine.rollout_cost(x0_rep, cand, cost, integrator, dt, want_traj=True, **rkw_r)
+        engine.gn_select(u, traj, c, mu, accepts, cand, s, ctraj, d["status"], L, mu_min, mu_max, mu_up, mu_down,
+                         costs_row=costs[it] if record_costs else None, alpha_row=alpha[it] if record_costs else None)
+    return {"u_last": u, "cost": c, "costs": costs, "mu": mu, "accepts": accepts, "alpha_hist": alpha}
+
+
+def _gn_eager(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
+              mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+    """The Gauss-Newton solve without a captured graph (_library_or); called as gn_solve is."""
+    return _library_or(engine, "solve_gn", gn_solve)(
+        x0, u_init, cost, integrator, dt, iters=iters, line_steps=line_steps, mu_init=mu_init, mu_min=mu_min, mu_max=mu_max,
+        mu_up=mu_up, mu_down=mu_down, record_costs=record_costs, workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
+
+
 def capture(device, fn):
     """Runs fn() once on a side stream (whatever it allocates for later calls, it allocates outside the capture), then
     captures a second fn() as a HIP graph.  -> (graph, what the captured fn() returned).  Recording executes nothing:
@@ -304,6 +355,14 @@ class GraphedCEM(Graphed):
         super().__init__(engine, _cem_eager)
 
 
+class GraphedGN(Graphed):
+    """The Gauss-Newton solve (_gn_eager) as a graph: the clamp, the state reset and the set-up K1 plus every iters x
+    (k_rollout_linearize, k_gn_direction, k_gn_candidates, K1, k_gn_select) launch.  x_ref behaves as in GraphedMPPI."""
+
+    def __init__(self, engine):
+        super().__init__(engine, _gn_eager)
+
+
 def _graphed_or(eager, cls, engine, use_graph, previous):
     if not use_graph or engine.device.type != "cuda":
         return eager
@@ -341,6 +400,14 @@ def cem_solver_for(engine, use_graph, previous=None):
     if not hasattr(engine, "cem_sample"):
         raise NotImplementedError(f"{type(engine).__name__} has no CEM kernels (RolloutEngine has)")
     return _graphed_or(_cem_eager, GraphedCEM, engine, use_graph, previous)
+
+
+def gn_solver_for(engine, use_graph, previous=None):
+    """-> callable(engine, x0, u_init, cost, ...) as _gn_eager: itself, or a GraphedGN bound to `engine` (reused from
+    `previous` when it already is one for this engine)."""
+    if not hasattr(engine, "gn_direction"):
+        raise NotImplementedError(f"{type(engine).__name__} has no Gauss-Newton kernels (RolloutEngine has)")
+    return _graphed_or(_gn_eager, GraphedGN, engine, use_graph, previous)
 
 
 # optimizer name of a sampling solve -> (its short name: engine.solve_<name>, controller.<name>_options(), solver_for)

@@ -1,0 +1,502 @@
+"""The batched Gauss-Newton solve on the GPU (phnn_solve_gn and its three kernels):
+
+  1 direction    k_gn_direction == gn_model.direction bit for bit on the device's own float32 A, Bm, traj and u: B in
+                 {1, 17, 65} x H in {1, 2, 7}, Euler and RK4, one spec per (n, m) in {(2,1), (3,1), (4,1), (4,2), (4,4)},
+                 per-problem mu, an active barrier, no / a shared / a per-problem reference with a device offset, and the
+                 failure cases (NaN in A_t, B_t, a trajectory row, a control; a negative definite R)
+  2 tvlqr        zero gradients and a uniform mu: du = 0, dV = 0 and the status of phnn_tvlqr on the same A, Bm
+  3 rows         k_gn_candidates and k_gn_select == their restatements bit for bit (a NaN control kept NaN, candidates in
+                 bounds, ties, non-finite costs, status != 0, mu at its floor and cap)
+  4 slope        sum(grad_u * du) against -dV with grad_u from phnn_rollout_grad.  Tolerance, per problem:
+                   grad_tol(spec) * max|grad_u| * sum|du|   -- what K2's stated tolerance (variant_census.grad_tol, of
+                                                               max|grad| per rollout) leaves of the sum --
+                 + 64 * 6.5e-7 * dV                         -- the float32 oracle's own deviation from the identity on
+                                                               these inputs (gn_model.SLOPE_F32_ORACLE, measured on the
+                                                               CPU by test_gn_model.py) times the margin of 64 used
+                                                               throughout for a measured rounding figure.
+  5 solve        phnn_solve_gn == the same sequence through the public entry points (solver.gn_solve) bit for bit in
+                 every output; eager == graph replay; one call == two half batches; cost never rises
+  6 footprint    every argument and the workspace in guarded buffers of exactly the reported sizes
+  7 arguments    the refusals, iters = 0 and B = 0
+  8 controllers  both controllers route 'GaussNewton' to the library solve, feedback_gains still works afterwards; 8 plants
+                 x 5 steps of DeviceClosedLoop (eager and graphed) == the host-driven loop, controls bit for bit
+  9 convergence  on the reference's cart-pole configuration two iterations end below the Adam solve's best of 30 on
+                 every x0 of the golden closed-loop runs (DESIGN.md section 18 tabulates it on the float64 oracle, where
+                 one iteration already does)"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import footprint as fp
+import gn_model as gm
+import oracle_lib as ol
+import tvlqr_model as tm
+import variant_census as vc
+from test_gpu_footprint import Report, engine, footprint, rng_of
+
+pytestmark = pytest.mark.gpu
+
+SPECS = gm.SLOPE_SPECS  # one per (n, m)
+HEADLINE = "phnn<n=4,hid=128,fixedG,f16x2>"
+BATCHES, HORIZONS = (1, 17, 65), (1, 2, 7)
+INVALID, UNSUPPORTED = -1, -2
+GN = dict(line_steps=4, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0, mu_down=0.1)
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+    assert t.cuda.is_available(), "GPU tests need a GPU"
+    return t
+
+
+def npf(t):
+    return t.detach().cpu().numpy()
+
+
+def dev(torch, a, dtype=None):
+    return torch.as_tensor(a, dtype=dtype, device="cuda:0")
+
+
+def check_direction(what, out, ref):
+    assert np.array_equal(npf(out["status"]), ref["status"]), (what, npf(out["status"]), ref["status"])
+    assert tm.same_floats(npf(out["du"]), ref["du"]), (what, "du")
+    assert tm.same_floats(npf(out["dV"]), ref["dV"]), (what, "dV")
+
+
+# ----------------------------------------------------------------------------- 1. direction
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+@pytest.mark.parametrize("sid", SPECS)
+def test_direction_equals_the_stated_order_model(torch, sid, integ):
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n, m = s["n"], s["m"]
+    active = accepted = 0
+    for B in BATCHES:
+        for H in HORIZONS:
+            rng = rng_of("gn-dir", sid, integ, B, H)
+            x0 = 0.5 * vc.states(rng, n, B)
+            u = vc.controls(rng, B, H, m)  # a fifth outside the bounds: those columns of Bm are zero
+            cost = vc.cost_of(s, rng, barrier=True)
+            mu = rng.choice([0.0, 1e-6, 0.125, 3.0], size=B)
+            A, Bm, traj = eng.rollout_linearize(x0, u, cost, integ, vc.dt_of(s))
+            An, Bn, tn = npf(A), npf(Bm), npf(traj)
+            ldiag, _, _ = gm.gradients(tn, u, cost, n, m)
+            active += int((ldiag != np.diag(tm.cost_matrices_of(cost, n, m)[0])).sum())
+            rows = 3
+            shared = rng.uniform(-0.2, 0.2, size=(rows, n)).astype(np.float32)
+            own = rng.uniform(-0.2, 0.2, size=(B, rows, n)).astype(np.float32)
+            off = dev(torch, [1], torch.int32)
+            for tag, kw, ref in (("target", {}, None),
+                                 ("shared", dict(x_ref=shared, ref_offset=0), gm.reference_rows(shared, 0, H, B, n)),
+                                 ("own+offset", dict(x_ref=own, ref_offset=off), gm.reference_rows(own, 1, H, B, n))):
+                out = eng.gn_direction(A, Bm, traj, u, cost, dev(torch, mu), **kw)
+                want = gm.direction(An, Bn, tn, u, cost, n, m, mu, ref)
+                check_direction((sid, integ, B, H, tag), out, want)
+                accepted += int((want["status"] == 0).sum())
+    assert active > 0 and accepted > 0
+
+
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[4]])
+def test_direction_failure_cases(torch, sid):
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n, m = s["n"], s["m"]
+    B, H = 17, 7
+    rng = rng_of("gn-fail", sid)
+    x0 = 0.5 * vc.states(rng, n, B)
+    u = np.clip(vc.controls(rng, B, H, m), vc.U_MIN, vc.U_MAX).astype(np.float32)
+    cost = vc.cost_of(s, rng)
+    A, Bm, traj = eng.rollout_linearize(x0, u, cost, "euler", vc.dt_of(s))
+    An, Bn, tn = npf(A), npf(Bm), npf(traj)
+    An[1, 4, 0, 0] = np.nan       # reaches the pivot of step 3
+    Bn[2, 5, 0, 0] = np.nan       # the pivot of its own step
+    An[3, 0, 0, 0] = np.nan       # no pivot: status 0, still no step
+    tn[4, 3, n - 1] = np.nan      # a trajectory row: status 0, no step
+    un = u.copy()
+    un[5, 2, 0] = np.nan          # a control: status 0, no step
+    out = eng.gn_direction(An, Bn, tn, un, cost, 0.0)
+    want = gm.direction(An, Bn, tn, un, cost, n, m, 0.0)
+    check_direction((sid, "nan"), out, want)
+    assert list(want["status"][:6]) == [0, 4, 6, 0, 0, 0]
+    for b in (1, 2, 3, 4, 5):
+        assert np.all(want["du"][b] == 0) and np.isnan(want["dV"][b])
+    assert np.isfinite(want["dV"][[0] + list(range(6, B))]).all()
+    from phnn_mpc_amd import _capi
+    Q = np.ctypeslib.as_array(cost.Q)[: n * n].reshape(n, n)
+    bad = _capi.make_cost(n, m, Q, -np.eye(m))
+    out = eng.gn_direction(A, Bm, traj, u, bad, 0.0)
+    want = gm.direction(npf(A), npf(Bm), npf(traj), u, bad, n, m, 0.0)
+    check_direction((sid, "negative R"), out, want)
+    assert (want["status"] == H).all() and np.isnan(want["dV"]).all() and np.all(want["du"] == 0)
+
+
+# ----------------------------------------------------------------------------- 2. against phnn_tvlqr
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[4]])
+def test_zero_gradients_give_no_step_and_the_status_of_tvlqr(torch, sid):
+    from phnn_mpc_amd import _capi
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n, m = s["n"], s["m"]
+    B, H = 65, 7
+    A, Bm, Q, R = tm.seeded_problem(5 + n + m, B, H, n, m)
+    Bm[3, 4] = 0.0  # with R = 0 and mu = 0 a singular Quu: status 5
+    target = np.float32([0.25, -0.5, 0.125, 1.0][:n])
+    traj = np.broadcast_to(target, (B, H + 1, n)).copy()
+    u = np.zeros((B, H, m), np.float32)
+    for Rm, mu in ((R, 0.0), (R, 0.125), (np.zeros_like(R), 0.0)):
+        cost = _capi.make_cost(n, m, Q, Rm, x_target=target)
+        out = eng.gn_direction(A, Bm, traj, u, cost, mu)
+        lqr = eng.tvlqr(A, Bm, cost, mu=mu)
+        assert torch.equal(out["status"], lqr["status"])
+        st = npf(out["status"])
+        assert (st[3] == 5) == (not Rm.any())
+        ok = st == 0
+        assert np.all(npf(out["du"]) == 0) and np.all(npf(out["dV"])[ok] == 0) and np.isnan(npf(out["dV"])[~ok]).all()
+
+
+# ----------------------------------------------------------------------------- 3. candidates and select
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[3]])
+def test_candidates_and_select_equal_their_restatements(torch, sid):
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n, m = s["n"], s["m"]
+    for B in BATCHES:
+        for H in HORIZONS:
+            for L in (1, 4, 32):
+                rng = rng_of("gn-rows", sid, B, H, L)
+                cost = vc.cost_of(s, rng)
+                x0 = vc.states(rng, n, B)
+                u = np.clip(vc.controls(rng, B, H, m), vc.U_MIN, vc.U_MAX).astype(np.float32)
+                du = (rng.normal(size=(B, H, m)) * 2.0).astype(np.float32)
+                du[0, 0, 0] = np.float32(3 * 2.0 ** -149)
+                if B > 1:
+                    u[1, H - 1, m - 1] = np.nan
+                    du[B - 1, 0, 0] = np.inf
+                cand, x0_rep = eng.gn_candidates(x0, u, du, cost, L)
+                want = gm.candidates(u, du, L, cost)
+                assert tm.same_floats(npf(cand), want), (sid, B, H, L)
+                assert np.array_equal(npf(x0_rep), np.repeat(x0, L, axis=0))
+                fin = want[np.isfinite(want)]
+                assert fin.min() >= vc.U_MIN and fin.max() <= vc.U_MAX
+                if B > 1:
+                    assert np.isnan(want.reshape(B, L, H, m)[1, :, H - 1, m - 1]).all()
+                # select on those candidates with made-up costs and trajectories
+                sc = rng.choice([1.0, 2.0, 2.0, 3.0, np.nan, np.inf, -np.inf, 0.5], size=(B * L,)).astype(np.float32)
+                ctraj = rng.normal(size=(B * L, H + 1, n)).astype(np.float32)
+                traj = rng.normal(size=(B, H + 1, n)).astype(np.float32)
+                cb = rng.choice([1.0, 2.0, 2.5, np.nan], size=B).astype(np.float32)
+                mu = rng.choice([1e-9, 5e-9, 1.0, 5e5, 1e6], size=B)
+                acc = rng.integers(0, 5, size=B).astype(np.int32)
+                st = rng.choice([0, 0, 0, 3], size=B).astype(np.int32)
+                r = gm.select(u, traj, cb, mu, acc, want, sc, ctraj, st, L, GN["mu_min"], GN["mu_max"], GN["mu_up"], GN["mu_down"])
+                t = dict(u=dev(torch, u), traj=dev(torch, traj), cost=dev(torch, cb), mu=dev(torch, mu), accepts=dev(torch, acc),
+                         costs_row=torch.empty(B, device="cuda:0"), alpha_row=torch.empty(B, device="cuda:0"))
+                eng.gn_select(t["u"], t["traj"], t["cost"], t["mu"], t["accepts"], cand, dev(torch, sc), dev(torch, ctraj),
+                              dev(torch, st), L, GN["mu_min"], GN["mu_max"], GN["mu_up"], GN["mu_down"],
+                              costs_row=t["costs_row"], alpha_row=t["alpha_row"])
+                for k in t:
+                    assert tm.same_floats(npf(t[k]), r[k]), (sid, B, H, L, k)
+
+
+# ----------------------------------------------------------------------------- 4. the slope, against K2
+@pytest.mark.parametrize("sid", SPECS)
+def test_slope_of_the_cost_along_the_step_is_minus_dv(torch, sid):
+    s, eng = vc.CENSUS[sid], engine(sid)
+    c = gm.slope_case(sid)
+    cost_b, g = eng.rollout_cost_grad(c["x0"], c["u"], c["cost"], "euler", c["dt"])
+    g = npf(g).copy()
+    A, Bm, traj = eng.rollout_linearize(c["x0"], c["u"], c["cost"], "euler", c["dt"])
+    d = eng.gn_direction(A, Bm, traj, c["u"], c["cost"], 0.0)
+    assert not bool(d["status"].any())
+    dV = npf(d["dV"])
+    miss, scale = gm.slope_mismatch(g, npf(d["du"]), dV)
+    tol = vc.grad_tol(s) * scale + 64 * gm.SLOPE_F32_ORACLE * dV
+    print(f"\n{sid}: worst |sum(g du) + dV| / dV {float((miss / dV).max()):.2e}, worst miss / tolerance {float((miss / tol).max()):.2e}")
+    assert np.all(dV > 0) and np.all(miss <= tol)
+
+
+# ----------------------------------------------------------------------------- 5. the composed solve
+OUT_KEYS = ("u_last", "cost", "costs", "mu", "accepts", "alpha_hist")
+
+
+def same_outputs(torch, a, b, what):
+    for k in OUT_KEYS:
+        assert fp.same_bytes(torch, fp.as_bytes(torch, a[k]), fp.as_bytes(torch, b[k])), (what, k)
+
+
+def solve_case(sid, B, H, key):
+    s = vc.CENSUS[sid]
+    rng = rng_of("gn-solve", sid, B, H, key)
+    x0 = 0.5 * vc.states(rng, s["n"], B)
+    u0 = (0.5 * vc.controls(rng, B, H, s["m"])).astype(np.float32)
+    if B > 1:
+        u0[B - 1] *= 8.0  # far outside the bounds: the set-up clamps it
+    return s, x0, u0, vc.cost_of(s, rng, barrier=True), rng
+
+
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+@pytest.mark.parametrize("sid", SPECS)
+def test_solve_equals_the_sequence_issued_by_hand(torch, sid, integ):
+    from phnn_mpc_amd import solver
+    eng = engine(sid)
+    rose = 0
+    for B, H, L, iters in ((1, 1, 1, 2), (17, 2, 4, 3), (65, 7, 4, 4)):
+        s, x0, u0, cost, rng = solve_case(sid, B, H, integ)
+        x0d, u0d = dev(torch, x0), dev(torch, u0)
+        own = rng.uniform(-0.1, 0.1, size=(B, 3, s["n"])).astype(np.float32)
+        off = dev(torch, [1], torch.int32)
+        for tag, kw in (("target", {}), ("shared", dict(x_ref=own[0], ref_offset=1)), ("own+offset", dict(x_ref=own, ref_offset=off))):
+            opt = dict(GN, line_steps=L)
+            lib = eng.solve_gn(x0d, u0d, cost, integ, vc.dt_of(s), iters=iters, **opt, **kw)
+            hand = solver.gn_solve(eng, x0d, u0d, cost, integ, vc.dt_of(s), iters, **opt, **kw)
+            same_outputs(torch, lib, hand, (sid, integ, B, H, tag))
+            chain = np.vstack([npf(lib["costs"]), npf(lib["cost"])[None]])
+            assert np.isfinite(chain).all() and np.all(chain[1:] <= chain[:-1])
+            rose += int((chain[-1] < chain[0]).sum())
+            assert np.array_equal(npf(lib["accepts"]), (npf(lib["alpha_hist"]) > 0).sum(axis=0))
+            ul = npf(lib["u_last"])
+            assert ul.min() >= vc.U_MIN and ul.max() <= vc.U_MAX
+            assert torch.equal(u0d, dev(torch, u0)) and torch.equal(x0d, dev(torch, x0))  # inputs untouched
+    assert rose > 0
+
+
+def test_graph_replay_and_half_batches_equal_the_eager_solve(torch):
+    from phnn_mpc_amd import solver
+    sid = HEADLINE
+    eng = engine(sid)
+    B, H = 18, 7
+    s, x0, u0, cost, rng = solve_case(sid, B, H, "graph")
+    x0d, u0d = dev(torch, x0), dev(torch, u0)
+    own = rng.uniform(-0.1, 0.1, size=(B, 3, 4)).astype(np.float32)
+    kw = dict(iters=3, **GN)
+    for ref in (None, own):
+        rkw = {} if ref is None else dict(x_ref=dev(torch, ref), ref_offset=1)
+        eager = eng.solve_gn(x0d, u0d, cost, "euler", 0.02, **kw, **rkw)
+        graphed = solver.GraphedGN(eng)
+        for _ in range(2):
+            same_outputs(torch, graphed(eng, x0d, u0d, cost, "euler", 0.02, **kw, **rkw), eager, "graph")
+        x1 = x0d * 0.5  # new inputs reach the captured buffers
+        same_outputs(torch, graphed(eng, x1, u0d, cost, "euler", 0.02, **kw, **rkw), eng.solve_gn(x1, u0d, cost, "euler", 0.02, **kw, **rkw),
+                     "graph, new x0")
+        h = B // 2
+        for lo, hi in ((0, h), (h, B)):
+            hkw = {} if ref is None else dict(x_ref=dev(torch, ref[lo:hi]), ref_offset=1)
+            part = eng.solve_gn(x0d[lo:hi], u0d[lo:hi], cost, "euler", 0.02, **kw, **hkw)
+            for k in OUT_KEYS:
+                whole = eager[k][:, lo:hi] if k in ("costs", "alpha_hist") else eager[k][lo:hi]
+                assert torch.equal(part[k], whole), (k, lo)
+
+
+# ----------------------------------------------------------------------------- 6. footprint
+class GnSolveOp(fp.Op):
+    """phnn_solve_gn in a workspace of exactly phnn_gn_workspace_bytes, every output given."""
+
+    def __init__(self, eng, cost, x0, U, integ, dt, L, iters=2):
+        super().__init__()
+        B, H, m = U.shape
+        n = x0.shape[1]
+        self.name = f"solve_gn B{B} H{H} m{m} integ{integ} L{L}"
+        self.cost, self.integ, self.dt, self.B, self.H, self.L, self.iters = cost, integ, dt, B, H, L, iters
+        f = np.float32
+        self.add("x0", f, (B, n), fp.IN, x0)
+        self.add("u", f, (B, H, m), fp.INOUT, U)
+        self.add("cost_out", f, (B,), fp.OUT)
+        self.add("costs", f, (iters, B), fp.OUT)
+        self.add("mu", np.float64, (B,), fp.OUT)
+        self.add("accepts", np.int32, (B,), fp.OUT)
+        self.add("alpha", f, (iters, B), fp.OUT)
+        self.nws = eng.gn_workspace_bytes(B, H, L)
+        assert self.nws > 0
+        self.add("ws", np.uint8, (self.nws,), fp.WS)
+
+    def call(self, eng, p):
+        opt = eng._gn_options(self.iters, self.L, GN["mu_init"], GN["mu_min"], GN["mu_max"], GN["mu_up"], GN["mu_down"])
+        fp.check_rc(eng, eng.lib.phnn_solve_gn(eng.h, p["x0"], p["u"], self.B, self.H, C.byref(self.cost), None, self.integ,
+                                               float(self.dt), C.byref(opt), p["ws"], self.nws, p["cost_out"], p["costs"],
+                                               p["mu"], p["accepts"], p["alpha"], eng._stream()))
+
+    def engine(self, eng):
+        r = eng.solve_gn(self.input("x0"), self.input("u"), self.cost, {0: "euler", 1: "rk4"}[self.integ], self.dt,
+                         iters=self.iters, **dict(GN, line_steps=self.L))
+        return {"u": r["u_last"], "cost_out": r["cost"], "costs": r["costs"], "mu": r["mu"], "accepts": r["accepts"],
+                "alpha": r["alpha_hist"]}
+
+
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[1], SPECS[2], SPECS[4]])
+def test_footprint(torch, sid):
+    """Nothing outside the outputs and the workspace is written, the inputs are unchanged, the outputs do not depend on
+    what the workspace and the outputs held (0xFF fill == 0x00 fill) nor on what lies around the inputs, at a row-slice
+    skew and with ragged B; the sizes are positive, 0 for invalid arguments and monotone."""
+    s, eng = vc.CENSUS[sid], engine(sid)
+    rep = Report(f"gauss-newton {sid}")
+    for B in (1, 17):
+        for H, L in ((1, 1), (7, 4)):
+            rng = rng_of("gn-fp", sid, B, H)
+            x0, U, cost = 0.3 * vc.states(rng, s["n"], B), vc.controls(rng, B, H, s["m"]), vc.cost_of(s, rng, barrier=True)
+            for integ in (0, 1):
+                footprint(rep, torch, eng, GnSolveOp(eng, cost, x0, U, integ, vc.dt_of(s), L))
+    size = eng.gn_workspace_bytes
+    for bad in ((-1, 5, 4), (3, 0, 4), (3, 5, 0), (3, 5, 33)):
+        rep.note("F5", size(*bad) == 0, f"size{bad} != 0")
+    for a, b in (((3, 5, 4), (4, 5, 4)), ((3, 5, 4), (3, 6, 4)), ((3, 5, 4), (3, 5, 5)), ((0, 5, 4), (1, 5, 4))):
+        rep.note("F5", 0 < size(*a) <= size(*b), f"size{a} > size{b}")
+    rep.finish()
+
+
+# ----------------------------------------------------------------------------- 7. arguments
+def test_bad_arguments(torch):
+    from phnn_mpc_amd import _capi
+    sid = HEADLINE
+    s, eng = vc.CENSUS[sid], engine(sid)
+    lib, h, st = eng.lib, eng.h, eng._stream()
+    assert lib.phnn_version() >= 280
+    B, H, n, m, L, iters = 5, 3, 4, 1, 4, 2
+    f = dict(dtype=torch.float32, device="cuda:0")
+    t = dict(x0=torch.zeros(B, n, **f), u=torch.full((B, H, m), 0.25, **f), cost=torch.full((B,), 7.0, **f),
+             costs=torch.full((iters, B), 7.0, **f), mu=torch.full((B,), 7.0, dtype=torch.float64, device="cuda:0"),
+             accepts=torch.full((B,), 7, dtype=torch.int32, device="cuda:0"), alpha=torch.full((iters, B), 7.0, **f),
+             ws=torch.zeros(eng.gn_workspace_bytes(B, H, L), dtype=torch.uint8, device="cuda:0"),
+             xref=torch.zeros(B * L, 2, n, **f))
+    p = {k: C.c_void_p(v.data_ptr()) for k, v in t.items()}
+    cost = vc.cost_of(s, np.random.default_rng(0))
+    bad_cost = vc.cost_of(s, np.random.default_rng(0))
+    bad_cost.u_min, bad_cost.u_max = 1.0, -1.0
+
+    def opt(**kw):
+        a = dict(iters=iters, line_steps=L, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0, mu_down=0.1)
+        a.update({k: v for k, v in kw.items() if k != "reserved"})
+        o = eng._gn_options(**a)
+        o.reserved[1] = kw.get("reserved", 0)
+        return C.byref(o)
+
+    def ref(**kw):
+        r = _capi.Reference()
+        r.x_ref, r.batch_stride, r.time_stride, r.rows, r.offset_host = t["xref"].data_ptr(), 2 * n, n, 2, 0
+        for k, v in kw.items():
+            setattr(r, k, v)
+        return C.byref(r)
+
+    def solve(x0=p["x0"], u=p["u"], nb=B, hh=H, c=C.byref(cost), r=None, integ=0, dt=0.02, o=None, ws=p["ws"], size=None,
+              cost_out=p["cost"], costs=p["costs"], mu=p["mu"], accepts=p["accepts"], alpha=p["alpha"]):
+        return lib.phnn_solve_gn(h, x0, u, nb, hh, c, r, integ, dt, o or opt(), ws, t["ws"].numel() if size is None else size,
+                                 cost_out, costs, mu, accepts, alpha, st)
+
+    nan, inf = float("nan"), float("inf")
+    cases = [
+        (lambda: solve(x0=None), "NULL"), (lambda: solve(u=None), "NULL"), (lambda: solve(c=None), "cost is NULL"),
+        (lambda: solve(cost_out=None), "required"), (lambda: solve(mu=None), "required"), (lambda: solve(accepts=None), "required"),
+        (lambda: solve(ws=None), "workspace"), (lambda: solve(size=t["ws"].numel() - 1), "workspace"),
+        (lambda: solve(nb=-1), "negative batch"), (lambda: solve(hh=0), "horizon < 1"), (lambda: solve(integ=2), "integrator"),
+        (lambda: solve(dt=nan), "dt"), (lambda: solve(c=C.byref(bad_cost)), "u_min > u_max"),
+        (lambda: solve(o=opt(line_steps=0)), "line_steps"), (lambda: solve(o=opt(line_steps=33)), "line_steps"),
+        (lambda: solve(o=opt(iters=-1)), "iters"), (lambda: solve(o=opt(mu_init=-1e-9)), "mu field"),
+        (lambda: solve(o=opt(mu_init=nan)), "mu field"), (lambda: solve(o=opt(mu_min=inf)), "mu field"),
+        (lambda: solve(o=opt(mu_max=inf)), "mu field"), (lambda: solve(o=opt(mu_up=nan)), "mu field"),
+        (lambda: solve(o=opt(mu_down=-0.5)), "mu field"), (lambda: solve(o=opt(mu_min=2.0, mu_max=1.0)), "mu_min > mu_max"),
+        (lambda: solve(o=opt(mu_up=0.5)), "mu_up"), (lambda: solve(o=opt(mu_down=0.0)), "mu_down"),
+        (lambda: solve(o=opt(mu_down=1.5)), "mu_down"), (lambda: solve(o=opt(reserved=1)), "reserved"),
+        (lambda: solve(r=ref(rows=0)), "rows < 1"), (lambda: solve(r=ref(batch_stride=-1)), "negative batch_stride"),
+        (lambda: solve(r=ref(offset_host=-1)), "offset_host"), (lambda: solve(r=ref(x_ref=None)), "x_ref is NULL"),
+    ]
+    for k, (call, why) in enumerate(cases):
+        rc = call()
+        msg = lib.phnn_last_error(h).decode()
+        assert rc == INVALID, (k, rc, msg)
+        assert why in msg, (k, why, msg)
+    torch.cuda.synchronize()
+    for k in ("cost", "costs", "mu", "accepts", "alpha"):
+        assert bool((t[k] == 7).all()), k  # nothing was launched
+    assert bool((t["u"] == 0.25).all())
+    assert lib.phnn_solve_gn(h, None, None, 0, H, C.byref(cost), None, 0, 0.02, opt(), None, 0, None, None, None, None, None, st) == 0
+    # iters = 0: the set-up alone -- the state outputs are defined, the per-iteration ones have no rows
+    assert solve(o=opt(iters=0), costs=None, alpha=None) == 0
+    torch.cuda.synchronize()
+    c0 = eng.rollout_cost(t["x0"], t["u"], cost, "euler", 0.02)
+    assert torch.equal(t["cost"], c0) and bool((t["mu"] == 1e-6).all()) and bool((t["accepts"] == 0).all())
+    assert bool((t["costs"] == 7).all()) and bool((t["alpha"] == 7).all())
+    assert solve() == 0 and solve(r=ref()) == 0 and solve(costs=None, alpha=None) == 0
+    torch.cuda.synchronize()
+    assert not bool((t["costs"] == 7).any()) and not bool((t["alpha"] == 7).any())
+
+
+# ----------------------------------------------------------------------------- 8. controllers
+CFG = os.path.join(vc.ROOT, "configs", "cartpole_mpc.yaml")
+
+
+@pytest.mark.parametrize("which", ["phnn", "canonical"])
+def test_controllers_route_gauss_newton_to_the_library_solve(torch, which):
+    from phnn_mpc_amd.models import pHNN, pHNN_Canonical
+    from phnn_mpc_amd.mpc_controller import MPCController
+    from phnn_mpc_amd.mpc_controller_canonical import MPCControllerCanonical
+    cls, name = (pHNN, "phnn_cartpole") if which == "phnn" else (pHNN_Canonical, "canonical_cartpole")
+    w = ol.load_weights(name)
+    model = cls(CFG)
+    model.load_state_dict({k: torch.tensor(v) for k, v in w.items()})
+    model.use_device("cuda:0")
+    rng = np.random.default_rng(51)
+    B = 8
+    x0 = (rng.uniform(-1, 1, size=(B, 4)) * [0.5, 0.2, 0.3, 0.3]).astype(np.float32)
+    if which == "phnn":
+        ctl = MPCController(phnn_model=model, horizon=12, dt=0.02, Q=[10.0, 200.0, 1.0, 10.0], R=0.01, u_min=-10.0, u_max=10.0,
+                            optimizer_type="GaussNewton", max_iterations=4, gn_line_steps=4)
+        out, m = ctl.solve_batch(x0, record_costs=True), 1
+    else:
+        ctl = MPCControllerCanonical(model, horizon=12, dt=0.02, optimizer="GaussNewton", optimizer_steps=4, gn_line_steps=4)
+        out, m = ctl.optimize_control_batch(x0), ctl.input_dim
+        assert torch.equal(out["best_u"], out["u_last"]) and torch.equal(out["best_cost"], out["cost"])
+    eng = ctl.engine
+    ref = eng.solve_gn(x0, torch.zeros(B, 12, m), ctl._cost(), "euler", 0.02, **ctl.gn_options())
+    same_outputs(torch, out, ref, which)
+    chain = np.vstack([npf(out["costs"]), npf(out["cost"])[None]])
+    assert np.all(chain[1:] <= chain[:-1]) and np.all(chain[-1] < chain[0])
+    ws = ctl._gn_ws["gn"]
+    again = ctl.solve_batch(x0, record_costs=True) if which == "phnn" else ctl.optimize_control_batch(x0)
+    same_outputs(torch, again, ref, which + " again")
+    assert ctl._gn_ws["gn"] is ws  # the workspace stays with the controller
+    ctl.use_graph = True
+    graphed = ctl.solve_batch(x0, record_costs=True) if which == "phnn" else ctl.optimize_control_batch(x0)
+    same_outputs(torch, graphed, ref, which + " graphed")
+    gains = ctl.feedback_gains(x0, out["u_last"], mu=1e-3)
+    assert not bool(gains["status"].any()) and bool(torch.isfinite(gains["K"]).all())
+
+
+def _load(cls, name, torch):
+    m = cls(CFG)
+    m.load_state_dict({k: torch.tensor(v) for k, v in ol.load_weights(name).items()})
+    return m
+
+
+def test_device_closed_loop_equals_host_loop(torch):
+    import yaml
+    from phnn_mpc_amd.closed_loop import BatchedCartPole, run_mpc_batch, run_mpc_batch_device
+    from phnn_mpc_amd.models import pHNN, pHNN_Canonical
+    from phnn_mpc_amd.mpc_controller import create_mpc_from_config
+    from phnn_mpc_amd.mpc_controller_canonical import create_mpc_controller
+    cfg = yaml.safe_load(open(CFG))
+    cfg["mpc"].update(optimizer="GaussNewton", optimizer_steps=2, gn_line_steps=4)
+    rng = np.random.default_rng(12)
+    X = rng.uniform(-1, 1, size=(8, 4)) * [0.2, 0.08, 0.1, 0.1]
+    T = 5
+    ref = (0.05 * rng.uniform(-1, 1, size=(8, T + 3, 4))).astype(np.float32)
+    for c in (create_mpc_from_config(_load(pHNN, "phnn_cartpole", torch), cfg),
+              create_mpc_controller(_load(pHNN_Canonical, "canonical_cartpole", torch), cfg)):
+        for x_ref in (None, ref):
+            host = run_mpc_batch(BatchedCartPole(0.02), c, X, T, x_ref=x_ref)
+            assert len(np.unique(host["controls"])) > T
+            for use_graph in (False, True):
+                dev_ = run_mpc_batch_device(c, X, T, use_graph=use_graph, x_ref=x_ref)
+                assert np.array_equal(dev_["controls"], host["controls"])
+                assert np.allclose(dev_["states"], host["states"], rtol=0, atol=1e-12)
+                assert np.array_equal(dev_["done_step"], host["done_step"])
+
+
+# ----------------------------------------------------------------------------- 9. convergence
+@pytest.mark.parametrize("name", ["phnn_cartpole", "canonical_cartpole"])
+def test_two_iterations_reach_below_the_adam_solve(torch, name):
+    from phnn_mpc_amd.engine import RolloutEngine
+    x0, cost, H, lr, iters = gm.convergence_case()
+    eng = RolloutEngine(ol.load_weights(name), "cuda:0")
+    u0 = torch.zeros(x0.shape[0], H, 1)
+    adam = eng.solve(x0, u0, cost, "euler", 0.02, lr=lr, iters=iters, track_best=True)
+    gn = eng.solve_gn(x0, u0, cost, "euler", 0.02, iters=gm.CONVERGENCE_ITERS)
+    print(f"\n{name}: Adam best of {iters} {npf(adam['best_cost'])}, Gauss-Newton after {gm.CONVERGENCE_ITERS} {npf(gn['cost'])}")
+    assert bool((gn["cost"] <= adam["best_cost"]).all())
