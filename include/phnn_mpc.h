@@ -727,7 +727,8 @@ int phnn_tvlqr(phnn_handle* h, const float* A_dev, const float* Bm_dev, int64_t 
  *                 alpha_{j*} or 0 on reject.
  * cost_b is therefore non-increasing bit for bit; a diverged problem shows as NaN or status plus rejections.  Not part
  * of this solve: a closed-loop forward pass inside K1 (true iLQR), a box-QP at the bounds (a control on a bound that is
- * pushed outwards loses that component to the clamp and the line search decides), early termination per problem.
+ * pushed outwards loses that component to the clamp and the line search decides; phnn_solve_gn_ex with PHNN_GN_BOX, below,
+ * is the solve with it), early termination per problem.
  * All calls are stream-ordered and capturable, allocate nothing and do not synchronise; inputs are never written. */
 typedef struct {
   int32_t iters;      /* >= 0 */
@@ -775,6 +776,46 @@ int phnn_solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, 
                   const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
                   size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
                   float* alpha_hist_dev, void* stream);
+
+/* ---- box-constrained LQ step for the Gauss-Newton solve ------------------------------------------------
+ * Control-limited DDP (Tassa, Mansard, Todorov 2014) on the Gauss-Newton model of the solve above: launch 2 with the
+ * cost's control bounds inside the LQ step instead of only in the candidates' clamp.  k_gn_direction_box<n,m>, float64,
+ * no fused multiply-adds, one thread per problem, the same (n, m) and the same scratch as k_gn_direction.  Step t of the
+ * backward sweep:
+ *   lx, lu, S, T, Qxx, Qux, Quu = Luu + B^T T + mu_b I, its L D L^T, qx, qu and the pivot rule: exactly phnn_gn_direction's.
+ *   lo_i = (double)u_min - (double)u_t,i, hi_i = (double)u_max - (double)u_t,i (without has_u_bounds: -inf, +inf).  A nominal
+ *   with !(lo_i <= 0 <= hi_i) -- a NaN control with bounds is one -- fails like a pivot: status = t + 1.
+ *   d = Quu^-1 qu.  Where no component has -d_i < lo_i or -d_i > hi_i the step is phnn_gn_direction's, operation for
+ *   operation (K = -X, k = -d, P = Qxx - Qux^T X, p = qx - Qux^T d, dV += qu^T d).  Otherwise the box-QP
+ *   min 1/2 x^T Quu x + qu^T x, lo <= x <= hi, is solved by enumerating the active sets in the order of their codes
+ *   c = 1 .. 3^m - 1 (digit i of c in base 3: 0 free, 1 at lo_i, 2 at hi_i): the free block is solved with the same
+ *   L D L^T routine (on Quu with the fixed rows and columns replaced by the identity), the right-hand side corrected for
+ *   the fixed components; the first code with lo <= x_free <= hi and g = qu + Quu x >= 0 at lo, <= 0 at hi is taken; if
+ *   none passes (borderline rounding) the step fails like a pivot and the solve raises mu.  Then k_t = x, the rows of K_t
+ *   are -(Quu_FF)^-1 Qux_F for the free and 0 for the fixed components, and the value function takes the general form
+ *     P_t = Qxx + K^T Quu K + K^T Qux + Qux^T K (symmetrised),  p_t = qx + K^T Quu k + K^T qu + Qux^T k,
+ *     dV_b += -(2 qu^T k + k^T Quu k)        (= qu^T d when nothing is fixed; the predicted change stays -dV/2).
+ * Forward: dx_0 = 0, du_t = min(max(k_t + K_t dx_t, lo), hi), dx_{t+1} = A_t dx_t + B_t du_t; du is rounded once to float32,
+ * so u + du lies inside the bounds up to that one rounding (the candidates' clamp stays).  Failure (status != 0, dV or a
+ * du element not finite): du_b = 0, dV_b = quiet NaN as in phnn_gn_direction, nclamp_b = 0.  nclamp (B) int32: the
+ * (t, component) pairs the backward sweep held on a bound.  Where nothing is clamped in either sweep every output equals
+ * phnn_gn_direction's bit for bit.  tests/gn_box_model.py states every operation in its order.
+ * Arguments, checks (in the same order) and scratch size: phnn_gn_direction's; nclamp_dev may be NULL. */
+int phnn_gn_direction_box(phnn_handle* h, const float* A_dev, const float* Bm_dev, const float* traj_dev, const float* u_dev,
+                          int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref, const double* mu_dev,
+                          float* du_dev /* (B,H,m) */, double* dV_dev /* (B) */, int32_t* status_dev /* (B) */,
+                          int32_t* nclamp_dev /* (B) int32 or NULL */, double* scratch_dev, void* stream);
+#define PHNN_GN_BOX 1 /* flags of phnn_solve_gn_ex: launch 2 of every iteration is phnn_gn_direction_box */
+/* phnn_solve_gn with flags.  flags == 0 and nclamp_hist_dev == NULL: phnn_solve_gn itself, the same launches and the
+ * same bits.  PHNN_GN_BOX: the direction of every iteration is phnn_gn_direction_box; linearise, candidates, K1 and
+ * select are unchanged.  nclamp_hist_dev (iters,B) int32 or NULL: row `it` is the direction's nclamp, written by the
+ * kernel itself (the workspace, and phnn_gn_workspace_bytes, are those of phnn_solve_gn).  PHNN_ERR_INVALID_ARG, nothing
+ * launched: unknown flag bits, nclamp_hist_dev without PHNN_GN_BOX, and whatever phnn_solve_gn refuses.  Stream-ordered
+ * and capturable; the reference conventions are phnn_solve_gn's. */
+int phnn_solve_gn_ex(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                     const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
+                     size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
+                     float* alpha_hist_dev, int32_t flags, int32_t* nclamp_hist_dev /* (iters,B) or NULL */, void* stream);
 
 /* Introspection for tests: copies the packed weight image the kernels stage into LDS (phnn_kernels.hip.h layouts; a
  * device-resident private format) to image_host after the work queued on `stream`, and waits for the copy.

@@ -37,7 +37,10 @@ EXPORTED = [
     "phnn_mppi_sample_shaped", "phnn_cem_sample_shaped", "phnn_solve_mppi_shaped", "phnn_solve_cem_shaped",
     "phnn_plant_step_ex", "phnn_model_jacobian", "phnn_rollout_linearize", "phnn_tvlqr",
     "phnn_gn_workspace_bytes", "phnn_gn_direction", "phnn_gn_candidates", "phnn_gn_select", "phnn_solve_gn",
+    "phnn_gn_direction_box", "phnn_solve_gn_ex",
 ]
+
+PHNN_GN_BOX = 1  # flags of phnn_solve_gn_ex
 
 
 class MlpShape(C.Structure):
@@ -336,6 +339,11 @@ def load_library():
     lib.phnn_solve_gn.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float, gno, vp,
                                   C.c_size_t, f32p, f32p, vp, vp, f32p, vp]
     lib.phnn_solve_gn.restype = C.c_int
+    # phnn_gn_direction's arguments with nclamp before the scratch; phnn_solve_gn's with flags and nclamp_hist before the stream
+    lib.phnn_gn_direction_box.argtypes = lib.phnn_gn_direction.argtypes[:13] + [vp] + lib.phnn_gn_direction.argtypes[13:]
+    lib.phnn_gn_direction_box.restype = C.c_int
+    lib.phnn_solve_gn_ex.argtypes = lib.phnn_solve_gn.argtypes[:-1] + [i32, vp, vp]
+    lib.phnn_solve_gn_ex.restype = C.c_int
     lib.phnn_kernel_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i64]
     lib.phnn_kernel_info.restype = C.c_int
     lib.phnn_variant_name.argtypes = [vp]

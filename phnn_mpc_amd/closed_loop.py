@@ -238,7 +238,8 @@ class DeviceClosedLoop:
     and resets, iters x (k_sample, K1, k_mppi_update) -- with step_dev as the noise epoch, so every replay draws the
     noise run_mpc_batch draws at that step.  A 'CrossEntropy' controller: engine.solve_cem in the same way.  A
     'GaussNewton' controller: engine.solve_gn -- the clamp, the state reset and the set-up K1, then iters x
-    (k_rollout_linearize, k_gn_direction, k_gn_candidates, K1, k_gn_select) -- in a workspace kept across the steps.
+    (k_rollout_linearize, k_gn_direction, k_gn_candidates, K1, k_gn_select) -- in a workspace kept across the steps; a
+    controller with gn_box=True hands box=True on (gn_options), and the direction is k_gn_direction_box.
 
     x_ref: reference trajectories broadcastable to (B, rows, 4) (engine.reference_view); every solve tracks them from
     row step_dev, the device counter the plant step logs with and the shift advances, so each replay of the captured

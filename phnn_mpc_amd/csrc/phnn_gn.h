@@ -1,6 +1,7 @@
 // phnn_gn.h -- the three kernels of the batched Gauss-Newton solve (phnn_solve_gn) as the host side (phnn_mpc.hip) sees
 // them: the LQ direction, the line-search candidates and the selection.  Kernels in phnn_gn.hip.  DESIGN.md section 18;
-// tests/gn_model.py states the operation order of all three.
+// tests/gn_model.py states the operation order of all three.  The box-constrained direction of phnn_solve_gn_ex
+// (PHNN_GN_BOX) is DESIGN.md section 19 and tests/gn_box_model.py.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,14 @@ struct GnDirectionParams {
   int ref_rows;
   const int* ref_off_dev;
   int ref_off_host;
+};
+
+// k_gn_direction_box (tests/gn_box_model.py): the plain step's arguments and the control bounds
+struct GnDirectionBoxParams {
+  GnDirectionParams d;
+  double u_min, u_max;  // (double) of the cost's float bounds, read when has_u_bounds
+  int has_u_bounds;     // 0: the step's bounds are -inf / +inf
+  int* nclamp;          // (B) or NULL: (t, component) pairs held on a bound in the backward sweep; 0 on failure
 };
 
 struct GnCandidatesParams {
@@ -70,6 +79,7 @@ GnLayout gn_layout(long long B, int H, int n, int m, int L);
 
 // hipErrorInvalidValue: no kernel for (n, m)
 hipError_t gn_direction_launch(int n, int m, const GnDirectionParams& p, hipStream_t st);
+hipError_t gn_direction_box_launch(int n, int m, const GnDirectionBoxParams& p, hipStream_t st);
 hipError_t gn_candidates_launch(const GnCandidatesParams& p, hipStream_t st);
 hipError_t gn_select_launch(const GnSelectParams& p, hipStream_t st);
 // mu[b] = mu_init, accepts[b] = 0: the entry state of phnn_solve_gn

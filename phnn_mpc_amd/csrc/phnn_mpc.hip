@@ -573,7 +573,7 @@ hipError_t upload_image(phnn_handle* h, const std::vector<float>& img) {
 
 extern "C" {
 
-int phnn_version(void) { return 280; }
+int phnn_version(void) { return 290; }
 
 const char* phnn_variant_name(const phnn_handle* h) { return h ? h->ks.name : ""; }
 
@@ -1716,19 +1716,21 @@ size_t phnn_gn_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32
   return std::max<size_t>(gn_layout(B, H, h->desc.n, h->desc.m, line_steps).total, 256);
 }
 
-int phnn_gn_direction(phnn_handle* h, const float* A_dev, const float* Bm_dev, const float* traj_dev, const float* u_dev,
-                      int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref, const double* mu_dev,
-                      float* du_dev, double* dV_dev, int32_t* status_dev, double* scratch_dev, void* stream) {
-  if (!h) return PHNN_ERR_INVALID_ARG;
+// The checks and the kernel arguments that phnn_gn_direction and phnn_gn_direction_box share.  -> PHNN_OK with *launch
+// set when a kernel is to be launched (B > 0), else the refusal.
+static int fill_gn_direction(phnn_handle* h, const char* who, const float* A_dev, const float* Bm_dev, const float* traj_dev,
+                             const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref,
+                             const double* mu_dev, float* du_dev, double* dV_dev, int32_t* status_dev, double* scratch_dev,
+                             GnDirectionParams* out, bool* launch) {
+  *launch = false;
   if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
   if (int rc = check_cost(h, cost)) return rc;
   RollParams rp{};  // the reference checks, and its fields, are K1's
   if (int rc = fill_ref(h, &rp, ref, B)) return rc;
   if (B == 0) return PHNN_OK;
   if (!A_dev || !Bm_dev || !traj_dev || !u_dev || !mu_dev || !du_dev || !dV_dev || !status_dev || !scratch_dev)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_direction: NULL tensor");
+    return fail(h, PHNN_ERR_INVALID_ARG, who);
   if (!gn_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no Gauss-Newton direction kernel for this (n, m)");
-  PHNN_ON_DEVICE(h);
   const int n = h->desc.n, m = h->desc.m;
   GnDirectionParams p{};
   p.A = A_dev;
@@ -1756,7 +1758,42 @@ int phnn_gn_direction(phnn_handle* h, const float* A_dev, const float* Bm_dev, c
   p.ref_rows = ref ? rp.ref_rows : 1;
   p.ref_off_dev = rp.ref_off_dev;
   p.ref_off_host = rp.ref_off_host;
-  return checked(h, gn_direction_launch(n, m, p, (hipStream_t)stream), "k_gn_direction launch");
+  *out = p;
+  *launch = true;
+  return PHNN_OK;
+}
+
+int phnn_gn_direction(phnn_handle* h, const float* A_dev, const float* Bm_dev, const float* traj_dev, const float* u_dev,
+                      int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref, const double* mu_dev,
+                      float* du_dev, double* dV_dev, int32_t* status_dev, double* scratch_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  GnDirectionParams p;
+  bool launch;
+  if (int rc = fill_gn_direction(h, "phnn_gn_direction: NULL tensor", A_dev, Bm_dev, traj_dev, u_dev, B, H, cost, ref, mu_dev,
+                                 du_dev, dV_dev, status_dev, scratch_dev, &p, &launch))
+    return rc;
+  if (!launch) return PHNN_OK;
+  PHNN_ON_DEVICE(h);
+  return checked(h, gn_direction_launch(h->desc.n, h->desc.m, p, (hipStream_t)stream), "k_gn_direction launch");
+}
+
+int phnn_gn_direction_box(phnn_handle* h, const float* A_dev, const float* Bm_dev, const float* traj_dev, const float* u_dev,
+                          int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref, const double* mu_dev,
+                          float* du_dev, double* dV_dev, int32_t* status_dev, int32_t* nclamp_dev, double* scratch_dev,
+                          void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  GnDirectionBoxParams q{};
+  bool launch;
+  if (int rc = fill_gn_direction(h, "phnn_gn_direction_box: NULL tensor", A_dev, Bm_dev, traj_dev, u_dev, B, H, cost, ref,
+                                 mu_dev, du_dev, dV_dev, status_dev, scratch_dev, &q.d, &launch))
+    return rc;
+  if (!launch) return PHNN_OK;
+  q.u_min = (double)cost->u_min;  // check_cost has refused u_min > u_max
+  q.u_max = (double)cost->u_max;
+  q.has_u_bounds = cost->has_u_bounds;
+  q.nclamp = nclamp_dev;
+  PHNN_ON_DEVICE(h);
+  return checked(h, gn_direction_box_launch(h->desc.n, h->desc.m, q, (hipStream_t)stream), "k_gn_direction_box launch");
 }
 
 int phnn_gn_candidates(phnn_handle* h, const float* x0_dev, const float* u_dev, const float* du_dev, int64_t B, int32_t H,
@@ -1816,11 +1853,11 @@ int phnn_gn_select(phnn_handle* h, float* u_dev, float* traj_dev, float* cost_de
   return checked(h, gn_select_launch(p, (hipStream_t)stream), "k_gn_select launch");
 }
 
-int phnn_solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
-                  const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
-                  size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
-                  float* alpha_hist_dev, void* stream) {
-  if (!h) return PHNN_ERR_INVALID_ARG;
+// phnn_solve_gn and phnn_solve_gn_ex: box selects launch 2 of every iteration, nothing else differs.
+static int solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                    const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
+                    size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
+                    float* alpha_hist_dev, bool box, int32_t* nclamp_hist_dev, void* stream) {
   if (int rc = check_gn(h, opt, B, H)) return rc;
   RollParams rp;
   if (int rc = fill_roll(h, &rp, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
@@ -1863,7 +1900,14 @@ int phnn_solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, 
   const int64_t rollouts = B * (int64_t)L;
   for (int it = 0; it < opt->iters; ++it) {
     if (int rc = phnn_rollout_linearize(h, u_dev, B, H, cost, integrator, dt, traj, A, Bm, stream)) return rc;
-    if (int rc = phnn_gn_direction(h, A, Bm, traj, u_dev, B, H, cost, prefp, mu_out, du, dV, status, scratch, stream)) return rc;
+    if (box) {
+      // the nclamp row goes straight to the caller's history; without one the kernel writes none
+      if (int rc = phnn_gn_direction_box(h, A, Bm, traj, u_dev, B, H, cost, prefp, mu_out, du, dV, status,
+                                         nclamp_hist_dev ? nclamp_hist_dev + (size_t)it * B : nullptr, scratch, stream))
+        return rc;
+    } else if (int rc = phnn_gn_direction(h, A, Bm, traj, u_dev, B, H, cost, prefp, mu_out, du, dV, status, scratch, stream)) {
+      return rc;
+    }
     if (int rc = phnn_gn_candidates(h, x0_dev, u_dev, du, B, H, cost, L, cand, it == 0 ? x0_rep : nullptr, stream)) return rc;
     if (int rc = rollout_fwd(h, x0_rep, cand, rollouts, H, cost, integrator, dt, cand_cost, cand_traj, nullptr, ref, stream)) return rc;
     if (int rc = phnn_gn_select(h, u_dev, traj, cost_out, mu_out, accepts_dev, cand, cand_cost, cand_traj, status, B, H, opt,
@@ -1872,6 +1916,27 @@ int phnn_solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, 
       return rc;
   }
   return PHNN_OK;
+}
+
+int phnn_solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                  const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
+                  size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
+                  float* alpha_hist_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  return solve_gn(h, x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, workspace, workspace_size, cost_out, costs_dev, mu_out,
+                  accepts_dev, alpha_hist_dev, false, nullptr, stream);
+}
+
+int phnn_solve_gn_ex(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                     const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
+                     size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
+                     float* alpha_hist_dev, int32_t flags, int32_t* nclamp_hist_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (flags & ~PHNN_GN_BOX) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn_ex: unknown flag bits");
+  const bool box = (flags & PHNN_GN_BOX) != 0;
+  if (nclamp_hist_dev && !box) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn_ex: nclamp_hist_dev without PHNN_GN_BOX");
+  return solve_gn(h, x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, workspace, workspace_size, cost_out, costs_dev, mu_out,
+                  accepts_dev, alpha_hist_dev, box, nclamp_hist_dev, stream);
 }
 
 int phnn_read_image(phnn_handle* h, float* image_host, size_t n_floats, size_t* image_floats, void* stream) {

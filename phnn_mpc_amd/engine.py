@@ -789,12 +789,13 @@ class RolloutEngine:
             return mu.to(device=self.device, dtype=torch.float64).reshape(B).contiguous()
         return torch.full((B,), float(mu), dtype=torch.float64, device=self.device)
 
-    def gn_direction(self, A, Bm, traj, u, cost, mu, x_ref=None, ref_offset=0):
+    def gn_direction(self, A, Bm, traj, u, cost, mu, x_ref=None, ref_offset=0, box=False):
         """k_gn_direction: the Gauss-Newton step of every problem on its local model.  A (B,H,n,n), Bm (B,H,n,m) from
         rollout_linearize, traj (B,H+1,n), u (B,H,m), mu (B) float64 or one value; x_ref / ref_offset: problem b's
         reference as in rollout_cost.  -> dict(du (B,H,m) float32, dV (B) float64 -- the cost's slope along du is -dV,
         the predicted change at the full step -dV/2 --, status (B) int32 as tvlqr's).  A failed problem has du = 0 and
-        dV = NaN."""
+        dV = NaN.  box: k_gn_direction_box, the step with the cost's control bounds inside the LQ problem (DESIGN.md
+        section 19); the dict gains nclamp (B) int32, the (t, component) pairs held on a bound."""
         A = self._t(A)
         B, H = A.shape[0], A.shape[1]
         A = A.reshape(B, H, self.n, self.n)
@@ -805,9 +806,14 @@ class RolloutEngine:
         status = torch.empty(B, dtype=torch.int32, device=self.device)
         scratch = torch.empty(B * H * (self.m * self.n + self.m), dtype=torch.float64, device=self.device)
         ref, _keep = self._reference(x_ref, ref_offset, B)
-        rc = self.lib.phnn_gn_direction(self.h, self._p(A), self._p(Bm), self._p(traj), self._p(u), B, H, C.byref(cost),
-                                        None if ref is None else C.byref(ref), self._p(mu), self._p(du), self._p(dV),
-                                        self._p(status), self._p(scratch), self._stream())
+        head = (self.h, self._p(A), self._p(Bm), self._p(traj), self._p(u), B, H, C.byref(cost),
+                None if ref is None else C.byref(ref), self._p(mu), self._p(du), self._p(dV), self._p(status))
+        if box:
+            nclamp = torch.empty(B, dtype=torch.int32, device=self.device)
+            rc = self.lib.phnn_gn_direction_box(*head, self._p(nclamp), self._p(scratch), self._stream())
+            _check(self.lib, self.h, rc)
+            return dict(du=du, dV=dV, status=status, nclamp=nclamp)
+        rc = self.lib.phnn_gn_direction(*head, self._p(scratch), self._stream())
         _check(self.lib, self.h, rc)
         return dict(du=du, dV=dV, status=status)
 
@@ -847,14 +853,15 @@ class RolloutEngine:
 
     def solve_gn(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=10, line_steps=8, mu_init=1e-6, mu_min=1e-9,
                  mu_max=1e6, mu_up=10.0, mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0,
-                 expanded_ref=False):
+                 expanded_ref=False, box=False):
         """phnn_solve_gn: projected Gauss-Newton shooting on B independent problems as ONE library call: the iterate is
         clamped and costed, then iters x (k_rollout_linearize, k_gn_direction, k_gn_candidates, K1 over B * line_steps
         candidates, k_gn_select).  -> dict(u_last (B,H,m) in bounds, cost (B) its cost, costs (iters,B) the cost at the
         start of every iteration or None, mu (B) float64, accepts (B) int32, alpha_hist (iters,B) the accepted step
         lengths, 0 where rejected, or None), same results bit for bit as solver.gn_solve.  The cost of a problem never
         rises.  x_ref, ref_offset, expanded_ref: as in solve_mppi, with line_steps rollouts per problem.  The workspace
-        (a dict reused across calls) keeps the device buffer of phnn_gn_workspace_bytes."""
+        (a dict reused across calls) keeps the device buffer of phnn_gn_workspace_bytes.  box: phnn_solve_gn_ex with
+        PHNN_GN_BOX -- the direction is k_gn_direction_box -- and the dict gains nclamp_hist (iters,B) int32."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u_init, H = self._controls(u_init, B)
@@ -875,11 +882,17 @@ class RolloutEngine:
         accepts = torch.empty(B, dtype=torch.int32, device=self.device)
         ref, _keep = self._reference(x_ref if expanded_ref else self.mppi_reference(x_ref, B, opt.line_steps), ref_offset,
                                      B * max(opt.line_steps, 1))
-        rc = self.lib.phnn_solve_gn(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), None if ref is None else C.byref(ref),
-                                    integ, float(dt), C.byref(opt), self._p(ws["gn"]), ws["gn"].numel(), self._p(cost_b),
-                                    self._p(costs), self._p(mu), self._p(accepts), self._p(alpha), self._stream())
+        head = (self.h, self._p(x0), self._p(u), B, H, C.byref(cost), None if ref is None else C.byref(ref), integ, float(dt),
+                C.byref(opt), self._p(ws["gn"]), ws["gn"].numel(), self._p(cost_b), self._p(costs), self._p(mu),
+                self._p(accepts), self._p(alpha))
+        out = {"u_last": u, "cost": cost_b, "costs": costs, "mu": mu, "accepts": accepts, "alpha_hist": alpha}
+        if box:
+            out["nclamp_hist"] = torch.empty(rows, B, dtype=torch.int32, device=self.device)
+            rc = self.lib.phnn_solve_gn_ex(*head, _capi.PHNN_GN_BOX, self._p(out["nclamp_hist"]), self._stream())
+        else:
+            rc = self.lib.phnn_solve_gn(*head, self._stream())
         _check(self.lib, self.h, rc)
-        return {"u_last": u, "cost": cost_b, "costs": costs, "mu": mu, "accepts": accepts, "alpha_hist": alpha}
+        return out
 
     # ------------------------------------------------------------------ the plant, on the device
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,

@@ -32,7 +32,7 @@ class MPCController:
     def __init__(self, phnn_model, horizon, dt, Q, R, target_state=None, u_min=None, u_max=None, x_min=None, x_max=None,
                  optimizer_type="Adam", lr=0.1, max_iterations=50, samples=64, lam=1.0, sigma=1.0, seed=0, elites=8,
                  alpha=0.25, sigma_min=0.05, noise=None, gn_line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
-                 mu_down=0.1):
+                 mu_down=0.1, gn_box=False):
         self.model = phnn_model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -59,6 +59,8 @@ class MPCController:
         # optimizer_type='GaussNewton': candidates per line search, and the Levenberg-Marquardt term's start, range and factors
         self.gn_line_steps, self.mu_init, self.mu_min, self.mu_max = gn_line_steps, mu_init, mu_min, mu_max
         self.mu_up, self.mu_down = mu_up, mu_down
+        # gn_box: the LQ step of every iteration respects u_min / u_max (control-limited DDP)
+        self.gn_box = bool(gn_box)
         self.integrator = "euler"  # src/mpc_controller.py:137-138
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -198,8 +200,11 @@ class MPCController:
 
     def gn_options(self):
         """solve_gn keyword arguments of this controller."""
-        return dict(iters=self.max_iterations, line_steps=self.gn_line_steps, mu_init=self.mu_init, mu_min=self.mu_min,
-                    mu_max=self.mu_max, mu_up=self.mu_up, mu_down=self.mu_down)
+        opt = dict(iters=self.max_iterations, line_steps=self.gn_line_steps, mu_init=self.mu_init, mu_min=self.mu_min,
+                   mu_max=self.mu_max, mu_up=self.mu_up, mu_down=self.mu_down)
+        if self.gn_box:  # present only when set: the plain solve is called as before
+            opt["box"] = True
+        return opt
 
     def _solve_batch_gn(self, states, record_costs, x_ref, ref_offset):
         """B independent Gauss-Newton solves (cold start from zeros) in one batched device solve (engine.solve_gn); the
@@ -262,8 +267,8 @@ class MPCController:
 
 def _mppi_keys(mpc):
     """The solver keywords present in the `mpc` config section: samples, lam, sigma, seed, elites, alpha, sigma_min, noise
-    (optimizer: MPPI or CrossEntropy) and gn_line_steps, mu_init, mu_min, mu_max, mu_up, mu_down (GaussNewton)."""
-    keys = ("samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise", "gn_line_steps", "mu_init", "mu_min",
+    (optimizer: MPPI or CrossEntropy) and gn_line_steps, gn_box, mu_init, mu_min, mu_max, mu_up, mu_down (GaussNewton)."""
+    keys = ("samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise", "gn_line_steps", "gn_box", "mu_init", "mu_min",
             "mu_max", "mu_up", "mu_down")
     return {k: mpc[k] for k in keys if k in mpc}
 

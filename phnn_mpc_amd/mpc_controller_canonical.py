@@ -29,7 +29,7 @@ class MPCControllerCanonical:
     def __init__(self, model, horizon=20, dt=0.02, Q=None, R=None, x_target=None, u_min=-10.0, u_max=10.0,
                  optimizer_steps=50, learning_rate=0.1, verbose=False, optimizer="Adam", samples=64, lam=1.0, sigma=1.0,
                  seed=0, elites=8, alpha=0.25, sigma_min=0.05, noise=None, gn_line_steps=8, mu_init=1e-6, mu_min=1e-9,
-                 mu_max=1e6, mu_up=10.0, mu_down=0.1):
+                 mu_max=1e6, mu_up=10.0, mu_down=0.1, gn_box=False):
         self.model = model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -59,6 +59,8 @@ class MPCControllerCanonical:
         # optimizer='GaussNewton': candidates per line search, and the Levenberg-Marquardt term's start, range and factors
         self.gn_line_steps, self.mu_init, self.mu_min, self.mu_max = gn_line_steps, mu_init, mu_min, mu_max
         self.mu_up, self.mu_down = mu_up, mu_down
+        # gn_box: the LQ step of every iteration respects u_min / u_max (control-limited DDP)
+        self.gn_box = bool(gn_box)
         self.integrator = "euler"
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -194,8 +196,11 @@ class MPCControllerCanonical:
 
     def gn_options(self):
         """solve_gn keyword arguments of this controller."""
-        return dict(iters=self.optimizer_steps, line_steps=self.gn_line_steps, mu_init=self.mu_init, mu_min=self.mu_min,
-                    mu_max=self.mu_max, mu_up=self.mu_up, mu_down=self.mu_down)
+        opt = dict(iters=self.optimizer_steps, line_steps=self.gn_line_steps, mu_init=self.mu_init, mu_min=self.mu_min,
+                   mu_max=self.mu_max, mu_up=self.mu_up, mu_down=self.mu_down)
+        if self.gn_box:  # present only when set: the plain solve is called as before
+            opt["box"] = True
+        return opt
 
     def _solve_batch_gn(self, x0, u0, record_costs, x_ref, ref_offset):
         """The Gauss-Newton solve of optimize_control_batch (engine.solve_gn); the workspace stays with the controller.
@@ -231,5 +236,5 @@ def create_mpc_controller(model, config):
         u_max=mpc.get("u_max", 10.0), optimizer_steps=mpc.get("optimizer_steps", 50),
         learning_rate=mpc.get("learning_rate", 0.1), verbose=mpc.get("verbose", False),
         **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise",
-                                   "gn_line_steps", "mu_init", "mu_min", "mu_max", "mu_up", "mu_down")
+                                   "gn_line_steps", "gn_box", "mu_init", "mu_min", "mu_max", "mu_up", "mu_down")
            if k in mpc})

@@ -190,7 +190,7 @@ def _cem_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, elites,
 
 
 def gn_solve(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
-             mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+             mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0, box=False):
     """Projected Gauss-Newton shooting with Levenberg-Marquardt regularisation and a parallel backtracking line search on
     B independent problems: x0 (B,n), u_init (B,H,m) -> dict(u_last, cost, costs, mu, accepts, alpha_hist).
 
@@ -203,7 +203,9 @@ def gn_solve(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_i
     costs     : (iters,B) cost of the iterate at the START of every iteration, if record_costs
     mu        : (B) float64, accepts: (B) int32 accepted iterations, alpha_hist: (iters,B) accepted step length or 0
     x_ref, ref_offset: as in shooting_solve (one reference per problem; the candidates of a problem share it).
-    The Python loop that engine.solve_gn (phnn_solve_gn) is pinned to bit for bit."""
+    box       : the direction is the box-constrained LQ step (engine.gn_direction(..., box=True), DESIGN.md section 19);
+                the result gains nclamp_hist (iters,B) int32, the (t, component) pairs each direction held on a bound
+    The Python loop that engine.solve_gn (phnn_solve_gn, phnn_solve_gn_ex) is pinned to bit for bit."""
     _need_reference(engine, x_ref)
     B, L = u_init.shape[0], int(line_steps)
     rkw_b, rkw_r = {}, {}
@@ -218,23 +220,31 @@ def gn_solve(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_i
     alpha = torch.empty(iters, B, dtype=torch.float32, device=dev) if record_costs else None
     mu = torch.full((B,), float(mu_init), dtype=torch.float64, device=dev)
     accepts = torch.zeros(B, dtype=torch.int32, device=dev)
+    nclamp = torch.empty(iters, B, dtype=torch.int32, device=dev) if box else None
+    bkw = {"box": True} if box else {}  # an engine without the box step is never handed the keyword
     c, traj = engine.rollout_cost(x0, u, cost, integrator, dt, want_traj=True, **rkw_b)
     for it in range(iters):
         A, Bm, _ = engine.rollout_linearize(x0, u, cost, integrator, dt, traj=traj)
-        d = engine.gn_direction(A, Bm, traj, u, cost, mu, **rkw_b)
+        d = engine.gn_direction(A, Bm, traj, u, cost, mu, **rkw_b, **bkw)
+        if box:
+            nclamp[it].copy_(d["nclamp"])
         cand, x0_rep = engine.gn_candidates(x0, u, d["du"], cost, L)
         s, ctraj = engine.rollout_cost(x0_rep, cand, cost, integrator, dt, want_traj=True, **rkw_r)
         engine.gn_select(u, traj, c, mu, accepts, cand, s, ctraj, d["status"], L, mu_min, mu_max, mu_up, mu_down,
                          costs_row=costs[it] if record_costs else None, alpha_row=alpha[it] if record_costs else None)
-    return {"u_last": u, "cost": c, "costs": costs, "mu": mu, "accepts": accepts, "alpha_hist": alpha}
+    out = {"u_last": u, "cost": c, "costs": costs, "mu": mu, "accepts": accepts, "alpha_hist": alpha}
+    if box:
+        out["nclamp_hist"] = nclamp
+    return out
 
 
 def _gn_eager(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
-              mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0):
+              mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0, box=False):
     """The Gauss-Newton solve without a captured graph (_library_or); called as gn_solve is."""
+    bkw = {"box": True} if box else {}
     return _library_or(engine, "solve_gn", gn_solve)(
         x0, u_init, cost, integrator, dt, iters=iters, line_steps=line_steps, mu_init=mu_init, mu_min=mu_min, mu_max=mu_max,
-        mu_up=mu_up, mu_down=mu_down, record_costs=record_costs, workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
+        mu_up=mu_up, mu_down=mu_down, record_costs=record_costs, workspace=workspace, x_ref=x_ref, ref_offset=ref_offset, **bkw)
 
 
 def capture(device, fn):
