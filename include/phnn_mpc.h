@@ -817,6 +817,72 @@ int phnn_solve_gn_ex(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t 
                      size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
                      float* alpha_hist_dev, int32_t flags, int32_t* nclamp_hist_dev /* (iters,B) or NULL */, void* stream);
 
+/* ---- batched extended Kalman filter on the learned model --------------------------------------------------
+ * The estimator between a noisy or partial measurement and the solve, per problem b of B independent ones.  The
+ * measurement is a selection of state components: bit i of meas_mask set means component i is measured, p = popcount,
+ * 0 <= p <= n.  k_ekf_update<n>, n in {2, 3, 4}: one thread per problem, float64, no fused multiply-adds, every inner
+ * product with its index ascending from an accumulator 0, each product rounded, then added; tests/ekf_model.py states the
+ * remaining order and the kernel equals it bit for bit.  With x- the predicted state (float32, widened), A the Jacobian
+ * of the prediction step (float32, widened), P the covariance (float64, in/out), y the measurement row (float32; ONLY
+ * the measured components are read):
+ *   predict     M = A P,  P- = M A^T + Qn,  symmetrised as 0.5 (P- + P-^T)
+ *   innovation  nu_a = (double)y[i_a] - (double)x-[i_a] over the measured components i_a;  S = P-[idx, idx] with Rn[i_a]
+ *               added on the diagonal;  S = L D L^T without square roots, with phnn_tvlqr's pivot rule (a pivot d with
+ *               !(d > 0) or d = +inf is a failure)
+ *   gain        K = P-[:, idx] S^-1 by column solves with those factors
+ *   state       xhat_i = (double)x-_i + sum_a K[i][a] nu_a, rounded once to float32
+ *   covariance  Joseph form: G = I - K C,  P = G P- G^T + K diag(Rn[idx]) K^T,  symmetrised
+ *   nis         sum_a nu_a (S^-1 nu)_a   (chi-square with p degrees of freedom for a consistent filter)
+ * status (B) int32 and the special cases:
+ *   0  updated; or p = 0: no update, xhat = x- as floats, P = P-, nis = quiet NaN
+ *   1  a measured component of y is not finite (a dropped measurement): no update, as for p = 0
+ *   2  a pivot failure, or an x- or A that is not finite: xhat and P are all quiet NaN, nis too -- never a finite wrong
+ *      estimate
+ * Qn (n x n, row-major in the leading n*n entries) is read as given; Rn[i] is read for measured components only.
+ * Optional outputs (NULL = skip): nis_dev (B) float64; innov_dev (B,n) float64, 0 at unmeasured components; and through
+ * a phnn_ekf_log one row each of log_xhat_dev (T+1,B,n) float32 at row step + 1 and log_nis_dev (T,B) float64 at row
+ * step, the step index being *step_dev when step_dev != NULL (a device counter, so that a captured graph can be
+ * replayed), else step_host -- as in the plant step.
+ * All calls are stream-ordered and capturable, allocate nothing and do not synchronise; B == 0 returns PHNN_OK with
+ * nothing launched; sizes are exact and inputs are never written.  For n = 4 the float32 state rows (xhat, y, x-) are
+ * 16-byte aligned and A follows the rule of the linearisation above.
+ * PHNN_ERR_INVALID_ARG, nothing launched and no output touched: NULL required buffers, B < 0, mask bits at or above n, a
+ * non-finite Qn entry, a non-positive or non-finite Rn at a measured component, non-zero reserved, a log without a step
+ * source (step_dev == NULL and step_host < 0), and for the step an unknown integrator, a non-finite dt or u_min > u_max;
+ * PHNN_ERR_UNSUPPORTED for n outside {2, 3, 4}. */
+typedef struct {
+  uint32_t meas_mask;                  /* bit i: component i is measured */
+  double Qn[PHNN_MAX_N * PHNN_MAX_N];  /* process noise covariance, (n,n) row-major in the leading entries, finite */
+  double Rn[PHNN_MAX_N];               /* measurement noise variances, > 0 and finite where measured */
+  int32_t reserved[4];                 /* zero */
+} phnn_ekf_options;
+typedef struct {
+  float* log_xhat_dev;      /* (T+1,B,n) float32, row step + 1 receives xhat, or NULL */
+  double* log_nis_dev;      /* (T,B) float64, row step receives nis, or NULL */
+  const int32_t* step_dev;  /* device step counter, or NULL */
+  int32_t step_host;        /* used when step_dev == NULL */
+} phnn_ekf_log;
+/* Bytes of the workspace of the step below: the control row (B,1,m), K1's trajectory (B,2,n) and cost (B), A (B,n,n)
+ * and Bm (B,n,m), each region 256-byte aligned.  0 for invalid arguments (B < 0, n outside {2, 3, 4}). */
+size_t phnn_ekf_workspace_bytes(const phnn_handle* h, int64_t B);
+/* The kernel on its own; A and x- may come from anywhere.  Problem b's prediction is xpred_dev[b * xpred_stride + i] (so
+ * that row 1 of a (B,2,n) trajectory is read in place with stride 2n) and its measurement y_dev[b * y_stride + i].
+ * A_dev (B,n,n), P_dev (B,n,n) float64 in/out, xhat_dev (B,n), status_dev (B) int32; nis_dev, innov_dev, log may be
+ * NULL. */
+int phnn_ekf_update(phnn_handle* h, const float* xpred_dev, int64_t xpred_stride, const float* A_dev, const float* y_dev,
+                    int64_t y_stride, int64_t B, const phnn_ekf_options* opt, double* P_dev, float* xhat_dev, double* nis_dev,
+                    double* innov_dev, int32_t* status_dev, const phnn_ekf_log* log, void* stream);
+/* One filter step through the learned model: xhat_dev (B,n) and P_dev (B,n,n) in/out.  u_dev[b * u_stride + k], k < m,
+ * is the control applied during the step (stride H*m: the first control of a solve's sequence, in place); cost is read
+ * for has_u_bounds / u_min / u_max only, NULL = no clamp -- the clamp of the control is K1's and the plant's.  Four
+ * launches in stream order: k_ekf_controls (the control row), K1 with H = 1 from xhat on the path of the forward
+ * rollout above (its trajectory into the workspace), the linearisation above with H = 1, k_ekf_update on row 1 of that
+ * trajectory.  workspace_dev: the bytes of the size query above, required when B > 0. */
+int phnn_ekf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u_dev, int64_t u_stride, const float* y_dev,
+                  int64_t y_stride, int64_t B, const phnn_cost* cost, int32_t integrator, float dt,
+                  const phnn_ekf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                  const phnn_ekf_log* log, void* workspace_dev, void* stream);
+
 /* Introspection for tests: copies the packed weight image the kernels stage into LDS (phnn_kernels.hip.h layouts; a
  * device-resident private format) to image_host after the work queued on `stream`, and waits for the copy.
  * *image_floats (may be NULL) receives its size; image_host == NULL only queries the size. */

@@ -38,6 +38,7 @@ EXPORTED = [
     "phnn_plant_step_ex", "phnn_model_jacobian", "phnn_rollout_linearize", "phnn_tvlqr",
     "phnn_gn_workspace_bytes", "phnn_gn_direction", "phnn_gn_candidates", "phnn_gn_select", "phnn_solve_gn",
     "phnn_gn_direction_box", "phnn_solve_gn_ex",
+    "phnn_ekf_workspace_bytes", "phnn_ekf_update", "phnn_ekf_step",
 ]
 
 PHNN_GN_BOX = 1  # flags of phnn_solve_gn_ex
@@ -113,6 +114,19 @@ class GnOptions(C.Structure):
     mu_up (cap mu_max) after a rejected one."""
     _fields_ = [("iters", C.c_int32), ("line_steps", C.c_int32), ("mu_init", C.c_double), ("mu_min", C.c_double),
                 ("mu_max", C.c_double), ("mu_up", C.c_double), ("mu_down", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class EkfOptions(C.Structure):
+    """phnn_ekf_options: bit i of meas_mask set = state component i is measured; Qn (n,n) row-major process noise
+    covariance in the leading entries; Rn the measurement noise variances (read where measured)."""
+    _fields_ = [("meas_mask", C.c_uint32), ("Qn", C.c_double * (PHNN_MAX_N * PHNN_MAX_N)), ("Rn", C.c_double * PHNN_MAX_N),
+                ("reserved", C.c_int32 * 4)]
+
+
+class EkfLog(C.Structure):
+    """phnn_ekf_log: row step + 1 of log_xhat (T+1,B,n) float32 and row step of log_nis (T,B) float64; the step is
+    *step_dev (device int32) when given, else step_host."""
+    _fields_ = [("log_xhat_dev", C.c_void_p), ("log_nis_dev", C.c_void_p), ("step_dev", C.c_void_p), ("step_host", C.c_int32)]
 
 
 class Plant(C.Structure):
@@ -344,6 +358,14 @@ def load_library():
     lib.phnn_gn_direction_box.restype = C.c_int
     lib.phnn_solve_gn_ex.argtypes = lib.phnn_solve_gn.argtypes[:-1] + [i32, vp, vp]
     lib.phnn_solve_gn_ex.restype = C.c_int
+    eko, ekl = C.POINTER(EkfOptions), C.POINTER(EkfLog)
+    lib.phnn_ekf_workspace_bytes.argtypes = [vp, i64]
+    lib.phnn_ekf_workspace_bytes.restype = C.c_size_t
+    lib.phnn_ekf_update.argtypes = [vp, f32p, i64, f32p, f32p, i64, i64, eko, vp, f32p, vp, vp, vp, ekl, vp]
+    lib.phnn_ekf_update.restype = C.c_int
+    lib.phnn_ekf_step.argtypes = [vp, f32p, vp, f32p, i64, f32p, i64, i64, C.POINTER(Cost), i32, C.c_float, eko, vp, vp, vp,
+                                  ekl, vp, vp]
+    lib.phnn_ekf_step.restype = C.c_int
     lib.phnn_kernel_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i64]
     lib.phnn_kernel_info.restype = C.c_int
     lib.phnn_variant_name.argtypes = [vp]

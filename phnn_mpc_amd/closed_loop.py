@@ -21,6 +21,12 @@
                          per-plant gravity / masses / length, a constant force bias, Gaussian force and measurement
                          noise, and a freeze at termination (include/phnn_mpc.h: phnn_plant_step_ex).
                          The device loop can also keep per-plant metrics (metrics=) and drop the logs (log=False).
+  estimator              (all three drivers, estimator=) an estimation.EKF between the measurement and the solve: the
+                         controller solves from the estimate xhat instead of the raw float32 measurement, and after every
+                         plant step the filter advances with the control the plant applied and the new measurement
+                         (phnn_ekf_step).  Only the `measured` components of the measurement are used, so a
+                         loop can run on positions alone.  The result gains estimates (T+1,B,4) float32, nis (T,B) and
+                         ekf_status (B,), the last step's.
 """
 import numpy as np
 
@@ -186,11 +192,14 @@ class BatchedCartPole:
         return self.state.copy()
 
 
-def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, scenario=None):
+def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, scenario=None, estimator=None):
     """-> dict(states (T+1,B,4), controls (T,B,1), done_step (B,) first step a plant terminated at, or -1).
     x_ref: reference trajectories broadcastable to (B, rows, 4); control step s tracks them from row s.
     scenario: a PlantScenario for the simulator (a BatchedCartPole built with scenario= / replay= has its own); the
-    result then also holds disturbance (T,B) float32, what each step added to the commanded force."""
+    result then also holds disturbance (T,B) float32, what each step added to the commanded force.
+    estimator: an estimation.EKF; every solve starts from its estimate, and after every plant step EKF.step advances it
+    on the controller's engine with the applied control and the new measurement.  The result then also holds estimates
+    (T+1,B,4) float32, nis (T,B) and ekf_status (B,)."""
     if scenario is not None:
         simulator.scenario = scenario
     measured = hasattr(simulator, "measurement")
@@ -203,11 +212,21 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
     from .solver import SAMPLING
     sampling = getattr(controller, "optimizer", getattr(controller, "optimizer_type", None)) in SAMPLING
     dist = []
+    if estimator is not None:
+        import torch
+        eng = controller.engine
+        xh0, P0 = estimator.initial(x)
+        xhat, P = torch.tensor(xh0, device=eng.device), torch.tensor(P0, device=eng.device)
+        ekf_opt, ekf_cost = estimator.options(eng.n), (None if canonical else controller._cost())
+        estimates, nis, ekf_status = [xh0], [], None
     for step in range(num_steps):
         rkw = {"epoch": step} if sampling else {}  # the noise counter of an MPPI / CrossEntropy solve: the control step
         if x_ref is not None:
             rkw.update(x_ref=x_ref, ref_offset=step)
-        x32 = simulator.measurement() if measured else x.astype(np.float32)
+        if estimator is not None:
+            x32 = xhat.cpu().numpy()
+        else:
+            x32 = simulator.measurement() if measured else x.astype(np.float32)
         if canonical:
             u, u_prev, _ = controller.control_batch(x32, u_prev, **rkw)
         else:
@@ -219,9 +238,20 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
         controls.append(np.asarray(u, dtype=np.float64).reshape(B, -1))
         if getattr(simulator, "disturbance", None) is not None:
             dist.append(simulator.disturbance.copy())
+        if estimator is not None:  # the filter advances with the control the plant applied and the new measurement
+            y32 = simulator.measurement() if measured else x.astype(np.float32)
+            r = estimator.step(eng, xhat, P, torch.as_tensor(np.asarray(u, dtype=np.float32).reshape(B, -1)),
+                               torch.tensor(np.ascontiguousarray(y32, dtype=np.float32), device=eng.device), ekf_cost,
+                               controller.integrator, controller.dt, opt=ekf_opt)
+            xhat, P, ekf_status = r["xhat"], r["P"], r["status"]
+            estimates.append(xhat.cpu().numpy())
+            nis.append(r["nis"].cpu().numpy())
     out = {"states": np.stack(states), "controls": np.stack(controls), "done_step": done_step}
     if dist:
         out["disturbance"] = np.stack(dist)
+    if estimator is not None:
+        out.update(estimates=np.stack(estimates), nis=np.stack(nis) if nis else np.zeros((0, B)),
+                   ekf_status=None if ekf_status is None else ekf_status.cpu().numpy().astype(np.int64))
     return out
 
 
@@ -255,10 +285,19 @@ class DeviceClosedLoop:
     the longest run inside the stability band; the result gains cost (B,), longest_run_s (B,) and stable (B,), the
     latter two equal to stability_report over states 0..T.  log=False: the (T+1,B,4) and (T,B) logs are neither
     allocated nor written; states, controls (and disturbance) are None.  With none of the three the loop is what it was.
+
+    estimator: an estimation.EKF.  The plant step then writes its float32 measurement into a buffer of its own (y32), the
+    solve reads the estimate (xhat32), and between the plant step and the shift / step advance engine.ekf_step -- the
+    control row, K1 with H = 1, its linearisation, k_ekf_update -- advances the estimate with the control the plant
+    applied (read in place from the solve's sequence, with the plant's bounds) and y32; all of it inside the captured
+    control step.  The result gains estimates (T+1,B,4) float32 and nis (T,B) (None with the estimator's log=False) and
+    ekf_status (B,), the last step's.  The filter predicts over the controller's dt: an estimator together with a dt=
+    other than controller.dt is refused (ValueError).  Without an estimator the loop is what it was: same launches, same
+    bits.
     """
 
     def __init__(self, controller, initial_states, num_steps, use_graph=True, dt=None, x_ref=None, scenario=None,
-                 metrics=False, log=True):
+                 metrics=False, log=True, estimator=None):
         import torch
         from . import _capi
         self.torch, self.ctl = torch, controller
@@ -312,6 +351,41 @@ class DeviceClosedLoop:
             self._scenario(scenario, log)
         if metrics:
             self._metrics(STABILITY_DEFAULTS if metrics is True else metrics, x)
+        self.ekf = estimator
+        if estimator is not None:
+            self._estimator(estimator, x)
+
+    def _estimator(self, est, x0):
+        """The filter's state and buffers: the estimate the solve reads, the covariance, the measurement the plant
+        writes, the logs and the options."""
+        torch, eng, B, k = self.torch, self.eng, self.B, self._keep
+        if self.plant.dt != float(self.ctl.dt):  # the filter predicts over the controller's dt, as the solve does
+            raise ValueError(f"estimator: the plant's dt ({self.plant.dt}) differs from the controller's ({self.ctl.dt}); "
+                             "the filter's one-step prediction would cover another interval than the plant stepped")
+        if not hasattr(eng, "ekf_step"):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched filter step (RolloutEngine has)")
+        dev = eng.device
+        xh0, P0 = est.initial(x0)
+        self.y32 = self.x32  # the plant keeps writing its measurement here
+        self.x32 = self.xhat32 = torch.tensor(xh0, device=dev)  # what every solve reads: the estimate
+        self.P = torch.tensor(P0, device=dev)
+        self.ekf_opt = est.options(eng.n)
+        self.ekf_cost = None if self.canonical else self.cost  # the plant's clamp: the canonical sequence is clamped already
+        k["ekf_status"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        k["ekf_nis"] = torch.empty(B, dtype=torch.float64, device=dev)
+        self.ekf_ws = {}  # the device buffer of the filter step, kept across steps
+        self.ekf_log = None
+        if est.log:
+            k["estimates"] = torch.empty(self.T + 1, B, eng.n, dtype=torch.float32, device=dev)
+            k["estimates"][0].copy_(self.xhat32)
+            k["nis"] = torch.empty(self.T, B, dtype=torch.float64, device=dev)
+            self.ekf_log = dict(log_xhat=k["estimates"], log_nis=k["nis"], step_dev=self.step_dev)
+
+    def _ekf_step(self, u, stride):
+        c = self.ctl
+        self.eng.ekf_step(self.xhat32, self.P, u, stride, self.y32, self.ekf_cost, c.integrator, c.dt, self.ekf_opt,
+                          nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"], log=self.ekf_log,
+                          workspace=self.ekf_ws)
 
     def _scenario(self, sc, log):
         """Fills self.ex (phnn_plant_ex) from a PlantScenario."""
@@ -361,8 +435,8 @@ class DeviceClosedLoop:
 
     def _control_step(self):
         eng, c = self.eng, self.ctl
-        log = dict(state_f32=self.x32, done_step=self.done_step, step_dev=self.step_dev, log_states=self.log_states,
-                   log_controls=self.log_controls)
+        log = dict(state_f32=self.x32 if self.ekf is None else self.y32, done_step=self.done_step, step_dev=self.step_dev,
+                   log_states=self.log_states, log_controls=self.log_controls)
         if self.ex is not None or self.metrics is not None:
             log.update(ex=self.ex, metrics=self.metrics)
         H = self.u_init.shape[1] * self.u_init.shape[2]
@@ -381,9 +455,13 @@ class DeviceClosedLoop:
                             ref_offset=self.step_dev)
         if self.canonical:  # best clamped iterate; next call warm-starts from its shift
             eng.plant_step(self.plant, self.state, out["best_u"], H, **log)
+            if self.ekf is not None:
+                self._ekf_step(out["best_u"], H)
             eng.shift_controls(out["best_u"], self.u_init, step_dev=self.step_dev)
         else:  # last iterate, clamp(u_0); every call cold-starts from zeros (u_init stays zero)
             eng.plant_step(self.plant, self.state, out["u_last"], H, u_min=c.u_min, u_max=c.u_max, **log)
+            if self.ekf is not None:
+                self._ekf_step(out["u_last"], H)
             eng.advance_step(self.step_dev)
 
     def _solve_sampling(self):
@@ -415,15 +493,20 @@ class DeviceClosedLoop:
         if self.metrics is not None:
             best = self._keep["best_run"].cpu().numpy().astype(np.int64)
             out.update(cost=self._keep["cost"].cpu().numpy(), longest_run_s=best * self.plant.dt, stable=best >= self.need)
+        if self.ekf is not None:
+            kept = self.ekf_log is not None
+            out.update(estimates=self._keep["estimates"].cpu().numpy() if kept else None,
+                       nis=self._keep["nis"].cpu().numpy() if kept else None,
+                       ekf_status=self._keep["ekf_status"].cpu().numpy().astype(np.int64))
         return out
 
 
 def run_mpc_batch_device(controller, initial_states, num_steps, use_graph=True, x_ref=None, scenario=None, metrics=False,
-                         log=True):
+                         log=True, estimator=None):
     """Device-resident version of run_mpc_batch: same return dict, one host synchronisation at the end.  scenario,
-    metrics, log: as in DeviceClosedLoop."""
+    metrics, log, estimator: as in DeviceClosedLoop."""
     return DeviceClosedLoop(controller, initial_states, num_steps, use_graph=use_graph, x_ref=x_ref, scenario=scenario,
-                            metrics=metrics, log=log).run()
+                            metrics=metrics, log=log, estimator=estimator).run()
 
 
 def stability_report(states, target, tolerance, min_duration, dt):

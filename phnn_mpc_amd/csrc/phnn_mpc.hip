@@ -19,6 +19,7 @@
 #include "phnn_lbfgs.h"
 #include "phnn_sampling.h"
 #include "phnn_gn.h"
+#include "phnn_ekf.h"
 #include "phnn_pack.h"
 
 namespace {
@@ -1937,6 +1938,116 @@ int phnn_solve_gn_ex(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t 
   if (nclamp_hist_dev && !box) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn_ex: nclamp_hist_dev without PHNN_GN_BOX");
   return solve_gn(h, x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, workspace, workspace_size, cost_out, costs_dev, mu_out,
                   accepts_dev, alpha_hist_dev, box, nclamp_hist_dev, stream);
+}
+
+// ---- batched extended Kalman filter: kernels in phnn_ekf.hip --------------------------------------
+static bool ekf_supported(const phnn_handle* h) { return h->desc.n >= 2 && h->desc.n <= 4; }
+
+// The checks of the options and the log that phnn_ekf_update and phnn_ekf_step share.
+static int check_ekf(phnn_handle* h, int64_t B, const phnn_ekf_options* o, const phnn_ekf_log* log) {
+  if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
+  if (!o) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options is NULL");
+  if (!ekf_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no extended Kalman filter kernel for this n");
+  const int n = h->desc.n;
+  if (o->meas_mask >> n) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options: meas_mask has bits at or above n");
+  for (int i = 0; i < n * n; ++i)
+    if (!std::isfinite(o->Qn[i])) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options: Qn is not finite");
+  for (int i = 0; i < n; ++i)
+    if (((o->meas_mask >> i) & 1u) && (!(o->Rn[i] > 0.0) || !std::isfinite(o->Rn[i])))
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options: Rn of a measured component is not positive and finite");
+  for (int r : o->reserved)
+    if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options: reserved must be zero");
+  if (log && (log->log_xhat_dev || log->log_nis_dev) && !log->step_dev && log->step_host < 0)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_log: a log without a step source");
+  return PHNN_OK;
+}
+
+static EkfUpdateParams ekf_update_params(const phnn_handle* h, const float* xpred_dev, int64_t xpred_stride, const float* A_dev,
+                                         const float* y_dev, int64_t y_stride, int64_t B, const phnn_ekf_options* o,
+                                         double* P_dev, float* xhat_dev, double* nis_dev, double* innov_dev,
+                                         int32_t* status_dev, const phnn_ekf_log* log) {
+  const int n = h->desc.n;
+  EkfUpdateParams p{};
+  p.xpred = xpred_dev;
+  p.xpred_stride = xpred_stride;
+  p.A = A_dev;
+  p.y = y_dev;
+  p.y_stride = y_stride;
+  p.P = P_dev;
+  p.xhat = xhat_dev;
+  p.nis = nis_dev;
+  p.innov = innov_dev;
+  p.status = status_dev;
+  if (log) {
+    p.log_xhat = log->log_xhat_dev;
+    p.log_nis = log->log_nis_dev;
+    p.step_dev = log->step_dev;
+    p.step_host = log->step_host;
+  }
+  p.B = (long long)B;
+  p.mask = o->meas_mask;
+  for (int i = 0; i < n * n; ++i) p.Qn[i] = o->Qn[i];
+  for (int i = 0; i < n; ++i) p.Rn[i] = o->Rn[i];
+  return p;
+}
+
+size_t phnn_ekf_workspace_bytes(const phnn_handle* h, int64_t B) {
+  if (!h || B < 0 || !ekf_supported(h)) return 0;
+  return std::max<size_t>(ekf_layout(B, h->desc.n, h->desc.m).total, 256);
+}
+
+int phnn_ekf_update(phnn_handle* h, const float* xpred_dev, int64_t xpred_stride, const float* A_dev, const float* y_dev,
+                    int64_t y_stride, int64_t B, const phnn_ekf_options* opt, double* P_dev, float* xhat_dev, double* nis_dev,
+                    double* innov_dev, int32_t* status_dev, const phnn_ekf_log* log, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_ekf(h, B, opt, log)) return rc;
+  if (xpred_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_update: negative stride");
+  if (B == 0) return PHNN_OK;
+  if (!xpred_dev || !A_dev || !P_dev || !xhat_dev || !status_dev || (opt->meas_mask && !y_dev))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_update: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  const EkfUpdateParams p = ekf_update_params(h, xpred_dev, xpred_stride, A_dev, y_dev, y_stride, B, opt, P_dev, xhat_dev,
+                                              nis_dev, innov_dev, status_dev, log);
+  return checked(h, ekf_update_launch(h->desc.n, p, (hipStream_t)stream), "k_ekf_update launch");
+}
+
+int phnn_ekf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u_dev, int64_t u_stride, const float* y_dev,
+                  int64_t y_stride, int64_t B, const phnn_cost* cost, int32_t integrator, float dt,
+                  const phnn_ekf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                  const phnn_ekf_log* log, void* workspace_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_ekf(h, B, opt, log)) return rc;
+  if (u_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_step: negative stride");
+  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
+  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
+  phnn_cost bounds = neutral_cost();  // what K1 and the linearisation take from the cost: the clamp
+  if (cost) {
+    if (int rc = check_cost(h, cost)) return rc;
+    bounds.has_u_bounds = cost->has_u_bounds;
+    bounds.u_min = cost->u_min;
+    bounds.u_max = cost->u_max;
+  }
+  if (B == 0) return PHNN_OK;
+  if (!xhat_dev || !P_dev || !u_dev || !status_dev || !workspace_dev || (opt->meas_mask && !y_dev))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_step: NULL tensor");
+  const int n = h->desc.n, m = h->desc.m;
+  const EkfLayout l = ekf_layout(B, n, m);
+  char* ws = (char*)workspace_dev;
+  float* ctrl = (float*)(ws + l.ctrl);
+  float* traj = (float*)(ws + l.traj);
+  {
+    PHNN_ON_DEVICE(h);
+    EkfControlsParams c{u_dev, (long long)u_stride, ctrl, (long long)B, m};
+    if (int rc = checked(h, ekf_controls_launch(c, (hipStream_t)stream), "k_ekf_controls launch")) return rc;
+  }
+  if (int rc = rollout_fwd(h, xhat_dev, ctrl, B, 1, &bounds, integrator, dt, (float*)(ws + l.cost), traj, nullptr, nullptr, stream))
+    return rc;
+  if (int rc = phnn_rollout_linearize(h, ctrl, B, 1, &bounds, integrator, dt, traj, (float*)(ws + l.A), (float*)(ws + l.Bm), stream))
+    return rc;
+  PHNN_ON_DEVICE(h);
+  const EkfUpdateParams p = ekf_update_params(h, traj + n, 2 * n, (float*)(ws + l.A), y_dev, y_stride, B, opt, P_dev, xhat_dev,
+                                              nis_dev, innov_dev, status_dev, log);
+  return checked(h, ekf_update_launch(n, p, (hipStream_t)stream), "k_ekf_update launch");
 }
 
 int phnn_read_image(phnn_handle* h, float* image_host, size_t n_floats, size_t* image_floats, void* stream) {

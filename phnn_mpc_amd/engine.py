@@ -894,6 +894,76 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return out
 
+    # ------------------------------------------------------------------ extended Kalman filter
+    def ekf_workspace_bytes(self, B):
+        return int(self.lib.phnn_ekf_workspace_bytes(self.h, int(B)))
+
+    def _ekf_log(self, log):
+        """log: None or dict(log_xhat (T+1,B,n) float32, log_nis (T,B) float64, step_dev int32 tensor or step int)."""
+        if log is None:
+            return None
+        lg = _capi.EkfLog()
+        lg.log_xhat_dev = log["log_xhat"].data_ptr() if log.get("log_xhat") is not None else None
+        lg.log_nis_dev = log["log_nis"].data_ptr() if log.get("log_nis") is not None else None
+        if log.get("step_dev") is not None:
+            lg.step_dev = log["step_dev"].data_ptr()
+        lg.step_host = int(log.get("step", -1))
+        return lg
+
+    def _ekf_outputs(self, B, nis, innov, status):
+        d = dict(dtype=torch.float64, device=self.device)
+        nis = torch.empty(B, **d) if nis is True else (None if nis is False else nis)
+        innov = torch.empty(B, self.n, **d) if innov is True else (None if innov is False else innov)
+        status = torch.empty(B, dtype=torch.int32, device=self.device) if status is None else status
+        return nis, innov, status
+
+    def ekf_update(self, xpred, A, y, P, opt, xhat=None, nis=True, innov=True, status=None, log=None, xpred_stride=None,
+                   y_stride=None):
+        """k_ekf_update on its own: the covariance propagation through A and the measurement update of the components
+        in opt (_capi.EkfOptions).  xpred: float32, problem b's prediction at xpred.view(-1)[b * xpred_stride + i] (default
+        stride n: a (B,n) tensor); A (B,n,n) float32; y float32 with y_stride likewise (only measured components are
+        read); P (B,n,n) float64, updated IN PLACE.  nis / innov: True = allocate, False = skip, or a float64 tensor (B) /
+        (B,n) to write.  -> dict(xhat (B,n) float32, P, nis, innov, status (B) int32: 0 updated or nothing measured, 1
+        dropped measurement, 2 failure with NaN outputs)."""
+        self._assert_device_f32(xpred, A, y)
+        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
+        B = P.shape[0]
+        assert P.numel() == B * self.n * self.n and A.numel() == B * self.n * self.n
+        if xhat is None:
+            xhat = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
+        self._assert_device_f32(xhat)
+        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
+        lg = self._ekf_log(log)
+        rc = self.lib.phnn_ekf_update(self.h, self._p(xpred), self.n if xpred_stride is None else int(xpred_stride), self._p(A),
+                                      self._p(y), self.n if y_stride is None else int(y_stride), B, C.byref(opt), self._p(P),
+                                      self._p(xhat), self._p(nis), self._p(innov), self._p(status),
+                                      None if lg is None else C.byref(lg), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(xhat=xhat, P=P, nis=nis, innov=innov, status=status)
+
+    def ekf_step(self, xhat, P, u, u_stride, y, cost, integrator, dt, opt, nis=True, innov=False, status=None, log=None,
+                 workspace=None, y_stride=None):
+        """phnn_ekf_step: one filter step through the learned model as ONE library call -- k_ekf_controls, K1 with H = 1
+        from xhat, the linearisation of that step, k_ekf_update -- IN PLACE on xhat (B,n) float32 and P (B,n,n) float64.
+        u: float32, problem b's applied control at u.view(-1)[b * u_stride + k]; cost: its bounds clamp the control as
+        K1 and the plant do (None: no clamp); y, opt, nis, innov, status, log: as in ekf_update.  workspace: a dict
+        reused across calls (keeps the device buffer of ekf_workspace_bytes).  -> dict(xhat, P, nis, innov, status)."""
+        self._assert_device_f32(xhat, u, y)
+        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
+        B = xhat.shape[0]
+        ws = {} if workspace is None else workspace
+        if ws.get("ekf_key") != B:
+            ws["ekf_key"] = B
+            ws["ekf"] = torch.empty(max(self.ekf_workspace_bytes(B), 256), dtype=torch.uint8, device=self.device)
+        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
+        lg = self._ekf_log(log)
+        rc = self.lib.phnn_ekf_step(self.h, self._p(xhat), self._p(P), self._p(u), int(u_stride), self._p(y),
+                                    self.n if y_stride is None else int(y_stride), B, C.byref(cost) if cost is not None else None,
+                                    self._integ(integrator), float(dt), C.byref(opt), self._p(nis), self._p(innov),
+                                    self._p(status), None if lg is None else C.byref(lg), self._p(ws["ekf"]), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(xhat=xhat, P=P, nis=nis, innov=innov, status=status)
+
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
                    step=0, step_dev=None, log_states=None, log_controls=None, ex=None, metrics=None):

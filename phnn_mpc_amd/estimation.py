@@ -1,0 +1,123 @@
+"""Model-based state estimation between the measurement and the solve (include/phnn_mpc.h: phnn_ekf_update,
+phnn_ekf_step).
+
+  EKF        an extended Kalman filter on the learned model for a measurement that is a selection of state components:
+             the prediction is one K1 step, its Jacobian the linearisation of exactly that step, the covariance algebra
+             k_ekf_update.  It holds the settings only (which components are measured, Qn, Rn, P0, the initial estimate);
+             the state of a running filter -- xhat (B,n) float32 and P (B,n,n) float64 -- belongs to the caller, so one EKF
+             serves any number of loops.
+  EKF.step   the Python statement of phnn_ekf_step over the engine's step methods (rollout_cost, rollout_linearize,
+             ekf_update): the same four launches on a RolloutEngine, and it runs on a CPU stand-in that has those three
+             methods, the way solver.gn_solve serves a Gauss-Newton stand-in.
+
+The closed-loop drivers (closed_loop.run_mpc_batch, DeviceClosedLoop, run_mpc_batch_device) take estimator=EKF(...): the
+controller then solves from the estimate instead of the raw measurement.
+"""
+import numpy as np
+
+from . import _capi
+
+
+def _square(v, n, what):
+    """scalar -> v I, (n,) -> diag(v), (n,n) -> as given; float64."""
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.eye(n) * float(a)
+    elif a.ndim == 1:
+        a = np.diag(a)
+    if a.shape != (n, n):
+        raise ValueError(f"{what} must be a scalar, ({n},) or ({n},{n}), got {np.shape(v)}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{what} must be finite")
+    return np.ascontiguousarray(a)
+
+
+class EKF:
+    """measured: indices of the measured state components (no duplicates; () = predict only).  Qn: process noise
+    covariance added at every step -- a scalar (times I), a diagonal or a full (n,n) matrix.  Rn: measurement noise
+    VARIANCES -- a scalar, or one value per state component (n,) or per measured component (len(measured),); positive
+    and finite where measured.  P0: the initial covariance, like Qn.  x0_hat: the initial estimate, broadcastable to
+    (B,n); None = float32 of the true initial state.  log: the closed-loop drivers record the estimates and the nis of
+    every step."""
+
+    def __init__(self, measured=(0, 1), Qn=1e-6, Rn=1e-4, P0=1e-2, x0_hat=None, log=True):
+        self.measured = tuple(int(i) for i in measured)
+        if len(set(self.measured)) != len(self.measured) or any(i < 0 or i >= _capi.PHNN_MAX_N for i in self.measured):
+            raise ValueError(f"measured: distinct component indices in 0 .. {_capi.PHNN_MAX_N - 1}, got {measured}")
+        self.Qn, self.Rn, self.P0 = Qn, Rn, P0
+        self.x0_hat = None if x0_hat is None else np.asarray(x0_hat, dtype=np.float32)
+        self.log = bool(log)
+
+    @classmethod
+    def from_config(cls, config):
+        """An EKF from the optional `estimator:` section of a config dict (keys: measured, Qn, Rn, P0, x0_hat, log; type:
+        "ekf" may be given), or None when there is no such section."""
+        sec = config.get("estimator")
+        if sec is None:
+            return None
+        sec = dict(sec)
+        kind = str(sec.pop("type", "ekf")).lower()
+        if kind != "ekf":
+            raise ValueError(f"Unknown estimator type: {kind}")
+        unknown = set(sec) - {"measured", "Qn", "Rn", "P0", "x0_hat", "log"}
+        if unknown:
+            raise ValueError(f"estimator: unknown key(s) {sorted(unknown)}")
+        return cls(**sec)
+
+    @property
+    def mask(self):
+        return sum(1 << i for i in self.measured)
+
+    def rn_vector(self, n):
+        """-> (n,) float64 variances, 0 at unmeasured components."""
+        r = np.asarray(self.Rn, dtype=np.float64).reshape(-1)
+        out = np.zeros(n)
+        idx = list(self.measured)
+        if r.size == 1:
+            out[idx] = r[0]
+        elif r.size == n:
+            out[idx] = r[idx]
+        elif r.size == len(idx):
+            out[idx] = r
+        else:
+            raise ValueError(f"Rn must be a scalar, ({n},) or ({len(idx)},), got {r.shape}")
+        if not (np.all(out[idx] > 0) and np.all(np.isfinite(out[idx]))):
+            raise ValueError("Rn must be positive and finite at the measured components")
+        return out
+
+    def options(self, n):
+        """-> _capi.EkfOptions (phnn_ekf_options) for an n-state model."""
+        if any(i >= n for i in self.measured):
+            raise ValueError(f"measured {self.measured}: the model has {n} state components")
+        o = _capi.EkfOptions()
+        o.meas_mask = self.mask
+        Qn, Rn = _square(self.Qn, n, "Qn"), self.rn_vector(n)
+        for i in range(n):
+            for j in range(n):
+                o.Qn[i * n + j] = Qn[i, j]
+            o.Rn[i] = Rn[i]
+        return o
+
+    def initial(self, x0, n=None):
+        """x0 (B,n) true initial states -> (xhat0 (B,n) float32, P0 (B,n,n) float64), numpy."""
+        x0 = np.asarray(x0, dtype=np.float64)
+        B, n = x0.shape[0], x0.shape[1] if n is None else n
+        xh = x0.astype(np.float32) if self.x0_hat is None else np.broadcast_to(self.x0_hat, (B, n)).astype(np.float32)
+        P = np.broadcast_to(_square(self.P0, n, "P0"), (B, n, n))
+        return np.ascontiguousarray(xh), np.ascontiguousarray(P)
+
+    def step(self, engine, xhat, P, u, y, cost, integrator, dt, opt=None, log=None):
+        """One filter step, the statement of phnn_ekf_step over the engine's step methods.  xhat (B,n) float32, P
+        (B,n,n) float64, u (B,m) or (B,1,m) the applied control, y (B,n) float32 (only the measured components matter),
+        tensors on the engine's device; cost: its bounds clamp the control as K1 and the plant do (None: no clamp).
+        -> dict(xhat, P, nis, innov, status); xhat and P are new tensors, the inputs keep their values."""
+        import torch
+        B = xhat.shape[0]
+        opt = self.options(engine.n) if opt is None else opt
+        row = torch.as_tensor(u, dtype=torch.float32).to(engine.device).reshape(B, 1, engine.m).contiguous()
+        bounds = _capi.Cost()  # what the prediction takes from the cost: the clamp
+        if cost is not None:
+            bounds.has_u_bounds, bounds.u_min, bounds.u_max = cost.has_u_bounds, cost.u_min, cost.u_max
+        _, traj = engine.rollout_cost(xhat, row, bounds, integrator, dt, want_traj=True)
+        A, _, _ = engine.rollout_linearize(xhat, row, bounds, integrator, dt, traj=traj)
+        return engine.ekf_update(traj[:, 1].contiguous(), A.reshape(B, engine.n, engine.n), y, P.clone(), opt, log=log)
