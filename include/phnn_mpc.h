@@ -883,6 +883,54 @@ int phnn_ekf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u
                   const phnn_ekf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
                   const phnn_ekf_log* log, void* workspace_dev, void* stream);
 
+/* ---- tracking the plan between two solves with its TV-LQR feedback ---------------------------------------
+ * A loop that solves every k-th control step applies, in between, row j of the last plan plus the time-varying LQR
+ * feedback around it:  u = clamp(clamp(u_j) + K_j (x - x_j^nominal)),  j = step % k.  phnn_feedback_plan makes the
+ * nominal trajectory and the gains of a plan, phnn_feedback_control applies the law, per problem b of B independent ones.
+ * k_feedback_control<n,m>, (n, m) in {2,3,4} x {1,2,3,4}: one thread per problem, float64, no fused multiply-adds;
+ * tests/feedback_model.py states the order and the kernel equals it bit for bit.  With clampf the library's
+ * NaN-preserving float32 clamp, applied only when the cost has bounds:
+ *   un_k = clampf(u[b,j,k])
+ *   dx_i = (double)x[b,i] - (double)traj[b,j,i]
+ *   s_k  = sum_i K[b,j,k,i] dx_i        index ascending from an accumulator 0.0, each product rounded, then added
+ *   v_k  = clampf((float)((double)un_k + s_k)), the sum rounded once to float32; where s_k == 0.0 the output keeps un_k's
+ *          bits (a -0.0 included): at j = 0, where x is the state the plan started from, the control is the plan's
+ * status (B) int32 and the special cases:
+ *   0  u_out[b,k] = v_k
+ *   1  an entry of K[b,j] is not finite (the rows phnn_tvlqr marked): u_out[b,k] = un_k
+ *   2  a dx_i is not finite (a NaN estimate or a NaN nominal row): u_out[b,k] = un_k, dev = quiet NaN
+ * -- open-loop tracking of the plan, never a finite control built from a NaN.  dev (B) float64 = max_i |dx_i|.
+ * Both calls are stream-ordered and capturable, allocate nothing, do not synchronise and never write their inputs;
+ * B == 0 returns PHNN_OK with nothing launched; sizes are exact. */
+/* Bytes of the workspace of phnn_feedback_plan: A (B,H,n,n) and Bm (B,H,n,m) float32, K1's cost vector (B) float32 and
+ * P0 (B,n,n) float64, each region 256-byte aligned.  0 for invalid arguments (B < 0, H < 1) or a model whose (n, m) has
+ * no TV-LQR kernel; non-decreasing in B and H. */
+size_t phnn_feedback_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H);
+/* The plan's nominal trajectory and gains.  Exactly three launches in stream order and nothing else: K1 from x0 with
+ * trajectories on phnn_rollout_fwd's path (the caller's cost, so the control clamp is K1's), phnn_rollout_linearize's
+ * launch on that trajectory with the cost's bounds, phnn_tvlqr's launch (opt NULL = {0}).  traj_dev (B,H+1,n) float32,
+ * K_dev (B,H,m,n) float64 and status_dev (B) int32 are bit for bit what those three public calls give when issued by
+ * hand.  Reference rows enter neither A, B nor K, so the call takes none.  PHNN_ERR_INVALID_ARG, nothing launched and
+ * no output touched: NULL required buffers (cost included), B < 0, H < 1, an unknown integrator, a non-finite dt,
+ * u_min > u_max, a negative or non-finite mu, non-zero reserved, workspace_size below the size query;
+ * PHNN_ERR_UNSUPPORTED for an (n, m) without a TV-LQR kernel. */
+int phnn_feedback_plan(phnn_handle* h, const float* x0_dev /* (B,n) */, const float* u_dev /* (B,H,m) */, int64_t B, int32_t H,
+                       const phnn_cost* cost, int32_t integrator, float dt, const phnn_tvlqr_options* opt, void* workspace,
+                       size_t workspace_size, float* traj_dev /* (B,H+1,n) */, double* K_dev /* (B,H,m,n) */,
+                       int32_t* status_dev /* (B) */, void* stream);
+/* The law above, one launch.  The plan row is j = step % solve_every with step = *step_dev when step_dev != NULL (a
+ * device counter >= 0, so that ONE captured launch serves every tracking step), else step_host; 1 <= solve_every <= H,
+ * so j is always a row of the plan.  cost is read for has_u_bounds / u_min / u_max only, NULL = no clamp.  x_dev (B,n)
+ * float32, u_dev (B,H,m), traj_dev and K_dev as phnn_feedback_plan wrote them, u_out (B,m) float32; status_out (B) int32
+ * and dev_out (B) float64 may be NULL; log_status_dev (T,B) int32 and log_dev_dev (T,B) float64 (NULL = skip) receive
+ * row `step`, as the plant step's logs do.  PHNN_ERR_INVALID_ARG, nothing launched and no output touched: NULL required
+ * buffers, B < 0, H < 1, solve_every outside 1 .. H, neither step_dev nor step_host >= 0, u_min > u_max;
+ * PHNN_ERR_UNSUPPORTED for an (n, m) without a kernel. */
+int phnn_feedback_control(phnn_handle* h, const float* x_dev, const float* u_dev, const float* traj_dev, const double* K_dev,
+                          int64_t B, int32_t H, const phnn_cost* cost, int32_t solve_every, const int32_t* step_dev,
+                          int32_t step_host, float* u_out, int32_t* status_out, double* dev_out, int32_t* log_status_dev,
+                          double* log_dev_dev, void* stream);
+
 /* Introspection for tests: copies the packed weight image the kernels stage into LDS (phnn_kernels.hip.h layouts; a
  * device-resident private format) to image_host after the work queued on `stream`, and waits for the copy.
  * *image_floats (may be NULL) receives its size; image_host == NULL only queries the size. */

@@ -39,6 +39,7 @@ EXPORTED = [
     "phnn_gn_workspace_bytes", "phnn_gn_direction", "phnn_gn_candidates", "phnn_gn_select", "phnn_solve_gn",
     "phnn_gn_direction_box", "phnn_solve_gn_ex",
     "phnn_ekf_workspace_bytes", "phnn_ekf_update", "phnn_ekf_step",
+    "phnn_feedback_workspace_bytes", "phnn_feedback_plan", "phnn_feedback_control",
 ]
 
 PHNN_GN_BOX = 1  # flags of phnn_solve_gn_ex
@@ -366,6 +367,14 @@ def load_library():
     lib.phnn_ekf_step.argtypes = [vp, f32p, vp, f32p, i64, f32p, i64, i64, C.POINTER(Cost), i32, C.c_float, eko, vp, vp, vp,
                                   ekl, vp, vp]
     lib.phnn_ekf_step.restype = C.c_int
+    lib.phnn_feedback_workspace_bytes.argtypes = [vp, i64, i32]
+    lib.phnn_feedback_workspace_bytes.restype = C.c_size_t
+    lib.phnn_feedback_plan.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), i32, C.c_float, C.POINTER(TvlqrOptions), vp,
+                                       C.c_size_t, f32p, vp, vp, vp]
+    lib.phnn_feedback_plan.restype = C.c_int
+    lib.phnn_feedback_control.argtypes = [vp, f32p, f32p, f32p, vp, i64, i32, C.POINTER(Cost), i32, vp, i32, f32p, vp, vp, vp, vp,
+                                          vp]
+    lib.phnn_feedback_control.restype = C.c_int
     lib.phnn_kernel_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i64]
     lib.phnn_kernel_info.restype = C.c_int
     lib.phnn_variant_name.argtypes = [vp]

@@ -27,6 +27,10 @@
                          (phnn_ekf_step).  Only the `measured` components of the measurement are used, so a
                          loop can run on positions alone.  The result gains estimates (T+1,B,4) float32, nis (T,B) and
                          ekf_status (B,), the last step's.
+  track                  (all three drivers, track=) a feedback.Tracking: the solve runs every solve_every-th control step
+                         only, and every step applies row step % solve_every of the last plan plus the time-varying LQR
+                         feedback on the deviation from its nominal trajectory (phnn_feedback_plan, phnn_feedback_control;
+                         DESIGN.md 21).  The result gains track_status (T,B) and track_dev (T,B).
 """
 import numpy as np
 
@@ -192,14 +196,33 @@ class BatchedCartPole:
         return self.state.copy()
 
 
-def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, scenario=None, estimator=None):
+def _track_solve(controller, canonical, x32, u_prev, k, rkw):
+    """The solve of a solve step of a loop with tracking -> the sequence that becomes the plan, (B,H,m) on the engine's
+    device: an MPCController's last iterate (cold start), a canonical controller's best clamped iterate, warm-started
+    from the previous one shifted by k rows (dst[t] = src[t+k], zeros in the last k rows: k shifts by one)."""
+    import torch
+    if not canonical:
+        return controller.solve_batch(x32, **rkw)["u_last"]
+    u_init = None
+    if u_prev is not None:
+        up = u_prev.cpu()
+        u_init = torch.cat([up[:, k:], torch.zeros(up.shape[0], k, up.shape[2])], dim=1)
+    return controller.optimize_control_batch(x32, u_init, record_costs=False, **rkw)["best_u"]
+
+
+def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, scenario=None, estimator=None, track=None):
     """-> dict(states (T+1,B,4), controls (T,B,1), done_step (B,) first step a plant terminated at, or -1).
     x_ref: reference trajectories broadcastable to (B, rows, 4); control step s tracks them from row s.
     scenario: a PlantScenario for the simulator (a BatchedCartPole built with scenario= / replay= has its own); the
     result then also holds disturbance (T,B) float32, what each step added to the commanded force.
     estimator: an estimation.EKF; every solve starts from its estimate, and after every plant step EKF.step advances it
     on the controller's engine with the applied control and the new measurement.  The result then also holds estimates
-    (T+1,B,4) float32, nis (T,B) and ekf_status (B,)."""
+    (T+1,B,4) float32, nis (T,B) and ekf_status (B,).
+    track: a feedback.Tracking; the solve runs at the steps s with s % solve_every == 0 only, Tracking.plan turns its
+    sequence into a plan, and every step applies Tracking.control from the measurement (or the estimate).  The result
+    then also holds track_status (T,B) and track_dev (T,B), or None with the tracking's log=False."""
+    if track is not None:
+        track.check(controller.engine, controller.horizon, controller.dt, getattr(simulator, "dt", None))
     if scenario is not None:
         simulator.scenario = scenario
     measured = hasattr(simulator, "measurement")
@@ -219,6 +242,11 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
         xhat, P = torch.tensor(xh0, device=eng.device), torch.tensor(P0, device=eng.device)
         ekf_opt, ekf_cost = estimator.options(eng.n), (None if canonical else controller._cost())
         estimates, nis, ekf_status = [xh0], [], None
+    if track is not None:
+        import torch
+        eng = controller.engine
+        track_cost = controller._cost()  # the plan's Q and R, and the bounds of both clamps
+        track_status, track_dev = [], []
     for step in range(num_steps):
         rkw = {"epoch": step} if sampling else {}  # the noise counter of an MPPI / CrossEntropy solve: the control step
         if x_ref is not None:
@@ -227,7 +255,17 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
             x32 = xhat.cpu().numpy()
         else:
             x32 = simulator.measurement() if measured else x.astype(np.float32)
-        if canonical:
+        if track is not None:
+            xd = torch.as_tensor(np.ascontiguousarray(x32, dtype=np.float32)).to(eng.device)
+            if step % track.solve_every == 0:  # the solve as always; its sequence becomes the plan
+                u_prev = seq = _track_solve(controller, canonical, x32, u_prev, track.solve_every, rkw).contiguous()
+                plan = track.plan(eng, xd, seq, track_cost, controller.integrator, controller.dt)
+            r = track.control(eng, xd, seq, plan, track_cost, step=step)
+            u = r["u"].cpu().numpy()
+            if track.log:
+                track_status.append(r["status"].cpu().numpy().astype(np.int64))
+                track_dev.append(r["dev"].cpu().numpy())
+        elif canonical:
             u, u_prev, _ = controller.control_batch(x32, u_prev, **rkw)
         else:
             u = controller.compute_control_batch(x32, **rkw)
@@ -252,6 +290,10 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
     if estimator is not None:
         out.update(estimates=np.stack(estimates), nis=np.stack(nis) if nis else np.zeros((0, B)),
                    ekf_status=None if ekf_status is None else ekf_status.cpu().numpy().astype(np.int64))
+    if track is not None:
+        kept = track.log
+        out.update(track_status=(np.stack(track_status) if track_status else np.zeros((0, B), np.int64)) if kept else None,
+                   track_dev=(np.stack(track_dev) if track_dev else np.zeros((0, B))) if kept else None)
     return out
 
 
@@ -294,10 +336,22 @@ class DeviceClosedLoop:
     ekf_status (B,), the last step's.  The filter predicts over the controller's dt: an estimator together with a dt=
     other than controller.dt is refused (ValueError).  Without an estimator the loop is what it was: same launches, same
     bits.
+
+    track: a feedback.Tracking(solve_every=k).  A solve step (s % k == 0) runs the solve as above, then
+    engine.feedback_plan from the same state on the solve's sequence (best_u of a canonical controller, u_last of an
+    MPCController, read in place): K1 with trajectories, the linearisation, the LQ backward pass.  Every step, the solve
+    step included, runs engine.feedback_control -- row s % k of the plan plus K (x - x_nominal), from the measurement or
+    the estimate, the row taken from the step counter --, the plant step (and the filter step) with the control it wrote
+    and the step advance; a tracking step runs nothing else.  A canonical controller's next warm start is its best
+    sequence shifted k times (made on the solve step, the last shift advancing the step); an MPCController cold-starts
+    as always.  With use_graph two graphs are captured, a solve step and a tracking step, and replayed by s % k from the
+    host, still with one synchronisation at the end.  The result gains track_status (T,B) and track_dev (T,B) (None with
+    the tracking's log=False).  solve_every outside 1 .. horizon and a dt= other than controller.dt are refused
+    (ValueError).  Without track the loop is what it was: same launches, same bits.
     """
 
     def __init__(self, controller, initial_states, num_steps, use_graph=True, dt=None, x_ref=None, scenario=None,
-                 metrics=False, log=True, estimator=None):
+                 metrics=False, log=True, estimator=None, track=None):
         import torch
         from . import _capi
         self.torch, self.ctl = torch, controller
@@ -354,6 +408,30 @@ class DeviceClosedLoop:
         self.ekf = estimator
         if estimator is not None:
             self._estimator(estimator, x)
+        self.track = track
+        if track is not None:
+            self._tracking(track)
+
+    def _tracking(self, tr):
+        """The buffers of a loop with tracking: the control the plant takes, the plan's workspace, the status and the
+        deviation with their logs, and for a canonical controller with solve_every > 1 the scratch of the k-fold shift."""
+        torch, eng, B, k = self.torch, self.eng, self.B, self._keep
+        tr.check(eng, self.ctl.horizon, self.ctl.dt, self.plant.dt)
+        if not hasattr(eng, "feedback_plan"):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched plan call (RolloutEngine has)")
+        dev = eng.device
+        self.seq = None  # the sequence of the last solve: the plan's controls, read in place
+        self.fb_ws = {}  # the device buffers of feedback_plan, kept across steps
+        k["track_u"] = torch.zeros(B, eng.m, dtype=torch.float32, device=dev)
+        k["track_status"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        k["track_dev"] = torch.zeros(B, dtype=torch.float64, device=dev)
+        self.track_log = {}
+        if tr.log:
+            k["track_status_log"] = torch.zeros(self.T, B, dtype=torch.int32, device=dev)
+            k["track_dev_log"] = torch.zeros(self.T, B, dtype=torch.float64, device=dev)
+            self.track_log = dict(log_status=k["track_status_log"], log_dev=k["track_dev_log"])
+        if self.canonical and tr.solve_every > 1:
+            k["shift"] = [torch.zeros_like(self.u_init) for _ in range(min(tr.solve_every - 1, 2))]
 
     def _estimator(self, est, x0):
         """The filter's state and buffers: the estimate the solve reads, the covariance, the measurement the plant
@@ -433,13 +511,17 @@ class DeviceClosedLoop:
         mt.cost_acc_dev, mt.run_dev, mt.best_run_dev = k["cost"].data_ptr(), k["run"].data_ptr(), k["best_run"].data_ptr()
         self.metrics = mt
 
-    def _control_step(self):
-        eng, c = self.eng, self.ctl
+    def _plant_log(self):
+        """The keyword arguments every plant step of the loop takes."""
         log = dict(state_f32=self.x32 if self.ekf is None else self.y32, done_step=self.done_step, step_dev=self.step_dev,
                    log_states=self.log_states, log_controls=self.log_controls)
         if self.ex is not None or self.metrics is not None:
             log.update(ex=self.ex, metrics=self.metrics)
-        H = self.u_init.shape[1] * self.u_init.shape[2]
+        return log
+
+    def _solve(self):
+        """The solve of one control step -> the engine's result dict."""
+        eng, c = self.eng, self.ctl
         if self.sampling:
             out = self._solve_sampling()
         elif self.gn:  # self.x_ref is already one row set per candidate rollout (or shared)
@@ -453,6 +535,13 @@ class DeviceClosedLoop:
             out = eng.solve(self.x32, self.u_init, self.cost, c.integrator, c.dt, lr=self.lr, iters=self.iters,
                             track_best=self.canonical, record_costs=False, workspace=self.ws, x_ref=self.x_ref,
                             ref_offset=self.step_dev)
+        return out
+
+    def _control_step(self):
+        eng, c = self.eng, self.ctl
+        log = self._plant_log()
+        H = self.u_init.shape[1] * self.u_init.shape[2]
+        out = self._solve()
         if self.canonical:  # best clamped iterate; next call warm-starts from its shift
             eng.plant_step(self.plant, self.state, out["best_u"], H, **log)
             if self.ekf is not None:
@@ -463,6 +552,58 @@ class DeviceClosedLoop:
             if self.ekf is not None:
                 self._ekf_step(out["u_last"], H)
             eng.advance_step(self.step_dev)
+
+    def _track_step(self, solve):
+        """One control step of a loop with tracking.  A solve step (solve=True): the solve as in _control_step, then
+        feedback_plan from the same state on the solve's sequence, read in place.  Every step: feedback_control on row
+        step % solve_every of the plan, the plant step (and the filter step) with the control it wrote, the step advance.
+        A canonical controller's warm start is made on the solve step, all at once: its best sequence shifted
+        solve_every times, the last shift advancing the step."""
+        eng, c, tr, k = self.eng, self.ctl, self.track, self._keep
+        if solve:
+            out = self._solve()
+            self.seq_before, self.seq = self.seq, out["best_u" if self.canonical else "u_last"]
+            eng.feedback_plan(self.x32, self.seq, self.cost, c.integrator, c.dt, mu=tr.mu, workspace=self.fb_ws)
+        eng.feedback_control(self.x32, self.seq, self.fb_ws["fb_traj"], self.fb_ws["fb_K"], self.cost, tr.solve_every,
+                             step_dev=self.step_dev, u_out=k["track_u"], status=k["track_status"], dev=k["track_dev"],
+                             **self.track_log)
+        bounds = {} if self.canonical else dict(u_min=c.u_min, u_max=c.u_max)
+        eng.plant_step(self.plant, self.state, k["track_u"], eng.m, **bounds, **self._plant_log())
+        if self.ekf is not None:
+            self._ekf_step(k["track_u"], eng.m)
+        if self.canonical and solve:
+            src = self.seq
+            for i in range(tr.solve_every):
+                last = i == tr.solve_every - 1
+                dst = self.u_init if last else k["shift"][i % 2]
+                eng.shift_controls(src, dst, step_dev=self.step_dev if last else None)
+                src = dst
+        else:
+            eng.advance_step(self.step_dev)
+
+    def _run_tracking(self):
+        """The steps of a loop with tracking: with a graph, the solve step and the tracking step are captured once each
+        (the plan row of a tracking step comes from the step counter, so one graph serves them all) and replayed by
+        s % solve_every from the host."""
+        ke = self.track.solve_every
+        if not (self.use_graph and self.T > 1):
+            for s in range(self.T):
+                self._track_step(s % ke == 0)
+            return
+        from .solver import capture
+        dev = self.eng.device
+        self.graph, _ = capture(dev, lambda: self._track_step(True))  # runs step 0
+        # the recorded step reads the solve's sequence where the graph will write it; step 0 wrote its own elsewhere
+        self.seq.copy_(self.seq_before)
+        self.seq_before = None
+        self.track_graph = None
+        for s in range(1, self.T):
+            if s % ke == 0:
+                self.graph.replay()
+            elif self.track_graph is None:
+                self.track_graph, _ = capture(dev, lambda: self._track_step(False))  # runs this step
+            else:
+                self.track_graph.replay()
 
     def _solve_sampling(self):
         """engine.solve_mppi / engine.solve_cem with the step counter as the noise epoch.  self.x_ref is already one row
@@ -475,7 +616,9 @@ class DeviceClosedLoop:
     def run(self):
         torch = self.torch
         dev = self.eng.device
-        if self.use_graph and self.T > 1:
+        if self.track is not None:
+            self._run_tracking()
+        elif self.use_graph and self.T > 1:
             from .solver import capture
             self.graph, _ = capture(dev, self._control_step)  # runs step 0; replay for steps 1 .. T-1
             for _ in range(1, self.T):
@@ -498,15 +641,19 @@ class DeviceClosedLoop:
             out.update(estimates=self._keep["estimates"].cpu().numpy() if kept else None,
                        nis=self._keep["nis"].cpu().numpy() if kept else None,
                        ekf_status=self._keep["ekf_status"].cpu().numpy().astype(np.int64))
+        if self.track is not None:
+            kept = self.track.log
+            out.update(track_status=self._keep["track_status_log"].cpu().numpy().astype(np.int64) if kept else None,
+                       track_dev=self._keep["track_dev_log"].cpu().numpy() if kept else None)
         return out
 
 
 def run_mpc_batch_device(controller, initial_states, num_steps, use_graph=True, x_ref=None, scenario=None, metrics=False,
-                         log=True, estimator=None):
+                         log=True, estimator=None, track=None):
     """Device-resident version of run_mpc_batch: same return dict, one host synchronisation at the end.  scenario,
-    metrics, log, estimator: as in DeviceClosedLoop."""
+    metrics, log, estimator, track: as in DeviceClosedLoop."""
     return DeviceClosedLoop(controller, initial_states, num_steps, use_graph=use_graph, x_ref=x_ref, scenario=scenario,
-                            metrics=metrics, log=log, estimator=estimator).run()
+                            metrics=metrics, log=log, estimator=estimator, track=track).run()
 
 
 def stability_report(states, target, tolerance, min_duration, dt):

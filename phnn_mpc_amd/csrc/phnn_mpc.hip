@@ -20,6 +20,7 @@
 #include "phnn_sampling.h"
 #include "phnn_gn.h"
 #include "phnn_ekf.h"
+#include "phnn_feedback.h"
 #include "phnn_pack.h"
 
 namespace {
@@ -2048,6 +2049,82 @@ int phnn_ekf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u
   const EkfUpdateParams p = ekf_update_params(h, traj + n, 2 * n, (float*)(ws + l.A), y_dev, y_stride, B, opt, P_dev, xhat_dev,
                                               nis_dev, innov_dev, status_dev, log);
   return checked(h, ekf_update_launch(n, p, (hipStream_t)stream), "k_ekf_update launch");
+}
+
+// ---- tracking the plan between solves: kernel in phnn_feedback.hip -------------------------------------
+static bool feedback_supported(const phnn_handle* h) {  // the (n, m) of k_tvlqr and k_feedback_control
+  return h->desc.n >= 2 && h->desc.n <= 4 && h->desc.m >= 1 && h->desc.m <= 4;
+}
+
+size_t phnn_feedback_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H) {
+  if (!h || B < 0 || H < 1 || !feedback_supported(h)) return 0;
+  return std::max<size_t>(feedback_layout(B, H, h->desc.n, h->desc.m).total, 256);
+}
+
+int phnn_feedback_plan(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                       int32_t integrator, float dt, const phnn_tvlqr_options* opt, void* workspace, size_t workspace_size,
+                       float* traj_dev, double* K_dev, int32_t* status_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  // everything the three calls below check, here: a refusal launches nothing
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
+  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
+  if (int rc = check_cost(h, cost)) return rc;
+  if (opt) {
+    if (!(opt->mu >= 0.0) || !std::isfinite(opt->mu))
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_tvlqr_options: mu is negative or not finite");
+    for (int r : opt->reserved)
+      if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_tvlqr_options: reserved must be zero");
+  }
+  if (!feedback_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no TV-LQR kernel for this (n, m)");
+  if (B == 0) return PHNN_OK;
+  if (!x0_dev || !u_dev || !traj_dev || !K_dev || !status_dev || !workspace)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_feedback_plan: NULL tensor");
+  const FeedbackLayout l = feedback_layout(B, H, h->desc.n, h->desc.m);
+  if (workspace_size < l.total) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_feedback_plan: workspace too small");
+  char* ws = (char*)workspace;
+  float* A = (float*)(ws + l.A);
+  float* Bm = (float*)(ws + l.Bm);
+  if (int rc = rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, (float*)(ws + l.cost), traj_dev, nullptr, nullptr, stream))
+    return rc;
+  if (int rc = phnn_rollout_linearize(h, u_dev, B, H, cost, integrator, dt, traj_dev, A, Bm, stream)) return rc;
+  return phnn_tvlqr(h, A, Bm, B, H, cost, opt, K_dev, (double*)(ws + l.P0), nullptr, status_dev, stream);
+}
+
+int phnn_feedback_control(phnn_handle* h, const float* x_dev, const float* u_dev, const float* traj_dev, const double* K_dev,
+                          int64_t B, int32_t H, const phnn_cost* cost, int32_t solve_every, const int32_t* step_dev,
+                          int32_t step_host, float* u_out, int32_t* status_out, double* dev_out, int32_t* log_status_dev,
+                          double* log_dev_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (solve_every < 1 || solve_every > H) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_feedback_control: solve_every outside 1 .. H");
+  if (!step_dev && step_host < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_feedback_control: no step source");
+  if (cost && cost->has_u_bounds && !(cost->u_min <= cost->u_max)) return fail(h, PHNN_ERR_INVALID_ARG, "u_min > u_max");
+  if (!feedback_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no feedback kernel for this (n, m)");
+  if (B == 0) return PHNN_OK;
+  if (!x_dev || !u_dev || !traj_dev || !K_dev || !u_out) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_feedback_control: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  FeedbackControlParams p{};
+  p.x = x_dev;
+  p.u = u_dev;
+  p.traj = traj_dev;
+  p.K = K_dev;
+  p.u_out = u_out;
+  p.status = status_out;
+  p.dev = dev_out;
+  p.log_status = log_status_dev;
+  p.log_dev = log_dev_dev;
+  p.step_dev = step_dev;
+  p.step_host = step_host;
+  p.solve_every = solve_every;
+  p.H = H;
+  p.B = (long long)B;
+  if (cost && cost->has_u_bounds) {
+    p.has_u_bounds = 1;
+    p.u_min = cost->u_min;
+    p.u_max = cost->u_max;
+  }
+  return checked(h, feedback_control_launch(h->desc.n, h->desc.m, p, (hipStream_t)stream), "k_feedback_control launch");
 }
 
 int phnn_read_image(phnn_handle* h, float* image_host, size_t n_floats, size_t* image_floats, void* stream) {

@@ -964,6 +964,60 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return dict(xhat=xhat, P=P, nis=nis, innov=innov, status=status)
 
+    # ------------------------------------------------------------------ tracking the plan between solves
+    def feedback_workspace_bytes(self, B, H):
+        return int(self.lib.phnn_feedback_workspace_bytes(self.h, int(B), int(H)))
+
+    def feedback_plan(self, x0, u, cost, integrator="euler", dt=0.02, mu=0.0, workspace=None, traj=None, K=None, status=None):
+        """phnn_feedback_plan: the nominal trajectory and the TV-LQR gains of a plan as ONE library call -- K1 from x0 with
+        trajectories, the linearisation of that rollout, the LQ backward pass.  x0 (B,n), u (B,H,m) float32 on the
+        engine's device, read in place; cost: the controller's (Q, R, bounds).  workspace: a dict reused across calls
+        (keeps the device buffer of feedback_workspace_bytes and, unless given, the outputs).  -> dict(traj (B,H+1,n)
+        float32, K (B,H,m,n) float64, status (B) int32: phnn_tvlqr's)."""
+        self._assert_device_f32(x0, u)
+        B, H = u.shape[0], u.shape[1]  # u is (B,H,m)
+        ws = {} if workspace is None else workspace
+        if ws.get("fb_key") != (B, H):
+            ws["fb_key"] = (B, H)
+            ws["fb"] = torch.empty(max(self.feedback_workspace_bytes(B, H), 256), dtype=torch.uint8, device=self.device)
+            ws["fb_traj"] = torch.empty(B, H + 1, self.n, dtype=torch.float32, device=self.device)
+            ws["fb_K"] = torch.empty(B, H, self.m, self.n, dtype=torch.float64, device=self.device)
+            ws["fb_status"] = torch.empty(B, dtype=torch.int32, device=self.device)
+        traj = ws["fb_traj"] if traj is None else traj
+        K = ws["fb_K"] if K is None else K
+        status = ws["fb_status"] if status is None else status
+        assert traj.dtype == torch.float32 and K.dtype == torch.float64 and status.dtype == torch.int32
+        opt = _capi.TvlqrOptions()
+        opt.mu = float(mu)
+        rc = self.lib.phnn_feedback_plan(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), self._integ(integrator), float(dt),
+                                         C.byref(opt), self._p(ws["fb"]), ws["fb"].numel(), self._p(traj), self._p(K),
+                                         self._p(status), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(traj=traj, K=K, status=status)
+
+    def feedback_control(self, x, u, traj, K, cost, solve_every, step=0, step_dev=None, u_out=None, status=True, dev=True,
+                         log_status=None, log_dev=None):
+        """phnn_feedback_control: u_out = clamp(clamp(u[:, j]) + K[:, j] (x - traj[:, j])) with j = step % solve_every,
+        one launch.  x (B,n), u (B,H,m), traj (B,H+1,n) float32, K (B,H,m,n) float64 on the engine's device; cost: its
+        bounds only (None: no clamp); step: an int, or step_dev an int32 device tensor (a captured launch follows it).
+        status / dev: True = allocate, False = skip, or an int32 (B) / float64 (B) tensor to write; log_status (T,B) int32
+        and log_dev (T,B) float64 receive row `step`.  -> dict(u (B,m) float32, status: 0 feedback, 1 gains not finite, 2
+        deviation not finite (1, 2: the plan's control), dev: max |x - traj[:, j]| or NaN for status 2)."""
+        self._assert_device_f32(x, u, traj)
+        assert K.dtype == torch.float64 and K.is_contiguous() and K.device == self.device
+        B, H = K.shape[0], K.shape[1]
+        if u_out is None:
+            u_out = torch.empty(B, self.m, dtype=torch.float32, device=self.device)
+        self._assert_device_f32(u_out)
+        status = torch.empty(B, dtype=torch.int32, device=self.device) if status is True else (None if status is False else status)
+        dev = torch.empty(B, dtype=torch.float64, device=self.device) if dev is True else (None if dev is False else dev)
+        rc = self.lib.phnn_feedback_control(self.h, self._p(x), self._p(u), self._p(traj), self._p(K), B, H,
+                                            C.byref(cost) if cost is not None else None, int(solve_every), self._p(step_dev),
+                                            -1 if step_dev is not None else int(step), self._p(u_out), self._p(status),
+                                            self._p(dev), self._p(log_status), self._p(log_dev), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(u=u_out, status=status, dev=dev)
+
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
                    step=0, step_dev=None, log_states=None, log_controls=None, ex=None, metrics=None):
