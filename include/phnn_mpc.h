@@ -29,7 +29,8 @@
  *     their contents on entry are data: grad_theta_dev with PHNN_WGRAD_ACCUMULATE / accumulate = 1; best_cost_dev and
  *     best_u_dev of phnn_adam_step, phnn_mppi_update and phnn_cem_update (the solves reset them first); done_step_dev of
  *     phnn_plant_step (initialise to -1); log_states_dev / log_controls_dev, of which a call writes one row (and of
- *     phnn_plant_step_ex: disturbance_log_dev likewise, cost_acc_dev / run_dev / best_run_dev of its metrics); and the
+ *     phnn_plant_step_ex: disturbance_log_dev likewise, cost_acc_dev / run_dev / best_run_dev of its metrics); cost_dev of
+ *     phnn_terminal_cost, which adds to what K1 wrote, and its traj_bar_dev, of which it writes row H only; and the
  *     documented in-place states (u_dev of the solves and updates, sigma_dev, exp_avg / exp_avg_sq of phnn_adam_step,
  *     state_dev, *step_dev);
  *   - alignment: float32 / int32 tensors need 4-byte and float64 tensors 8-byte alignment, with two exceptions.
@@ -265,6 +266,15 @@ int phnn_rollout_grad_ref(phnn_handle* h, const float* x0_dev, const float* u_de
                           const float* traj_dev, const void* workspace_dev, float* grad_u_dev, float* grad_x0_dev,
                           void* stream);
 
+/* phnn_rollout_vjp tracking a reference: the stage cost's part of the gradient is taken about the reference rows, as in
+ * phnn_rollout_grad_ref; traj_bar_dev and cost_bar_dev as in phnn_rollout_vjp.  The same K2 launch as
+ * phnn_rollout_grad_ref, which is the special case traj_bar = 0, cost_bar = 1 (the solve with a terminal weight hands the
+ * terminal term's gradient in through traj_bar_dev). */
+int phnn_rollout_vjp_ref(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                         const phnn_cost* cost, const phnn_reference* ref, int32_t integrator, float dt,
+                         const float* traj_dev, const void* workspace_dev, const float* traj_bar_dev,
+                         const float* cost_bar_dev, float* grad_u_dev, float* grad_x0_dev, void* stream);
+
 /* ---- training side: rollouts with gradients w.r.t. the MODEL PARAMETERS ----------------------
  * What loss.backward() does in the reference's training loops (scripts/train_cartpole_phnn.py:112-178,
  * scripts/train_cartpole_phnn_canonical.py:83-196, main.py:93-148): an Euler (or RK4) rollout from x_batch[:,0] with
@@ -273,7 +283,9 @@ int phnn_rollout_grad_ref(phnn_handle* h, const float* x0_dev, const float* u_de
  * its cotangents on the two outputs and return the parameter gradient as a blob laid out exactly like the weight blob
  * of phnn_create (buffers of the reference modules -- G_fixed, the canonical G -- and the CartPoleMassMatrix
  * parameters, which are constants to autograd through .item(), src/mass_matrix.py:299-301, stay zero).
- * Available for PHNN and CANONICAL handles (PHNN_ERR_UNSUPPORTED for ODEFUNC). */
+ * Available for the variants with weight-gradient kernels: the tanh PHNN and CANONICAL ones.  PHNN_ERR_UNSUPPORTED for
+ * every other handle -- ODEFUNC, and the all-f32 kernels of the other activations -- whose
+ * phnn_wgrad_workspace_bytes() is 0. */
 
 /* Forward of a training rollout: no clamp, no cost.  -> traj_dev (B,H+1,n) = X_pred, dx_dev (B,H,n) = dX_pred
  * (f(x_t,u_t) at the first stage of each step; may be NULL). */
@@ -930,6 +942,101 @@ int phnn_feedback_control(phnn_handle* h, const float* x_dev, const float* u_dev
                           int64_t B, int32_t H, const phnn_cost* cost, int32_t solve_every, const int32_t* step_dev,
                           int32_t step_host, float* u_out, int32_t* status_out, double* dev_out, int32_t* log_status_dev,
                           double* log_dev_dev, void* stream);
+
+/* ---- terminal cost and its LQR weight for the Adam and Gauss-Newton solves -------------------------------
+ * Every solve above weights the last state like every other one.  A terminal weight adds, per rollout b,
+ *   cost_b += e_H^T W e_H,   e_H = x_H - r_{b,row(H)},
+ * with row(H) exactly K1's rule min(offset + H, rows - 1) -- the device offset when the reference has one -- and the
+ * cost's x_target without a reference.  W is n x n float32, row-major, on the device, never written: ONE matrix for the
+ * batch (batch_stride 0) or one per problem; row i of a batch uses the W of problem i / group, so group is 1 for a plain
+ * batch and L for the L line-search candidates per problem of the Gauss-Newton solve.  The usual W is the cost-to-go of
+ * the infinite-horizon LQR of the model linearised at the target, which phnn_dare computes.  A NULL phnn_terminal means
+ * no terminal term: the entry points below then issue the launches of their plain counterparts and return their bits.
+ * L-BFGS, MPPI and CEM take no terminal weight; the TV-LQR of phnn_feedback_plan stays on the stage cost. */
+typedef struct {
+  const float* W_dev;   /* device, (n,n) row-major per problem */
+  int64_t batch_stride; /* floats between problems; 0 = one W shared by all */
+  int32_t group;        /* rows per problem, >= 1 */
+} phnn_terminal;
+
+/* k_terminal_cost<n>, n in {2, 3, 4}: one thread per rollout, float32, behind the K1 launch that wrote traj_dev (B,H+1,n)
+ * and cost_dev (B).  Operation order (tests/terminal_model.py; the kernel equals it bit for bit), the fused
+ * multiply-adds below being the only ones:
+ *   e_i = x_H,i - r_i                         formed as the stage cost forms it
+ *   s_j = fma(e_i, W[i][j], s_j)              i ascending, from 0
+ *   c   = fma(s_j, e_j, c)                    j ascending, from 0
+ *   cost_dev[b] = cost_dev[b] + c
+ *   traj_bar_dev[b,H,i] = g_i, g_i = fma(W[i][j] + W[j][i], e_j, g_i)   j ascending from 0, the sum of the two weights
+ *                                             rounded once in float32 -- only when traj_bar_dev != NULL
+ * Rows t < H of traj_bar_dev (B,H+1,n) are never written: the caller zeroes them once, and phnn_rollout_vjp with that
+ * cotangent returns the gradient of the total cost.  A NaN state gives a NaN cost and a NaN row.  ref: NULL = the cost's
+ * x_target, else K1's reference (batch_stride indexes the B rows).  B == 0: PHNN_OK, nothing launched.
+ * PHNN_ERR_INVALID_ARG, nothing launched: NULL handle, cost or term, B < 0, H < 1, W_dev == NULL (B > 0), group < 1, a
+ * negative batch_stride, NULL traj_dev / cost_dev (B > 0), the reference checks of phnn_rollout_fwd_ref;
+ * PHNN_ERR_UNSUPPORTED for n outside {2, 3, 4}. */
+int phnn_terminal_cost(phnn_handle* h, const float* traj_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                       const phnn_reference* ref, const phnn_terminal* term, float* cost_dev, float* traj_bar_dev,
+                       void* stream);
+
+/* k_dare<n,m>, the (n, m) of phnn_tvlqr: one thread per problem, float64, no fused multiply-adds.  The Riccati step of
+ * phnn_tvlqr -- ONE device function both kernels call, operation order in tests/tvlqr_model.py -- with the constant
+ * A_dev (B,n,n), Bm_dev (B,n,m) float32 of problem b, from P_0 = Lxx = Q + Q^T:  step k = 1, 2, ... gives P_k and the
+ * gain K_k = -X_k, so after N steps the kernel holds what phnn_tvlqr returns as P0 and K[0] on N copies of (A, B), bit
+ * for bit.  After each step d = max |P_k - P_{k-1}| and s = max |P_k| over the entries:
+ *   status 1  a pivot failure, or an s that is NaN or +inf, or a W entry that is not finite: P, K, W all quiet NaN
+ *   status 0  d <= tol * s: converged
+ *   status 2  k == max_iters: the outputs are the last iterate
+ * Outputs: P_dev (B,n,n) float64 = P_k (in the cost's units the cost-to-go of a deviation e is e^T (P/2) e), K_dev
+ * (B,m,n) float64, W_dev (B,n,n) float32 = (float)(0.5 * (P_k - Lxx)) -- the stage cost already charges Q at t = H --,
+ * iters_dev (B) int32 = k, status_dev (B) int32.  mu >= 0 is added to the diagonal of Quu as in phnn_tvlqr.
+ * opt NULL = {200000, 1e-12, 0}: untrained models of this family need some 62 000 steps at tol 1e-12.
+ * PHNN_ERR_INVALID_ARG, nothing launched: NULL handle or cost, B < 0, max_iters < 1, a negative or non-finite tol or mu,
+ * non-zero reserved, NULL tensors (B > 0); PHNN_ERR_UNSUPPORTED for an (n, m) without a TV-LQR kernel. */
+typedef struct {
+  int32_t max_iters;   /* >= 1 */
+  double tol;          /* >= 0, finite; relative to max |P| */
+  double mu;           /* >= 0, finite */
+  int32_t reserved[4]; /* zero */
+} phnn_dare_options;
+int phnn_dare(phnn_handle* h, const float* A_dev, const float* Bm_dev, int64_t B, const phnn_cost* cost,
+              const phnn_dare_options* opt, double* P_dev, double* K_dev, float* W_dev, int32_t* iters_dev,
+              int32_t* status_dev, void* stream);
+
+/* The Gauss-Newton direction with a terminal weight: phnn_gn_direction (flags 0) or phnn_gn_direction_box (PHNN_GN_BOX;
+ * nclamp_dev as there, NULL without the flag) with the backward sweep started from
+ *   Tf[i][j] = (double)W[i][j] + (double)W[j][i],   P_H = Lxx_H + Tf,
+ *   p_H[i] = lx_H[i] + sum_k Tf[i][k] e_k           k ascending from 0.0, each product rounded, then added,
+ * e = (double)x_H - (double)r_H, W the matrix of problem b / group.  term == NULL: those additions are not executed at
+ * all and the call is the plain one, bit for bit.  Checks: the plain call's, then the terminal's of phnn_terminal_cost. */
+int phnn_gn_direction_term(phnn_handle* h, const float* A_dev, const float* Bm_dev, const float* traj_dev, const float* u_dev,
+                           int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref, const phnn_terminal* term,
+                           const double* mu_dev, float* du_dev /* (B,H,m) */, double* dV_dev /* (B) */,
+                           int32_t* status_dev /* (B) */, int32_t flags, int32_t* nclamp_dev /* (B) or NULL */,
+                           double* scratch_dev, void* stream);
+
+/* phnn_solve / phnn_solve_ref with an optional terminal weight: ref may be NULL and term may be NULL in the same call.
+ * Per iteration: K1 -> k_terminal_cost (cost and row H of traj_bar_dev) -> K2 with that cotangent -> K3, so the cost
+ * history and the best-iterate tracking see the total cost.  traj_bar_dev (B,H+1,n): caller-owned scratch, required
+ * with a terminal weight (B > 0, iters > 0); the call zeroes it once, before the first iteration.  term == NULL:
+ * traj_bar_dev is not touched and the launches and bits are phnn_solve's / phnn_solve_ref's.  term->group applies to the
+ * B rows (1 for a plain batch). */
+int phnn_solve_term(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                    const phnn_reference* ref, const phnn_terminal* term, int32_t integrator, float dt,
+                    const phnn_solve_options* opt, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_dev,
+                    float* cost_dev, float* traj_dev, void* workspace_dev, float* costs_dev, float* best_cost_dev,
+                    float* best_u_dev, float* traj_bar_dev, void* stream);
+
+/* phnn_solve_gn_ex with an optional terminal weight.  The set-up K1 and the candidates' K1 are each followed by
+ * k_terminal_cost (cost only; the candidates with group * L rows per W), the direction of every iteration takes the
+ * terminal as phnn_gn_direction_term does, k_gn_select is unchanged: it compares total costs.  term->batch_stride and
+ * term->group index the B PROBLEMS (group 1: problem b uses W_dev + b * batch_stride).  The workspace is
+ * phnn_solve_gn's (phnn_gn_workspace_bytes; the terminal needs none of its own).  term == NULL: phnn_solve_gn_ex
+ * itself, the same launches and the same bits. */
+int phnn_solve_gn_term(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                       const phnn_reference* ref, const phnn_terminal* term, int32_t integrator, float dt,
+                       const phnn_gn_options* opt, void* workspace, size_t workspace_size, float* cost_out, float* costs_dev,
+                       double* mu_out, int32_t* accepts_dev, float* alpha_hist_dev, int32_t flags,
+                       int32_t* nclamp_hist_dev /* (iters,B) or NULL */, void* stream);
 
 /* Introspection for tests: copies the packed weight image the kernels stage into LDS (phnn_kernels.hip.h layouts; a
  * device-resident private format) to image_host after the work queued on `stream`, and waits for the copy.

@@ -40,6 +40,8 @@ EXPORTED = [
     "phnn_gn_direction_box", "phnn_solve_gn_ex",
     "phnn_ekf_workspace_bytes", "phnn_ekf_update", "phnn_ekf_step",
     "phnn_feedback_workspace_bytes", "phnn_feedback_plan", "phnn_feedback_control",
+    "phnn_rollout_vjp_ref", "phnn_terminal_cost", "phnn_dare", "phnn_gn_direction_term", "phnn_solve_term",
+    "phnn_solve_gn_term",
 ]
 
 PHNN_GN_BOX = 1  # flags of phnn_solve_gn_ex
@@ -115,6 +117,17 @@ class GnOptions(C.Structure):
     mu_up (cap mu_max) after a rejected one."""
     _fields_ = [("iters", C.c_int32), ("line_steps", C.c_int32), ("mu_init", C.c_double), ("mu_min", C.c_double),
                 ("mu_max", C.c_double), ("mu_up", C.c_double), ("mu_down", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class Terminal(C.Structure):
+    """phnn_terminal: row i of a batch adds e_H^T W e_H with W = W_dev + (i // group) * batch_stride, (n,n) row-major."""
+    _fields_ = [("W_dev", C.c_void_p), ("batch_stride", C.c_int64), ("group", C.c_int32)]
+
+
+class DareOptions(C.Structure):
+    """phnn_dare_options: at most max_iters Riccati steps, stopped where max|P_k - P_{k-1}| <= tol * max|P_k|; mu >= 0
+    on the diagonal of Quu."""
+    _fields_ = [("max_iters", C.c_int32), ("tol", C.c_double), ("mu", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
 class EkfOptions(C.Structure):
@@ -375,6 +388,27 @@ def load_library():
     lib.phnn_feedback_control.argtypes = [vp, f32p, f32p, f32p, vp, i64, i32, C.POINTER(Cost), i32, vp, i32, f32p, vp, vp, vp, vp,
                                           vp]
     lib.phnn_feedback_control.restype = C.c_int
+    # the terminal cost
+    trm = C.POINTER(Terminal)
+    lib.phnn_rollout_vjp_ref.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), i32, C.c_float, f32p,
+                                         vp, f32p, f32p, f32p, f32p, vp]
+    lib.phnn_rollout_vjp_ref.restype = C.c_int
+    lib.phnn_terminal_cost.argtypes = [vp, f32p, i64, i32, C.POINTER(Cost), C.POINTER(Reference), trm, f32p, f32p, vp]
+    lib.phnn_terminal_cost.restype = C.c_int
+    lib.phnn_dare.argtypes = [vp, f32p, f32p, i64, C.POINTER(Cost), C.POINTER(DareOptions), vp, vp, f32p, vp, vp, vp]
+    lib.phnn_dare.restype = C.c_int
+    # phnn_gn_direction's arguments with the terminal after the reference and flags, nclamp before the scratch
+    gd = lib.phnn_gn_direction.argtypes
+    lib.phnn_gn_direction_term.argtypes = gd[:9] + [trm] + gd[9:13] + [i32, vp] + gd[13:]
+    lib.phnn_gn_direction_term.restype = C.c_int
+    # phnn_solve_ref's arguments with the terminal after the reference and traj_bar before the stream
+    sr = lib.phnn_solve_ref.argtypes
+    lib.phnn_solve_term.argtypes = sr[:7] + [trm] + sr[7:-1] + [f32p, vp]
+    lib.phnn_solve_term.restype = C.c_int
+    # phnn_solve_gn_ex's arguments with the terminal after the reference
+    sg = lib.phnn_solve_gn_ex.argtypes
+    lib.phnn_solve_gn_term.argtypes = sg[:7] + [trm] + sg[7:]
+    lib.phnn_solve_gn_term.restype = C.c_int
     lib.phnn_kernel_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i64]
     lib.phnn_kernel_info.restype = C.c_int
     lib.phnn_variant_name.argtypes = [vp]

@@ -31,6 +31,9 @@
                          only, and every step applies row step % solve_every of the last plan plus the time-varying LQR
                          feedback on the deviation from its nominal trajectory (phnn_feedback_plan, phnn_feedback_control;
                          DESIGN.md 21).  The result gains track_status (T,B) and track_dev (T,B).
+  terminal               (all three drivers) a controller built with terminal= (terminal.TerminalCost: the terminal weight
+                         of the Adam and Gauss-Newton solves) solves with it at every step, inside the
+                         captured control step too; a controller whose solve has no terminal term refuses it.
 """
 import numpy as np
 
@@ -397,6 +400,11 @@ class DeviceClosedLoop:
             raise ValueError(f"Unknown optimizer type: {controller.optimizer_type}")
         if self.lbfgs and not hasattr(eng, "solve_lbfgs"):
             raise NotImplementedError(f"{type(eng).__name__} has no batched L-BFGS solve (RolloutEngine has)")
+        # the controller's terminal weight (None: none); its device tensor is read in place by the captured step.  The
+        # solves without a terminal term refuse one here (controller.terminal_cost)
+        self.terminal = controller.terminal_cost() if hasattr(controller, "terminal_cost") else None
+        if self.terminal is not None and not hasattr(eng, "terminal_cost"):
+            raise NotImplementedError(f"{type(eng).__name__} has no terminal cost (RolloutEngine has)")
         self.graph = None
         self.use_graph = use_graph and dev.type == "cuda"
         self.ex = self.metrics = None
@@ -534,7 +542,7 @@ class DeviceClosedLoop:
         else:
             out = eng.solve(self.x32, self.u_init, self.cost, c.integrator, c.dt, lr=self.lr, iters=self.iters,
                             track_best=self.canonical, record_costs=False, workspace=self.ws, x_ref=self.x_ref,
-                            ref_offset=self.step_dev)
+                            ref_offset=self.step_dev, **({} if self.terminal is None else {"terminal": self.terminal}))
         return out
 
     def _control_step(self):

@@ -32,6 +32,12 @@ struct GnDirectionParams {
   int ref_rows;
   const int* ref_off_dev;
   int ref_off_host;
+  // terminal weight (phnn_terminal), read only where the backward sweep starts: with
+  // W = term_W + (b / term_group) * term_bs, Tf[i][j] = (double)W[i][j] + (double)W[j][i], P_H = Lxx_H + Tf and
+  // p_H = lx_H + Tf e_H (k ascending from 0.0, each product rounded, then added).  NULL: none of this is executed.
+  const float* term_W;
+  long long term_bs;
+  int term_group;
 };
 
 // k_gn_direction_box (tests/gn_box_model.py): the plain step's arguments and the control bounds

@@ -18,6 +18,29 @@ constexpr int kFlat = 256;
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// The terminal weight in the initialisation of both backward sweeps (tests/terminal_model.py):
+// Tf[i][j] = (double)W[i][j] + (double)W[j][i], P_H = Lxx_H + Tf, p_H = lx_H + Tf e_H with k ascending from 0.0, each
+// product rounded, then added.  Called only with a terminal weight, so a solve without one executes none of it.
+template <int N>
+__device__ __forceinline__ void terminal_init(const GnDirectionParams& p, long long b, const double (&e)[N],
+                                              const double (&lx)[N], double (&P)[N][N], double (&pv)[N]) {
+  const float* W = p.term_W + (b / p.term_group) * p.term_bs;
+  double Tf[N][N];
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) Tf[i][j] = (double)W[i * N + j] + (double)W[j * N + i];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) P[i][j] = P[i][j] + Tf[i][j];
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) a = a + Tf[i][k] * e[k];
+    pv[i] = lx[i] + a;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ k_gn_direction
 // One thread per problem, float64 in registers.  The backward step is the TWIN of k_tvlqr's (phnn_kernels.hip.h) with the
 // affine terms added: S, T, Qxx, Qux, Quu, the LDL^T factorisation, X, K_t and the symmetrised P_t are formed exactly
@@ -89,6 +112,7 @@ __global__ __launch_bounds__(kDirThreads) void k_gn_direction(GnDirectionParams 
         for (int j = 0; j < N; ++j) P[i][j] = i == j ? ldiag[i] : p.Lxx[i * N + j];
         pv[i] = lx[i];
       }
+      if (p.term_W) terminal_init<N>(p, b, e, lx, P, pv);
       continue;
     }
     double A[N][N], Bt[N][MI];
@@ -357,6 +381,7 @@ __global__ __launch_bounds__(kDirThreads) void k_gn_direction_box(GnDirectionBox
         for (int j = 0; j < N; ++j) P[i][j] = i == j ? ldiag[i] : p.Lxx[i * N + j];
         pv[i] = lx[i];
       }
+      if (p.term_W) terminal_init<N>(p, b, e, lx, P, pv);
       continue;
     }
     double A[N][N], Bt[N][MI];

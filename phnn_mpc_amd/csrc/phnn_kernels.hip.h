@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "../../include/phnn_mpc.h"
+#include "phnn_riccati.hip.h"
 
 #define DEV __device__ __forceinline__
 // The K1 -> K2 tape is streamed once each way at large batches: non-temporal stores / loads (worth 3 % each over plain
@@ -3578,118 +3579,13 @@ __global__ __launch_bounds__(64) void k_tvlqr(TvlqrParams p) {
 #pragma unroll
       for (int j = 0; j < MI; ++j) Bt[i][j] = (double)Bb[(long long)t * (N * MI) + i * MI + j];
     }
-    double S[N][N], T[N][MI];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        double a = 0.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) a = a + P[i][k] * A[k][j];
-        S[i][j] = a;
-      }
-#pragma unroll
-      for (int j = 0; j < MI; ++j) {
-        double a = 0.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) a = a + P[i][k] * Bt[k][j];
-        T[i][j] = a;
-      }
-    }
-    double Qxx[N][N], Qux[MI][N], Quu[MI][MI];
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        double a = 0.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) a = a + A[k][i] * S[k][j];
-        Qxx[i][j] = p.Lxx[i * N + j] + a;
-      }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        double a = 0.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) a = a + Bt[k][i] * S[k][j];
-        Qux[i][j] = a;
-      }
-#pragma unroll
-      for (int j = 0; j <= i; ++j) {  // lower triangle only
-        double a = 0.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) a = a + Bt[k][i] * T[k][j];
-        double q = p.Luu[i * MI + j] + a;
-        if (i == j) q = q + p.mu;
-        Quu[i][j] = q;
-      }
-    }
-    // Quu = L D L^T, no square roots
-    double Lf[MI][MI], D[MI];
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < MI; ++j) {
-      double w[MI];
-      double d = Quu[j][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) {
-        w[k] = Lf[j][k] * D[k];
-        d = d - Lf[j][k] * w[k];
-      }
-      D[j] = d;
-      if (!(d > 0.0) || d == __builtin_inf()) bad = true;
-#pragma unroll
-      for (int i = j + 1; i < MI; ++i) {
-        double s = Quu[i][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s = s - Lf[i][k] * w[k];
-        Lf[i][j] = s / d;
-      }
-    }
-    if (bad) break;
+    // the step itself is riccati_step (phnn_riccati.hip.h), which k_dare iterates on one (A, B)
     double X[MI][N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-      double y[MI];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        double s = Qux[i][c];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s = s - Lf[i][k] * y[k];
-        y[i] = s;
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i) y[i] = y[i] / D[i];
-#pragma unroll
-      for (int i = MI - 1; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < MI; ++k) s = s - Lf[k][i] * X[k][c];
-        X[i][c] = s;
-      }
-    }
+    if (!riccati_step<N, MI>(P, A, Bt, p.Lxx, p.Luu, p.mu, X)) break;
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int j = 0; j < N; ++j) Kb[(long long)t * (MI * N) + i * N + j] = -X[i][j];
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        double a = 0.0;
-#pragma unroll
-        for (int k = 0; k < MI; ++k) a = a + Qux[k][i] * X[k][j];
-        S[i][j] = Qxx[i][j] - a;
-      }
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-      for (int j = i; j < N; ++j) {
-        const double s = 0.5 * (S[i][j] + S[j][i]);
-        P[i][j] = s;
-        P[j][i] = s;
-      }
     if (Pa) {
 #pragma unroll
       for (int i = 0; i < N; ++i)

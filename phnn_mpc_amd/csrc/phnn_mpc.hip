@@ -21,6 +21,7 @@
 #include "phnn_gn.h"
 #include "phnn_ekf.h"
 #include "phnn_feedback.h"
+#include "phnn_terminal.h"
 #include "phnn_pack.h"
 
 namespace {
@@ -855,6 +856,16 @@ int phnn_rollout_vjp(phnn_handle* h, const float* x0_dev, const float* u_dev, in
                      grad_u_dev, grad_x0_dev, nullptr, stream);
 }
 
+int phnn_rollout_vjp_ref(phnn_handle* h, const float* x0_dev, const float* u_dev, int64_t B, int32_t H,
+                         const phnn_cost* cost, const phnn_reference* ref, int32_t integrator, float dt, const float* traj_dev,
+                         const void* workspace_dev, const float* traj_bar_dev, const float* cost_bar_dev, float* grad_u_dev,
+                         float* grad_x0_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (!ref) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference is NULL");
+  return rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, traj_bar_dev, cost_bar_dev,
+                     grad_u_dev, grad_x0_dev, ref, stream);
+}
+
 // ---- training side --------------------------------------------------------------------------
 static long long wgrad_records(int64_t B, int32_t H, int32_t integrator) {
   long long tiles = tiles_of(B);
@@ -1016,19 +1027,117 @@ int phnn_adam_step(phnn_handle* h, float* u_dev, const float* grad_dev, float* e
   return checked(h, hipGetLastError(), "adam launch");  // read once, behind both launches
 }
 
+// ---- terminal cost: kernels in phnn_terminal.hip ---------------------------------------------------
+static int check_terminal(phnn_handle* h, const phnn_terminal* term, int64_t B) {
+  if (!term) return PHNN_OK;
+  if (term->group < 1) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_terminal: group < 1");
+  if (term->batch_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_terminal: negative batch_stride");
+  if (B > 0 && !term->W_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_terminal: W_dev is NULL");
+  return PHNN_OK;
+}
+
+// k_terminal_cost behind a K1 launch over `rows` rollouts, `group` of them per W (the solves' callers have checked
+// cost, ref and term; the public entry point below checks them first).
+static int terminal_cost(phnn_handle* h, const float* traj_dev, int64_t rows, int32_t H, const phnn_cost* cost,
+                         const phnn_reference* ref, const phnn_terminal* term, int64_t group, float* cost_dev,
+                         float* traj_bar_dev, void* stream) {
+  RollParams rp{};  // the reference checks, and its fields, are K1's
+  if (int rc = fill_ref(h, &rp, ref, rows)) return rc;
+  if (rows == 0) return PHNN_OK;
+  if (!traj_dev || !cost_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_terminal_cost: traj_dev / cost_dev is NULL");
+  if (group > INT32_MAX) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_terminal: group too large");
+  const int n = h->desc.n;
+  if (n < 2 || n > 4) return fail(h, PHNN_ERR_UNSUPPORTED, "no terminal-cost kernel for this state dimension");
+  TerminalCostParams p{};
+  p.traj = traj_dev;
+  p.cost = cost_dev;
+  p.traj_bar = traj_bar_dev;
+  p.W = term->W_dev;
+  p.w_bs = term->batch_stride;
+  p.group = (int)group;
+  p.B = (long long)rows;
+  p.H = H;
+  for (int i = 0; i < n; ++i) p.x_target[i] = cost->x_target[i];
+  p.x_ref = rp.x_ref;
+  p.ref_bs = rp.ref_bs;
+  p.ref_ts = rp.ref_ts;
+  p.ref_rows = ref ? rp.ref_rows : 1;
+  p.ref_off_dev = rp.ref_off_dev;
+  p.ref_off_host = rp.ref_off_host;
+  PHNN_ON_DEVICE(h);
+  return checked(h, terminal_cost_launch(n, p, (hipStream_t)stream), "k_terminal_cost launch");
+}
+
+int phnn_terminal_cost(phnn_handle* h, const float* traj_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                       const phnn_reference* ref, const phnn_terminal* term, float* cost_dev, float* traj_bar_dev,
+                       void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
+  if (int rc = check_cost(h, cost)) return rc;
+  if (!term) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_terminal is NULL");
+  if (int rc = check_terminal(h, term, B)) return rc;
+  return terminal_cost(h, traj_dev, B, H, cost, ref, term, term->group, cost_dev, traj_bar_dev, stream);
+}
+
+int phnn_dare(phnn_handle* h, const float* A_dev, const float* Bm_dev, int64_t B, const phnn_cost* cost,
+              const phnn_dare_options* opt, double* P_dev, double* K_dev, float* W_dev, int32_t* iters_dev,
+              int32_t* status_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
+  if (!cost) return fail(h, PHNN_ERR_INVALID_ARG, "cost is NULL");
+  phnn_dare_options o{};
+  o.max_iters = 200000;
+  o.tol = 1e-12;
+  if (opt) o = *opt;
+  if (o.max_iters < 1) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dare_options: max_iters < 1");
+  if (!(o.tol >= 0.0) || !std::isfinite(o.tol)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dare_options: tol is negative or not finite");
+  if (!(o.mu >= 0.0) || !std::isfinite(o.mu)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dare_options: mu is negative or not finite");
+  for (int r : o.reserved)
+    if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dare_options: reserved must be zero");
+  if (B == 0) return PHNN_OK;
+  if (!A_dev || !Bm_dev || !P_dev || !K_dev || !W_dev || !iters_dev || !status_dev) return fail(h, PHNN_ERR_INVALID_ARG, "NULL tensor");
+  const int n = h->desc.n, m = h->desc.m;
+  if (n < 2 || n > 4 || m < 1 || m > 4) return fail(h, PHNN_ERR_UNSUPPORTED, "no DARE kernel for this (n, m)");
+  PHNN_ON_DEVICE(h);
+  DareParams p{};
+  p.A = A_dev;
+  p.Bm = Bm_dev;
+  p.P = P_dev;
+  p.K = K_dev;
+  p.W = W_dev;
+  p.iters = iters_dev;
+  p.status = status_dev;
+  p.B = (long long)B;
+  p.max_iters = o.max_iters;
+  p.tol = o.tol;
+  p.mu = o.mu;
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) p.Lxx[i * n + j] = (double)cost->Q[i * n + j] + (double)cost->Q[j * n + i];
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) p.Luu[i * m + j] = (double)cost->R[i * m + j] + (double)cost->R[j * m + i];
+  return checked(h, dare_launch(n, m, p, (hipStream_t)stream), "k_dare launch");
+}
+
+// term == NULL: phnn_solve / phnn_solve_ref, launch for launch.  With one, every K1 is followed by k_terminal_cost, which
+// also writes row H of traj_bar_dev, and K2 reads that cotangent.
 static int solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
                  int32_t integrator, float dt, const phnn_solve_options* opt, float* exp_avg_dev, float* exp_avg_sq_dev,
                  float* grad_dev, float* cost_dev, float* traj_dev, void* workspace_dev, float* costs_dev,
-                 float* best_cost_dev, float* best_u_dev, const phnn_reference* ref, void* stream) {
+                 float* best_cost_dev, float* best_u_dev, const phnn_reference* ref, void* stream,
+                 const phnn_terminal* term = nullptr, float* traj_bar_dev = nullptr) {
   if (!h) return PHNN_ERR_INVALID_ARG;
   if (!opt || opt->iters < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_options: NULL or iters < 0");
   RollParams p;
   if (int rc = fill_roll(h, &p, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
   if (int rc = fill_ref(h, &p, ref, B)) return rc;
+  if (int rc = check_terminal(h, term, B)) return rc;
   if (B == 0 || opt->iters == 0) return PHNN_OK;
   if (!exp_avg_dev || !exp_avg_sq_dev || !grad_dev || !cost_dev || !traj_dev)
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve: exp_avg, exp_avg_sq, grad, cost and traj buffers are required");
   if (opt->track_best && (!best_cost_dev || !best_u_dev)) return fail(h, PHNN_ERR_INVALID_ARG, "track_best needs best_cost_dev and best_u_dev");
+  if (term && !traj_bar_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_term: a terminal weight needs traj_bar_dev");
+  if (term && (h->desc.n < 2 || h->desc.n > 4)) return fail(h, PHNN_ERR_UNSUPPORTED, "no terminal-cost kernel for this state dimension");
+  if (!term) traj_bar_dev = nullptr;
   PHNN_ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
   const int m = h->desc.m;
@@ -1038,14 +1147,18 @@ static int solve(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, i
   if (e == hipSuccess) e = hipMemsetAsync(exp_avg_sq_dev, 0, sizeof(float) * count, st);
   if (e == hipSuccess && opt->track_best) e = hipMemsetD32Async((hipDeviceptr_t)best_cost_dev, 0x7F800000, (size_t)B, st);
   if (e == hipSuccess && opt->track_best) e = hipMemsetAsync(best_u_dev, 0, sizeof(float) * count, st);
+  // rows t < H of the cotangent stay zero through the whole solve: k_terminal_cost writes row H only
+  if (e == hipSuccess && term) e = hipMemsetAsync(traj_bar_dev, 0, sizeof(float) * (size_t)B * (H + 1) * h->desc.n, st);
   if (e != hipSuccess) return hip_fail(h, e, "phnn_solve: state reset");
   for (int k = 0; k < opt->iters; ++k) {
     if (int rc = rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, cost_dev, traj_dev, workspace_dev, ref, stream)) return rc;
+    if (term)
+      if (int rc = terminal_cost(h, traj_dev, B, H, cost, ref, term, term->group, cost_dev, traj_bar_dev, stream)) return rc;
     if (costs_dev) {
       e = hipMemcpyAsync(costs_dev + (size_t)k * B, cost_dev, sizeof(float) * (size_t)B, hipMemcpyDeviceToDevice, st);
       if (e != hipSuccess) return hip_fail(h, e, "phnn_solve: cost history copy");
     }
-    if (int rc = rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, nullptr, nullptr, grad_dev,
+    if (int rc = rollout_vjp(h, x0_dev, u_dev, B, H, cost, integrator, dt, traj_dev, workspace_dev, traj_bar_dev, nullptr, grad_dev,
                              nullptr, ref, stream))
       return rc;
     if (int rc = phnn_adam_step(h, u_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, (int64_t)count, opt->lr, opt->beta1, opt->beta2,
@@ -1073,6 +1186,15 @@ int phnn_solve_ref(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B,
   if (!ref) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_reference is NULL");
   return solve(h, x0_dev, u_dev, B, H, cost, integrator, dt, opt, exp_avg_dev, exp_avg_sq_dev, grad_dev, cost_dev, traj_dev,
                workspace_dev, costs_dev, best_cost_dev, best_u_dev, ref, stream);
+}
+
+int phnn_solve_term(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                    const phnn_reference* ref, const phnn_terminal* term, int32_t integrator, float dt,
+                    const phnn_solve_options* opt, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_dev,
+                    float* cost_dev, float* traj_dev, void* workspace_dev, float* costs_dev, float* best_cost_dev,
+                    float* best_u_dev, float* traj_bar_dev, void* stream) {
+  return solve(h, x0_dev, u_dev, B, H, cost, integrator, dt, opt, exp_avg_dev, exp_avg_sq_dev, grad_dev, cost_dev, traj_dev,
+               workspace_dev, costs_dev, best_cost_dev, best_u_dev, ref, stream, term, traj_bar_dev);
 }
 
 size_t phnn_lbfgs_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32_t history_size) {
@@ -1723,12 +1845,13 @@ size_t phnn_gn_workspace_bytes(const phnn_handle* h, int64_t B, int32_t H, int32
 static int fill_gn_direction(phnn_handle* h, const char* who, const float* A_dev, const float* Bm_dev, const float* traj_dev,
                              const float* u_dev, int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref,
                              const double* mu_dev, float* du_dev, double* dV_dev, int32_t* status_dev, double* scratch_dev,
-                             GnDirectionParams* out, bool* launch) {
+                             GnDirectionParams* out, bool* launch, const phnn_terminal* term = nullptr) {
   *launch = false;
   if (B < 0 || H < 1) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch or horizon < 1");
   if (int rc = check_cost(h, cost)) return rc;
   RollParams rp{};  // the reference checks, and its fields, are K1's
   if (int rc = fill_ref(h, &rp, ref, B)) return rc;
+  if (int rc = check_terminal(h, term, B)) return rc;
   if (B == 0) return PHNN_OK;
   if (!A_dev || !Bm_dev || !traj_dev || !u_dev || !mu_dev || !du_dev || !dV_dev || !status_dev || !scratch_dev)
     return fail(h, PHNN_ERR_INVALID_ARG, who);
@@ -1760,6 +1883,11 @@ static int fill_gn_direction(phnn_handle* h, const char* who, const float* A_dev
   p.ref_rows = ref ? rp.ref_rows : 1;
   p.ref_off_dev = rp.ref_off_dev;
   p.ref_off_host = rp.ref_off_host;
+  if (term) {  // NULL leaves term_W null: the kernels then skip the terminal initialisation altogether
+    p.term_W = term->W_dev;
+    p.term_bs = term->batch_stride;
+    p.term_group = term->group;
+  }
   *out = p;
   *launch = true;
   return PHNN_OK;
@@ -1795,6 +1923,29 @@ int phnn_gn_direction_box(phnn_handle* h, const float* A_dev, const float* Bm_de
   q.has_u_bounds = cost->has_u_bounds;
   q.nclamp = nclamp_dev;
   PHNN_ON_DEVICE(h);
+  return checked(h, gn_direction_box_launch(h->desc.n, h->desc.m, q, (hipStream_t)stream), "k_gn_direction_box launch");
+}
+
+int phnn_gn_direction_term(phnn_handle* h, const float* A_dev, const float* Bm_dev, const float* traj_dev, const float* u_dev,
+                           int64_t B, int32_t H, const phnn_cost* cost, const phnn_reference* ref, const phnn_terminal* term,
+                           const double* mu_dev, float* du_dev, double* dV_dev, int32_t* status_dev, int32_t flags,
+                           int32_t* nclamp_dev, double* scratch_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (flags & ~PHNN_GN_BOX) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_direction_term: unknown flag bits");
+  const bool box = (flags & PHNN_GN_BOX) != 0;
+  if (nclamp_dev && !box) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_gn_direction_term: nclamp_dev without PHNN_GN_BOX");
+  GnDirectionBoxParams q{};
+  bool launch;
+  if (int rc = fill_gn_direction(h, "phnn_gn_direction_term: NULL tensor", A_dev, Bm_dev, traj_dev, u_dev, B, H, cost, ref,
+                                 mu_dev, du_dev, dV_dev, status_dev, scratch_dev, &q.d, &launch, term))
+    return rc;
+  if (!launch) return PHNN_OK;
+  PHNN_ON_DEVICE(h);
+  if (!box) return checked(h, gn_direction_launch(h->desc.n, h->desc.m, q.d, (hipStream_t)stream), "k_gn_direction launch");
+  q.u_min = (double)cost->u_min;
+  q.u_max = (double)cost->u_max;
+  q.has_u_bounds = cost->has_u_bounds;
+  q.nclamp = nclamp_dev;
   return checked(h, gn_direction_box_launch(h->desc.n, h->desc.m, q, (hipStream_t)stream), "k_gn_direction_box launch");
 }
 
@@ -1859,12 +2010,14 @@ int phnn_gn_select(phnn_handle* h, float* u_dev, float* traj_dev, float* cost_de
 static int solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
                     const phnn_reference* ref, int32_t integrator, float dt, const phnn_gn_options* opt, void* workspace,
                     size_t workspace_size, float* cost_out, float* costs_dev, double* mu_out, int32_t* accepts_dev,
-                    float* alpha_hist_dev, bool box, int32_t* nclamp_hist_dev, void* stream) {
+                    float* alpha_hist_dev, bool box, int32_t* nclamp_hist_dev, void* stream,
+                    const phnn_terminal* term = nullptr) {
   if (int rc = check_gn(h, opt, B, H)) return rc;
   RollParams rp;
   if (int rc = fill_roll(h, &rp, x0_dev, u_dev, B, H, cost, integrator, dt)) return rc;
   if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
   if (int rc = fill_ref(h, &rp, ref, B)) return rc;
+  if (int rc = check_terminal(h, term, B)) return rc;
   if (B == 0) return PHNN_OK;
   if (!cost_out || !mu_out || !accepts_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn: cost_out, mu_out and accepts_dev are required");
   if (!gn_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no Gauss-Newton direction kernel for this (n, m)");
@@ -1899,10 +2052,18 @@ static int solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B
     if (e != hipSuccess) return hip_fail(h, e, "phnn_solve_gn: state reset");
   }
   if (int rc = rollout_fwd(h, x0_dev, u_dev, B, H, cost, integrator, dt, cost_out, traj, nullptr, prefp, stream)) return rc;
+  // with a terminal weight every K1 is followed by k_terminal_cost (cost only): the iterate's here, the candidates' below
+  if (term)
+    if (int rc = terminal_cost(h, traj, B, H, cost, prefp, term, term->group, cost_out, nullptr, stream)) return rc;
   const int64_t rollouts = B * (int64_t)L;
   for (int it = 0; it < opt->iters; ++it) {
     if (int rc = phnn_rollout_linearize(h, u_dev, B, H, cost, integrator, dt, traj, A, Bm, stream)) return rc;
-    if (box) {
+    if (term) {
+      if (int rc = phnn_gn_direction_term(h, A, Bm, traj, u_dev, B, H, cost, prefp, term, mu_out, du, dV, status,
+                                          box ? PHNN_GN_BOX : 0,
+                                          box && nclamp_hist_dev ? nclamp_hist_dev + (size_t)it * B : nullptr, scratch, stream))
+        return rc;
+    } else if (box) {
       // the nclamp row goes straight to the caller's history; without one the kernel writes none
       if (int rc = phnn_gn_direction_box(h, A, Bm, traj, u_dev, B, H, cost, prefp, mu_out, du, dV, status,
                                          nclamp_hist_dev ? nclamp_hist_dev + (size_t)it * B : nullptr, scratch, stream))
@@ -1912,6 +2073,9 @@ static int solve_gn(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B
     }
     if (int rc = phnn_gn_candidates(h, x0_dev, u_dev, du, B, H, cost, L, cand, it == 0 ? x0_rep : nullptr, stream)) return rc;
     if (int rc = rollout_fwd(h, x0_rep, cand, rollouts, H, cost, integrator, dt, cand_cost, cand_traj, nullptr, ref, stream)) return rc;
+    if (term)
+      if (int rc = terminal_cost(h, cand_traj, rollouts, H, cost, ref, term, (int64_t)term->group * L, cand_cost, nullptr, stream))
+        return rc;
     if (int rc = phnn_gn_select(h, u_dev, traj, cost_out, mu_out, accepts_dev, cand, cand_cost, cand_traj, status, B, H, opt,
                                 costs_dev ? costs_dev + (size_t)it * B : nullptr,
                                 alpha_hist_dev ? alpha_hist_dev + (size_t)it * B : nullptr, stream))
@@ -1939,6 +2103,19 @@ int phnn_solve_gn_ex(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t 
   if (nclamp_hist_dev && !box) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn_ex: nclamp_hist_dev without PHNN_GN_BOX");
   return solve_gn(h, x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, workspace, workspace_size, cost_out, costs_dev, mu_out,
                   accepts_dev, alpha_hist_dev, box, nclamp_hist_dev, stream);
+}
+
+int phnn_solve_gn_term(phnn_handle* h, const float* x0_dev, float* u_dev, int64_t B, int32_t H, const phnn_cost* cost,
+                       const phnn_reference* ref, const phnn_terminal* term, int32_t integrator, float dt,
+                       const phnn_gn_options* opt, void* workspace, size_t workspace_size, float* cost_out, float* costs_dev,
+                       double* mu_out, int32_t* accepts_dev, float* alpha_hist_dev, int32_t flags, int32_t* nclamp_hist_dev,
+                       void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (flags & ~PHNN_GN_BOX) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn_term: unknown flag bits");
+  const bool box = (flags & PHNN_GN_BOX) != 0;
+  if (nclamp_hist_dev && !box) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_solve_gn_term: nclamp_hist_dev without PHNN_GN_BOX");
+  return solve_gn(h, x0_dev, u_dev, B, H, cost, ref, integrator, dt, opt, workspace, workspace_size, cost_out, costs_dev, mu_out,
+                  accepts_dev, alpha_hist_dev, box, nclamp_hist_dev, stream, term);
 }
 
 // ---- batched extended Kalman filter: kernels in phnn_ekf.hip --------------------------------------

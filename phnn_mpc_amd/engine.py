@@ -190,6 +190,22 @@ class RolloutEngine:
             r.offset_host = int(ref_offset)
         return r, (t, ref_offset)
 
+    def _terminal(self, terminal, B, group=1):
+        """-> (phnn_terminal, tensors to keep alive until the launches are enqueued), or (None, None) without one.
+        terminal: a terminal.TerminalCost, or an (n,n) / (B,n,n) array or tensor (wrapped in one)."""
+        if terminal is None:
+            return None, None
+        from .terminal import TerminalCost
+        if not isinstance(terminal, TerminalCost):
+            terminal = TerminalCost(terminal)
+        terminal.check(B, self.n)
+        W = terminal.tensor(self.device)
+        t = _capi.Terminal()
+        t.W_dev = W.data_ptr()
+        t.batch_stride = self.n * self.n if terminal.per_problem else 0
+        t.group = int(group)
+        return t, (W, terminal)
+
     def _roll_call(self, name, ref, x0, u, B, H, cost, *rest):
         """lib.<name>(h, x0, u, B, H, cost, *rest, stream); with a phnn_reference its twin <name>_ref, which takes the
         reference right after the cost."""
@@ -287,8 +303,10 @@ class RolloutEngine:
             return ws["cost"], ws["grad_u"], ws["grad_x0"]
         return ws["cost"], ws["grad_u"]
 
-    def rollout_vjp(self, x0, u, traj, cost, integrator="euler", dt=0.02, traj_bar=None, cost_bar=None):
-        """General reverse pass: cotangents on the trajectory (B,H+1,n) and/or the cost (B) -> (grad_u, grad_x0)."""
+    def rollout_vjp(self, x0, u, traj, cost, integrator="euler", dt=0.02, traj_bar=None, cost_bar=None, x_ref=None,
+                    ref_offset=0):
+        """General reverse pass: cotangents on the trajectory (B,H+1,n) and/or the cost (B) -> (grad_u, grad_x0).
+        x_ref, ref_offset: reference tracking as in rollout_cost (phnn_rollout_vjp_ref)."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u, H = self._controls(u, B)
@@ -297,11 +315,57 @@ class RolloutEngine:
         cb = self._t(cost_bar, (B,)) if cost_bar is not None else None
         gu = torch.empty(B, H, self.m, dtype=torch.float32, device=self.device)
         gx = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
-        rc = self.lib.phnn_rollout_vjp(self.h, self._p(x0), self._p(u), B, H, C.byref(cost), self._integ(integrator),
-                                       float(dt), self._p(traj), None, self._p(tb), self._p(cb), self._p(gu),
-                                       self._p(gx), self._stream())
-        _check(self.lib, self.h, rc)
+        ref, _keep = self._reference(x_ref, ref_offset, B)
+        self._roll_call("phnn_rollout_vjp", ref, x0, u, B, H, cost, self._integ(integrator), float(dt), self._p(traj), None,
+                        self._p(tb), self._p(cb), self._p(gu), self._p(gx))
         return gu, gx
+
+    # ------------------------------------------------------------------ terminal cost and its LQR weight
+    def terminal_cost(self, traj, cost, terminal, cost_b, traj_bar=None, want_traj_bar=False, x_ref=None, ref_offset=0,
+                      group=1):
+        """k_terminal_cost behind a K1 launch: cost_b (B) += e_H^T W e_H in place, with e_H = traj[:, H] - the cost's
+        x_target or the reference row min(ref_offset + H, rows - 1).  terminal: a terminal.TerminalCost (or its W);
+        row i uses the W of problem i // group.  traj_bar (B,H+1,n): row H receives the gradient of the term, the rows
+        before it are not touched (want_traj_bar: a zeroed one is made here).  -> traj_bar or None."""
+        traj = self._t(traj)
+        B, H = traj.shape[0], traj.shape[1] - 1
+        traj = traj.reshape(B, H + 1, self.n)
+        self._assert_device_f32(cost_b, traj_bar)
+        assert cost_b.numel() == B and (traj_bar is None or traj_bar.numel() == traj.numel())
+        if traj_bar is None and want_traj_bar:
+            traj_bar = torch.zeros_like(traj)
+        g = max(int(group), 1)  # a group < 1 is the library's to refuse
+        term, _keep_t = self._terminal(terminal, (B + g - 1) // g, group)
+        ref, _keep = self._reference(x_ref, ref_offset, B)
+        rc = self.lib.phnn_terminal_cost(self.h, self._p(traj), B, H, C.byref(cost), None if ref is None else C.byref(ref),
+                                         None if term is None else C.byref(term), self._p(cost_b), self._p(traj_bar),
+                                         self._stream())
+        _check(self.lib, self.h, rc)
+        return traj_bar
+
+    def dare(self, A, Bm, cost, max_iters=None, tol=None, mu=0.0):
+        """k_dare: the Riccati step of tvlqr iterated on the constant A (B,n,n), Bm (B,n,m) from P_0 = Q + Q^T until
+        max|P_k - P_{k-1}| <= tol * max|P_k| -> dict(P (B,n,n) float64, K (B,m,n) float64 the gain of the last step,
+        W (B,n,n) float32 = 0.5 (P - (Q + Q^T)) the terminal weight, iters (B) int32, status (B) int32: 0 converged,
+        1 failed (P, K, W NaN), 2 max_iters reached (the last iterate)).  max_iters / tol None: terminal.DARE_MAX_ITERS /
+        terminal.DARE_TOL."""
+        from .terminal import DARE_MAX_ITERS, DARE_TOL
+        A = self._t(A)
+        B = A.shape[0]
+        A = A.reshape(B, self.n, self.n)
+        Bm = self._t(Bm, (B, self.n, self.m))
+        d = dict(dtype=torch.float64, device=self.device)
+        P, K = torch.empty(B, self.n, self.n, **d), torch.empty(B, self.m, self.n, **d)
+        W = torch.empty(B, self.n, self.n, dtype=torch.float32, device=self.device)
+        iters = torch.empty(B, dtype=torch.int32, device=self.device)
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        opt = _capi.DareOptions()
+        opt.max_iters = int(DARE_MAX_ITERS if max_iters is None else max_iters)
+        opt.tol, opt.mu = float(DARE_TOL if tol is None else tol), float(mu)
+        rc = self.lib.phnn_dare(self.h, self._p(A), self._p(Bm), B, C.byref(cost), C.byref(opt), self._p(P), self._p(K),
+                                self._p(W), self._p(iters), self._p(status), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(P=P, K=K, W=W, iters=iters, status=status)
 
     # ------------------------------------------------------------------ linearisation, TV-LQR gains (DESIGN.md 17)
     def jacobian(self, x, u):
@@ -489,12 +553,14 @@ class RolloutEngine:
 
     # ------------------------------------------------------------------ the whole shooting solve (K1, K2, K3 x iters)
     def solve(self, x0, u_init, cost, integrator="euler", dt=0.02, lr=0.015, iters=30, track_best=False, record_costs=True,
-              beta1=0.9, beta2=0.999, eps=1e-8, workspace=None, x_ref=None, ref_offset=0):
+              beta1=0.9, beta2=0.999, eps=1e-8, workspace=None, x_ref=None, ref_offset=0, terminal=None):
         """phnn_solve: Adam on the control sequences of B independent problems, the loops of
         src/mpc_controller.py:164-209 / src/mpc_controller_canonical.py:163-228, as ONE library call that enqueues the
         K1 / K2 / K3 launches of every iteration (no Python between them).  -> dict as solver.shooting_solve, same
         results bit for bit.  workspace: optional dict reused across calls (K1 / K2 buffers and Adam's moments).
-        x_ref, ref_offset: every problem tracks its own reference (rollout_cost; phnn_solve_ref)."""
+        x_ref, ref_offset: every problem tracks its own reference (rollout_cost; phnn_solve_ref).
+        terminal: a terminal.TerminalCost (or its W): phnn_solve_term -- every K1 is followed by k_terminal_cost, K2 reads
+        its cotangent, and costs / best_cost are total costs.  None: the calls and bits of before."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u_init, H = self._controls(u_init, B)
@@ -512,9 +578,20 @@ class RolloutEngine:
             best_u.zero_()
         opt = _capi.SolveOptions(int(iters), float(lr), float(beta1), float(beta2), float(eps), int(bool(track_best)))
         ref, _keep = self._reference(x_ref, ref_offset, B)
-        self._roll_call("phnn_solve", ref, x0, u, B, H, cost, integ, float(dt), C.byref(opt), self._p(ws["m"]),
-                        self._p(ws["v"]), self._p(ws["grad_u"]), self._p(ws["cost"]), self._p(ws["traj"]),
-                        self._p(ws["stash"]), self._p(costs), self._p(best_cost), self._p(best_u))
+        term, _keep_t = self._terminal(terminal, B)
+        if term is not None:
+            if "traj_bar" not in ws:  # the cotangent K2 reads; phnn_solve_term zeroes it
+                ws["traj_bar"] = torch.empty(B, H + 1, self.n, **f)
+            rc = self.lib.phnn_solve_term(self.h, self._p(x0), self._p(u), B, H, C.byref(cost),
+                                          None if ref is None else C.byref(ref), C.byref(term), integ, float(dt),
+                                          C.byref(opt), self._p(ws["m"]), self._p(ws["v"]), self._p(ws["grad_u"]),
+                                          self._p(ws["cost"]), self._p(ws["traj"]), self._p(ws["stash"]), self._p(costs),
+                                          self._p(best_cost), self._p(best_u), self._p(ws["traj_bar"]), self._stream())
+            _check(self.lib, self.h, rc)
+        else:
+            self._roll_call("phnn_solve", ref, x0, u, B, H, cost, integ, float(dt), C.byref(opt), self._p(ws["m"]),
+                            self._p(ws["v"]), self._p(ws["grad_u"]), self._p(ws["cost"]), self._p(ws["traj"]),
+                            self._p(ws["stash"]), self._p(costs), self._p(best_cost), self._p(best_u))
         out = {"u_last": u, "costs": costs}
         if track_best:
             out["best_u"], out["best_cost"] = best_u, best_cost
@@ -526,14 +603,16 @@ class RolloutEngine:
 
     def solve_lbfgs(self, x0, u_init, cost, integrator="euler", dt=0.02, lr=1.0, outer_steps=1, max_iter=20, max_eval=None,
                     tolerance_grad=1e-7, tolerance_change=1e-9, history_size=100, record_costs=True, workspace=None,
-                    x_ref=None, ref_offset=0):
+                    x_ref=None, ref_offset=0, terminal=None):
         """phnn_solve_lbfgs: B independent torch.optim.LBFGS(lr, max_iter, max_eval, tolerance_grad, tolerance_change,
         history_size) optimizers, each created fresh and stepped outer_steps times on its problem's K1 cost and K2
         gradient (src/mpc_controller.py:169-170,196-197), as ONE library call: outer_steps x max_iter x (K1, K2,
         k_lbfgs) launches.  -> dict(u_last (B,H,m) unclamped last iterate, costs (outer_steps,B) orig_loss of every
         step() or None, n_iter (B) int32 state['n_iter'], func_evals (B) int32 state['func_evals']).
         workspace: optional dict reused across calls (K1 / K2 buffers and the optimizer state).  x_ref, ref_offset:
-        every problem tracks its own reference (rollout_cost)."""
+        every problem tracks its own reference (rollout_cost).  terminal: refused (the L-BFGS solve has no terminal term)."""
+        from .terminal import refuse
+        refuse(terminal, "the L-BFGS solve")
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u_init, H = self._controls(u_init, B)
@@ -740,7 +819,7 @@ class RolloutEngine:
 
     def solve_mppi(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=4, samples=64, lam=1.0, sigma=1.0, seed=0,
                    epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None, ref_offset=0, expanded_ref=False,
-                   noise=None):
+                   noise=None, terminal=None):
         """phnn_solve_mppi: sampling MPC (MPPI) on B independent problems as ONE library call: the nominal is clamped,
         then iters x (k_sample, K1 over B * samples rollouts, k_mppi_update); no gradient is taken anywhere.
         -> dict(u_last (B,H,m) last nominal (in bounds), costs (iters,B) the nominal's cost at every iteration or None,
@@ -751,14 +830,17 @@ class RolloutEngine:
         per-problem reference is expanded to one row set per rollout (mppi_reference: samples times its bytes) once per
         call, unless expanded_ref says x_ref already is what mppi_reference returned (a closed loop expands it once).
         noise: None = white noise; a noise.Noise (or an (H, P) array) = time-correlated noise (phnn_solve_mppi_shaped:
-        k_shaped_sample in k_sample's place, everything else as it is); a captured graph reads its device tensor in place."""
+        k_shaped_sample in k_sample's place, everything else as it is); a captured graph reads its device tensor in place.
+        terminal: refused (the sampling solves have no terminal term)."""
+        from .terminal import refuse
+        refuse(terminal, "the MPPI solve")
         opt, _keep = self._mppi_options(iters, samples, lam, sigma, seed, epoch, problem_offset)
         return self._solve_sampling("mppi", opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
                                     expanded_ref, noise)
 
     def solve_cem(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=4, samples=64, elites=8, alpha=0.25, sigma=1.0,
                   sigma_min=0.05, seed=0, epoch=0, problem_offset=0, record_costs=True, workspace=None, x_ref=None,
-                  ref_offset=0, expanded_ref=False, noise=None):
+                  ref_offset=0, expanded_ref=False, noise=None, terminal=None):
         """phnn_solve_cem: sampling MPC by the cross-entropy method on B independent problems as ONE library call: the
         mean is clamped and the standard deviation set to sigma, then iters x (k_sample, K1 over B * samples
         rollouts, k_cem_update); no gradient is taken anywhere.  -> dict(u_last (B,H,m) last mean (in bounds), sigma_last
@@ -766,7 +848,9 @@ class RolloutEngine:
         best_cost (B) the best sample over all iterations), same results bit for bit as solver.cem_solve.  elites: how
         many of the lowest-cost samples mean and standard deviation are refitted to; alpha: smoothing in [0, 1);
         sigma: initial standard deviation, one value or one per control component; sigma_min: its floor.  seed, epoch,
-        problem_offset, x_ref, ref_offset, expanded_ref, noise (phnn_solve_cem_shaped): as in solve_mppi."""
+        problem_offset, x_ref, ref_offset, expanded_ref, noise (phnn_solve_cem_shaped): as in solve_mppi.  terminal: refused."""
+        from .terminal import refuse
+        refuse(terminal, "the cross-entropy solve")
         opt, _keep = self._cem_options(iters, samples, elites, alpha, sigma, sigma_min, seed, epoch, problem_offset)
         return self._solve_sampling("cem", opt, x0, u_init, cost, integrator, dt, record_costs, workspace, x_ref, ref_offset,
                                     expanded_ref, noise)
@@ -789,13 +873,15 @@ class RolloutEngine:
             return mu.to(device=self.device, dtype=torch.float64).reshape(B).contiguous()
         return torch.full((B,), float(mu), dtype=torch.float64, device=self.device)
 
-    def gn_direction(self, A, Bm, traj, u, cost, mu, x_ref=None, ref_offset=0, box=False):
+    def gn_direction(self, A, Bm, traj, u, cost, mu, x_ref=None, ref_offset=0, box=False, terminal=None):
         """k_gn_direction: the Gauss-Newton step of every problem on its local model.  A (B,H,n,n), Bm (B,H,n,m) from
         rollout_linearize, traj (B,H+1,n), u (B,H,m), mu (B) float64 or one value; x_ref / ref_offset: problem b's
         reference as in rollout_cost.  -> dict(du (B,H,m) float32, dV (B) float64 -- the cost's slope along du is -dV,
         the predicted change at the full step -dV/2 --, status (B) int32 as tvlqr's).  A failed problem has du = 0 and
         dV = NaN.  box: k_gn_direction_box, the step with the cost's control bounds inside the LQ problem (DESIGN.md
-        section 19); the dict gains nclamp (B) int32, the (t, component) pairs held on a bound."""
+        section 19); the dict gains nclamp (B) int32, the (t, component) pairs held on a bound.  terminal: a
+        terminal.TerminalCost (or its W): the backward sweep starts from the stage terms at H plus the terminal weight's
+        (phnn_gn_direction_term)."""
         A = self._t(A)
         B, H = A.shape[0], A.shape[1]
         A = A.reshape(B, H, self.n, self.n)
@@ -808,6 +894,16 @@ class RolloutEngine:
         ref, _keep = self._reference(x_ref, ref_offset, B)
         head = (self.h, self._p(A), self._p(Bm), self._p(traj), self._p(u), B, H, C.byref(cost),
                 None if ref is None else C.byref(ref), self._p(mu), self._p(du), self._p(dV), self._p(status))
+        term, _keep_t = self._terminal(terminal, B)
+        if term is not None:
+            nclamp = torch.empty(B, dtype=torch.int32, device=self.device) if box else None
+            rc = self.lib.phnn_gn_direction_term(*head[:9], C.byref(term), *head[9:], _capi.PHNN_GN_BOX if box else 0,
+                                                 self._p(nclamp), self._p(scratch), self._stream())
+            _check(self.lib, self.h, rc)
+            out = dict(du=du, dV=dV, status=status)
+            if box:
+                out["nclamp"] = nclamp
+            return out
         if box:
             nclamp = torch.empty(B, dtype=torch.int32, device=self.device)
             rc = self.lib.phnn_gn_direction_box(*head, self._p(nclamp), self._p(scratch), self._stream())
@@ -853,7 +949,7 @@ class RolloutEngine:
 
     def solve_gn(self, x0, u_init, cost, integrator="euler", dt=0.02, iters=10, line_steps=8, mu_init=1e-6, mu_min=1e-9,
                  mu_max=1e6, mu_up=10.0, mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0,
-                 expanded_ref=False, box=False):
+                 expanded_ref=False, box=False, terminal=None):
         """phnn_solve_gn: projected Gauss-Newton shooting on B independent problems as ONE library call: the iterate is
         clamped and costed, then iters x (k_rollout_linearize, k_gn_direction, k_gn_candidates, K1 over B * line_steps
         candidates, k_gn_select).  -> dict(u_last (B,H,m) in bounds, cost (B) its cost, costs (iters,B) the cost at the
@@ -861,7 +957,10 @@ class RolloutEngine:
         lengths, 0 where rejected, or None), same results bit for bit as solver.gn_solve.  The cost of a problem never
         rises.  x_ref, ref_offset, expanded_ref: as in solve_mppi, with line_steps rollouts per problem.  The workspace
         (a dict reused across calls) keeps the device buffer of phnn_gn_workspace_bytes.  box: phnn_solve_gn_ex with
-        PHNN_GN_BOX -- the direction is k_gn_direction_box -- and the dict gains nclamp_hist (iters,B) int32."""
+        PHNN_GN_BOX -- the direction is k_gn_direction_box -- and the dict gains nclamp_hist (iters,B) int32.
+        terminal: a terminal.TerminalCost (or its W): phnn_solve_gn_term -- k_terminal_cost behind the set-up K1 and the
+        candidates' K1, the direction started from the terminal weight; every cost is a total cost.  None: the calls and
+        bits of before."""
         x0 = self._t(x0, (-1, self.n))
         B = x0.shape[0]
         u_init, H = self._controls(u_init, B)
@@ -886,7 +985,13 @@ class RolloutEngine:
                 C.byref(opt), self._p(ws["gn"]), ws["gn"].numel(), self._p(cost_b), self._p(costs), self._p(mu),
                 self._p(accepts), self._p(alpha))
         out = {"u_last": u, "cost": cost_b, "costs": costs, "mu": mu, "accepts": accepts, "alpha_hist": alpha}
-        if box:
+        term, _keep_t = self._terminal(terminal, B)
+        if term is not None:
+            if box:
+                out["nclamp_hist"] = torch.empty(rows, B, dtype=torch.int32, device=self.device)
+            rc = self.lib.phnn_solve_gn_term(*head[:7], C.byref(term), *head[7:], _capi.PHNN_GN_BOX if box else 0,
+                                             self._p(out.get("nclamp_hist")), self._stream())
+        elif box:
             out["nclamp_hist"] = torch.empty(rows, B, dtype=torch.int32, device=self.device)
             rc = self.lib.phnn_solve_gn_ex(*head, _capi.PHNN_GN_BOX, self._p(out["nclamp_hist"]), self._stream())
         else:
@@ -973,7 +1078,9 @@ class RolloutEngine:
         trajectories, the linearisation of that rollout, the LQ backward pass.  x0 (B,n), u (B,H,m) float32 on the
         engine's device, read in place; cost: the controller's (Q, R, bounds).  workspace: a dict reused across calls
         (keeps the device buffer of feedback_workspace_bytes and, unless given, the outputs).  -> dict(traj (B,H+1,n)
-        float32, K (B,H,m,n) float64, status (B) int32: phnn_tvlqr's)."""
+        float32, K (B,H,m,n) float64, status (B) int32: phnn_tvlqr's).  The backward pass starts from the stage cost
+        (P_H = Q + Q^T) also when the solve that made the plan had a terminal weight: the gains track the plan, they
+        do not re-optimise it."""
         self._assert_device_f32(x0, u)
         B, H = u.shape[0], u.shape[1]  # u is (B,H,m)
         ws = {} if workspace is None else workspace

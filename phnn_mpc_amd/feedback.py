@@ -22,7 +22,9 @@ PLAN_METHODS = ("rollout_cost", "rollout_linearize", "tvlqr")
 class Tracking:
     """solve_every: k >= 1, the solve runs at the control steps s with s % k == 0 (at most the controller's horizon: the
     plan has that many rows).  mu: the regularisation of Quu in the LQ backward pass (phnn_tvlqr_options.mu; >= 0 and
-    finite).  log: the closed-loop drivers record the status and the deviation of every step."""
+    finite).  log: the closed-loop drivers record the status and the deviation of every step.
+    The TV-LQR of the plan stays on the stage cost: a controller's terminal weight (terminal.TerminalCost) shapes the solve
+    that makes the plan, not the gains that track it (P_H = Q + Q^T in the backward pass, with or without one)."""
 
     def __init__(self, solve_every, mu=0.0, log=True):
         if isinstance(solve_every, bool) or int(solve_every) != solve_every or int(solve_every) < 1:

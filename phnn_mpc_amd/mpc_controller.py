@@ -17,6 +17,8 @@ optimizer_type='GaussNewton' (not in the reference): projected Gauss-Newton shoo
 (engine.solve_gn): every call cold-starts from zeros, runs max_iterations iterations (linearise, LQ direction with
 Levenberg-Marquardt term mu, gn_line_steps candidates u + 2^-j du in one K1 launch, select) and returns clamp(u_0) of the
 last iterate, whose cost never rises from one iteration to the next.  lr is not used.
+terminal= (not in the reference): a terminal.TerminalCost, or the config's `terminal` section, adds e_H^T W e_H to the
+cost of the 'Adam' and 'GaussNewton' solves; 'LBFGS', 'MPPI' and 'CrossEntropy' refuse one.
 """
 import os
 
@@ -25,14 +27,17 @@ import torch
 
 from . import _capi
 from .noise import resolve as resolve_noise
-from .solver import SAMPLING, _noise_kw, gn_solver_for, lbfgs_solver_for, solver_for
+from .solver import SAMPLING, _noise_kw, _terminal_kw, gn_solver_for, lbfgs_solver_for, solver_for
+from .terminal import refuse as refuse_terminal
+from .terminal import TerminalCost
+from .terminal import resolve as resolve_terminal
 
 
 class MPCController:
     def __init__(self, phnn_model, horizon, dt, Q, R, target_state=None, u_min=None, u_max=None, x_min=None, x_max=None,
                  optimizer_type="Adam", lr=0.1, max_iterations=50, samples=64, lam=1.0, sigma=1.0, seed=0, elites=8,
                  alpha=0.25, sigma_min=0.05, noise=None, gn_line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
-                 mu_down=0.1, gn_box=False):
+                 mu_down=0.1, gn_box=False, terminal=None):
         self.model = phnn_model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -61,6 +66,9 @@ class MPCController:
         self.mu_up, self.mu_down = mu_up, mu_down
         # gn_box: the LQ step of every iteration respects u_min / u_max (control-limited DDP)
         self.gn_box = bool(gn_box)
+        # terminal weight of the Adam and Gauss-Newton solves: None, a terminal.TerminalCost, or its config section
+        # ({type: lqr} is resolved on the engine at the first solve: terminal_cost())
+        self.terminal = terminal
         self.integrator = "euler"  # src/mpc_controller.py:137-138
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -76,6 +84,17 @@ class MPCController:
                                self.u_min, self.u_max,
                                None if self.x_min is None else self.x_min.numpy(),
                                None if self.x_max is None else self.x_max.numpy(), 1000.0)
+
+    def terminal_cost(self):
+        """The controller's terminal.TerminalCost, or None.  A config section is resolved here, once (type lqr: the
+        linearisation and the DARE iteration run on the engine); a solve without a terminal term refuses one."""
+        if self.terminal is None:
+            return None
+        if self.optimizer_type not in ("Adam", "GaussNewton"):
+            refuse_terminal(self.terminal, f"optimizer_type {self.optimizer_type!r}")
+        if not isinstance(self.terminal, TerminalCost):  # a config section: resolved once, on the engine
+            self.terminal = resolve_terminal(self.terminal, self.engine, self._cost(), self.integrator, self.dt)
+        return self.terminal
 
     def _cost_noclamp(self):
         c = self._cost()
@@ -128,6 +147,7 @@ class MPCController:
         """current_state (n,) -> optimal first control, np.ndarray (1,)   (src/mpc_controller.py:143-209)"""
         if isinstance(current_state, np.ndarray):
             current_state = torch.tensor(current_state, dtype=torch.float32)
+        self.terminal_cost()  # refused here by the solves without a terminal term
         if self.optimizer_type == "LBFGS":
             return self._compute_control_lbfgs(current_state)
         u = self.compute_control_batch(current_state.reshape(1, -1))
@@ -164,6 +184,7 @@ class MPCController:
         x_ref: per-problem reference trajectories broadcastable to (B, rows, n), tracked from row ref_offset (int or
         device int32 tensor; past its end a reference holds its last row) instead of target_state.
         epoch (MPPI, CrossEntropy): the noise counter of this solve; None: self.epoch, which then advances by one."""
+        term = self.terminal_cost()  # refused here by the solves without a terminal term
         if self.optimizer_type == "LBFGS":
             return self._solve_batch_lbfgs(states, record_costs, x_ref, ref_offset)
         if self.optimizer_type in SAMPLING:
@@ -177,7 +198,7 @@ class MPCController:
         u0 = torch.zeros(x0.shape[0], self.horizon, 1, dtype=torch.float32, device=eng.device)
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.lr, self.max_iterations,
                                  track_best=False, u_min=self.u_min, u_max=self.u_max, record_costs=record_costs,
-                                 x_ref=x_ref, ref_offset=ref_offset)
+                                 x_ref=x_ref, ref_offset=ref_offset, **_terminal_kw(term))
 
     def lbfgs_options(self):
         """solve_lbfgs keyword arguments of the reference's optimizer: torch.optim.LBFGS([u], lr=self.lr, max_iter=20)
@@ -204,6 +225,7 @@ class MPCController:
                    mu_max=self.mu_max, mu_up=self.mu_up, mu_down=self.mu_down)
         if self.gn_box:  # present only when set: the plain solve is called as before
             opt["box"] = True
+        opt.update(_terminal_kw(self.terminal_cost()))
         return opt
 
     def _solve_batch_gn(self, states, record_costs, x_ref, ref_offset):
@@ -267,9 +289,10 @@ class MPCController:
 
 def _mppi_keys(mpc):
     """The solver keywords present in the `mpc` config section: samples, lam, sigma, seed, elites, alpha, sigma_min, noise
-    (optimizer: MPPI or CrossEntropy) and gn_line_steps, gn_box, mu_init, mu_min, mu_max, mu_up, mu_down (GaussNewton)."""
+    (optimizer: MPPI or CrossEntropy), gn_line_steps, gn_box, mu_init, mu_min, mu_max, mu_up, mu_down (GaussNewton) and terminal
+    (Adam, GaussNewton: {type: lqr} or {type: matrix, W: [...]})."""
     keys = ("samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise", "gn_line_steps", "gn_box", "mu_init", "mu_min",
-            "mu_max", "mu_up", "mu_down")
+            "mu_max", "mu_up", "mu_down", "terminal")
     return {k: mpc[k] for k in keys if k in mpc}
 
 

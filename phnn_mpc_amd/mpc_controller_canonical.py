@@ -13,6 +13,8 @@ returning as the MPPI one does.  (The name is not 'CEM': that string stays an un
 optimizer='GaussNewton' (not in the reference): projected Gauss-Newton shooting on the rollout's linearisation
 (engine.solve_gn), optimizer_steps iterations; a problem's cost never rises, so the sequence returned (best_u) is the
 last iterate and best_cost its cost; 'costs' is the cost at the start of every iteration; learning_rate is not used.
+terminal= (not in the reference): a terminal.TerminalCost, or the config's `terminal` section, adds e_H^T W e_H to the
+cost of the 'Adam' and 'GaussNewton' solves; 'MPPI' and 'CrossEntropy' refuse one.
 """
 import os
 import time
@@ -22,14 +24,17 @@ import torch
 
 from . import _capi
 from .noise import resolve as resolve_noise
-from .solver import SAMPLING, _noise_kw, gn_solver_for, solver_for
+from .solver import SAMPLING, _noise_kw, _terminal_kw, gn_solver_for, solver_for
+from .terminal import refuse as refuse_terminal
+from .terminal import TerminalCost
+from .terminal import resolve as resolve_terminal
 
 
 class MPCControllerCanonical:
     def __init__(self, model, horizon=20, dt=0.02, Q=None, R=None, x_target=None, u_min=-10.0, u_max=10.0,
                  optimizer_steps=50, learning_rate=0.1, verbose=False, optimizer="Adam", samples=64, lam=1.0, sigma=1.0,
                  seed=0, elites=8, alpha=0.25, sigma_min=0.05, noise=None, gn_line_steps=8, mu_init=1e-6, mu_min=1e-9,
-                 mu_max=1e6, mu_up=10.0, mu_down=0.1, gn_box=False):
+                 mu_max=1e6, mu_up=10.0, mu_down=0.1, gn_box=False, terminal=None):
         self.model = model
         self.model.eval()
         self.horizon, self.dt = horizon, dt
@@ -61,6 +66,9 @@ class MPCControllerCanonical:
         self.mu_up, self.mu_down = mu_up, mu_down
         # gn_box: the LQ step of every iteration respects u_min / u_max (control-limited DDP)
         self.gn_box = bool(gn_box)
+        # terminal weight of the Adam and Gauss-Newton solves: None, a terminal.TerminalCost, or its config section
+        # ({type: lqr} is resolved on the engine at the first solve: terminal_cost())
+        self.terminal = terminal
         self.integrator = "euler"
         # True (or PHNN_GRAPH=1): replay the whole solve as one HIP graph instead of 3 x iterations launches
         self.use_graph = os.environ.get("PHNN_GRAPH", "0") == "1"
@@ -76,6 +84,17 @@ class MPCControllerCanonical:
         if not clamp:
             c.has_u_bounds = 0
         return c
+
+    def terminal_cost(self):
+        """The controller's terminal.TerminalCost, or None.  A config section is resolved here, once (type lqr: the
+        linearisation and the DARE iteration run on the engine); a solve without a terminal term refuses one."""
+        if self.terminal is None:
+            return None
+        if self.optimizer not in ("Adam", "GaussNewton"):
+            refuse_terminal(self.terminal, f"optimizer {self.optimizer!r}")
+        if not isinstance(self.terminal, TerminalCost):  # a config section: resolved once, on the engine
+            self.terminal = resolve_terminal(self.terminal, self.engine, self._cost(), self.integrator, self.dt)
+        return self.terminal
 
     @property
     def engine(self):
@@ -171,6 +190,7 @@ class MPCControllerCanonical:
         device int32 tensor; past its end a reference holds its last row) instead of x_target.
         epoch (MPPI, CrossEntropy): the noise counter of this solve; None: self.epoch, which then advances by one."""
         eng = self.engine
+        term = self.terminal_cost()  # refused here by the solves without a terminal term
         x0 = torch.as_tensor(x0, dtype=torch.float32).reshape(-1, self.state_dim).to(eng.device)
         B = x0.shape[0]
         if u_init is None:
@@ -183,7 +203,7 @@ class MPCControllerCanonical:
             return self._solve_batch_gn(x0, u0, record_costs, x_ref, ref_offset)
         return self._solver(eng)(eng, x0, u0, self._cost(), self.integrator, self.dt, self.learning_rate,
                                  self.optimizer_steps, track_best=True, u_min=self.u_min, u_max=self.u_max,
-                                 record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset)
+                                 record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, **_terminal_kw(term))
 
     def _solve_batch_sampling(self, x0, u0, record_costs, x_ref, ref_offset, epoch):
         """The MPPI or cross-entropy solve of optimize_control_batch (engine.solve_mppi / engine.solve_cem)."""
@@ -200,6 +220,7 @@ class MPCControllerCanonical:
                    mu_max=self.mu_max, mu_up=self.mu_up, mu_down=self.mu_down)
         if self.gn_box:  # present only when set: the plain solve is called as before
             opt["box"] = True
+        opt.update(_terminal_kw(self.terminal_cost()))
         return opt
 
     def _solve_batch_gn(self, x0, u0, record_costs, x_ref, ref_offset):
@@ -236,5 +257,5 @@ def create_mpc_controller(model, config):
         u_max=mpc.get("u_max", 10.0), optimizer_steps=mpc.get("optimizer_steps", 50),
         learning_rate=mpc.get("learning_rate", 0.1), verbose=mpc.get("verbose", False),
         **{k: mpc[k] for k in ("optimizer", "samples", "lam", "sigma", "seed", "elites", "alpha", "sigma_min", "noise",
-                                   "gn_line_steps", "gn_box", "mu_init", "mu_min", "mu_max", "mu_up", "mu_down")
+                                   "gn_line_steps", "gn_box", "mu_init", "mu_min", "mu_max", "mu_up", "mu_down", "terminal")
            if k in mpc})

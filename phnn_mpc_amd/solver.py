@@ -33,8 +33,19 @@ def _need_reference(engine, x_ref):
         raise NotImplementedError(f"{type(engine).__name__} has no reference tracking (x_ref): RolloutEngine has")
 
 
+def _need_terminal(engine, terminal):
+    if terminal is not None and not hasattr(engine, "terminal_cost"):
+        raise NotImplementedError(f"{type(engine).__name__} has no terminal cost (terminal): RolloutEngine has")
+
+
+def _terminal_kw(terminal):
+    """The `terminal` keyword of an engine call: passed only when there is a terminal weight, so that an engine written
+    before the terminal cost existed is called exactly as it always was."""
+    return {} if terminal is None else {"terminal": terminal}
+
+
 def shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=False, u_min=None, u_max=None,
-                   record_costs=True, x_ref=None, ref_offset=0, workspace=None):
+                   record_costs=True, x_ref=None, ref_offset=0, workspace=None, terminal=None):
     """x0 (B,n), u_init (B,H,m) on engine.device -> dict(u_last, costs[, best_u, best_cost]).
 
     u_last   : unclamped last iterate (B,H,m)
@@ -43,8 +54,12 @@ def shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_be
     x_ref    : reference trajectory broadcastable to (B, rows, n), tracked from row ref_offset (int or device int32
                tensor) on (RolloutEngine.rollout_cost); None: the cost's x_target
     workspace: optional dict that keeps the engine's buffers alive across calls
+    terminal : a terminal.TerminalCost, or None.  With one an iteration is K1 (engine.rollout_cost with the trajectory),
+               engine.terminal_cost (the total cost, and row H of the cotangent), K2 (engine.rollout_vjp with that
+               cotangent), K3: the sequence phnn_solve_term enqueues
     """
     _need_reference(engine, x_ref)
+    _need_terminal(engine, terminal)
     rkw = {} if x_ref is None else {"x_ref": x_ref, "ref_offset": ref_offset}  # an engine without tracking takes neither
     dev = x0.device
     u = u_init.detach().clone().contiguous()
@@ -57,8 +72,14 @@ def shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_be
         best_cost = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
         best_u = torch.zeros_like(u)
     ws = {} if workspace is None else workspace
+    tb = None
     for k in range(iters):
-        c, g = engine.rollout_cost_grad(x0, u, cost, integrator, dt, workspace=ws, **rkw)
+        if terminal is None:
+            c, g = engine.rollout_cost_grad(x0, u, cost, integrator, dt, workspace=ws, **rkw)
+        else:
+            c, traj = engine.rollout_cost(x0, u, cost, integrator, dt, want_traj=True, **rkw)
+            tb = engine.terminal_cost(traj, cost, terminal, c, traj_bar=tb, want_traj_bar=True, **rkw)
+            g = engine.rollout_vjp(x0, u, traj, cost, integrator, dt, traj_bar=tb, **rkw)[0]
         if record_costs:
             costs[k].copy_(c)
         engine.adam_step(u, g, exp_avg, exp_avg_sq, lr, k + 1, cost=c if track_best else None, best_cost=best_cost,
@@ -70,19 +91,20 @@ def shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_be
 
 
 def _eager(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=False, u_min=None, u_max=None, record_costs=True,
-           x_ref=None, ref_offset=0, workspace=None):
+           x_ref=None, ref_offset=0, workspace=None, terminal=None):
     """The solve without a captured graph: the library's own loop (phnn_solve: one call enqueues every launch) when the
     engine has one and the Adam-side bounds are the cost's (they are for both controller classes); else the Python loop.
-    Same launches, same order: identical results.  x_ref / ref_offset / workspace: see shooting_solve."""
+    Same launches, same order: identical results.  x_ref / ref_offset / workspace / terminal: see shooting_solve."""
     _need_reference(engine, x_ref)
+    _need_terminal(engine, terminal)
     has_b = u_min is not None and u_max is not None
     same = bool(cost.has_u_bounds) == has_b and (not has_b or (float(cost.u_min) == float(ctypes.c_float(u_min).value)
                                                                 and float(cost.u_max) == float(ctypes.c_float(u_max).value)))
     if hasattr(engine, "solve") and same:
         return engine.solve(x0, u_init, cost, integrator, dt, lr=lr, iters=iters, track_best=track_best, record_costs=record_costs,
-                            workspace=workspace, x_ref=x_ref, ref_offset=ref_offset)
+                            workspace=workspace, x_ref=x_ref, ref_offset=ref_offset, **_terminal_kw(terminal))
     return shooting_solve(engine, x0, u_init, cost, integrator, dt, lr, iters, track_best=track_best, u_min=u_min, u_max=u_max,
-                          record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, workspace=workspace)
+                          record_costs=record_costs, x_ref=x_ref, ref_offset=ref_offset, workspace=workspace, terminal=terminal)
 
 
 def _sampling_solve(engine, x0, u_init, cost, integrator, dt, iters, samples, sample, update, record_costs, workspace, x_ref,
@@ -190,7 +212,7 @@ def _cem_eager(engine, x0, u_init, cost, integrator, dt, iters, samples, elites,
 
 
 def gn_solve(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
-             mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0, box=False):
+             mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0, box=False, terminal=None):
     """Projected Gauss-Newton shooting with Levenberg-Marquardt regularisation and a parallel backtracking line search on
     B independent problems: x0 (B,n), u_init (B,H,m) -> dict(u_last, cost, costs, mu, accepts, alpha_hist).
 
@@ -205,8 +227,12 @@ def gn_solve(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_i
     x_ref, ref_offset: as in shooting_solve (one reference per problem; the candidates of a problem share it).
     box       : the direction is the box-constrained LQ step (engine.gn_direction(..., box=True), DESIGN.md section 19);
                 the result gains nclamp_hist (iters,B) int32, the (t, component) pairs each direction held on a bound
-    The Python loop that engine.solve_gn (phnn_solve_gn, phnn_solve_gn_ex) is pinned to bit for bit."""
+    terminal  : a terminal.TerminalCost, or None.  With one engine.terminal_cost follows the set-up K1 and the candidates'
+                K1 (group = line_steps rows per problem there) and the direction takes it (engine.gn_direction(...,
+                terminal=)): the sequence phnn_solve_gn_term enqueues
+    The Python loop that engine.solve_gn (phnn_solve_gn, phnn_solve_gn_ex, phnn_solve_gn_term) is pinned to bit for bit."""
     _need_reference(engine, x_ref)
+    _need_terminal(engine, terminal)
     B, L = u_init.shape[0], int(line_steps)
     rkw_b, rkw_r = {}, {}
     if x_ref is not None:
@@ -223,13 +249,17 @@ def gn_solve(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_i
     nclamp = torch.empty(iters, B, dtype=torch.int32, device=dev) if box else None
     bkw = {"box": True} if box else {}  # an engine without the box step is never handed the keyword
     c, traj = engine.rollout_cost(x0, u, cost, integrator, dt, want_traj=True, **rkw_b)
+    if terminal is not None:
+        engine.terminal_cost(traj, cost, terminal, c, **rkw_b)
     for it in range(iters):
         A, Bm, _ = engine.rollout_linearize(x0, u, cost, integrator, dt, traj=traj)
-        d = engine.gn_direction(A, Bm, traj, u, cost, mu, **rkw_b, **bkw)
+        d = engine.gn_direction(A, Bm, traj, u, cost, mu, **rkw_b, **bkw, **_terminal_kw(terminal))
         if box:
             nclamp[it].copy_(d["nclamp"])
         cand, x0_rep = engine.gn_candidates(x0, u, d["du"], cost, L)
         s, ctraj = engine.rollout_cost(x0_rep, cand, cost, integrator, dt, want_traj=True, **rkw_r)
+        if terminal is not None:
+            engine.terminal_cost(ctraj, cost, terminal, s, group=L, **rkw_r)
         engine.gn_select(u, traj, c, mu, accepts, cand, s, ctraj, d["status"], L, mu_min, mu_max, mu_up, mu_down,
                          costs_row=costs[it] if record_costs else None, alpha_row=alpha[it] if record_costs else None)
     out = {"u_last": u, "cost": c, "costs": costs, "mu": mu, "accepts": accepts, "alpha_hist": alpha}
@@ -239,9 +269,11 @@ def gn_solve(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_i
 
 
 def _gn_eager(engine, x0, u_init, cost, integrator, dt, iters, line_steps=8, mu_init=1e-6, mu_min=1e-9, mu_max=1e6, mu_up=10.0,
-              mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0, box=False):
+              mu_down=0.1, record_costs=True, workspace=None, x_ref=None, ref_offset=0, box=False, terminal=None):
     """The Gauss-Newton solve without a captured graph (_library_or); called as gn_solve is."""
+    _need_terminal(engine, terminal)
     bkw = {"box": True} if box else {}
+    bkw.update(_terminal_kw(terminal))
     return _library_or(engine, "solve_gn", gn_solve)(
         x0, u_init, cost, integrator, dt, iters=iters, line_steps=line_steps, mu_init=mu_init, mu_min=mu_min, mu_max=mu_max,
         mu_up=mu_up, mu_down=mu_down, record_costs=record_costs, workspace=workspace, x_ref=x_ref, ref_offset=ref_offset, **bkw)
@@ -278,6 +310,9 @@ class Graphed:
     and every call copies the caller's x_ref (and ref_offset, int or device int32 tensor) into it: a reference of
     another shape re-captures, one updated in place is seen by the next call.  The static buffer stays alive as long
     as this object holds the graph.
+
+    Terminal cost (terminal): a terminal.TerminalCost keys the graph by identity and its device tensor is what the graph
+    reads: keep the object, another one re-captures.
     """
 
     def __init__(self, engine, fn):
@@ -302,6 +337,12 @@ class Graphed:
         x0, u_init, cost = a.pop("x0"), a.pop("u_init"), a.pop("cost")
         x_ref, ref_offset = a.pop("x_ref"), a.pop("ref_offset")
         del a["workspace"]  # the graph keeps its own
+        if a.get("terminal") is not None:
+            from .terminal import TerminalCost
+            if not isinstance(a["terminal"], TerminalCost):  # an array neither hashes nor gives the graph a pointer that stays
+                raise TypeError("a captured solve takes terminal= as a terminal.TerminalCost (it keys the graph by identity and "
+                                f"holds the device tensor the graph reads), not a {type(a['terminal']).__name__}: wrap the "
+                                "matrix once, TerminalCost(W), and keep the object")
         _need_reference(self.engine, x_ref)
         ref = None if x_ref is None else self._compact_reference(x_ref, x0.shape[0])
         key = (tuple(x0.shape), tuple(u_init.shape), bytes(ctypes.string_at(ctypes.addressof(cost), ctypes.sizeof(cost))),

@@ -1,0 +1,782 @@
+"""The terminal cost on the GPU (phnn_terminal_cost, phnn_dare, phnn_gn_direction_term, phnn_solve_term,
+phnn_solve_gn_term):
+
+  1 cost        k_terminal_cost == terminal_model.terminal_cost bit for bit: n in {2, 4}, B in {1, 37, 257} (one thread, a
+                ragged block, more than one block), H in {1, 6}, a shared and a per-problem W, group in {1, 3}, the cost's
+                x_target and a reference whose row clamps at rows - 1 through a device offset, a NaN state, and the rows
+                t < H of a 0xFF-filled traj_bar untouched
+  2 dare        k_dare == terminal_model.dare bit for bit (P, K, W, iters, status): the trained cart-pole model linearised
+                at the target, Euler (127 steps) and RK4 (73), the pendulum model (n = 2; 119 steps, Euler and RK4), each
+                with its fixture's own cost and dt; the seed-0 model stopped at max_iters = 64 (status 2, the last iterate);
+                seeded systems for (n, m) in {(2,1), (4,1), (4,3)}, B in {1, 5}; a singular Quu (R = 0, B = 0: status 1,
+                NaN outputs)
+  3 direction   k_gn_direction / k_gn_direction_box with a terminal weight == terminal_model.direction bit for bit; with
+                NULL == phnn_gn_direction / phnn_gn_direction_box bit for bit
+  4 gradient    K1 + k_terminal_cost + K2 against the float64 oracle's rollout_vjp with traj_bar = the float64 gradient
+                of the term, at the tolerance variant_census.grad_tol gives the model: B = 37, H = 6, Euler and RK4,
+                pHNN and canonical; and the same about a per-problem reference with a device offset (K2 through
+                phnn_rollout_vjp_ref: a cotangent AND a reference), the oracle's stage cost taken about zero and the
+                reference's terms added in float64
+  5 solves      phnn_solve_term / phnn_solve_gn_term == the same sequence through the primitives bit for bit (B = 37,
+                H = 6, 3 iterations, with and without a reference); terminal NULL == phnn_solve / phnn_solve_gn_ex;
+                graph replay == eager
+  6 closed loop 8 plants x 5 steps of DeviceClosedLoop (eager and graphed) == the host-driven loop, controls bit for bit
+  7 arguments   the refusals
+  8 footprint   every new entry point, phnn_rollout_vjp_ref included, in guarded buffers of exactly the reported sizes"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import footprint as fp
+import gn_model as gm
+import oracle_lib as ol
+import terminal_model as trm
+import tvlqr_model as tm
+import variant_census as vc
+from test_gpu_footprint import Report, engine, footprint, rng_of
+from test_gpu_gn import CFG, GN, HEADLINE, INVALID, OUT_KEYS, SPECS, GnSolveOp, dev, npf, solve_case
+
+pytestmark = pytest.mark.gpu
+
+N2 = SPECS[0]  # phnn<n=2,...>
+M3 = "phnn<n=4,m=3,hid=128,fixedG,f16x2>"
+CANON = "canonical<hid=128,f16x2>"
+B_, H_ = 37, 6
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+    assert t.cuda.is_available(), "GPU tests need a GPU"
+    return t
+
+
+def same(torch, a, b):
+    return fp.same_bytes(torch, fp.as_bytes(torch, a), fp.as_bytes(torch, b))
+
+
+def weights(rng, P, n):
+    """(P,n,n) float32, positive definite symmetric part, not symmetric."""
+    M = rng.normal(size=(P, n, n))
+    return (np.einsum("bij,bkj->bik", M, M) + 0.3 * rng.normal(size=(P, n, n))).astype(np.float32)
+
+
+# ----------------------------------------------------------------------------- 1. k_terminal_cost
+@pytest.mark.parametrize("sid", [N2, HEADLINE])
+def test_terminal_cost_equals_the_stated_order_model(torch, sid):
+    from phnn_mpc_amd.terminal import TerminalCost
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n = s["n"]
+    cases = 0
+    for B in (1, 37, 257):
+        for H in (1, 6):
+            rng = rng_of("terminal-cost", sid, B, H)
+            traj = rng.normal(size=(B, H + 1, n)).astype(np.float32)
+            traj[B // 2, H, n - 1] = np.nan  # a NaN state: that rollout's cost and row are NaN
+            cost = vc.cost_of(s, rng)
+            c0 = rng.uniform(0, 50, size=B).astype(np.float32)
+            rows = 4  # shorter than offset + H: the row clamps at rows - 1
+            own = rng.uniform(-0.3, 0.3, size=(B, rows, n)).astype(np.float32)
+            off = dev(torch, [2], torch.int32)
+            for group in (1, 3):
+                P = (B + group - 1) // group
+                for W in (weights(rng, 1, n)[0], weights(rng, P, n)):
+                    for kw, ref_kw in (({}, {}), (dict(x_ref=own, ref_offset=off), dict(x_ref=own, ref_offset=2))):
+                        Wb = trm.weights_of(W, B, n, group)
+                        r = trm.target_rows(cost, n, B, H, **ref_kw)
+                        if ref_kw:
+                            assert np.array_equal(r, own[:, min(2 + H, rows - 1)])
+                        tb0 = np.zeros((B, H + 1, n), np.float32)
+                        tb0.view(np.uint32)[:] = 0xFFFFFFFF
+                        want_c, want_tb = trm.terminal_cost(traj, Wb, r, c0, tb0)
+                        cd, tbd = dev(torch, c0.copy()), dev(torch, tb0.copy())
+                        eng.terminal_cost(dev(torch, traj), cost, TerminalCost(W), cd, traj_bar=tbd, group=group, **kw)
+                        assert tm.same_floats(npf(cd), want_c), (sid, B, H, group, W.ndim, bool(kw))
+                        assert tm.same_floats(npf(tbd)[:, H], want_tb[:, H])
+                        assert np.all(npf(tbd)[:, :H].view(np.uint32) == 0xFFFFFFFF)  # rows t < H are never written
+                        assert np.isnan(want_c[B // 2]) and np.isnan(want_tb[B // 2, H]).all()
+                        assert np.isfinite(np.delete(want_c, B // 2)).all()
+                        # cost only: the same cost, no cotangent
+                        cd2 = dev(torch, c0.copy())
+                        assert eng.terminal_cost(dev(torch, traj), cost, W, cd2, group=group, **kw) is None
+                        assert same(torch, cd2, cd)
+                        cases += 1
+    assert cases == 3 * 2 * 2 * 2 * 2
+
+
+# ----------------------------------------------------------------------------- 2. k_dare
+def check_dare(what, out, want):
+    for k in ("iters", "status"):
+        assert np.array_equal(npf(out[k]), want[k]), (what, k, npf(out[k]), want[k])
+    for k in ("P", "K", "W"):
+        assert tm.same_floats(npf(out[k]), want[k]), (what, k)
+
+
+def test_dare_equals_the_stated_order_model_on_the_golden_models(torch):
+    # k_dare reads A, Bm and the cost, not the handle's weights: any handle of the same (n, m) serves
+    for name, integ, max_iters, iters, status in (("phnn_cartpole_trained", "euler", None, 127, 0),
+                                                   ("phnn_cartpole_trained", "rk4", None, 73, 0),
+                                                   ("phnn_pendulum", "euler", None, 119, 0),
+                                                   ("phnn_pendulum", "rk4", None, 119, 0),
+                                                   ("phnn_cartpole", "euler", 64, 64, 2)):
+        A, Bm, cost = trm.linearize_at_target(name, integ)
+        n = A.shape[1]
+        eng = engine(HEADLINE if n == 4 else N2)
+        assert (eng.n, eng.m) == (n, 1)
+        Lxx, Luu = tm.cost_matrices_of(cost, n, 1)
+        from phnn_mpc_amd.terminal import DARE_MAX_ITERS
+        want = trm.dare(A, Bm, Lxx, Luu, max_iters or DARE_MAX_ITERS, 1e-12)
+        assert want["iters"].tolist() == [iters] and want["status"].tolist() == [status]
+        check_dare((name, integ), eng.dare(A, Bm, cost, max_iters=max_iters, tol=1e-12), want)
+
+
+@pytest.mark.parametrize("sid,n,m", [(N2, 2, 1), (HEADLINE, 4, 1), (M3, 4, 3)])
+def test_dare_equals_the_stated_order_model_on_seeded_systems(torch, sid, n, m):
+    from phnn_mpc_amd import _capi
+    eng = engine(sid)
+    assert (eng.n, eng.m) == (n, m)
+    for B in (1, 5):
+        A, Bm, Q, R = tm.seeded_problem(7000 + 10 * n + m + B, B, 1, n, m)
+        A, Bm = A[:, 0], Bm[:, 0]
+        cost = _capi.make_cost(n, m, Q, R)
+        Lxx, Luu = tm.cost_matrices_of(cost, n, m)
+        for max_iters, tol, mu in ((100000, 1e-12, 0.0), (9, 1e-12, 0.0), (100000, 1e-6, 0.125)):
+            want = trm.dare(A, Bm, Lxx, Luu, max_iters, tol, mu)
+            check_dare((sid, B, max_iters, tol, mu), eng.dare(A, Bm, cost, max_iters=max_iters, tol=tol, mu=mu), want)
+            assert np.all(want["status"] == (2 if max_iters == 9 else 0))
+    # a singular Quu: R = 0 and B = 0 -- and one such problem among good ones
+    B = 5
+    A, Bm, Q, R = tm.seeded_problem(7100 + n + m, B, 1, n, m)
+    A, Bm = A[:, 0], Bm[:, 0].copy()
+    zero_r = _capi.make_cost(n, m, Q, np.zeros((m, m)))
+    want = trm.dare(A, 0 * Bm, *tm.cost_matrices_of(zero_r, n, m), 50, 1e-12)
+    check_dare((sid, "singular"), eng.dare(A, 0 * Bm, zero_r, max_iters=50, tol=1e-12), want)
+    assert np.all(want["status"] == 1) and np.isnan(want["P"]).all() and np.isnan(want["W"]).all()
+    Bm[1] = np.nan
+    cost = _capi.make_cost(n, m, Q, R)
+    want = trm.dare(A, Bm, *tm.cost_matrices_of(cost, n, m), 100000, 1e-12)
+    check_dare((sid, "one NaN"), eng.dare(A, Bm, cost, max_iters=100000, tol=1e-12), want)
+    assert want["status"].tolist() == [0, 1, 0, 0, 0]
+
+
+# ----------------------------------------------------------------------------- 3. the direction
+@pytest.mark.parametrize("sid", [N2, HEADLINE, M3])
+def test_direction_with_a_terminal_weight_equals_the_stated_order_model(torch, sid):
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n, m = s["n"], s["m"]
+    held = 0
+    for B, H in ((1, 1), (37, 6)):
+        rng = rng_of("terminal-dir", sid, B, H)
+        x0 = 0.5 * vc.states(rng, n, B)
+        u = np.clip(vc.controls(rng, B, H, m), vc.U_MIN, vc.U_MAX).astype(np.float32)
+        cost = vc.cost_of(s, rng, barrier=True)
+        mu = rng.choice([0.0, 1e-6, 0.125, 3.0], size=B)
+        A, Bm, traj = eng.rollout_linearize(x0, u, cost, "euler", vc.dt_of(s))
+        An, Bn, tn = npf(A), npf(Bm), npf(traj)
+        own = rng.uniform(-0.2, 0.2, size=(B, 3, n)).astype(np.float32)
+        off = dev(torch, [1], torch.int32)
+        for W in (weights(rng, 1, n)[0], weights(rng, B, n)):
+            Wb = trm.weights_of(W, B, n)
+            for kw, ref in (({}, None), (dict(x_ref=own, ref_offset=off), gm.reference_rows(own, 1, H, B, n))):
+                for box in (False, True):
+                    out = eng.gn_direction(A, Bm, traj, u, cost, dev(torch, mu), box=box, terminal=W, **kw)
+                    want = trm.direction(An, Bn, tn, u, cost, n, m, mu, Wb, ref, box)
+                    what = (sid, B, H, W.ndim, bool(kw), box)
+                    assert np.array_equal(npf(out["status"]), want["status"]), what
+                    assert tm.same_floats(npf(out["du"]), want["du"]) and tm.same_floats(npf(out["dV"]), want["dV"]), what
+                    assert not want["status"].any()
+                    if box:
+                        assert np.array_equal(npf(out["nclamp"]), want["nclamp"]), what
+                        held += int(want["nclamp"].sum())
+                    # the terminal weight moves the step; without one the call is today's, bit for bit
+                    plain = eng.gn_direction(A, Bm, traj, u, cost, dev(torch, mu), box=box, **kw)
+                    assert not same(torch, plain["du"], out["du"])
+                    null = direction_term_null(torch, eng, A, Bm, traj, u, cost, mu, box, kw)
+                    for k in plain:
+                        assert same(torch, null[k], plain[k]), (what, k)
+    assert held > 0
+
+
+def direction_term_null(torch, eng, A, Bm, traj, u, cost, mu, box, kw):
+    """phnn_gn_direction_term with term = NULL, called directly (engine.gn_direction reaches it only with a terminal)."""
+    from phnn_mpc_amd import _capi
+    B, H = traj.shape[0], traj.shape[1] - 1
+    u, mu = dev(torch, u), dev(torch, mu)
+    ref, _keep = eng._reference(kw.get("x_ref"), kw.get("ref_offset", 0), B)
+    out = dict(du=torch.empty(B, H, eng.m, dtype=torch.float32, device=eng.device),
+               dV=torch.empty(B, dtype=torch.float64, device=eng.device),
+               status=torch.empty(B, dtype=torch.int32, device=eng.device))
+    if box:
+        out["nclamp"] = torch.empty(B, dtype=torch.int32, device=eng.device)
+    scratch = torch.empty(B * H * (eng.m * eng.n + eng.m), dtype=torch.float64, device=eng.device)
+    rc = eng.lib.phnn_gn_direction_term(eng.h, eng._p(A), eng._p(Bm), eng._p(traj), eng._p(u), B, H, C.byref(cost),
+                                        None if ref is None else C.byref(ref), None, eng._p(mu), eng._p(out["du"]),
+                                        eng._p(out["dV"]), eng._p(out["status"]), _capi.PHNN_GN_BOX if box else 0,
+                                        eng._p(out.get("nclamp")), eng._p(scratch), eng._stream())
+    fp.check_rc(eng, rc)
+    return out
+
+
+# ----------------------------------------------------------------------------- 4. the total gradient
+@pytest.mark.parametrize("tracking", [False, True], ids=["target", "reference"])
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+@pytest.mark.parametrize("sid", [HEADLINE, CANON])
+def test_total_gradient_against_the_float64_oracle(torch, sid, integ, tracking):
+    from phnn_mpc_amd import _capi
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n, m = s["n"], s["m"]
+    rng = rng_of("terminal-grad", sid, integ, tracking)
+    x0, u, cost, dt = vc.states(rng, n, B_), vc.controls(rng, B_, H_, m), vc.cost_of(s, rng), vc.dt_of(s)
+    W = weights(rng, B_, n)
+    kw = {}
+    if tracking:  # rows offset + t of a per-problem reference; the last rows clamp at rows - 1
+        own = (0.2 * rng.uniform(-1, 1, size=(B_, H_, n)) * vc.X_SCALE[n]).astype(np.float32)
+        kw = dict(x_ref=own, ref_offset=dev(torch, [2], torch.int32))
+    c, traj = eng.rollout_cost(x0, u, cost, integ, dt, want_traj=True, **kw)
+    c_stage = npf(c).copy()
+    tb = eng.terminal_cost(traj, cost, W, c, want_traj_bar=True, **kw)
+    gu, gx = eng.rollout_vjp(x0, u, traj, cost, integ, dt, traj_bar=tb, **kw)
+    # the float64 oracle on its own trajectory, with the float64 gradient of the term as the cotangent.  The oracle has
+    # no reference: its stage cost is taken about zero and the reference's terms are added here, as test_gpu_tracking.py
+    # does -- C = C0 - sum_t r_t^T (Q + Q^T) x_t + sum_t r_t^T Q r_t, cotangent -(Q + Q^T) r_t on every row
+    o = ol.OracleModel(vc.build_state_dict(sid, s), "f64", activation=s["act"])
+    tb64 = np.zeros((B_, H_ + 1, n))
+    if tracking:
+        cost0 = _capi.Cost.from_buffer_copy(cost)
+        for i in range(n):
+            cost0.x_target[i] = 0.0
+        rows = gm.reference_rows(own, 2, H_, B_, n).astype(np.float64)
+        assert np.array_equal(rows[:, H_], own[:, H_ - 1]) and not np.array_equal(rows[:, 0], rows[:, 1])
+        Q = np.array(cost.Q[: n * n], dtype=np.float64).reshape(n, n)
+        r = o.rollout(x0, u, cost0, integ, dt, grad=False, traj=True)
+        stage = r["cost"] - np.einsum("bti,ij,btj->b", rows, Q + Q.T, r["traj"]) + np.einsum("bti,ij,btj->b", rows, Q, rows)
+        tb64 -= np.einsum("ij,btj->bti", Q + Q.T, rows)
+        tgt, ocost = rows[:, H_], cost0
+    else:
+        r = o.rollout(x0, u, cost, integ, dt, grad=False, traj=True)
+        stage, tgt, ocost = r["cost"], trm.target_rows(cost, n, B_, H_).astype(np.float64), cost
+    e = r["traj"][:, H_] - tgt
+    W64 = W.astype(np.float64)
+    tb64[:, H_] += np.einsum("bij,bj->bi", W64 + np.swapaxes(W64, 1, 2), e)
+    ref_gu, ref_gx = o.rollout_vjp(x0, u, ocost, integ, dt, traj_bar=tb64)
+    term = np.einsum("bi,bij,bj->b", e, W64, e)
+    eu, ex = vc.err_rows(npf(gu), ref_gu), vc.err_rows(npf(gx), ref_gx)
+    ec = vc.err_cost(npf(c), stage + term)
+    print(f"\n{sid} {integ} {'reference' if tracking else 'target'}: total cost {ec:.2e} relative, grad_u {eu:.2e}, grad_x0 {ex:.2e} of max|grad| per rollout "
+          f"(allowed {vc.grad_tol(s):.1e}); the term is {float(np.median(term / stage)):.2f} of the stage cost (median)")
+    assert eu <= vc.grad_tol(s) and ex <= vc.grad_tol(s) and ec <= vc.COST_RTOL * s["tol"]
+    assert np.all(npf(c) != c_stage)
+
+
+# ----------------------------------------------------------------------------- 5. the solves
+def adam_by_hand(torch, eng, x0, u0, cost, integ, dt, lr, iters, terminal, stash, x_ref=None, ref_offset=0):
+    """The sequence phnn_solve_term enqueues, issued through the public entry points on the same buffers: per iteration
+    K1 (with the K1 -> K2 workspace when stash), k_terminal_cost, the cost history copy, K2 with the cotangent, K3."""
+    B, H = u0.shape[0], u0.shape[1]
+    integ_i = eng._integ(integ)
+    f = dict(dtype=torch.float32, device=eng.device)
+    u = u0.detach().clone()
+    m_, v_, g = torch.zeros_like(u), torch.zeros_like(u), torch.empty_like(u)
+    c, traj = torch.empty(B, **f), torch.empty(B, H + 1, eng.n, **f)
+    tb = torch.zeros(B, H + 1, eng.n, **f)
+    costs = torch.empty(iters, B, **f)
+    best_cost, best_u = torch.full((B,), float("inf"), **f), torch.zeros_like(u)
+    ws = torch.empty(eng.workspace_bytes(B, H, integ), dtype=torch.uint8, device=eng.device) if stash else None
+    ref, _keep = eng._reference(x_ref, ref_offset, B)
+    term, _keep_t = eng._terminal(terminal, B)
+    for k in range(iters):
+        eng._roll_call("phnn_rollout_fwd", ref, x0, u, B, H, cost, integ_i, float(dt), eng._p(c), eng._p(traj), eng._p(ws))
+        fp.check_rc(eng, eng.lib.phnn_terminal_cost(eng.h, eng._p(traj), B, H, C.byref(cost), None if ref is None else C.byref(ref),
+                                                    C.byref(term), eng._p(c), eng._p(tb), eng._stream()))
+        costs[k].copy_(c)
+        eng._roll_call("phnn_rollout_vjp", ref, x0, u, B, H, cost, integ_i, float(dt), eng._p(traj), eng._p(ws), eng._p(tb), None,
+                       eng._p(g), None)
+        eng.adam_step(u, g, m_, v_, lr, k + 1, cost=c, best_cost=best_cost, best_u=best_u, u_min=float(cost.u_min),
+                      u_max=float(cost.u_max))
+    return dict(u_last=u, costs=costs, best_u=best_u, best_cost=best_cost)
+
+
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+@pytest.mark.parametrize("sid", [N2, HEADLINE])
+def test_adam_solve_with_a_terminal_weight_equals_the_sequence_issued_by_hand(torch, sid, integ):
+    from phnn_mpc_amd import solver
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n = s["n"]
+    _, x0, u0, cost, rng = solve_case(sid, B_, H_, ("terminal", integ))
+    x0d, u0d = dev(torch, x0), dev(torch, u0)
+    own = rng.uniform(-0.1, 0.1, size=(B_, 3, n)).astype(np.float32)
+    off = dev(torch, [1], torch.int32)
+    keep = eng.use_stash
+    try:
+        for W in (weights(rng, 1, n)[0], weights(rng, B_, n)):
+            for kw in ({}, dict(x_ref=own, ref_offset=off)):
+                for stash in (True, False):
+                    eng.use_stash = stash
+                    lib = eng.solve(x0d, u0d, cost, integ, vc.dt_of(s), lr=0.05, iters=3, track_best=True, terminal=W, **kw)
+                    hand = adam_by_hand(torch, eng, x0d, u0d, cost, integ, vc.dt_of(s), 0.05, 3, W, stash, **kw)
+                    for k in hand:
+                        assert same(torch, lib[k], hand[k]), (sid, integ, W.ndim, bool(kw), stash, k)
+                # the Python loop of the solver module (no K1 -> K2 workspace): the same sequence again
+                loop = solver.shooting_solve(eng, x0d, u0d, cost, integ, vc.dt_of(s), 0.05, 3, track_best=True, u_min=vc.U_MIN,
+                                             u_max=vc.U_MAX, terminal=W, **kw)
+                for k in loop:
+                    assert same(torch, lib[k], loop[k]), (sid, integ, "loop", k)
+                plain = eng.solve(x0d, u0d, cost, integ, vc.dt_of(s), lr=0.05, iters=3, track_best=True, **kw)
+                # the first iterate is the same: its total cost is another number, and the solve goes another way
+                assert not same(torch, plain["u_last"], lib["u_last"]) and bool((lib["costs"][0] != plain["costs"][0]).all())
+                # terminal NULL through the new entry point: phnn_solve / phnn_solve_ref, bit for bit
+                null = solve_term_null(torch, eng, x0d, u0d, cost, integ, vc.dt_of(s), 0.05, 3, kw)
+                for k in null:
+                    assert same(torch, null[k], plain[k]), (sid, integ, "NULL", k)
+    finally:
+        eng.use_stash = keep
+
+
+def solve_term_null(torch, eng, x0, u0, cost, integ, dt, lr, iters, kw):
+    from phnn_mpc_amd import _capi
+    B, H = u0.shape[0], u0.shape[1]
+    f = dict(dtype=torch.float32, device=eng.device)
+    ws = eng._roll_workspace(None, B, H, eng._integ(integ))
+    u = u0.detach().clone()
+    m_, v_ = torch.empty_like(u), torch.empty_like(u)
+    out = dict(u_last=u, costs=torch.empty(iters, B, **f), best_cost=torch.empty(B, **f), best_u=torch.empty_like(u))
+    poison = torch.full((B, H + 1, eng.n), 7.0, **f)
+    opt = _capi.SolveOptions(iters, lr, 0.9, 0.999, 1e-8, 1)
+    ref, _keep = eng._reference(kw.get("x_ref"), kw.get("ref_offset", 0), B)
+    rc = eng.lib.phnn_solve_term(eng.h, eng._p(x0), eng._p(u), B, H, C.byref(cost), None if ref is None else C.byref(ref), None,
+                                 eng._integ(integ), float(dt), C.byref(opt), eng._p(m_), eng._p(v_), eng._p(ws["grad_u"]),
+                                 eng._p(ws["cost"]), eng._p(ws["traj"]), eng._p(ws["stash"]), eng._p(out["costs"]),
+                                 eng._p(out["best_cost"]), eng._p(out["best_u"]), eng._p(poison), eng._stream())
+    fp.check_rc(eng, rc)
+    assert bool((poison == 7.0).all())  # without a terminal weight the cotangent buffer is not touched
+    return out
+
+
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+@pytest.mark.parametrize("sid", [N2, HEADLINE])
+def test_gn_solve_with_a_terminal_weight_equals_the_sequence_issued_by_hand(torch, sid, integ):
+    from phnn_mpc_amd import solver
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n = s["n"]
+    _, x0, u0, cost, rng = solve_case(sid, B_, H_, ("terminal-gn", integ))
+    x0d, u0d = dev(torch, x0), dev(torch, u0)
+    own = rng.uniform(-0.1, 0.1, size=(B_, 3, n)).astype(np.float32)
+    off = dev(torch, [1], torch.int32)
+    fell = 0
+    for W in (weights(rng, 1, n)[0], weights(rng, B_, n)):
+        for kw in ({}, dict(x_ref=own, ref_offset=off)):
+            for box in (False, True):
+                keys = OUT_KEYS + (("nclamp_hist",) if box else ())
+                lib = eng.solve_gn(x0d, u0d, cost, integ, vc.dt_of(s), iters=3, box=box, terminal=W, **GN, **kw)
+                hand = solver.gn_solve(eng, x0d, u0d, cost, integ, vc.dt_of(s), 3, box=box, terminal=W, **GN, **kw)
+                for k in keys:
+                    assert same(torch, lib[k], hand[k]), (sid, integ, W.ndim, bool(kw), box, k)
+                chain = np.vstack([npf(lib["costs"]), npf(lib["cost"])[None]])
+                assert np.isfinite(chain).all() and np.all(chain[1:] <= chain[:-1])  # the TOTAL cost never rises
+                fell += int((chain[-1] < chain[0]).sum())
+                # the final cost is K1's plus the term
+                c2 = eng.rollout_cost(x0d, lib["u_last"], cost, integ, vc.dt_of(s), want_traj=True, **kw)
+                eng.terminal_cost(c2[1], cost, W, c2[0], **kw)
+                assert same(torch, c2[0], lib["cost"])
+                plain = eng.solve_gn(x0d, u0d, cost, integ, vc.dt_of(s), iters=3, box=box, **GN, **kw)
+                assert not same(torch, plain["u_last"], lib["u_last"])
+                null = solve_gn_term_null(torch, eng, x0d, u0d, cost, integ, vc.dt_of(s), 3, box, kw)
+                for k in keys:
+                    assert same(torch, null[k], plain[k]), (sid, integ, "NULL", box, k)
+    assert fell > 0
+
+
+def solve_gn_term_null(torch, eng, x0, u0, cost, integ, dt, iters, box, kw):
+    from phnn_mpc_amd import _capi
+    B, H = u0.shape[0], u0.shape[1]
+    o = eng._gn_options(iters, **GN)
+    ws = torch.empty(max(eng.gn_workspace_bytes(B, H, o.line_steps), 256), dtype=torch.uint8, device=eng.device)
+    f = dict(dtype=torch.float32, device=eng.device)
+    i32 = dict(dtype=torch.int32, device=eng.device)
+    out = {"u_last": u0.detach().clone(), "cost": torch.empty(B, **f), "costs": torch.empty(iters, B, **f),
+           "mu": torch.empty(B, dtype=torch.float64, device=eng.device), "accepts": torch.empty(B, **i32),
+           "alpha_hist": torch.empty(iters, B, **f), "nclamp_hist": torch.empty(iters, B, **i32) if box else None}
+    ref, _keep = eng._reference(eng.mppi_reference(kw.get("x_ref"), B, o.line_steps), kw.get("ref_offset", 0), B * o.line_steps)
+    rc = eng.lib.phnn_solve_gn_term(eng.h, eng._p(x0), eng._p(out["u_last"]), B, H, C.byref(cost),
+                                    None if ref is None else C.byref(ref), None, eng._integ(integ), float(dt), C.byref(o),
+                                    eng._p(ws), ws.numel(), eng._p(out["cost"]), eng._p(out["costs"]), eng._p(out["mu"]),
+                                    eng._p(out["accepts"]), eng._p(out["alpha_hist"]), _capi.PHNN_GN_BOX if box else 0,
+                                    eng._p(out["nclamp_hist"]), eng._stream())
+    fp.check_rc(eng, rc)
+    return out
+
+
+def test_graph_replay_equals_the_eager_solves(torch):
+    from phnn_mpc_amd import solver
+    from phnn_mpc_amd.terminal import TerminalCost
+    sid = HEADLINE
+    s, eng = vc.CENSUS[sid], engine(sid)
+    _, x0, u0, cost, rng = solve_case(sid, 18, H_, "terminal-graph")
+    x0d, u0d = dev(torch, x0), dev(torch, u0)
+    term = TerminalCost(weights(rng, 18, 4))
+    own = dev(torch, rng.uniform(-0.1, 0.1, size=(18, 3, 4)).astype(np.float32))
+    for rkw in ({}, dict(x_ref=own, ref_offset=1)):
+        eager = eng.solve(x0d, u0d, cost, "euler", 0.02, lr=0.05, iters=3, track_best=True, terminal=term, **rkw)
+        graphed = solver.GraphedSolve(eng)
+        args = (eng, x0d, u0d, cost, "euler", 0.02, 0.05, 3)
+        akw = dict(track_best=True, u_min=vc.U_MIN, u_max=vc.U_MAX, terminal=term, **rkw)
+        for _ in range(2):
+            out = graphed(*args, **akw)
+            for k in eager:
+                assert same(torch, out[k], eager[k]), ("adam", k)
+        x1 = x0d * 0.5  # new inputs reach the captured buffers
+        out = graphed(eng, x1, *args[2:], **akw)
+        want = eng.solve(x1, u0d, cost, "euler", 0.02, lr=0.05, iters=3, track_best=True, terminal=term, **rkw)
+        for k in want:
+            assert same(torch, out[k], want[k]), ("adam, new x0", k)
+        eager = eng.solve_gn(x0d, u0d, cost, "euler", 0.02, iters=3, terminal=term, **GN, **rkw)
+        ggn = solver.GraphedGN(eng)
+        for _ in range(2):
+            out = ggn(eng, x0d, u0d, cost, "euler", 0.02, iters=3, terminal=term, **GN, **rkw)
+            for k in OUT_KEYS:
+                assert same(torch, out[k], eager[k]), ("gn", k)
+
+
+# ----------------------------------------------------------------------------- 6. the closed loop
+def _load(cls, name, torch):
+    m = cls(CFG)
+    m.load_state_dict({k: torch.tensor(v) for k, v in ol.load_weights(name).items()})
+    return m
+
+
+@pytest.mark.parametrize("optimizer", ["Adam", "GaussNewton"])
+def test_device_closed_loop_with_a_terminal_weight_equals_the_host_loop(torch, optimizer):
+    import yaml
+    from phnn_mpc_amd.closed_loop import BatchedCartPole, run_mpc_batch, run_mpc_batch_device
+    from phnn_mpc_amd.models import pHNN, pHNN_Canonical
+    from phnn_mpc_amd.mpc_controller import create_mpc_from_config
+    from phnn_mpc_amd.mpc_controller_canonical import create_mpc_controller
+    from phnn_mpc_amd.terminal import TerminalCost
+    cfg = yaml.safe_load(open(CFG))
+    cfg["mpc"].update(optimizer=optimizer, optimizer_steps=3, gn_line_steps=4, horizon=10)
+    rng = np.random.default_rng(13)
+    X = rng.uniform(-1, 1, size=(8, 4)) * [0.2, 0.08, 0.1, 0.1]
+    T = 5
+    W = weights(rng, 1, 4)[0] * np.float32(20.0)
+    for model, section in ((_load(pHNN, "phnn_cartpole_trained", torch), {"type": "lqr"}),
+                           (_load(pHNN_Canonical, "canonical_cartpole", torch), {"type": "matrix", "W": W.tolist()})):
+        canonical = isinstance(model, pHNN_Canonical)
+        cfg["mpc"]["terminal"] = section
+        c = (create_mpc_controller if canonical else create_mpc_from_config)(model, cfg)
+        term = c.terminal_cost()
+        assert isinstance(term, TerminalCost) and (canonical or term.info["iters"].tolist() == [127])
+        host = run_mpc_batch(BatchedCartPole(0.02), c, X, T)
+        c.terminal = None
+        assert not np.array_equal(run_mpc_batch(BatchedCartPole(0.02), c, X, T)["controls"], host["controls"])
+        c.terminal = term
+        for use_graph in (False, True):
+            dev_ = run_mpc_batch_device(c, X, T, use_graph=use_graph)
+            assert np.array_equal(dev_["controls"], host["controls"]), (optimizer, canonical, use_graph)
+            assert np.allclose(dev_["states"], host["states"], rtol=0, atol=1e-12)
+    # the solves without a terminal term refuse the controller's weight, in the device loop too
+    cfg["mpc"].update(optimizer="MPPI")
+    with pytest.raises(ValueError, match="terminal"):
+        run_mpc_batch_device(create_mpc_from_config(_load(pHNN, "phnn_cartpole", torch), cfg), X, 2)
+
+
+# ----------------------------------------------------------------------------- 7. arguments
+def test_bad_arguments(torch):
+    from phnn_mpc_amd import _capi
+    from phnn_mpc_amd.engine import PhnnError
+    sid = HEADLINE
+    s, eng = vc.CENSUS[sid], engine(sid)
+    lib, h, st = eng.lib, eng.h, eng._stream()
+    B, H, n, m = 5, 3, 4, 1
+    f = dict(dtype=torch.float32, device="cuda:0")
+    i32 = dict(dtype=torch.int32, device="cuda:0")
+    f64 = dict(dtype=torch.float64, device="cuda:0")
+    cost = vc.cost_of(s, np.random.default_rng(0))
+    t = dict(traj=torch.zeros(B, H + 1, n, **f), c=torch.full((B,), 7.0, **f), tb=torch.full((B, H + 1, n), 7.0, **f),
+             W=torch.eye(n, **f), A=torch.eye(n, **f).repeat(B, 1, 1), Bm=torch.full((B, n, m), 0.1, **f),
+             P=torch.full((B, n, n), 7.0, **f64), K=torch.full((B, m, n), 7.0, **f64), Wo=torch.full((B, n, n), 7.0, **f),
+             it=torch.full((B,), 7, **i32), stt=torch.full((B,), 7, **i32))
+    p = {k: C.c_void_p(v.data_ptr()) for k, v in t.items()}
+
+    def term(W=p["W"], bs=0, group=1):
+        x = _capi.Terminal()
+        x.W_dev, x.batch_stride, x.group = (W.value if W is not None else None), bs, group
+        return C.byref(x)
+
+    def tc(traj=p["traj"], nb=B, hh=H, c=C.byref(cost), tm_=None, cd=p["c"]):
+        return lib.phnn_terminal_cost(h, traj, nb, hh, c, None, term() if tm_ is None else tm_, cd, p["tb"], st)
+
+    def dare(nb=B, c=C.byref(cost), max_iters=50, tol=1e-12, mu=0.0, reserved=0, P=p["P"]):
+        o = _capi.DareOptions()
+        o.max_iters, o.tol, o.mu = max_iters, tol, mu
+        o.reserved[0] = reserved
+        return lib.phnn_dare(h, p["A"], p["Bm"], nb, c, C.byref(o), P, p["K"], p["Wo"], p["it"], p["stt"], st)
+
+    cases = [
+        (lambda: tc(tm_=term(W=None)), "W_dev is NULL"), (lambda: tc(tm_=term(group=0)), "group < 1"),
+        (lambda: tc(tm_=term(group=-3)), "group < 1"), (lambda: tc(tm_=term(bs=-16)), "batch_stride"),
+        (lambda: tc(tm_=C.POINTER(_capi.Terminal)()), "phnn_terminal is NULL"),
+        (lambda: tc(traj=None), "NULL"), (lambda: tc(cd=None), "NULL"), (lambda: tc(nb=-1), "negative batch"),
+        (lambda: tc(hh=0), "horizon < 1"), (lambda: tc(c=None), "cost is NULL"),
+        (lambda: dare(max_iters=0), "max_iters < 1"), (lambda: dare(max_iters=-5), "max_iters < 1"),
+        (lambda: dare(tol=-1e-9), "tol"), (lambda: dare(tol=float("nan")), "tol"), (lambda: dare(tol=float("inf")), "tol"),
+        (lambda: dare(mu=-1.0), "mu"), (lambda: dare(reserved=1), "reserved"), (lambda: dare(nb=-1), "negative batch"),
+        (lambda: dare(c=None), "cost is NULL"), (lambda: dare(P=None), "NULL tensor"),
+    ]
+    for k, (call, why) in enumerate(cases):
+        rc = call()
+        msg = lib.phnn_last_error(h).decode()
+        assert rc == INVALID, (k, rc, msg)
+        assert why in msg, (k, why, msg)
+    torch.cuda.synchronize()
+    for k in ("c", "tb", "P", "K", "Wo", "it", "stt"):
+        assert bool((t[k] == 7).all()), k  # nothing was launched
+    assert tc(nb=0) == 0 and dare(nb=0) == 0 and tc(tm_=term(W=None), nb=0) == 0
+    # the solves refuse a bad terminal as the kernel's entry point does, before anything is enqueued
+    x0, u0 = torch.zeros(B, n, **f), torch.zeros(B, H, m, **f)
+    with pytest.raises(ValueError, match="does not fit"):
+        eng.solve(x0, u0, cost, "euler", 0.02, iters=1, terminal=np.eye(3, dtype=np.float32))
+    with pytest.raises(ValueError, match="does not fit"):
+        eng.solve_gn(x0, u0, cost, "euler", 0.02, iters=1, terminal=np.zeros((B + 1, n, n), np.float32))
+    for solve in (eng.solve_lbfgs, eng.solve_mppi, eng.solve_cem):
+        with pytest.raises(ValueError, match="terminal"):
+            solve(x0, u0, cost, "euler", 0.02, terminal=np.eye(n, dtype=np.float32))
+    # a terminal weight without its scratch
+    opt = _capi.SolveOptions(1, 0.01, 0.9, 0.999, 1e-8, 0)
+    ws = eng._roll_workspace(None, B, H, 0)
+    buf = [torch.empty(B, H, m, **f) for _ in range(3)]
+    rc = lib.phnn_solve_term(h, eng._p(x0), eng._p(u0), B, H, C.byref(cost), None, term(), 0, 0.02, C.byref(opt), eng._p(buf[0]),
+                             eng._p(buf[1]), eng._p(buf[2]), eng._p(ws["cost"]), eng._p(ws["traj"]), None, None, None, None, None, st)
+    assert rc == INVALID and "traj_bar_dev" in lib.phnn_last_error(h).decode()
+    with pytest.raises(PhnnError, match="group < 1"):
+        eng.terminal_cost(t["traj"], cost, np.eye(n, dtype=np.float32), t["c"], group=0)
+
+
+# ----------------------------------------------------------------------------- 8. footprint
+class TerminalCostOp(fp.Op):
+    """phnn_terminal_cost: the cost accumulates, row H of traj_bar is written, the rows before it keep what they held."""
+
+    def __init__(self, cost, traj, W, c0, tb0, group, x_ref=None):
+        super().__init__()
+        B, H1, n = traj.shape
+        self.name = f"terminal_cost B{B} H{H1 - 1} n{n} W{W.ndim} group{group} ref={int(x_ref is not None)}"
+        self.cost, self.B, self.H, self.n, self.group, self.per = cost, B, H1 - 1, n, group, W.ndim == 3
+        f = np.float32
+        self.add("traj", f, traj.shape, fp.IN, traj)
+        self.add("W", f, W.shape, fp.IN, W)
+        if x_ref is not None:
+            self.add("x_ref", f, x_ref.shape, fp.IN, x_ref)
+        self.add("cost", f, (B,), fp.INOUT, c0)
+        self.add("traj_bar", f, traj.shape, fp.INOUT, tb0)
+
+    def _ref(self, p_ref):
+        from phnn_mpc_amd import _capi
+        if p_ref is None:
+            return None
+        r = _capi.Reference()
+        rows = self.input("x_ref").shape[1]
+        r.x_ref, r.batch_stride, r.time_stride, r.rows, r.offset_host = p_ref.value, rows * self.n, self.n, rows, 1
+        return C.byref(r)
+
+    def call(self, eng, p):
+        from phnn_mpc_amd import _capi
+        t = _capi.Terminal()
+        t.W_dev, t.batch_stride, t.group = p["W"].value, self.n * self.n if self.per else 0, self.group
+        fp.check_rc(eng, eng.lib.phnn_terminal_cost(eng.h, p["traj"], self.B, self.H, C.byref(self.cost), self._ref(p.get("x_ref")),
+                                                    C.byref(t), p["cost"], p["traj_bar"], eng._stream()))
+
+    def engine(self, eng):
+        import torch
+        c = torch.as_tensor(self.input("cost").copy(), device=eng.device)
+        tb = torch.as_tensor(self.input("traj_bar").copy(), device=eng.device)
+        kw = {} if not any(b.name == "x_ref" for b in self.bufs) else dict(x_ref=self.input("x_ref"), ref_offset=1)
+        eng.terminal_cost(self.input("traj"), self.cost, self.input("W"), c, traj_bar=tb, group=self.group, **kw)
+        return {"cost": c, "traj_bar": tb}
+
+
+class VjpRefOp(fp.RollOp):
+    """phnn_rollout_fwd_ref -> phnn_rollout_vjp_ref: K2 with trajectory and cost cotangents AND a per-problem reference
+    (footprint.RollOp's 'ref' case with its 'vjp' case's cotangents)."""
+
+    def __init__(self, eng, cost, x0, U, integ, dt, stash, optional, rng):
+        super().__init__(eng, cost, x0, U, integ, dt, kind="ref", stash=stash, optional=optional, rng=rng)
+        B, H, n = self.B, self.H, x0.shape[1]
+        self.name = "vjp_" + self.name
+        self.add("traj_bar", np.float32, (B, H + 1, n), fp.IN, rng.normal(size=(B, H + 1, n)).astype(np.float32))
+        self.add("cost_bar", np.float32, (B,), fp.IN, rng.normal(size=B).astype(np.float32))
+
+    def call(self, eng, p):
+        lib, h, st = eng.lib, eng.h, eng._stream()
+        B, H, c, integ, dt = self.B, self.H, C.byref(self.cost), self.integ, float(self.dt)
+        ws, r = p.get("stash"), self._ref(p)
+        fp.check_rc(eng, lib.phnn_rollout_fwd_ref(h, p["x0"], p["u"], B, H, c, C.byref(r), integ, dt, p["cost"], p["traj"], ws, st))
+        fp.check_rc(eng, lib.phnn_rollout_vjp_ref(h, p["x0"], p["u"], B, H, c, C.byref(r), integ, dt, p["traj"], ws, p["traj_bar"],
+                                                  p["cost_bar"], p["grad_u"], p.get("grad_x0"), st))
+        if not self.optional:
+            fp.check_rc(eng, lib.phnn_rollout_fwd_ref(h, p["x0"], p["u"], B, H, c, C.byref(r), integ, dt, p["cost_nt"], None, None, st))
+
+    def engine(self, eng):
+        x0, U = self.input("x0"), self.input("u")
+        kw = dict(x_ref=self.input("x_ref"), ref_offset=2)
+        name = {0: "euler", 1: "rk4"}[self.integ]
+        c, traj = eng.rollout_cost(x0, U, self.cost, name, self.dt, want_traj=True, **kw)
+        out = {"cost": c, "traj": traj}
+        if not self.optional:
+            out["cost_nt"] = eng.rollout_cost(x0, U, self.cost, name, self.dt, **kw)
+        if not self.stash:  # the engine's rollout_vjp passes no stash
+            gu, gx = eng.rollout_vjp(x0, U, traj, self.cost, name, self.dt, traj_bar=self.input("traj_bar"),
+                                     cost_bar=self.input("cost_bar"), **kw)
+            out["grad_u"] = gu
+            if self.optional:
+                out["grad_x0"] = gx
+        return out
+
+
+class DareOp(fp.Op):
+    def __init__(self, cost, A, Bm, max_iters):
+        super().__init__()
+        B, n, m = Bm.shape
+        self.name = f"dare B{B} n{n} m{m} max_iters{max_iters}"
+        self.cost, self.B, self.max_iters = cost, B, max_iters
+        self.add("A", np.float32, A.shape, fp.IN, A)
+        self.add("Bm", np.float32, Bm.shape, fp.IN, Bm)
+        self.add("P", np.float64, (B, n, n), fp.OUT)
+        self.add("K", np.float64, (B, m, n), fp.OUT)
+        self.add("W", np.float32, (B, n, n), fp.OUT)
+        self.add("iters", np.int32, (B,), fp.OUT)
+        self.add("status", np.int32, (B,), fp.OUT)
+
+    def call(self, eng, p):
+        from phnn_mpc_amd import _capi
+        o = _capi.DareOptions()
+        o.max_iters, o.tol = self.max_iters, 1e-12
+        fp.check_rc(eng, eng.lib.phnn_dare(eng.h, p["A"], p["Bm"], self.B, C.byref(self.cost), C.byref(o), p["P"], p["K"], p["W"],
+                                           p["iters"], p["status"], eng._stream()))
+
+    def engine(self, eng):
+        return eng.dare(self.input("A"), self.input("Bm"), self.cost, max_iters=self.max_iters, tol=1e-12)
+
+
+class DirectionTermOp(fp.Op):
+    """phnn_gn_direction_term (box) with a per-problem W and a scratch of exactly B*H*(m*n + m) float64."""
+
+    def __init__(self, cost, A, Bm, traj, u, mu, W):
+        super().__init__()
+        B, H, m = u.shape
+        n = traj.shape[2]
+        self.name = f"gn_direction_term B{B} H{H} n{n} m{m}"
+        self.cost, self.B, self.H, self.n = cost, B, H, n
+        f = np.float32
+        for k, a in (("A", A), ("Bm", Bm), ("traj", traj), ("u", u), ("W", W)):
+            self.add(k, f, a.shape, fp.IN, a)
+        self.add("mu", np.float64, (B,), fp.IN, mu)
+        self.add("du", f, (B, H, m), fp.OUT)
+        self.add("dV", np.float64, (B,), fp.OUT)
+        self.add("status", np.int32, (B,), fp.OUT)
+        self.add("nclamp", np.int32, (B,), fp.OUT)
+        self.add("scratch", np.float64, (B * H * (m * n + m),), fp.WS)
+
+    def call(self, eng, p):
+        from phnn_mpc_amd import _capi
+        t = _capi.Terminal()
+        t.W_dev, t.batch_stride, t.group = p["W"].value, self.n * self.n, 1
+        fp.check_rc(eng, eng.lib.phnn_gn_direction_term(eng.h, p["A"], p["Bm"], p["traj"], p["u"], self.B, self.H, C.byref(self.cost),
+                                                        None, C.byref(t), p["mu"], p["du"], p["dV"], p["status"], _capi.PHNN_GN_BOX,
+                                                        p["nclamp"], p["scratch"], eng._stream()))
+
+    def engine(self, eng):
+        import torch
+        return eng.gn_direction(self.input("A"), self.input("Bm"), self.input("traj"), self.input("u"), self.cost,
+                                torch.as_tensor(np.asarray(self.input("mu"))), box=True, terminal=self.input("W"))
+
+
+class SolveTermOp(fp.SolveOp):
+    """phnn_solve_term (Adam, track_best on), 2 iterations, a per-problem W and the cotangent scratch."""
+
+    def __init__(self, eng, cost, x0, U, integ, dt, W, stash=True):
+        super().__init__(eng, cost, x0, U, integ, dt, stash)
+        self.name = "term " + self.name
+        self.add("W", np.float32, W.shape, fp.IN, W)
+        self.add("traj_bar", np.float32, (self.B, self.H + 1, x0.shape[1]), fp.OUT)
+
+    def call(self, eng, p):
+        from phnn_mpc_amd import _capi
+        n = self.input("x0").shape[1]
+        t = _capi.Terminal()
+        t.W_dev, t.batch_stride, t.group = p["W"].value, n * n, 1
+        opt = _capi.SolveOptions(self.ITERS, 0.015, 0.9, 0.999, 1e-8, 1)
+        fp.check_rc(eng, eng.lib.phnn_solve_term(eng.h, p["x0"], p["u"], self.B, self.H, C.byref(self.cost), None, C.byref(t), self.integ,
+                                                 float(self.dt), C.byref(opt), p["m"], p["v"], p["grad"], p["cost"], p["traj"],
+                                                 p.get("stash"), p["costs"], p["best_cost"], p["best_u"], p["traj_bar"], eng._stream()))
+
+    def engine(self, eng):
+        keep = eng.use_stash
+        eng.use_stash = self.stash
+        try:
+            ws = {}
+            r = eng.solve(self.input("x0"), self.input("u"), self.cost, {0: "euler", 1: "rk4"}[self.integ], self.dt, lr=0.015,
+                          iters=self.ITERS, track_best=True, workspace=ws, terminal=self.input("W"))
+        finally:
+            eng.use_stash = keep
+        return {"u": r["u_last"], "costs": r["costs"], "best_cost": r["best_cost"], "best_u": r["best_u"], "m": ws["m"], "v": ws["v"],
+                "grad": ws["grad_u"], "cost": ws["cost"], "traj": ws["traj"], "traj_bar": ws["traj_bar"]}
+
+
+class GnSolveTermOp(GnSolveOp):
+    """phnn_solve_gn_term (box) in a workspace of exactly phnn_gn_workspace_bytes, with a per-problem W."""
+
+    def __init__(self, eng, cost, x0, U, integ, dt, L, W, iters=2):
+        super().__init__(eng, cost, x0, U, integ, dt, L, iters)
+        self.name = "term " + self.name
+        self.add("nclamp", np.int32, (iters, self.B), fp.OUT)
+        self.add("W", np.float32, W.shape, fp.IN, W)
+
+    def call(self, eng, p):
+        from phnn_mpc_amd import _capi
+        n = self.input("x0").shape[1]
+        t = _capi.Terminal()
+        t.W_dev, t.batch_stride, t.group = p["W"].value, n * n, 1
+        opt = eng._gn_options(self.iters, self.L, GN["mu_init"], GN["mu_min"], GN["mu_max"], GN["mu_up"], GN["mu_down"])
+        fp.check_rc(eng, eng.lib.phnn_solve_gn_term(eng.h, p["x0"], p["u"], self.B, self.H, C.byref(self.cost), None, C.byref(t),
+                                                    self.integ, float(self.dt), C.byref(opt), p["ws"], self.nws, p["cost_out"],
+                                                    p["costs"], p["mu"], p["accepts"], p["alpha"], _capi.PHNN_GN_BOX, p["nclamp"],
+                                                    eng._stream()))
+
+    def engine(self, eng):
+        r = eng.solve_gn(self.input("x0"), self.input("u"), self.cost, {0: "euler", 1: "rk4"}[self.integ], self.dt,
+                         iters=self.iters, box=True, terminal=self.input("W"), **dict(GN, line_steps=self.L))
+        return {"u": r["u_last"], "cost_out": r["cost"], "costs": r["costs"], "mu": r["mu"], "accepts": r["accepts"],
+                "alpha": r["alpha_hist"], "nclamp": r["nclamp_hist"]}
+
+
+@pytest.mark.parametrize("sid", [N2, HEADLINE])
+def test_footprint(torch, sid):
+    """Every new entry point: nothing outside the outputs and the workspace is written, the inputs are unchanged, the
+    outputs do not depend on what the buffers held nor on what lies around the inputs, at a row-slice skew and with
+    ragged B."""
+    s, eng = vc.CENSUS[sid], engine(sid)
+    n, m = s["n"], s["m"]
+    rep = Report(f"terminal {sid}")
+    for B in (1, 17):
+        for H, L in ((1, 1), (6, 4)):
+            rng = rng_of("terminal-fp", sid, B, H)
+            x0, cost = 0.3 * vc.states(rng, n, B), vc.cost_of(s, rng, barrier=True)
+            U = np.clip(vc.controls(rng, B, H, m), vc.U_MIN, vc.U_MAX).astype(np.float32)
+            W = weights(rng, B, n)
+            traj = rng.normal(size=(B, H + 1, n)).astype(np.float32)
+            c0, tb0 = rng.uniform(0, 9, size=B).astype(np.float32), rng.normal(size=(B, H + 1, n)).astype(np.float32)
+            x_ref = rng.uniform(-0.2, 0.2, size=(B, H + 1, n)).astype(np.float32)  # offset 1: the last row clamps
+            footprint(rep, torch, eng, TerminalCostOp(cost, traj, W, c0, tb0, 1))
+            footprint(rep, torch, eng, TerminalCostOp(cost, traj, W[0], c0, tb0, 1, x_ref))
+            footprint(rep, torch, eng, TerminalCostOp(cost, traj, W[: (B + 2) // 3], c0, tb0, 3))
+            A1, B1, Q, R = tm.seeded_problem(90 + B + H, B, 1, n, m)
+            footprint(rep, torch, eng, DareOp(cost, A1[:, 0], B1[:, 0], 40 if H == 1 else 100000))
+            A, Bm, tr = eng.rollout_linearize(x0, U, cost, "euler", vc.dt_of(s))
+            mu = rng.choice([0.0, 1e-6, 0.125], size=B)
+            footprint(rep, torch, eng, DirectionTermOp(cost, npf(A), npf(Bm), npf(tr), U, mu, W))
+            footprint(rep, torch, eng, SolveTermOp(eng, cost, x0, U, (B + H) % 2, vc.dt_of(s), W, stash=H == 1))
+            footprint(rep, torch, eng, GnSolveTermOp(eng, cost, x0, U, (B + H) % 2, vc.dt_of(s), L, W))
+            for integ in (0, 1):
+                footprint(rep, torch, eng, VjpRefOp(eng, cost, x0, U, integ, vc.dt_of(s), stash=(B + H + integ) % 2 == 0,
+                                                    optional=H == 1, rng=rng))
+    rep.finish()
