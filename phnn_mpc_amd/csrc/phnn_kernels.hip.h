@@ -1017,8 +1017,11 @@ DEV float gelu_cdf(float z) { return __builtin_fmaf(0.5f, erff(z * 0.70710678118
 template <int ACT>
 DEV void act_eval(float z, float& a, float& d1) {  // phi(z), phi'(z)
   if (ACT == ACT_RELU) {
-    a = fmaxf(z, 0.f);
-    d1 = z > 0.f ? 1.0f : 0.0f;  // torch: subgradient 0 at 0
+    // a NaN pre-activation stays NaN, as through nn.ReLU, and its slope is NaN too (fmaxf(z, 0) and z > 0 would turn it
+    // into a finite 0: a diverged stage state would then give finite outputs and Jacobians); every other z as before
+    const bool pos = !(z <= 0.f);  // z > 0, or NaN
+    a = pos ? z : 0.f;
+    d1 = pos ? (z == z ? 1.0f : z) : 0.0f;  // torch: subgradient 0 at 0
   } else if (ACT == ACT_ELU) {  // nn.ELU, alpha = 1: z | expm1(z);  1 | exp(z)
     a = z > 0.f ? z : expm1f(z);
     d1 = z > 0.f ? 1.0f : __builtin_amdgcn_exp2f(z * 1.4426950408889634f);

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 import tvlqr_model as tm
+import variant_census as vc
 from linearize_model import LinOracleEngine
 from tvlqr_model import _dot
 
@@ -272,8 +273,7 @@ class GnOracleEngine(LinOracleEngine):
 # ----------------------------------------------------------------------------- the slope identity (cross-check with K2)
 # In exact arithmetic sum(grad_u * du) = -dV for every mu: du = -(H + mu)^-1 g and dV = g^T (H + mu)^-1 g with g the
 # gradient of the cost at u.  The specs and inputs of that check, shared by the CPU measurement and the GPU test.
-SLOPE_SPECS = ["phnn<n=2,hid=64,Gnet>", "odefunc<n=3,hid=128,f16x2>", "phnn<n=4,hid=128,fixedG,f16x2>",
-               "phnn<n=4,m=2,hid=128,fixedG,f16x2>", "phnn<n=4,m=4,hid=128,fixedG,f16x2>"]
+SLOPE_SPECS = list(vc.NM_SPEC.values())  # one per (n, m) a handle can have
 SLOPE_SHAPE = (17, 7)
 # worst |sum(g du) + dV| / dV of the float32 oracle on these inputs (test_gn_model prints it; the float64 oracle reaches
 # 9.1e-8, because A, Bm and traj are rounded to float32 as the device returns them)
@@ -282,7 +282,6 @@ SLOPE_F32_ORACLE = 6.5e-7
 
 def slope_case(sid):
     """x0 (B,n), in-bounds u (B,H,m), cost, dt of the slope check of one spec."""
-    import variant_census as vc
     s = vc.CENSUS[sid]
     rng = np.random.default_rng(vc.seed_of(sid, s) + 77)
     B, H = SLOPE_SHAPE

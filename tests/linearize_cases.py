@@ -19,6 +19,18 @@ SPECS = [
 POINT_BATCHES = [1, 5, 16, 17, 37]
 SHAPES = [(1, 1), (5, 3), (37, 6)]
 
+# the linearisation census (every spec of variant_census.ALL_SPECS, tests/test_gpu_linearize_census.py): point Jacobians on
+# the census inputs (variant_census.inputs, POINT_B = 37 points: two full tiles and a ragged one of 5) at the census
+# weights and with every MLP weight matrix x3; step Jacobians on case() at a single lane and at 35 points whose H
+# divides neither 16 nor the tile, so that tiles straddle rollouts
+CENSUS_SCALES = (1.0, 3.0)
+CENSUS_SHAPES = [(1, 1), (5, 7)]
+
+
+def point_tol(s):
+    """The census tolerance of the point VJP (test_gpu_variant_census._check_points), which a Jacobian row is."""
+    return vc.POINT_TOL * s["tol"] if s["act"] != "relu" else vc.grad_tol(s)
+
 
 def case(sid, s, B, H, bounded):
     """x0 (B,n), u (B,H,m), the census cost with or without the control bounds, dt.  Bounded: about a fifth of the

@@ -11,6 +11,7 @@ import torch
 
 import feedback_model as fm
 import oracle_lib as ol
+import variant_census as vc
 from phnn_mpc_amd import _capi
 from phnn_mpc_amd.closed_loop import BatchedCartPole, PlantScenario, run_mpc_batch
 from phnn_mpc_amd.estimation import EKF
@@ -29,7 +30,7 @@ CFG = os.path.join(ROOT, "configs", "cartpole_mpc.yaml")
 MARGIN = 64.0
 MEASURED_U, CEILING_U = 1.2e-7, 1e-5      # |control - K_j x_j| / max |u*|, worst over the grid (the test prints 1.10e-07)
 MEASURED_V, CEILING_V = 3.8e-15, 1e-8     # |feedback cost - 1/2 x^T P_j x| / that, worst over the grid (prints 3.79e-15)
-GRID = [(n, m, H) for (n, m) in ((2, 1), (4, 1), (4, 3)) for H in (1, 6, 50)]
+GRID = [(n, m, H) for (n, m) in vc.NM_PAIRS for H in (1, 6, 50)]
 SEEDS = (7, 11)
 NB = 9
 

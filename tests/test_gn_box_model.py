@@ -187,16 +187,22 @@ NO_SET = dict(Q=[["0x1.3b36d810b92c5p+0", "-0x1.66456e8bd3ff4p-1"], ["-0x1.66456
               hi=["0x1.f5e9e400a51e0p-1", "0x1.b94b85ef33860p-2"])
 
 
+# the control bound of test_failure_semantics.  At (3, 1) the step of the seeded case stays inside +-0.5 in every
+# component (a property of that input, not of the model), so the clean step would hold nothing: its box is +-0.25
+FAILURE_BOUND = {(3, 1): 0.25}
+
+
 @pytest.mark.parametrize("n,m", SHAPES)
 def test_failure_semantics(n, m):
     H = 6
+    c = FAILURE_BOUND.get((n, m), 0.5)
     A, Bm, Q, R, traj, u = _case(n, m, H, nb=3)
-    cost = _capi.make_cost(n, m, Q, R, None, -0.5, 0.5)
-    u = np.clip(u, -0.5, 0.5).astype(np.float32)
+    cost = _capi.make_cost(n, m, Q, R, None, -c, c)
+    u = np.clip(u, -c, c).astype(np.float32)
     clean = gb.direction_box(A, Bm, traj, u, cost, n, m, 0.0)
     assert not clean["status"].any() and np.isfinite(clean["dV"]).all() and clean["nclamp"].sum() > 0
     # an infeasible nominal and a NaN control fail at their step, like a pivot
-    for value, t in ((0.75, 4), (-0.75, 0), (np.nan, 2)):
+    for value, t in ((1.5 * c, 4), (-1.5 * c, 0), (np.nan, 2)):
         u1 = u.copy()
         u1[1, t, m - 1] = value
         check_failed(gb.direction_box(A, Bm, traj, u1, cost, n, m, 0.0), clean, 1, t + 1)
@@ -206,7 +212,7 @@ def test_failure_semantics(n, m):
     r = gb.direction_box(A, B1, traj, u, cost, n, m, 0.0)
     assert r["status"][1] == gm.direction(A, B1, traj, u, cost, n, m, 0.0)["status"][1] == 3
     check_failed(r, clean, 1, 3)
-    bad = _capi.make_cost(n, m, Q, -R - np.eye(m, dtype=np.float32), None, -0.5, 0.5)
+    bad = _capi.make_cost(n, m, Q, -R - np.eye(m, dtype=np.float32), None, -c, c)
     r = gb.direction_box(A, Bm, traj, u, bad, n, m, 0.0)
     assert (r["status"] == H).all() and np.all(r["du"] == 0) and np.isnan(r["dV"]).all() and not r["nclamp"].any()
     # a NaN that reaches no pivot and no bound: status 0, and still no step

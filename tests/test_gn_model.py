@@ -20,6 +20,7 @@ import torch
 import gn_model as gm
 import oracle_lib as ol
 import tvlqr_model as tm
+import variant_census as vc
 from phnn_mpc_amd import _capi, solver
 from phnn_mpc_amd.models import pHNN, pHNN_Canonical
 from phnn_mpc_amd.mpc_controller import MPCController
@@ -30,7 +31,7 @@ CFG = os.path.join(ROOT, "configs", "cartpole_mpc.yaml")
 
 MARGIN, CEILING = 64.0, 1e-8
 MEASURED_U, MEASURED_SLOPE, MEASURED_PRED = 3.1e-15, 6.4e-16, 1.2e-15
-SHAPES = [(2, 1), (4, 1), (4, 3)]
+SHAPES = vc.NM_PAIRS  # every (n, m) a handle can have
 HORIZONS = [1, 6, 50]
 NB = 5
 

@@ -98,6 +98,44 @@ def test_seeded_batch_vs_oracle_and_repeatable(bundle, torch):
     assert frac_bad <= (2e-3 if act == "relu" else 0.0)  # ReLU: a mask flip in a few rollouts at most
 
 
+def same_nans(a, b):
+    return np.array_equal(np.isnan(npy(a)), np.isnan(np.asarray(b)))
+
+
+def test_a_nan_state_or_control_shows_where_the_oracle_shows_it(bundle):
+    """A diverged point or rollout is NaN on the device exactly where it is NaN in the float64 oracle, for every
+    activation -- ReLU included, whose max(z, 0) and z > 0 would turn a NaN pre-activation into a finite 0 (nn.ReLU
+    keeps it): the point operations and Jacobians at a NaN state, rollouts with a NaN control at step 2 of one rollout."""
+    from test_oracle_activations import poisoned_points
+    name, act, g, m64, eng = bundle
+    b = 3
+    x, u, lam, xv, uv = poisoned_points(g, b=b)
+    dx, H = eng.forward(x, u)
+    rdx, rH = m64.forward(x, u)
+    assert np.isnan(npy(dx)[b]).all() and same_nans(dx, rdx) and same_nans(H, rH)
+    xb, ub = eng.vjp(xv, uv, lam)
+    rxb, rub = m64.vjp(xv, uv, lam)
+    assert np.isnan(npy(xb)[b]).all() and same_nans(xb, rxb) and same_nans(ub, rub)
+    A, Bm = eng.jacobian(xv, uv)
+    assert np.isnan(npy(A)[b]).any() and np.isfinite(np.delete(npy(A), b, axis=0)).all()
+    cost = ol.cost_from_golden(g)
+    cost.has_u_bounds = 0
+    key = "roll_euler_B8_H50"
+    x0, U = g[key + "_x0"], g[key + "_U"].copy()
+    U[b, 2, 0] = np.nan
+    for integ in ("euler", "rk4"):
+        ref = m64.rollout(x0, U, cost, integ, float(g["dt"]))
+        c, gu, gx = eng.rollout_cost_grad(x0, U, cost, integ, float(g["dt"]), want_grad_x0=True)
+        _, tr = eng.rollout_cost(x0, U, cost, integ, float(g["dt"]), want_traj=True)
+        assert np.isnan(npy(c)[b]) and np.isnan(npy(tr)[b, 4:]).all() and np.isfinite(npy(tr)[b, :3]).all()
+        assert same_nans(c, ref["cost"]) and same_nans(tr, ref["traj"]) and same_nans(gu, ref["grad_u"]) and same_nans(gx, ref["grad_x0"])
+        A, Bm, _ = eng.rollout_linearize(x0, U, cost, integ, float(g["dt"]), traj=tr)
+        A = npy(A)
+        assert np.isnan(A[b, 3:]).any(axis=(1, 2)).all() and np.isfinite(np.delete(A, b, axis=0)).all()  # every step from a NaN state
+        if integ == "rk4":
+            assert np.isnan(A[b, 2]).any()  # and the step of the NaN control, whose stage states are NaN
+
+
 def test_drop_in_modules_select_the_activation_from_the_yaml(torch, tmp_path):
     """models.pHNN built from a YAML whose H_mlp / R_mlp say nn.SiLU runs the SiLU kernels; mixed activations and
     activations without kernels are refused with a clear error (the reference would accept any nn.Module)."""

@@ -1,11 +1,13 @@
 """Device-side weight packing (phnn_update_weights_dev, SURVEY 8 row f4 / VERDICT round 2 item 6): the image packed by
 the one-workgroup kernel from a GPU-resident blob equals the host-packed image -- bit for bit for pHNN and ODEFunc
 models; for canonical models everywhere except the eleven constants that go through exp / log1p (softplus(R_diag_raw),
-sigmoid, the mass-matrix constants), which may differ in the last bit between the two math libraries."""
+sigmoid, the mass-matrix constants), which may differ in the last bit between the two math libraries.  The golden
+models first, then every spec of the variant census: the packing kernel is instantiated once per variant."""
 import numpy as np
 import pytest
 
 import oracle_lib as ol
+import variant_census as vc
 
 pytestmark = pytest.mark.gpu
 
@@ -117,3 +119,33 @@ def test_device_packed_image_equals_host_packed_multi_input_and_mass_models(torc
             assert np.allclose(host[diff], dev[diff], rtol=2.5e-7, atol=0.0)
         else:
             assert diff.size == 0, (name, scale, diff[:8])
+
+
+@pytest.mark.parametrize("sid", list(vc.ALL_SPECS))
+def test_device_packed_image_equals_host_packed_for_every_census_spec(torch, sid):
+    """k_pack_image<M> is one instantiation per variant: every census spec (tests/variant_census.py), the zero-padded
+    models through the d_padsrc map, at the census weights and with every MLP weight matrix x3 (other power-of-two
+    scales), each packed over the image of the other scale."""
+    from phnn_mpc_amd import weights
+    from phnn_mpc_amd.engine import RolloutEngine
+    variant, s = vc.ALL_SPECS[sid]
+    sds = {scale: vc.build_state_dict(sid, s, hidden_scale=scale) for scale in (1.0, 3.0)}
+    eng = RolloutEngine(sds[1.0], "cuda:0", **vc.engine_kwargs(s))
+    assert eng.variant == variant, (sid, eng.variant)
+    ndiff = []
+    for scale, other in ((1.0, 3.0), (3.0, 1.0)):
+        _, blob = weights.pack_state_dict(sds[scale], kind=eng.kind, activation=s["act"])
+        eng.update_weights(sds[scale])
+        host = eng.read_image()
+        eng.update_weights(sds[other])  # the image of the other scale, for the device pack to overwrite
+        assert not np.array_equal(eng.read_image().view(np.uint32), host.view(np.uint32))
+        eng.update_weights_dev(torch.tensor(blob, device=eng.device))
+        dev = eng.read_image()
+        diff = np.flatnonzero(host.view(np.uint32) != dev.view(np.uint32))
+        ndiff.append(diff.size)
+        if eng.kind == 1:  # canonical: the libm-dependent constants, as above
+            assert diff.size <= 14, (sid, scale, diff.size)
+            assert np.allclose(host[diff], dev[diff], rtol=2.5e-7, atol=0.0)
+        else:
+            assert diff.size == 0, (sid, scale, diff[:8], host[diff[:8]], dev[diff[:8]])
+    print(f"\n{sid}: device-packed image of {host.size} floats, {ndiff[0]} (x1) and {ndiff[1]} (x3) entries differ from the host-packed")

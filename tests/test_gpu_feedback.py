@@ -1,6 +1,6 @@
 """Tracking the plan between solves on the device.
 
-  1 k_feedback_control   bits == feedback_model.control for (n, m) in {(2,1), (3,1), (4,1), (4,2), (4,4)}, B in {1, 17, 65}
+  1 k_feedback_control   bits == feedback_model.control for every reachable (n, m) (variant_census.NM_PAIRS), B in {1, 17, 65}
                          (one thread, a partial workgroup, a workgroup plus one), H in {1, 2, 7}, the first and the last row
                          of the plan, the step from the host and from a device counter, with and without bounds, the
                          status 1 and 2 cases and a NaN control mixed into the batch, optional outputs NULL and given, log
@@ -21,8 +21,8 @@ import yaml
 
 import feedback_model as fm
 import footprint as fp
-import linearize_cases as lc
 import oracle_lib as ol
+import variant_census as vc
 from test_gpu_footprint import Report, footprint, rng_of
 from test_gpu_footprint import engine as census_engine
 from test_gpu_mppi import engine
@@ -31,9 +31,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = os.path.join(ROOT, "configs", "cartpole_mpc.yaml")
 
-# (n, m) -> a census spec with those dimensions (k_feedback_control reads n and m from the handle, nothing else)
-MODEL_OF = {(2, 1): "phnn<n=2,hid=64,Gnet>", (3, 1): "odefunc<n=3,hid=128,f16x2>", (4, 1): lc.HEADLINE,
-            (4, 2): "phnn<n=4,m=2,hid=128,fixedG,f16x2>", (4, 4): "phnn<n=4,m=4,hid=128,fixedG,f16x2>"}
+# (n, m) -> a census spec with those dimensions (k_feedback_control reads n and m from the handle, nothing else): every
+# pair a handle can have
+MODEL_OF = vc.NM_SPEC
 BOUNDS = (-0.25, 0.4)
 
 

@@ -1,7 +1,7 @@
 """The batched Gauss-Newton solve on the GPU (phnn_solve_gn and its three kernels):
 
   1 direction    k_gn_direction == gn_model.direction bit for bit on the device's own float32 A, Bm, traj and u: B in
-                 {1, 17, 65} x H in {1, 2, 7}, Euler and RK4, one spec per (n, m) in {(2,1), (3,1), (4,1), (4,2), (4,4)},
+                 {1, 17, 65} x H in {1, 2, 7}, Euler and RK4, one spec per reachable (n, m) (variant_census.NM_SPEC),
                  per-problem mu, an active barrier, no / a shared / a per-problem reference with a device offset, and the
                  failure cases (NaN in A_t, B_t, a trajectory row, a control; a negative definite R)
   2 tvlqr        zero gradients and a uniform mu: du = 0, dV = 0 and the status of phnn_tvlqr on the same A, Bm
@@ -38,7 +38,7 @@ from test_gpu_footprint import Report, engine, footprint, rng_of
 
 pytestmark = pytest.mark.gpu
 
-SPECS = gm.SLOPE_SPECS  # one per (n, m)
+SPECS = gm.SLOPE_SPECS  # one per (n, m) a handle can have: (2,1) (3,1) (4,1) (4,2) (4,3) (4,4)
 HEADLINE = "phnn<n=4,hid=128,fixedG,f16x2>"
 BATCHES, HORIZONS = (1, 17, 65), (1, 2, 7)
 INVALID, UNSUPPORTED = -1, -2
@@ -98,7 +98,7 @@ def test_direction_equals_the_stated_order_model(torch, sid, integ):
     assert active > 0 and accepted > 0
 
 
-@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[4]])
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[5]])
 def test_direction_failure_cases(torch, sid):
     s, eng = vc.CENSUS[sid], engine(sid)
     n, m = s["n"], s["m"]
@@ -132,7 +132,7 @@ def test_direction_failure_cases(torch, sid):
 
 
 # ----------------------------------------------------------------------------- 2. against phnn_tvlqr
-@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[4]])
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[5]])
 def test_zero_gradients_give_no_step_and_the_status_of_tvlqr(torch, sid):
     from phnn_mpc_amd import _capi
     s, eng = vc.CENSUS[sid], engine(sid)
@@ -321,7 +321,7 @@ class GnSolveOp(fp.Op):
                 "alpha": r["alpha_hist"]}
 
 
-@pytest.mark.parametrize("sid", [SPECS[0], SPECS[1], SPECS[2], SPECS[4]])
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[1], SPECS[2], SPECS[5]])
 def test_footprint(torch, sid):
     """Nothing outside the outputs and the workspace is written, the inputs are unchanged, the outputs do not depend on
     what the workspace and the outputs held (0xFF fill == 0x00 fill) nor on what lies around the inputs, at a row-slice

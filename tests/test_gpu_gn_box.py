@@ -2,7 +2,7 @@
 
   1 direction    k_gn_direction_box == gn_box_model.direction_box bit for bit (du, dV, status, nclamp) on the device's own
                  float32 A, Bm, traj and u: B in {1, 17, 65} x H in {1, 2, 7}, Euler and RK4, one spec per (n, m) in
-                 {(2,1), (3,1), (4,1), (4,2), (4,4)}.  The inputs reach every branch, asserted on the model: nominals on the
+                 {(2,1), (3,1), (4,1), (4,2), (4,3), (4,4)}.  The inputs reach every branch, asserted on the model: nominals on the
                  upper and on the lower bound pushed outwards, interior nominals whose step ends on a bound, all-free
                  steps, steps only the forward sweep clips (asserted on the headline spec), per-problem mu, an active
                  barrier, no / a shared / a per-problem reference with a device offset; >= 25 % of the problem-steps hold
@@ -119,7 +119,7 @@ def test_box_direction_equals_the_stated_order_model(torch, sid, integ):
     assert seen["forward_only"] > 0 or sid != HEADLINE
 
 
-@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[4]])
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[5]])
 def test_box_direction_failure_cases(torch, sid):
     from phnn_mpc_amd import _capi
     s, eng = vc.CENSUS[sid], engine(sid)
@@ -411,7 +411,7 @@ class GnBoxDirectionOp(fp.Op):
                                 torch.as_tensor(np.asarray(self.input("mu"))), box=True)
 
 
-@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[4]])
+@pytest.mark.parametrize("sid", [SPECS[0], SPECS[2], SPECS[5]])
 def test_footprint(torch, sid):
     """Both entry points: nothing outside the outputs and the workspace is written, the inputs are unchanged, the outputs
     do not depend on what the buffers held nor on what lies around the inputs, at a row-slice skew and with ragged B."""

@@ -9,23 +9,19 @@
   3 isolation        a NaN / inf / 1e30 state or a NaN control at one (b, t) changes no other rollout-step's bits
   4 tile loop        B*H around one grid stride against the same points run in two halves
 
-"As floats": -0 == +0, NaN at the same positions.
-
-The composed reference at a NaN control.  A one-step rollout from a NaN control ends in a NaN state, and the reverse pass
-multiplies the stage-cost gradient there by cost_bar = 0: 0 * NaN = NaN enters the costate, so at that rollout-step the
-composed form returns NaN in every entry the clamp mask does not zero -- whatever the Jacobian is.  The kernel has no
-such term (its cotangent is e_i itself), so an entry that does not depend on that control (the A rows of an Euler step
-with a constant G) stays finite.  At that one rollout-step the comparison is therefore: equal as floats, or the reference
-is NaN and the kernel's entry equals, bit for bit, what it returns with the NaN control replaced by 0."""
+"As floats": -0 == +0, NaN at the same positions.  The bodies of 1 and 2 live in tests/linearize_checks.py, which states the rule
+of the composed reference at a NaN control; tests/test_gpu_linearize_census.py runs them on every census spec."""
 import numpy as np
 import pytest
 
 import heterogeneous as het
 import linearize_cases as lc
+import linearize_checks as lk
 import linearize_model as lm
 import oracle_lib as ol
 import variant_census as vc
 import wgrad_checks as wc
+from linearize_checks import npf
 from test_gpu_footprint import engine
 from tvlqr_model import same_floats
 
@@ -40,40 +36,16 @@ def torch():
     return t
 
 
-def npf(t):
-    return t.detach().cpu().numpy()
-
-
-def first_diff(a, b):
-    bad = ~((a == b) | (np.isnan(a) & np.isnan(b)))
-    k = np.argwhere(bad)
-    return f"{int(bad.sum())} entries differ, first at {tuple(k[0])}: {a[tuple(k[0])]!r} vs {b[tuple(k[0])]!r}" if len(k) else "equal"
-
-
-def unit(npts, n, i):
-    e = np.zeros((npts, n), np.float32)
-    e[:, i] = 1.0
-    return e
-
-
 # ----------------------------------------------------------------------------- 1. point Jacobian
 @pytest.mark.parametrize("sid", lc.SPECS)
 def test_point_jacobian(torch, sid):
     s, eng = vc.CENSUS[sid], engine(sid)
     d = vc.inputs(sid, s)
-    n, m = s["n"], s["m"]
     for B in lc.POINT_BATCHES:
-        x, u = d["x"][:B], d["u"][:B]
-        A, Bm = eng.jacobian(x, u)
-        assert A.shape == (B, n, n) and Bm.shape == (B, n, m)
-        A, Bm = npf(A), npf(Bm)
-        for i in range(n):
-            xb, ub = eng.vjp(x, u, unit(B, n, i))
-            assert same_floats(A[:, i], npf(xb)), (sid, B, i, first_diff(A[:, i], npf(xb)))
-            assert same_floats(Bm[:, i], npf(ub)), (sid, B, i, first_diff(Bm[:, i], npf(ub)))
+        A, Bm, bad = lk.point_rows(eng, d["x"][:B], d["u"][:B], sid)
+        assert not bad, bad
     m64 = ol.OracleModel(vc.build_state_dict(sid, s), "f64", activation=s["act"])
-    rA, rB = lm.oracle_jacobian(m64, d["x"], d["u"])
-    eA, eB, tol = vc.err_max(A, rA), vc.err_max(Bm, rB), vc.POINT_TOL * s["tol"]
+    (eA, eB), tol = lk.point_errors(m64, d["x"], d["u"], A, Bm), vc.POINT_TOL * s["tol"]
     print(f"\n{sid}: point Jacobian A {eA / tol:.3f}, Bm {eB / tol:.3f} of the tolerance {tol:.1e}")
     assert eA <= tol and eB <= tol
 
@@ -97,78 +69,24 @@ def test_point_jacobian_of_a_model_class(torch):
 
 
 # ----------------------------------------------------------------------------- 2. step Jacobians
-def composed(eng, traj, u, cost, integ, dt, points=None):
-    """The only way to these numbers without the kernel: n general reverse passes over the B*H one-step rollouts (or
-    over the listed points, each run alone)."""
-    B, H, m = u.shape
-    n = traj.shape[2]
-    x0 = np.ascontiguousarray(traj[:, :H].reshape(B * H, n))
-    ur = np.ascontiguousarray(u.reshape(B * H, 1, m))
-    if points is not None:
-        out = [composed(eng, x0[p].reshape(1, 1, n).repeat(2, axis=1), ur[p].reshape(1, 1, m), cost, integ, dt) for p in points]
-        return np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out])
-    _, tr = eng.rollout_cost(x0, ur, cost, integ, dt, want_traj=True)
-    zero = np.zeros(B * H, np.float32)
-    A, Bm = np.empty((B * H, n, n), np.float32), np.empty((B * H, n, m), np.float32)
-    for i in range(n):
-        tb = np.zeros((B * H, 2, n), np.float32)
-        tb[:, 1, i] = 1.0
-        gu, gx = eng.rollout_vjp(x0, ur, tr, cost, integ, dt, traj_bar=tb, cost_bar=zero)
-        A[:, i], Bm[:, i] = npf(gx), npf(gu)[:, 0]
-    return A, Bm
-
-
-def check_against_composed(what, got, ref, got_clean_u, nan_points):
-    ok = (got == ref) | (np.isnan(got) & np.isnan(ref))
-    if nan_points.any():  # module docstring: the composed reference at a NaN control
-        plain = int(ok[nan_points].sum())
-        ok[nan_points] |= np.isnan(ref[nan_points]) & (got[nan_points].view(np.uint32) == got_clean_u[nan_points].view(np.uint32))
-        if int(ok[nan_points].sum()) != plain:
-            print(f"\n{what}: {int(ok[nan_points].sum()) - plain} of {ok[nan_points].size} entries at the NaN control are finite "
-                  f"where the composed form is NaN")
-    assert ok.all(), (what, f"{int((~ok).sum())} entries differ, first at {tuple(np.argwhere(~ok)[0])}")
-
-
 @pytest.mark.parametrize("integ", INTEGS)
 @pytest.mark.parametrize("sid", lc.SPECS)
 def test_rollout_linearize(torch, sid, integ):
     s, eng = vc.CENSUS[sid], engine(sid)
-    n, m = s["n"], s["m"]
     m64 = ol.OracleModel(vc.build_state_dict(sid, s), "f64", activation=s["act"])
     worst = 0.0
     for B, H in lc.SHAPES:
         for bounded in (False, True):
             c = lc.case(sid, s, B, H, bounded)
-            x0, u, cost, dt = c["x0"], c["u"], c["cost"], c["dt"]
             what = f"{sid} {integ} B{B} H{H} bounded={bounded}"
-            A, Bm, traj = eng.rollout_linearize(x0, u, cost, integ, dt)
-            assert A.shape == (B, H, n, n) and Bm.shape == (B, H, n, m) and traj.shape == (B, H + 1, n)
-            A2, B2, _ = eng.rollout_linearize(x0, u, cost, integ, dt, traj=traj)  # the trajectory given == K1 run here
-            assert torch.equal(A.view(torch.int32), A2.view(torch.int32)) and torch.equal(Bm.view(torch.int32), B2.view(torch.int32))
-            A, Bm, traj = npf(A).reshape(B * H, n, n), npf(Bm).reshape(B * H, n, m), npf(traj)
-            assert np.isfinite(traj[:, :H]).all(), what
-            # bitwise against the composed form
-            rA, rB = composed(eng, traj, u, cost, integ, dt)
-            nan_pts = ~lc.finite_points(u)
-            assert int(nan_pts.sum()) == (1 if bounded and B * H > 1 else 0)
-            Ac, Bc, _ = eng.rollout_linearize(x0, np.nan_to_num(u), cost, integ, dt, traj=traj)
-            check_against_composed(what + " A", A, rA, npf(Ac).reshape(A.shape), nan_pts)
-            check_against_composed(what + " Bm", Bm, rB, npf(Bc).reshape(Bm.shape), nan_pts)
-            # the mask: a control outside the bounds, the NaN among them, gives an exactly zero column
-            if bounded:
-                cols = np.broadcast_to(lc.outside(u).reshape(B * H, 1, m), Bm.shape)
-                assert np.all(Bm[cols] == 0.0), what
+            r = lk.step_jacobians(torch, eng, m64, s, c, integ, bounded, what)
+            assert not r["bad"], r["bad"]
             # a reference rollout run alone gives the bits it gives in the batch
             pts = sorted({0, (B * H) // 2, B * H - 1})
-            sA, sB = composed(eng, traj, u, cost, integ, dt, points=pts)
-            assert same_floats(sA, rA[pts]) and same_floats(sB, rB[pts]), what
-            # parity against the float64 oracle on the same stored trajectory, per rollout-step
-            keep = ~nan_pts
-            oA, oB = lm.oracle_linearize(m64, traj, u, cost, integ, dt)
-            e = max(vc.err_rows(A.reshape(B * H, -1)[keep], lm.rows_of(oA)[keep]),
-                    vc.err_rows(Bm.reshape(B * H, -1)[keep], lm.rows_of(oB)[keep]))
-            worst = max(worst, e / vc.grad_tol(s))
-            assert e <= vc.grad_tol(s), (what, e, vc.grad_tol(s))
+            sA, sB = lk.composed(eng, r["traj"], c["u"], c["cost"], integ, c["dt"], points=pts)
+            assert same_floats(sA, r["rA"][pts]) and same_floats(sB, r["rB"][pts]), what
+            worst = max(worst, r["err"] / vc.grad_tol(s))
+            assert r["err"] <= vc.grad_tol(s), (what, r["err"], vc.grad_tol(s))
     print(f"\n{sid} {integ}: worst step-Jacobian error {worst:.3f} of the tolerance {vc.grad_tol(s):.1e}")
 
 

@@ -1,14 +1,14 @@
 """The terminal cost on the GPU (phnn_terminal_cost, phnn_dare, phnn_gn_direction_term, phnn_solve_term,
 phnn_solve_gn_term):
 
-  1 cost        k_terminal_cost == terminal_model.terminal_cost bit for bit: n in {2, 4}, B in {1, 37, 257} (one thread, a
+  1 cost        k_terminal_cost == terminal_model.terminal_cost bit for bit: n in {2, 3, 4}, B in {1, 37, 257} (one thread, a
                 ragged block, more than one block), H in {1, 6}, a shared and a per-problem W, group in {1, 3}, the cost's
                 x_target and a reference whose row clamps at rows - 1 through a device offset, a NaN state, and the rows
                 t < H of a 0xFF-filled traj_bar untouched
   2 dare        k_dare == terminal_model.dare bit for bit (P, K, W, iters, status): the trained cart-pole model linearised
                 at the target, Euler (127 steps) and RK4 (73), the pendulum model (n = 2; 119 steps, Euler and RK4), each
                 with its fixture's own cost and dt; the seed-0 model stopped at max_iters = 64 (status 2, the last iterate);
-                seeded systems for (n, m) in {(2,1), (4,1), (4,3)}, B in {1, 5}; a singular Quu (R = 0, B = 0: status 1,
+                seeded systems for every reachable (n, m), B in {1, 5}; a singular Quu (R = 0, B = 0: status 1,
                 NaN outputs)
   3 direction   k_gn_direction / k_gn_direction_box with a terminal weight == terminal_model.direction bit for bit; with
                 NULL == phnn_gn_direction / phnn_gn_direction_box bit for bit
@@ -39,8 +39,7 @@ from test_gpu_gn import CFG, GN, HEADLINE, INVALID, OUT_KEYS, SPECS, GnSolveOp, 
 
 pytestmark = pytest.mark.gpu
 
-N2 = SPECS[0]  # phnn<n=2,...>
-M3 = "phnn<n=4,m=3,hid=128,fixedG,f16x2>"
+N2, N3 = SPECS[0], SPECS[1]  # phnn<n=2,...>, odefunc<n=3,...>
 CANON = "canonical<hid=128,f16x2>"
 B_, H_ = 37, 6
 
@@ -63,7 +62,7 @@ def weights(rng, P, n):
 
 
 # ----------------------------------------------------------------------------- 1. k_terminal_cost
-@pytest.mark.parametrize("sid", [N2, HEADLINE])
+@pytest.mark.parametrize("sid", [N2, N3, HEADLINE])
 def test_terminal_cost_equals_the_stated_order_model(torch, sid):
     from phnn_mpc_amd.terminal import TerminalCost
     s, eng = vc.CENSUS[sid], engine(sid)
@@ -131,7 +130,7 @@ def test_dare_equals_the_stated_order_model_on_the_golden_models(torch):
         check_dare((name, integ), eng.dare(A, Bm, cost, max_iters=max_iters, tol=1e-12), want)
 
 
-@pytest.mark.parametrize("sid,n,m", [(N2, 2, 1), (HEADLINE, 4, 1), (M3, 4, 3)])
+@pytest.mark.parametrize("sid,n,m", [(sid, n, m) for (n, m), sid in vc.NM_SPEC.items()])
 def test_dare_equals_the_stated_order_model_on_seeded_systems(torch, sid, n, m):
     from phnn_mpc_amd import _capi
     eng = engine(sid)
@@ -161,7 +160,7 @@ def test_dare_equals_the_stated_order_model_on_seeded_systems(torch, sid, n, m):
 
 
 # ----------------------------------------------------------------------------- 3. the direction
-@pytest.mark.parametrize("sid", [N2, HEADLINE, M3])
+@pytest.mark.parametrize("sid", SPECS)
 def test_direction_with_a_terminal_weight_equals_the_stated_order_model(torch, sid):
     s, eng = vc.CENSUS[sid], engine(sid)
     n, m = s["n"], s["m"]

@@ -1,7 +1,7 @@
 """phnn_tvlqr on the GPU, and the properties the three linearisation entry points share:
 
   1 bitwise      k_tvlqr == tests/tvlqr_model.py bit for bit (NaN at the same positions, the same status) on the CPU
-                 tests' seeded inputs, B in {1, 65, 300} x H in {1, 6, 50} x (n, m) in {(2,1), (4,1), (4,3)}, on (A, Bm)
+                 tests' seeded inputs, B in {1, 65, 300} x H in {1, 6, 50} x every reachable (n, m) (variant_census.NM_PAIRS), on (A, Bm)
                  downloaded from phnn_rollout_linearize of the headline spec, and on the failure cases; P_all = NULL gives
                  the same K and P0
   2 arguments    one bad argument at a time through the three entry points: PHNN_ERR_INVALID_ARG, outputs untouched,
@@ -25,8 +25,9 @@ from test_tvlqr_model import FAILURES, failure_case
 
 pytestmark = pytest.mark.gpu
 
-# (n, m) -> a census spec with those dimensions (phnn_tvlqr reads n and m from the handle, nothing else)
-MODEL_OF = {(2, 1): "phnn<n=2,hid=64,Gnet>", (4, 1): lc.HEADLINE, (4, 3): "phnn<n=4,m=3,hid=128,Gnet,f16x2>"}
+# (n, m) -> a census spec with those dimensions (phnn_tvlqr reads n and m from the handle, nothing else): every pair a
+# handle can have
+MODEL_OF = vc.NM_SPEC
 INVALID = -1
 
 

@@ -51,13 +51,13 @@ class Report:
             d = float((a.double() - b.double()).abs().max()) if a.shape == b.shape else float("nan")
             self.bad.append(f"{what}: not bitwise equal (max diff {d:.3g})")
 
-    def finish(self):
+    def finish(self, digits=2):
         worst = {}
         for what, err, bound in self.rows:
             k = what.split(" ")[0]
             if bound > 0:
                 worst[k] = max(worst.get(k, 0.0), err / bound)
-        print(f"\n{self.sid}: " + ", ".join(f"{k} {v:.2f}" for k, v in worst.items()) + " (worst error / bound)")
+        print(f"\n{self.sid}: " + ", ".join(f"{k} {v:.{digits}f}" for k, v in worst.items()) + " (worst error / bound)")
         assert not self.bad, (self.sid, self.bad)
 
 

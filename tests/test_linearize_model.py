@@ -97,3 +97,44 @@ def test_float32_oracle_is_inside_the_gpu_tolerances(sid):
                 worst["rollout"] = max(worst.get("rollout", 0.0), e / vc.grad_tol(s))
     print(f"\n{sid}: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()) + " (float32 oracle error / tolerance)")
     assert worst["point"] <= 1.0 and worst["rollout"] <= 1.0
+
+
+MARGIN = 0.2  # test_variant_census.MARGIN: the float32 oracle's error as a fraction of the stated tolerance
+
+
+def census_margins(sid, s):
+    """{check: float32-oracle error / tolerance} on exactly the inputs of tests/test_gpu_linearize_census.py."""
+    d = vc.inputs(sid, s)
+    out = {}
+    for scale in lc.CENSUS_SCALES:
+        sd = vc.build_state_dict(sid, s, hidden_scale=scale)
+        m32, m64 = (ol.OracleModel(sd, p, activation=s["act"]) for p in ("f32", "f64"))
+        A, Bm = lm.oracle_jacobian(m32, d["x"], d["u"])
+        rA, rB = lm.oracle_jacobian(m64, d["x"], d["u"])
+        out[f"point x{scale:g}"] = max(vc.err_max(A, rA), vc.err_max(Bm, rB)) / lc.point_tol(s)
+        if scale != 1.0:
+            continue
+        for B, H in lc.CENSUS_SHAPES:
+            for integ in ("euler", "rk4"):
+                for bounded in (False, True):
+                    case = lc.case(sid, s, B, H, bounded)
+                    traj = m64.rollout(case["x0"], case["u"], case["cost"], integ, case["dt"], grad=False)["traj"]
+                    traj = traj.astype(np.float32)
+                    assert np.isfinite(traj[:, :H]).all(), (sid, B, H, integ, bounded)  # every row the linearisation reads
+                    keep = lc.finite_points(case["u"])
+                    assert int((~keep).sum()) == (1 if bounded and B * H > 1 else 0)
+                    A, Bm = lm.oracle_linearize(m32, traj, case["u"], case["cost"], integ, case["dt"])
+                    rA, rB = lm.oracle_linearize(m64, traj, case["u"], case["cost"], integ, case["dt"])
+                    e = max(vc.err_rows(lm.rows_of(A)[keep], lm.rows_of(rA)[keep]),
+                            vc.err_rows(lm.rows_of(Bm)[keep], lm.rows_of(rB)[keep]))
+                    out["rollout"] = max(out.get("rollout", 0.0), e / vc.grad_tol(s))
+    return out
+
+
+@pytest.mark.parametrize("sid", list(vc.ALL_SPECS))
+def test_float32_oracle_leaves_room_under_the_census_tolerances(sid):
+    """The same yardstick for the linearisation census, every spec: a fifth of each tolerance, so that a correct float32
+    kernel has room."""
+    out = census_margins(sid, vc.ALL_SPECS[sid][1])
+    print(f"\n{sid}: " + ", ".join(f"{k} {v:.3f}" for k, v in out.items()) + " (float32 oracle error / tolerance)")
+    assert all(v <= MARGIN for v in out.values()), (sid, out)

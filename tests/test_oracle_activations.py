@@ -58,3 +58,28 @@ def test_reverse_pass_with_cotangents(bundle, integ):
     gu, gx = m64.rollout_vjp(g["tvjp_x0"], g["tvjp_U"], ol.cost_from_golden(g), integ, float(g["dt"]),
                              traj_bar=g["tvjp_traj_bar"], cost_bar=g["tvjp_cost_bar"])
     assert rel(gu, g[f"tvjp_{integ}_gu_f64"]) < 1e-9 and rel(gx, g[f"tvjp_{integ}_gx0_f64"]) < 1e-9
+
+
+def poisoned_points(g, k=8, b=3):
+    """k points of the golden point sets with one NaN state component in point b -> (x, u, lam, x of the VJP set)."""
+    x, xv = g["fwd_x"][:k].copy(), g["vjp_x"][:k].copy()
+    x[b, -1] = xv[b, -1] = np.nan
+    return x, g["fwd_u"][:k], g["vjp_lam"][:k], xv, g["vjp_u"][:k]
+
+
+def test_a_nan_state_gives_nan_and_touches_no_other_point(bundle):
+    """A diverged state must show: every activation passes a NaN pre-activation on in phi and in phi' (ReLU too, whose
+    max(z, 0) and z > 0 would otherwise turn it into a finite 0, unlike nn.ReLU), in float64 and in float32."""
+    name, act, g, m64, m32 = bundle
+    b = 3
+    x, u, lam, xv, uv = poisoned_points(g, b=b)
+    for m in (m64, m32):
+        dx, H = m.forward(x, u)
+        dx0, H0 = m.forward(g["fwd_x"][:8], u)
+        assert np.isnan(dx[b]).all(), (name, dx[b])
+        keep = np.arange(8) != b
+        assert np.array_equal(dx[keep], dx0[keep]) and np.array_equal(H[keep], H0[keep])
+        xb, ub = m.vjp(xv, uv, lam)
+        xb0, ub0 = m.vjp(g["vjp_x"][:8], uv, lam)
+        assert np.isnan(xb[b]).all(), (name, xb[b])
+        assert np.array_equal(xb[keep], xb0[keep]) and np.array_equal(ub[keep], ub0[keep])

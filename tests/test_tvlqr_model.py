@@ -21,6 +21,7 @@ import torch
 import linearize_model as lm
 import oracle_lib as ol
 import tvlqr_model as tm
+import variant_census as vc
 from phnn_mpc_amd import _capi
 from phnn_mpc_amd.models import pHNN, pHNN_Canonical
 from phnn_mpc_amd.mpc_controller import MPCController
@@ -33,7 +34,7 @@ MARGIN, CEILING = 64.0, 1e-8
 MEASURED_K, MEASURED_P0 = 4.9e-16, 5.5e-16          # second formulation (worst case of the nine)
 MEASURED_RESIDUAL, MEASURED_K01 = 4.9e-17, 0.0   # fixed point
 
-SHAPES = [(2, 1), (4, 1), (4, 3)]
+SHAPES = vc.NM_PAIRS  # every (n, m) a handle can have
 HORIZONS = [1, 6, 50]
 NB = 5
 

@@ -57,6 +57,15 @@ def test_spec_packs_and_builds_in_the_oracle(sid):
         assert not np.array_equal(sd["H_net.net.0.weight"], vc.build_state_dict(sid + "/x", s)["H_net.net.0.weight"])
 
 
+def test_nm_table_covers_every_reachable_pair():
+    """Every (n, m) a handle can have is listed and mapped to a spec with that pair, so the tests of the kernels
+    dispatched on (n, m), which take their specs from NM_SPEC, leave no reachable instantiation out."""
+    assert set(vc.NM_PAIRS) == {(s["n"], s["m"]) for s in vc.CENSUS.values()}
+    assert list(vc.NM_SPEC) == vc.NM_PAIRS
+    for pair, sid in vc.NM_SPEC.items():
+        assert (vc.CENSUS[sid]["n"], vc.CENSUS[sid]["m"]) == pair, (pair, sid)
+
+
 def _create_error(s, sd):
     """phnn_create_ex on this machine: the description is validated and a variant picked before any device is
     opened, so a refusal reads the same with or without a GPU."""

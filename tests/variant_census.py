@@ -123,6 +123,19 @@ PADDED = {
 # every spec the GPU test runs: spec id -> (variant, spec)
 ALL_SPECS = dict({k: (k, v) for k, v in CENSUS.items()}, **PADDED)
 
+# the (n, m) a handle can have (pick_variant refuses m >= 2 unless n = 4), and the spec the tests of the per-problem
+# dense-algebra kernels dispatched on (n, m) use for each: k_tvlqr, k_gn_direction(_box), k_dare, k_terminal_cost<N>,
+# k_feedback_control.  Those kernels read n and m from the handle and nothing else of the model.
+NM_PAIRS = [(2, 1), (3, 1), (4, 1), (4, 2), (4, 3), (4, 4)]
+NM_SPEC = {
+    (2, 1): "phnn<n=2,hid=64,Gnet>",
+    (3, 1): "odefunc<n=3,hid=128,f16x2>",
+    (4, 1): "phnn<n=4,hid=128,fixedG,f16x2>",
+    (4, 2): "phnn<n=4,m=2,hid=128,fixedG,f16x2>",
+    (4, 3): "phnn<n=4,m=3,hid=128,fixedG,f16x2>",
+    (4, 4): "phnn<n=4,m=4,hid=128,fixedG,f16x2>",
+}
+
 # requests phnn_create must refuse: spec id -> (spec, regex the error message must match)
 REFUSED = {
     "odefunc<n=2,silu>": (ode(2, 128, act="silu"), "activation"),
