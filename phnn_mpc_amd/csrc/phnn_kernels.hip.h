@@ -1815,6 +1815,20 @@ struct PhnnModel {
   static constexpr int NBIG = 4 + (RECHB ? (FIXG ? 1 : 2) : 0);
   using Rec = WRec<T, NBIG>;
 
+  // Fixed G: the control cotangent ubar = G^T lam needs neither the state nor the tape, so a march whose state cotangent
+  // of a step is read by nobody can take it from here alone (grad_march, step 0).  vjp forms its ubar with this
+  // function: the same FMAs in the same order.
+  static constexpr bool UBAR_DIRECT = FIXG;
+  DEV static f32x4 ubar_direct(const float* L, f32x4 lam) {
+    static_assert(FIXG, "G_net's control cotangent goes through the state path");
+    f32x4 ubar = splat4(0.f);
+#pragma unroll
+    for (int k = 0; k < MI; ++k)
+#pragma unroll
+      for (int i = 0; i < N; ++i) ubar[k] = __builtin_fmaf(L[oG + i * MI + k], lam[i], ubar[k]);
+    return ubar;
+  }
+
   // xbar = (df/dx)^T lam, ubar = (df/du)^T lam at (x,u); recomputes the forward tape it needs.
   // WG: also writes the weight-gradient record of this evaluation to `rec` (Hbar = cotangent on H, adds Hbar dH to xbar);
   // the tape it reads (ST) is the training tape and the q1 arithmetic stays.  Otherwise, CURV models: the tape is the
@@ -1877,11 +1891,8 @@ struct PhnnModel {
       }
     }
     ubar = splat4(0.f);
-    if (FIXG) {
-#pragma unroll
-      for (int k = 0; k < MI; ++k)
-#pragma unroll
-        for (int i = 0; i < N; ++i) ubar[k] = __builtin_fmaf(L[oG + i * MI + k], lam[i], ubar[k]);
+    if constexpr (FIXG) {
+      ubar = ubar_direct(L, lam);
     } else {
       Act<T> hG;
       float gf[16], gbar[16];
@@ -2530,6 +2541,9 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
     return Base::combine(L, rf, dH, G, u);
   }
 
+  static constexpr bool UBAR_DIRECT = true;  // fixed G: as PhnnModel (every wave of the tile forms the same ubar)
+  DEV static f32x4 ubar_direct(const float* L, f32x4 lam) { return Base::ubar_direct(L, lam); }
+
   template <bool ST = false, bool WG = false, int INH = -1, int FE = 0>  // INH: mask on the f16 input-layer sites (in_layer_mm); FE: as f
   DEV static void vjp(const float* L, float* scr, Lane ln, f32x4 x, f32x4 u, f32x4 lam, f32x4& xbar, f32x4& ubar,
                       const float* stash = nullptr, float* rec = nullptr, float Hbar = 0.f) {
@@ -2596,9 +2610,7 @@ struct PhnnSplit {  // PhnnModel<N_, 128, fixed G, f16x2> with the tile split ov
       keep_lds_reads_local();
       PR = to4_group<2>(L + oR + YR::oV1T + (ln.i & 3) * YR::LR + 16 * t0, ln, hb.v);
     }
-    ubar = splat4(0.f);
-#pragma unroll
-    for (int i = 0; i < N; ++i) ubar[0] = __builtin_fmaf(L[oG + i], lam[i], ubar[0]);
+    ubar = ubar_direct(L, lam);
     f32x4 v = splat4(0.f);  // v = A^T lam: the same lines as in PhnnModel::vjp
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -3150,6 +3162,28 @@ struct FuseOf<M, decltype((void)M::FUSE)> {
 template <class M, int INTEG, bool REF, bool MPC_TAPE, int SITES>
 constexpr int kFuseEpi = (INTEG == PHNN_INTEG_EULER && !REF && MPC_TAPE) ? (FuseOf<M>::value & SITES) : 0;
 
+// Which adjoint marches may leave out the dynamics VJP of step 0 when nobody reads lambda_0 (grad_march): the model
+// says that its control cotangent needs no state path (M::UBAR_DIRECT with ubar_direct; false where it says nothing:
+// learned G, ODEFunc and the canonical models, whose ubar comes out of the state path), the march is Euler (RK4's stage
+// chain needs the stage VJPs) and writes no weight-gradient records.  f16x2 models only: five all-f32 / bf16x3 recompute
+// kernels, at their register limit, spill more with the branch in their loop (tools/resource_usage.py) and keep the
+// parent's march.  -DPHNN_NO_STEP0_SKIP compiles every march without it.
+template <class M, class = void>
+struct UbarDirectOf {
+  static constexpr bool value = false;
+};
+template <class M>
+struct UbarDirectOf<M, decltype((void)M::UBAR_DIRECT)> {
+  static constexpr bool value = M::UBAR_DIRECT;
+};
+#ifdef PHNN_NO_STEP0_SKIP
+template <class M, int INTEG, bool WG>
+constexpr bool kStep0Skip = false;
+#else
+template <class M, int INTEG, bool WG>
+constexpr bool kStep0Skip = UbarDirectOf<M>::value && M::MM == MM_F16X2 && INTEG == PHNN_INTEG_EULER && !WG;
+#endif
+
 template <class M, int INTEG, int TK, bool REF = false>
 DEV void fwd_march(const RollParams& p, const float* L, const TileCtx& tc) {
   constexpr int N = M::N;
@@ -3261,15 +3295,28 @@ DEV void grad_march(const RollParams& p, const float* L, const TileCtx& tc) {
     float* rec = nullptr;
     if constexpr (WG) rec = p.wrec + ((tile * p.H + t) * STAGES) * (long long)M::Rec::SIZE;
     if constexpr (INTEG == PHNN_INTEG_EULER) {
-      if constexpr (WG) {
-        M::template vjp<STASH, true>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
-                                     STASH ? p.stash + (tile * p.H + t) * (long long)SS::TAPE : nullptr, rec);
-      } else {
-        M::template vjp<STASH, false, -1, kFuseEpi<M, INTEG, REF, STASH, kFuseK2Act | kFuseK2Red>>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
-                               STASH ? p.stash + (tile * p.H + t) * (long long)SS::TAPE : nullptr);
+      // Step 0's state cotangent only reaches lambda_0, which grad_x0 alone reads (with row 0 of the trajectory
+      // cotangent).  Where nobody asked for it and the model's control cotangent needs no state path, step 0 takes the
+      // control cotangent from the cotangent vjp would be given, through the FMAs of vjp's ubar: no tape load, no R_net,
+      // no Hessian-vector product.  Uniform over the launch: the waves of a split tile skip vjp's barriers together.
+      bool skipped = false;
+      if constexpr (kStep0Skip<M, INTEG, WG>) {
+        if (t == 0 && !p.grad_x0 && !p.traj_bar) {
+          utot = M::ubar_direct(L, p.dt * lam + dxb);
+          skipped = true;
+        }
       }
-      lam = lam + xb;
-      utot = ub;
+      if (!skipped) {
+        if constexpr (WG) {
+          M::template vjp<STASH, true>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
+                                       STASH ? p.stash + (tile * p.H + t) * (long long)SS::TAPE : nullptr, rec);
+        } else {
+          M::template vjp<STASH, false, -1, kFuseEpi<M, INTEG, REF, STASH, kFuseK2Act | kFuseK2Red>>(L, scr, ln, x, u, p.dt * lam + dxb, xb, ub,
+                                 STASH ? p.stash + (tile * p.H + t) * (long long)SS::TAPE : nullptr);
+        }
+        lam = lam + xb;
+        utot = ub;
+      }
     } else {
       // RK4, stages as rolled loops (one copy of f / vjp in the instruction stream, no cross-stage hoisting of tape
       // loads: that is what made the unrolled form spill).  STASH: the stage states and tapes come from K1's stash.

@@ -19,6 +19,10 @@ for t in mpc grad wgrad split; do
   fi
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o "$ROOT/build/ab/lib_$name.so" $objs "$src/phnn_pack.o"
+# the other translation units of the Makefile's link rule come from the product build as they are
+for o in $(sed -n 's/^libphnn_mpc\.so:\(.*\)$/\1/p' "$src/Makefile"); do
+  case "$o" in phnn_mpc.o|phnn_grad.o|phnn_wgrad.o|phnn_split.o) ;; *) objs="$objs $src/$o" ;; esac
+done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o "$ROOT/build/ab/lib_$name.so" $objs
 rm -f "$ROOT/build/ab/"*_"$name.o"
 echo "build/ab/lib_$name.so"
