@@ -1038,6 +1038,74 @@ int phnn_solve_gn_term(phnn_handle* h, const float* x0_dev, float* u_dev, int64_
                        double* mu_out, int32_t* accepts_dev, float* alpha_hist_dev, int32_t flags,
                        int32_t* nclamp_hist_dev /* (iters,B) or NULL */, void* stream);
 
+/* ---- input-disturbance estimation and offset-free control ------------------------------------------------
+ * The filter above on the augmented state z = (x in R^n, d in R^m), nz = n + m, with the model x+ = F(x, c(u) + d),
+ * d+ = d: d is an input disturbance that enters where the control enters, F is K1's integrator step WITHOUT a control
+ * clamp, and c is the library's float32 clamp to the cost's bounds (a NaN stays NaN), applied to the command only.  The
+ * measurement is a selection of STATE components (bit i of meas_mask, i < n).  xhat (B,n) and dhat (B,m) are float32,
+ * Pz (B,nz,nz) is float64, in/out.  The Jacobian of the augmented step is A_z = [[A, Bm], [0, I]] with A (B,n,n) and
+ * Bm (B,n,m) the float32 outputs of the linearisation of that step taken with no bounds (cost = NULL), so that Bm is
+ * d x+ / d d with no clamp mask.  k_dekf_update<n, m>, (n, m) in {(2,1), (3,1), (4,1), (4,2)}: one thread per problem,
+ * the operations of k_ekf_update above at size nz on the prediction (x-, dhat), A_z (read from A and Bm, never
+ * assembled in memory, its d rows the exact constants 0 and 1), Qz and Rn, with the rows of S of every unmeasured
+ * component -- all of d included -- held as the identity; (xhat, dhat) are rounded once to float32.
+ * tests/dekf_model.py states it around tests/ekf_model.py's update and the kernel equals it bit for bit.  With the d
+ * rows and columns of Pz and Qz zero the x part equals phnn_ekf_update's bit for bit, dhat keeps its bits and the d
+ * rows of Pz stay exactly 0.
+ * status (B) int32 and the special cases are the filter's above:
+ *   0  updated; or nothing measured: xhat = x- and dhat keep their float bits, Pz = Pz-, nis = quiet NaN
+ *   1  a dropped measurement: no update, as for nothing measured
+ *   2  a pivot failure, or an x-, dhat, A or Bm that is not finite: xhat, dhat, Pz and nis all quiet NaN
+ * Two small kernels go with it: k_dekf_controls, row[b,k] = c(u[b * u_stride + k]) + dhat[b,k], and k_dist_compensate,
+ * u_cmd[b,k] = c(c(v[b * v_stride + k]) - dhat[b,k]), both float32 with the sum / difference rounded once.
+ * Conventions as above: stream-ordered, capturable, no allocation, no synchronisation; B == 0 returns PHNN_OK with
+ * nothing launched; sizes are exact and inputs are never written.  PHNN_ERR_INVALID_ARG, nothing launched and no output
+ * touched: NULL required buffers, B < 0, mask bits at or above n, a non-finite Qz entry, a non-positive or non-finite
+ * Rn at a measured component, non-zero reserved, a log without a step source, and for the step an unknown integrator,
+ * a non-finite dt or u_min > u_max; PHNN_ERR_UNSUPPORTED for an (n, m) without a kernel ((4,3), (4,4), n outside
+ * {2, 3, 4}). */
+#define PHNN_DEKF_MAX_Z 6 /* largest n + m with a k_dekf_update */
+typedef struct {
+  uint32_t meas_mask;    /* bit i < n: state component i is measured */
+  double Qz[36];         /* process noise covariance of (x, d), (nz,nz) row-major in the leading entries, finite */
+  double Rn[PHNN_MAX_N]; /* measurement noise variances, > 0 and finite where measured */
+  int32_t reserved[4];   /* zero */
+} phnn_dekf_options;
+typedef struct {
+  float* log_xhat_dev;      /* (T+1,B,n) float32, row step + 1 receives xhat, or NULL */
+  double* log_nis_dev;      /* (T,B) float64, row step receives nis, or NULL */
+  const int32_t* step_dev;  /* device step counter, or NULL */
+  int32_t step_host;        /* used when step_dev == NULL */
+  float* log_dhat_dev;      /* (T+1,B,m) float32, row step + 1 receives dhat, or NULL */
+} phnn_dekf_log;
+/* Bytes of the workspace of the step below: the control row (B,1,m), K1's trajectory (B,2,n) and cost (B), A (B,n,n)
+ * and Bm (B,n,m), each region 256-byte aligned.  0 for invalid arguments (B < 0, an (n, m) without a kernel). */
+size_t phnn_dekf_workspace_bytes(const phnn_handle* h, int64_t B);
+/* The kernel on its own; x-, A and Bm may come from anywhere.  Problem b's prediction is xpred_dev[b * xpred_stride + i]
+ * and its measurement y_dev[b * y_stride + i], i < n.  A_dev (B,n,n), Bm_dev (B,n,m), Pz_dev (B,nz,nz) float64 in/out,
+ * xhat_dev (B,n), dhat_dev (B,m) in/out (the predicted disturbance is the one held), status_dev (B) int32; nis_dev (B),
+ * innov_dev (B,n) and log may be NULL. */
+int phnn_dekf_update(phnn_handle* h, const float* xpred_dev, int64_t xpred_stride, const float* A_dev, const float* Bm_dev,
+                     const float* y_dev, int64_t y_stride, int64_t B, const phnn_dekf_options* opt, double* Pz_dev,
+                     float* xhat_dev, float* dhat_dev, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                     const phnn_dekf_log* log, void* stream);
+/* One filter step through the learned model: xhat_dev (B,n), dhat_dev (B,m) and Pz_dev (B,nz,nz) in/out.
+ * u_dev[b * u_stride + k], k < m, is the command applied during the step; cost is read for has_u_bounds / u_min /
+ * u_max only and clamps the COMMAND only, NULL = no clamp.  Four launches in stream order and nothing else:
+ * k_dekf_controls (the control row c(u) + dhat), K1 with H = 1 from xhat on the path of the forward rollout above with a
+ * zero cost and no bounds (its trajectory into the workspace), the linearisation above with H = 1 and cost = NULL,
+ * k_dekf_update on row 1 of that trajectory.  workspace_dev: the bytes of the size query above, required when B > 0. */
+int phnn_dekf_step(phnn_handle* h, float* xhat_dev, float* dhat_dev, double* Pz_dev, const float* u_dev, int64_t u_stride,
+                   const float* y_dev, int64_t y_stride, int64_t B, const phnn_cost* cost, int32_t integrator, float dt,
+                   const phnn_dekf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                   const phnn_dekf_log* log, void* workspace_dev, void* stream);
+/* The compensated command u_cmd_dev (B,m): c(c(v) - dhat) per component, v_dev[b * v_stride + k] the controller's
+ * command (stride H*m: the first control of a solve's sequence, in place), cost read for its bounds as above (NULL: no
+ * clamp).  Where dhat[b,k] is not finite the component is c(v) and status_dev[b] (B, int32, may be NULL) is 1, else 0:
+ * never a finite command built from a NaN estimate.  A NaN v stays NaN.  One launch.  Any m the handle has. */
+int phnn_dist_compensate(phnn_handle* h, const float* v_dev, int64_t v_stride, const float* dhat_dev, int64_t B,
+                         const phnn_cost* cost, float* u_cmd_dev, int32_t* status_dev, void* stream);
+
 /* Introspection for tests: copies the packed weight image the kernels stage into LDS (phnn_kernels.hip.h layouts; a
  * device-resident private format) to image_host after the work queued on `stream`, and waits for the copy.
  * *image_floats (may be NULL) receives its size; image_host == NULL only queries the size. */

@@ -39,6 +39,7 @@ EXPORTED = [
     "phnn_gn_workspace_bytes", "phnn_gn_direction", "phnn_gn_candidates", "phnn_gn_select", "phnn_solve_gn",
     "phnn_gn_direction_box", "phnn_solve_gn_ex",
     "phnn_ekf_workspace_bytes", "phnn_ekf_update", "phnn_ekf_step",
+    "phnn_dekf_workspace_bytes", "phnn_dekf_update", "phnn_dekf_step", "phnn_dist_compensate",
     "phnn_feedback_workspace_bytes", "phnn_feedback_plan", "phnn_feedback_control",
     "phnn_rollout_vjp_ref", "phnn_terminal_cost", "phnn_dare", "phnn_gn_direction_term", "phnn_solve_term",
     "phnn_solve_gn_term",
@@ -135,6 +136,22 @@ class EkfOptions(C.Structure):
     covariance in the leading entries; Rn the measurement noise variances (read where measured)."""
     _fields_ = [("meas_mask", C.c_uint32), ("Qn", C.c_double * (PHNN_MAX_N * PHNN_MAX_N)), ("Rn", C.c_double * PHNN_MAX_N),
                 ("reserved", C.c_int32 * 4)]
+
+
+PHNN_DEKF_MAX_Z = 6  # largest n + m with a k_dekf_update
+
+
+class DekfOptions(C.Structure):
+    """phnn_dekf_options: bit i < n of meas_mask set = state component i is measured; Qz (nz,nz) row-major process noise
+    covariance of (x, d) in the leading entries; Rn the measurement noise variances (read where measured)."""
+    _fields_ = [("meas_mask", C.c_uint32), ("Qz", C.c_double * (PHNN_DEKF_MAX_Z * PHNN_DEKF_MAX_Z)), ("Rn", C.c_double * PHNN_MAX_N),
+                ("reserved", C.c_int32 * 4)]
+
+
+class DekfLog(C.Structure):
+    """phnn_dekf_log: phnn_ekf_log's fields, then log_dhat (T+1,B,m) float32, row step + 1."""
+    _fields_ = [("log_xhat_dev", C.c_void_p), ("log_nis_dev", C.c_void_p), ("step_dev", C.c_void_p), ("step_host", C.c_int32),
+                ("log_dhat_dev", C.c_void_p)]
 
 
 class EkfLog(C.Structure):
@@ -380,6 +397,16 @@ def load_library():
     lib.phnn_ekf_step.argtypes = [vp, f32p, vp, f32p, i64, f32p, i64, i64, C.POINTER(Cost), i32, C.c_float, eko, vp, vp, vp,
                                   ekl, vp, vp]
     lib.phnn_ekf_step.restype = C.c_int
+    dko, dkl = C.POINTER(DekfOptions), C.POINTER(DekfLog)
+    lib.phnn_dekf_workspace_bytes.argtypes = [vp, i64]
+    lib.phnn_dekf_workspace_bytes.restype = C.c_size_t
+    lib.phnn_dekf_update.argtypes = [vp, f32p, i64, f32p, f32p, f32p, i64, i64, dko, vp, f32p, f32p, vp, vp, vp, dkl, vp]
+    lib.phnn_dekf_update.restype = C.c_int
+    lib.phnn_dekf_step.argtypes = [vp, f32p, f32p, vp, f32p, i64, f32p, i64, i64, C.POINTER(Cost), i32, C.c_float, dko, vp, vp,
+                                   vp, dkl, vp, vp]
+    lib.phnn_dekf_step.restype = C.c_int
+    lib.phnn_dist_compensate.argtypes = [vp, f32p, i64, f32p, i64, C.POINTER(Cost), f32p, vp, vp]
+    lib.phnn_dist_compensate.restype = C.c_int
     lib.phnn_feedback_workspace_bytes.argtypes = [vp, i64, i32]
     lib.phnn_feedback_workspace_bytes.restype = C.c_size_t
     lib.phnn_feedback_plan.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), i32, C.c_float, C.POINTER(TvlqrOptions), vp,

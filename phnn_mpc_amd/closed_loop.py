@@ -26,7 +26,9 @@
                          plant step the filter advances with the control the plant applied and the new measurement
                          (phnn_ekf_step).  Only the `measured` components of the measurement are used, so a
                          loop can run on positions alone.  The result gains estimates (T+1,B,4) float32, nis (T,B) and
-                         ekf_status (B,), the last step's.
+                         ekf_status (B,), the last step's.  An estimation.DisturbanceEKF also estimates an input
+                         disturbance d (phnn_dekf_step): the result gains disturbances (T+1,B,m), and with
+                         its compensate the plant is handed c(c(v) - dhat) (phnn_dist_compensate) instead of the command v.
   track                  (all three drivers, track=) a feedback.Tracking: the solve runs every solve_every-th control step
                          only, and every step applies row step % solve_every of the last plan plus the time-varying LQR
                          feedback on the deviation from its nominal trajectory (phnn_feedback_plan, phnn_feedback_control;
@@ -220,7 +222,10 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
     result then also holds disturbance (T,B) float32, what each step added to the commanded force.
     estimator: an estimation.EKF; every solve starts from its estimate, and after every plant step EKF.step advances it
     on the controller's engine with the applied control and the new measurement.  The result then also holds estimates
-    (T+1,B,4) float32, nis (T,B) and ekf_status (B,).
+    (T+1,B,4) float32, nis (T,B) and ekf_status (B,).  An estimation.DisturbanceEKF also estimates an input disturbance:
+    the result gains disturbances (T+1,B,m) float32, and with its compensate the simulator is handed
+    engine.dist_compensate(u, dhat) -- the controller's (or the tracking law's) control with dhat taken off -- and the
+    filter advances with that.
     track: a feedback.Tracking; the solve runs at the steps s with s % solve_every == 0 only, Tracking.plan turns its
     sequence into a plan, and every step applies Tracking.control from the measurement (or the estimate).  The result
     then also holds track_status (T,B) and track_dev (T,B), or None with the tracking's log=False."""
@@ -241,9 +246,15 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
     if estimator is not None:
         import torch
         eng = controller.engine
-        xh0, P0 = estimator.initial(x)
+        augmented = hasattr(estimator, "compensate")  # an estimation.DisturbanceEKF: the state of the filter is (x, d)
+        if augmented:
+            xh0, dh0, P0 = estimator.initial(x, eng.m)
+            dhat, disturbances = torch.tensor(dh0, device=eng.device), [dh0]
+            ekf_opt, ekf_cost = estimator.options(eng.n, eng.m), controller._cost()  # the bounds of the command's clamps
+        else:
+            xh0, P0 = estimator.initial(x)
+            ekf_opt, ekf_cost = estimator.options(eng.n), (None if canonical else controller._cost())
         xhat, P = torch.tensor(xh0, device=eng.device), torch.tensor(P0, device=eng.device)
-        ekf_opt, ekf_cost = estimator.options(eng.n), (None if canonical else controller._cost())
         estimates, nis, ekf_status = [xh0], [], None
     if track is not None:
         import torch
@@ -272,6 +283,9 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
             u, u_prev, _ = controller.control_batch(x32, u_prev, **rkw)
         else:
             u = controller.compute_control_batch(x32, **rkw)
+        if estimator is not None and augmented and estimator.compensate:  # the plant is handed c(c(v) - dhat)
+            v = torch.as_tensor(np.ascontiguousarray(np.asarray(u, dtype=np.float32).reshape(B, -1))).to(eng.device)
+            u = eng.dist_compensate(v, eng.m, dhat, ekf_cost)[0].cpu().numpy()
         x, done = simulator.step(u)
         newly = done & (done_step < 0)
         done_step[newly] = step
@@ -281,10 +295,14 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
             dist.append(simulator.disturbance.copy())
         if estimator is not None:  # the filter advances with the control the plant applied and the new measurement
             y32 = simulator.measurement() if measured else x.astype(np.float32)
-            r = estimator.step(eng, xhat, P, torch.as_tensor(np.asarray(u, dtype=np.float32).reshape(B, -1)),
+            state = (xhat, dhat, P) if augmented else (xhat, P)
+            r = estimator.step(eng, *state, torch.as_tensor(np.asarray(u, dtype=np.float32).reshape(B, -1)),
                                torch.tensor(np.ascontiguousarray(y32, dtype=np.float32), device=eng.device), ekf_cost,
                                controller.integrator, controller.dt, opt=ekf_opt)
             xhat, P, ekf_status = r["xhat"], r["P"], r["status"]
+            if augmented:
+                dhat = r["dhat"]
+                disturbances.append(dhat.cpu().numpy())
             estimates.append(xhat.cpu().numpy())
             nis.append(r["nis"].cpu().numpy())
     out = {"states": np.stack(states), "controls": np.stack(controls), "done_step": done_step}
@@ -293,6 +311,8 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
     if estimator is not None:
         out.update(estimates=np.stack(estimates), nis=np.stack(nis) if nis else np.zeros((0, B)),
                    ekf_status=None if ekf_status is None else ekf_status.cpu().numpy().astype(np.int64))
+        if augmented:
+            out["disturbances"] = np.stack(disturbances)
     if track is not None:
         kept = track.log
         out.update(track_status=(np.stack(track_status) if track_status else np.zeros((0, B), np.int64)) if kept else None,
@@ -338,7 +358,10 @@ class DeviceClosedLoop:
     control step.  The result gains estimates (T+1,B,4) float32 and nis (T,B) (None with the estimator's log=False) and
     ekf_status (B,), the last step's.  The filter predicts over the controller's dt: an estimator together with a dt=
     other than controller.dt is refused (ValueError).  Without an estimator the loop is what it was: same launches, same
-    bits.
+    bits.  An estimation.DisturbanceEKF: the filter step is engine.dekf_step on (xhat, dhat, Pz), the result gains
+    disturbances (T+1,B,m) float32 (None with log=False), and with its compensate engine.dist_compensate turns the
+    solve's first control (or the tracking law's output) into u_cmd = c(c(v) - dhat) in a (B,m) buffer that the plant
+    step and the filter step read with stride m -- one more launch per control step, inside the captured step.
 
     track: a feedback.Tracking(solve_every=k).  A solve step (s % k == 0) runs the solve as above, then
     engine.feedback_plan from the same state on the solve's sequence (best_u of a canonical controller, u_last of an
@@ -451,12 +474,25 @@ class DeviceClosedLoop:
         if not hasattr(eng, "ekf_step"):
             raise NotImplementedError(f"{type(eng).__name__} has no batched filter step (RolloutEngine has)")
         dev = eng.device
-        xh0, P0 = est.initial(x0)
+        self.augmented = hasattr(est, "compensate")  # an estimation.DisturbanceEKF: the state of the filter is (x, d)
+        if self.augmented and not hasattr(eng, "dekf_step"):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched disturbance filter step (RolloutEngine has)")
+        if self.augmented:
+            xh0, dh0, P0 = est.initial(x0, eng.m)
+            k["dhat"] = torch.tensor(dh0, device=dev)
+            self.comp = None  # the command the plant takes when dhat is taken off it
+            if est.compensate:
+                k["u_cmd"] = torch.zeros(B, eng.m, dtype=torch.float32, device=dev)
+                self.comp = k["u_cmd"]
+        else:
+            xh0, P0 = est.initial(x0)
         self.y32 = self.x32  # the plant keeps writing its measurement here
         self.x32 = self.xhat32 = torch.tensor(xh0, device=dev)  # what every solve reads: the estimate
         self.P = torch.tensor(P0, device=dev)
-        self.ekf_opt = est.options(eng.n)
+        self.ekf_opt = est.options(eng.n, eng.m) if self.augmented else est.options(eng.n)
         self.ekf_cost = None if self.canonical else self.cost  # the plant's clamp: the canonical sequence is clamped already
+        if self.augmented:
+            self.ekf_cost = self.cost  # the bounds of the command's clamps, in the compensation and in the filter
         k["ekf_status"] = torch.zeros(B, dtype=torch.int32, device=dev)
         k["ekf_nis"] = torch.empty(B, dtype=torch.float64, device=dev)
         self.ekf_ws = {}  # the device buffer of the filter step, kept across steps
@@ -466,9 +502,26 @@ class DeviceClosedLoop:
             k["estimates"][0].copy_(self.xhat32)
             k["nis"] = torch.empty(self.T, B, dtype=torch.float64, device=dev)
             self.ekf_log = dict(log_xhat=k["estimates"], log_nis=k["nis"], step_dev=self.step_dev)
+            if self.augmented:
+                k["disturbances"] = torch.empty(self.T + 1, B, eng.m, dtype=torch.float32, device=dev)
+                k["disturbances"][0].copy_(k["dhat"])
+                self.ekf_log["log_dhat"] = k["disturbances"]
+
+    def _applied(self, v, stride):
+        """The control the plant takes and its stride: the command v itself, or with a compensating DisturbanceEKF
+        c(c(v) - dhat), written by engine.dist_compensate into a (B,m) buffer."""
+        if self.ekf is None or not self.augmented or self.comp is None:
+            return v, stride
+        self.eng.dist_compensate(v, stride, self._keep["dhat"], self.ekf_cost, u_cmd=self.comp)
+        return self.comp, self.eng.m
 
     def _ekf_step(self, u, stride):
         c = self.ctl
+        if self.augmented:
+            self.eng.dekf_step(self.xhat32, self._keep["dhat"], self.P, u, stride, self.y32, self.ekf_cost, c.integrator, c.dt,
+                               self.ekf_opt, nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"],
+                               log=self.ekf_log, workspace=self.ekf_ws)
+            return
         self.eng.ekf_step(self.xhat32, self.P, u, stride, self.y32, self.ekf_cost, c.integrator, c.dt, self.ekf_opt,
                           nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"], log=self.ekf_log,
                           workspace=self.ekf_ws)
@@ -551,14 +604,16 @@ class DeviceClosedLoop:
         H = self.u_init.shape[1] * self.u_init.shape[2]
         out = self._solve()
         if self.canonical:  # best clamped iterate; next call warm-starts from its shift
-            eng.plant_step(self.plant, self.state, out["best_u"], H, **log)
+            u, stride = self._applied(out["best_u"], H)
+            eng.plant_step(self.plant, self.state, u, stride, **log)
             if self.ekf is not None:
-                self._ekf_step(out["best_u"], H)
+                self._ekf_step(u, stride)
             eng.shift_controls(out["best_u"], self.u_init, step_dev=self.step_dev)
         else:  # last iterate, clamp(u_0); every call cold-starts from zeros (u_init stays zero)
-            eng.plant_step(self.plant, self.state, out["u_last"], H, u_min=c.u_min, u_max=c.u_max, **log)
+            u, stride = self._applied(out["u_last"], H)
+            eng.plant_step(self.plant, self.state, u, stride, u_min=c.u_min, u_max=c.u_max, **log)
             if self.ekf is not None:
-                self._ekf_step(out["u_last"], H)
+                self._ekf_step(u, stride)
             eng.advance_step(self.step_dev)
 
     def _track_step(self, solve):
@@ -576,9 +631,10 @@ class DeviceClosedLoop:
                              step_dev=self.step_dev, u_out=k["track_u"], status=k["track_status"], dev=k["track_dev"],
                              **self.track_log)
         bounds = {} if self.canonical else dict(u_min=c.u_min, u_max=c.u_max)
-        eng.plant_step(self.plant, self.state, k["track_u"], eng.m, **bounds, **self._plant_log())
+        u, stride = self._applied(k["track_u"], eng.m)
+        eng.plant_step(self.plant, self.state, u, stride, **bounds, **self._plant_log())
         if self.ekf is not None:
-            self._ekf_step(k["track_u"], eng.m)
+            self._ekf_step(u, stride)
         if self.canonical and solve:
             src = self.seq
             for i in range(tr.solve_every):
@@ -649,6 +705,8 @@ class DeviceClosedLoop:
             out.update(estimates=self._keep["estimates"].cpu().numpy() if kept else None,
                        nis=self._keep["nis"].cpu().numpy() if kept else None,
                        ekf_status=self._keep["ekf_status"].cpu().numpy().astype(np.int64))
+            if self.augmented:
+                out["disturbances"] = self._keep["disturbances"].cpu().numpy() if kept else None
         if self.track is not None:
             kept = self.track.log
             out.update(track_status=self._keep["track_status_log"].cpu().numpy().astype(np.int64) if kept else None,

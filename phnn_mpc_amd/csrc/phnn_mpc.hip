@@ -20,6 +20,7 @@
 #include "phnn_sampling.h"
 #include "phnn_gn.h"
 #include "phnn_ekf.h"
+#include "phnn_dekf.h"
 #include "phnn_feedback.h"
 #include "phnn_terminal.h"
 #include "phnn_pack.h"
@@ -2226,6 +2227,132 @@ int phnn_ekf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u
   const EkfUpdateParams p = ekf_update_params(h, traj + n, 2 * n, (float*)(ws + l.A), y_dev, y_stride, B, opt, P_dev, xhat_dev,
                                               nis_dev, innov_dev, status_dev, log);
   return checked(h, ekf_update_launch(n, p, (hipStream_t)stream), "k_ekf_update launch");
+}
+
+// ---- input-disturbance estimation and offset-free control: kernels in phnn_dekf.hip ------------------
+// The checks of the options and the log that phnn_dekf_update and phnn_dekf_step share.
+static int check_dekf(phnn_handle* h, int64_t B, const phnn_dekf_options* o, const phnn_dekf_log* log) {
+  if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
+  if (!o) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options is NULL");
+  const int n = h->desc.n, nz = h->desc.n + h->desc.m;
+  if (!dekf_has_kernel(n, h->desc.m)) return fail(h, PHNN_ERR_UNSUPPORTED, "no disturbance filter kernel for this (n, m)");
+  if (o->meas_mask >> n) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options: meas_mask has bits at or above n");
+  for (int i = 0; i < nz * nz; ++i)
+    if (!std::isfinite(o->Qz[i])) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options: Qz is not finite");
+  for (int i = 0; i < n; ++i)
+    if (((o->meas_mask >> i) & 1u) && (!(o->Rn[i] > 0.0) || !std::isfinite(o->Rn[i])))
+      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options: Rn of a measured component is not positive and finite");
+  for (int r : o->reserved)
+    if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options: reserved must be zero");
+  if (log && (log->log_xhat_dev || log->log_dhat_dev || log->log_nis_dev) && !log->step_dev && log->step_host < 0)
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_log: a log without a step source");
+  return PHNN_OK;
+}
+
+static DekfUpdateParams dekf_update_params(const phnn_handle* h, const float* xpred_dev, int64_t xpred_stride,
+                                           const float* A_dev, const float* Bm_dev, const float* y_dev, int64_t y_stride,
+                                           int64_t B, const phnn_dekf_options* o, double* Pz_dev, float* xhat_dev,
+                                           float* dhat_dev, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                                           const phnn_dekf_log* log) {
+  const int n = h->desc.n, nz = h->desc.n + h->desc.m;
+  DekfUpdateParams p{};
+  p.xpred = xpred_dev;
+  p.xpred_stride = xpred_stride;
+  p.A = A_dev;
+  p.Bm = Bm_dev;
+  p.y = y_dev;
+  p.y_stride = y_stride;
+  p.Pz = Pz_dev;
+  p.xhat = xhat_dev;
+  p.dhat = dhat_dev;
+  p.nis = nis_dev;
+  p.innov = innov_dev;
+  p.status = status_dev;
+  if (log) {
+    p.log_xhat = log->log_xhat_dev;
+    p.log_dhat = log->log_dhat_dev;
+    p.log_nis = log->log_nis_dev;
+    p.step_dev = log->step_dev;
+    p.step_host = log->step_host;
+  }
+  p.B = (long long)B;
+  p.mask = o->meas_mask;
+  for (int i = 0; i < nz * nz; ++i) p.Qz[i] = o->Qz[i];
+  for (int i = 0; i < n; ++i) p.Rn[i] = o->Rn[i];
+  return p;
+}
+
+size_t phnn_dekf_workspace_bytes(const phnn_handle* h, int64_t B) {
+  if (!h || B < 0 || !dekf_has_kernel(h->desc.n, h->desc.m)) return 0;
+  return std::max<size_t>(dekf_layout(B, h->desc.n, h->desc.m).total, 256);
+}
+
+int phnn_dekf_update(phnn_handle* h, const float* xpred_dev, int64_t xpred_stride, const float* A_dev, const float* Bm_dev,
+                     const float* y_dev, int64_t y_stride, int64_t B, const phnn_dekf_options* opt, double* Pz_dev,
+                     float* xhat_dev, float* dhat_dev, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                     const phnn_dekf_log* log, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_dekf(h, B, opt, log)) return rc;
+  if (xpred_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_update: negative stride");
+  if (B == 0) return PHNN_OK;
+  if (!xpred_dev || !A_dev || !Bm_dev || !Pz_dev || !xhat_dev || !dhat_dev || !status_dev || (opt->meas_mask && !y_dev))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_update: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  const DekfUpdateParams p = dekf_update_params(h, xpred_dev, xpred_stride, A_dev, Bm_dev, y_dev, y_stride, B, opt, Pz_dev,
+                                                xhat_dev, dhat_dev, nis_dev, innov_dev, status_dev, log);
+  return checked(h, dekf_update_launch(h->desc.n, h->desc.m, p, (hipStream_t)stream), "k_dekf_update launch");
+}
+
+int phnn_dekf_step(phnn_handle* h, float* xhat_dev, float* dhat_dev, double* Pz_dev, const float* u_dev, int64_t u_stride,
+                   const float* y_dev, int64_t y_stride, int64_t B, const phnn_cost* cost, int32_t integrator, float dt,
+                   const phnn_dekf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                   const phnn_dekf_log* log, void* workspace_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (int rc = check_dekf(h, B, opt, log)) return rc;
+  if (u_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_step: negative stride");
+  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
+  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
+  if (cost)
+    if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!xhat_dev || !dhat_dev || !Pz_dev || !u_dev || !status_dev || !workspace_dev || (opt->meas_mask && !y_dev))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_step: NULL tensor");
+  const int n = h->desc.n, m = h->desc.m;
+  const DekfLayout l = dekf_layout(B, n, m);
+  char* ws = (char*)workspace_dev;
+  float* ctrl = (float*)(ws + l.ctrl);
+  float* traj = (float*)(ws + l.traj);
+  {
+    PHNN_ON_DEVICE(h);
+    DekfControlsParams c{u_dev, (long long)u_stride, dhat_dev, ctrl, (long long)B, m, cost ? cost->has_u_bounds : 0,
+                         cost ? cost->u_min : 0.f, cost ? cost->u_max : 0.f};
+    if (int rc = checked(h, dekf_controls_launch(c, (hipStream_t)stream), "k_dekf_controls launch")) return rc;
+  }
+  // the disturbed control c(u) + dhat enters the model as it is: a zero cost and no bounds for K1, none for the Jacobians
+  const phnn_cost none = neutral_cost();
+  if (int rc = rollout_fwd(h, xhat_dev, ctrl, B, 1, &none, integrator, dt, (float*)(ws + l.cost), traj, nullptr, nullptr, stream))
+    return rc;
+  if (int rc = phnn_rollout_linearize(h, ctrl, B, 1, nullptr, integrator, dt, traj, (float*)(ws + l.A), (float*)(ws + l.Bm), stream))
+    return rc;
+  PHNN_ON_DEVICE(h);
+  const DekfUpdateParams p = dekf_update_params(h, traj + n, 2 * n, (float*)(ws + l.A), (float*)(ws + l.Bm), y_dev, y_stride, B,
+                                                opt, Pz_dev, xhat_dev, dhat_dev, nis_dev, innov_dev, status_dev, log);
+  return checked(h, dekf_update_launch(n, m, p, (hipStream_t)stream), "k_dekf_update launch");
+}
+
+int phnn_dist_compensate(phnn_handle* h, const float* v_dev, int64_t v_stride, const float* dhat_dev, int64_t B,
+                         const phnn_cost* cost, float* u_cmd_dev, int32_t* status_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
+  if (v_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dist_compensate: negative stride");
+  if (cost)
+    if (int rc = check_cost(h, cost)) return rc;
+  if (B == 0) return PHNN_OK;
+  if (!v_dev || !dhat_dev || !u_cmd_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dist_compensate: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  DistCompensateParams p{v_dev, (long long)v_stride, dhat_dev, u_cmd_dev, status_dev, (long long)B, h->desc.m,
+                         cost ? cost->has_u_bounds : 0, cost ? cost->u_min : 0.f, cost ? cost->u_max : 0.f};
+  return checked(h, dist_compensate_launch(p, (hipStream_t)stream), "k_dist_compensate launch");
 }
 
 // ---- tracking the plan between solves: kernel in phnn_feedback.hip -------------------------------------

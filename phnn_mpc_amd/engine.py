@@ -1125,6 +1125,88 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return dict(u=u_out, status=status, dev=dev)
 
+    # ------------------------------------------------------------------ disturbance-augmented filter
+    def dekf_workspace_bytes(self, B):
+        return int(self.lib.phnn_dekf_workspace_bytes(self.h, int(B)))
+
+    def _dekf_log(self, log):
+        """log: None or dict(log_xhat (T+1,B,n) float32, log_dhat (T+1,B,m) float32, log_nis (T,B) float64, step_dev int32
+        tensor or step int)."""
+        if log is None:
+            return None
+        lg = _capi.DekfLog()
+        lg.log_xhat_dev = log["log_xhat"].data_ptr() if log.get("log_xhat") is not None else None
+        lg.log_dhat_dev = log["log_dhat"].data_ptr() if log.get("log_dhat") is not None else None
+        lg.log_nis_dev = log["log_nis"].data_ptr() if log.get("log_nis") is not None else None
+        if log.get("step_dev") is not None:
+            lg.step_dev = log["step_dev"].data_ptr()
+        lg.step_host = int(log.get("step", -1))
+        return lg
+
+    def dekf_update(self, xpred, A, Bm, y, Pz, dhat, opt, xhat=None, nis=True, innov=True, status=None, log=None,
+                    xpred_stride=None, y_stride=None):
+        """k_dekf_update on its own: ekf_update on the augmented state z = (x, d) with the Jacobian [[A, Bm], [0, I]] and
+        the options of _capi.DekfOptions.  xpred, y, strides, nis, innov, status: as in ekf_update; A (B,n,n) and Bm
+        (B,n,m) float32; Pz (B,n+m,n+m) float64 and dhat (B,m) float32 are updated IN PLACE.  -> dict(xhat (B,n) float32,
+        dhat, P (= Pz), nis, innov (B,n), status (B) int32)."""
+        self._assert_device_f32(xpred, A, Bm, y, dhat)
+        nz = self.n + self.m
+        assert Pz.dtype == torch.float64 and Pz.is_contiguous() and Pz.device == self.device
+        B = Pz.shape[0]
+        assert Pz.numel() == B * nz * nz and A.numel() == B * self.n * self.n and Bm.numel() == B * self.n * self.m
+        assert dhat.numel() == B * self.m
+        if xhat is None:
+            xhat = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
+        self._assert_device_f32(xhat)
+        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
+        lg = self._dekf_log(log)
+        rc = self.lib.phnn_dekf_update(self.h, self._p(xpred), self.n if xpred_stride is None else int(xpred_stride), self._p(A),
+                                       self._p(Bm), self._p(y), self.n if y_stride is None else int(y_stride), B, C.byref(opt),
+                                       self._p(Pz), self._p(xhat), self._p(dhat), self._p(nis), self._p(innov), self._p(status),
+                                       None if lg is None else C.byref(lg), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(xhat=xhat, dhat=dhat, P=Pz, nis=nis, innov=innov, status=status)
+
+    def dekf_step(self, xhat, dhat, Pz, u, u_stride, y, cost, integrator, dt, opt, nis=True, innov=False, status=None, log=None,
+                  workspace=None, y_stride=None):
+        """phnn_dekf_step: one step of the disturbance-augmented filter as ONE library call -- k_dekf_controls (the row
+        c(u) + dhat), K1 with H = 1 from xhat without bounds, the linearisation of that step without bounds,
+        k_dekf_update -- IN PLACE on xhat (B,n) float32, dhat (B,m) float32 and Pz (B,n+m,n+m) float64.  u: float32,
+        problem b's applied command at u.view(-1)[b * u_stride + k]; cost: its bounds clamp the command (None: no clamp);
+        the rest as in ekf_step.  -> dict(xhat, dhat, P, nis, innov, status)."""
+        self._assert_device_f32(xhat, dhat, u, y)
+        assert Pz.dtype == torch.float64 and Pz.is_contiguous() and Pz.device == self.device
+        B = xhat.shape[0]
+        ws = {} if workspace is None else workspace
+        if ws.get("dekf_key") != B:
+            ws["dekf_key"] = B
+            ws["dekf"] = torch.empty(max(self.dekf_workspace_bytes(B), 256), dtype=torch.uint8, device=self.device)
+        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
+        lg = self._dekf_log(log)
+        rc = self.lib.phnn_dekf_step(self.h, self._p(xhat), self._p(dhat), self._p(Pz), self._p(u), int(u_stride), self._p(y),
+                                     self.n if y_stride is None else int(y_stride), B, C.byref(cost) if cost is not None else None,
+                                     self._integ(integrator), float(dt), C.byref(opt), self._p(nis), self._p(innov),
+                                     self._p(status), None if lg is None else C.byref(lg), self._p(ws["dekf"]), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(xhat=xhat, dhat=dhat, P=Pz, nis=nis, innov=innov, status=status)
+
+    def dist_compensate(self, v, v_stride, dhat, cost, u_cmd=None, status=None):
+        """phnn_dist_compensate: u_cmd (B,m) = c(c(v) - dhat), c the clamp to the cost's bounds (None: none); v: float32,
+        problem b's command at v.view(-1)[b * v_stride + k]; dhat (B,m) float32.  A component whose dhat is not finite
+        keeps c(v), and status (B) int32 (True = allocate, None = skip, or a tensor) is 1 for that problem.
+        -> (u_cmd, status)."""
+        self._assert_device_f32(v, dhat, u_cmd)
+        B = dhat.numel() // self.m
+        if u_cmd is None:
+            u_cmd = torch.empty(B, self.m, dtype=torch.float32, device=self.device)
+        if status is True:
+            status = torch.empty(B, dtype=torch.int32, device=self.device)
+        rc = self.lib.phnn_dist_compensate(self.h, self._p(v), int(v_stride), self._p(dhat), B,
+                                           C.byref(cost) if cost is not None else None, self._p(u_cmd), self._p(status),
+                                           self._stream())
+        _check(self.lib, self.h, rc)
+        return u_cmd, status
+
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
                    step=0, step_dev=None, log_states=None, log_controls=None, ex=None, metrics=None):

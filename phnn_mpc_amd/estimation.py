@@ -10,6 +10,11 @@ phnn_ekf_step).
              ekf_update): the same four launches on a RolloutEngine, and it runs on a CPU stand-in that has those three
              methods, the way solver.gn_solve serves a Gauss-Newton stand-in.
 
+  DisturbanceEKF  the same filter on the state (x, d) with an input disturbance d that enters where the control enters
+             (x+ = F(x, c(u) + d), d+ = d; phnn_dekf_update, phnn_dekf_step), and the switch that
+             lets the closed loops take dhat off the command (phnn_dist_compensate): offset-free control against a
+             constant force bias.
+
 The closed-loop drivers (closed_loop.run_mpc_batch, DeviceClosedLoop, run_mpc_batch_device) take estimator=EKF(...): the
 controller then solves from the estimate instead of the raw measurement.
 """
@@ -57,9 +62,12 @@ class EKF:
             return None
         sec = dict(sec)
         kind = str(sec.pop("type", "ekf")).lower()
-        if kind != "ekf":
+        if kind not in ("ekf", "ekf_disturbance"):
             raise ValueError(f"Unknown estimator type: {kind}")
-        unknown = set(sec) - {"measured", "Qn", "Rn", "P0", "x0_hat", "log"}
+        keys = {"measured", "Qn", "Rn", "P0", "x0_hat", "log"}
+        if kind == "ekf_disturbance":  # the filter with an input disturbance in its state (DisturbanceEKF below)
+            cls, keys = DisturbanceEKF, keys | {"Qd", "Pd0", "Qz", "d0_hat", "compensate"}
+        unknown = set(sec) - keys
         if unknown:
             raise ValueError(f"estimator: unknown key(s) {sorted(unknown)}")
         return cls(**sec)
@@ -121,3 +129,69 @@ class EKF:
         _, traj = engine.rollout_cost(xhat, row, bounds, integrator, dt, want_traj=True)
         A, _, _ = engine.rollout_linearize(xhat, row, bounds, integrator, dt, traj=traj)
         return engine.ekf_update(traj[:, 1].contiguous(), A.reshape(B, engine.n, engine.n), y, P.clone(), opt, log=log)
+
+
+class DisturbanceEKF(EKF):
+    """EKF on the augmented state z = (x, d): d (m components) is an input disturbance, constant in the model, that adds
+    to the clamped command.  measured, Qn, Rn, P0, x0_hat, log: as in EKF (the measurement is a selection of STATE
+    components).  Qd: the process noise covariance of d and Pd0 its initial covariance -- a scalar, (m,) or (m,m); Qz:
+    optionally the full (n+m, n+m) process noise covariance, which then replaces Qn and Qd.  d0_hat: the initial
+    disturbance estimate, broadcastable to (B,m).  compensate: the closed-loop drivers hand the plant
+    c(c(v) - dhat) instead of the controller's command v (engine.dist_compensate); False: the plain loop's control, the
+    disturbance is estimated only."""
+
+    def __init__(self, measured=(0, 1), Qn=1e-6, Rn=1e-4, P0=1e-2, Qd=0.0, Pd0=1.0, Qz=None, x0_hat=None, d0_hat=0.0,
+                 compensate=True, log=True):
+        super().__init__(measured=measured, Qn=Qn, Rn=Rn, P0=P0, x0_hat=x0_hat, log=log)
+        self.Qd, self.Pd0, self.Qz = Qd, Pd0, Qz
+        self.d0_hat = np.asarray(d0_hat, dtype=np.float32)
+        self.compensate = bool(compensate)
+
+    def options(self, n, m):
+        """-> _capi.DekfOptions (phnn_dekf_options) for an n-state, m-input model."""
+        if any(i >= n for i in self.measured):
+            raise ValueError(f"measured {self.measured}: the model has {n} state components")
+        nz = n + m
+        if nz > _capi.PHNN_DEKF_MAX_Z:
+            raise ValueError(f"n + m = {nz}: the disturbance filter holds at most {_capi.PHNN_DEKF_MAX_Z} components")
+        if self.Qz is not None:
+            Qz = _square(self.Qz, nz, "Qz")
+        else:
+            Qz = np.zeros((nz, nz))
+            Qz[:n, :n], Qz[n:, n:] = _square(self.Qn, n, "Qn"), _square(self.Qd, m, "Qd")
+        o = _capi.DekfOptions()
+        o.meas_mask = self.mask
+        Rn = self.rn_vector(n)
+        for i in range(nz * nz):
+            o.Qz[i] = Qz.reshape(-1)[i]
+        for i in range(n):
+            o.Rn[i] = Rn[i]
+        return o
+
+    def initial(self, x0, m, n=None):
+        """x0 (B,n) true initial states -> (xhat0 (B,n) float32, dhat0 (B,m) float32, Pz0 (B,n+m,n+m) float64 =
+        blockdiag(P0, Pd0)), numpy."""
+        xh, P = super().initial(x0, n)
+        B, n = xh.shape
+        Pz = np.zeros((B, n + m, n + m))
+        Pz[:, :n, :n], Pz[:, n:, n:] = P, _square(self.Pd0, m, "Pd0")
+        return xh, np.ascontiguousarray(np.broadcast_to(self.d0_hat, (B, m)).astype(np.float32)), Pz
+
+    def step(self, engine, xhat, dhat, Pz, u, y, cost, integrator, dt, opt=None, log=None):
+        """One filter step, the statement of phnn_dekf_step over the engine's step methods.  xhat (B,n) and dhat (B,m)
+        float32, Pz (B,n+m,n+m) float64, u (B,m) or (B,1,m) the applied command, y (B,n) float32, tensors on the engine's
+        device; cost: its bounds clamp the command (None: no clamp) -- the model itself runs without bounds on c(u) + dhat.
+        -> dict(xhat, dhat, P, nis, innov, status); xhat, dhat and P are new tensors, the inputs keep their values."""
+        import torch
+        B, n, m = xhat.shape[0], engine.n, engine.m
+        opt = self.options(n, m) if opt is None else opt
+        cu = torch.as_tensor(u, dtype=torch.float32).to(engine.device).reshape(B, m)
+        if cost is not None and cost.has_u_bounds:
+            if cost.u_min > cost.u_max:
+                raise ValueError("u_min > u_max")
+            cu = torch.clamp(cu, float(cost.u_min), float(cost.u_max))  # a NaN stays NaN
+        row = (cu + dhat.reshape(B, m)).reshape(B, 1, m).contiguous()
+        _, traj = engine.rollout_cost(xhat, row, _capi.Cost(), integrator, dt, want_traj=True)  # a zero cost, no bounds
+        A, Bm, _ = engine.rollout_linearize(xhat, row, None, integrator, dt, traj=traj)
+        return engine.dekf_update(traj[:, 1].contiguous(), A.reshape(B, n, n), Bm.reshape(B, n, m), y, Pz.clone(),
+                                  dhat.clone().reshape(B, m), opt, log=log)
