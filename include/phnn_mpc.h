@@ -1106,6 +1106,66 @@ int phnn_dekf_step(phnn_handle* h, float* xhat_dev, float* dhat_dev, double* Pz_
 int phnn_dist_compensate(phnn_handle* h, const float* v_dev, int64_t v_stride, const float* dhat_dev, int64_t B,
                          const phnn_cost* cost, float* u_cmd_dev, int32_t* status_dev, void* stream);
 
+/* ---- batched unscented Kalman filter -----------------------------------------------------------------------
+ * The filter of phnn_ekf_* without a Jacobian: per problem the S = 2 n + 1 sigma points of (xhat, P) go through the real
+ * integrator step -- its activations and its control clamp included -- as B * S rollouts of K1 with H = 1, and the
+ * prediction is the weighted mean and covariance of their images.  n in {2, 3, 4}; xhat (B,n) float32, P (B,n,n) float64.
+ * The caller computes the weights of the scaled unscented transform in float64 and passes them; the library never sees
+ * alpha, beta or kappa:  lambda = alpha^2 (n + kappa) - n,  gamma = sqrt(n + lambda),  wm0 = lambda / (n + lambda),
+ * wc0 = wm0 + (1 - alpha^2 + beta),  wi = 1 / (2 (n + lambda)).  (alpha, beta, kappa) = (1, 0, 1) is the default of the
+ * Python layer: the sigma points are float32, and a small alpha sinks their spread into the rounding of xhat.
+ * Float64, no fused multiply-adds, sums in ascending index order (tests/ukf_model.py states both kernels):
+ *   k_ukf_sigma<n>    P = L L^T by columns from the LOWER triangle of P: d_j = P[j][j] - L[j][0]^2 - ..., L[j][j] =
+ *                     sqrt(d_j), L[i][j] = (P[i][j] - L[i][0] L[j][0] - ...) / L[j][j];  chi_0 = xhat (its own bits),
+ *                     chi_{1+c} = (float)(xhat + gamma L[:,c]),  chi_{1+n+c} = (float)(xhat - gamma L[:,c]), the product
+ *                     first, then the sum, one rounding.  A pivot with !(d > 0) or d = +inf, or an xhat that is not
+ *                     finite: every chi of the problem is a quiet NaN (K1 keeps it NaN, the update below reports status
+ *                     2).  P must be positive definite; an exactly singular P is such a failure.  The control rows
+ *                     (B,S,1,m) are u[b * u_stride + k] for every sigma point of problem b, unclamped: the clamp is K1's.
+ *   k_ukf_moments<n>  Y_k the image of sigma point k, widened:  x-_i = wm0 Y_0i + wi Y_1i + ... + wi Y_{S-1,i};
+ *                     e_k = Y_k - x- (the float64 mean);  Pm[i][j] = Pm[j][i] = wc0 (e_0i e_0j) + sum_{k>=1} wi (e_ki e_kj)
+ *                     (i <= j; the product of the deviations rounded first, then the weight times it, then the sum);
+ *                     xm = (float)x-.  It also writes the float32 identity (B,n,n).
+ *   then k_ekf_update above on (xm, A = that identity, P = Pm): it adds Qn, symmetrises, and updates with the measured
+ *   components; nis, innov, status, the dropped measurement and the empty mask are phnn_ekf_update's.
+ * Conventions as above: stream-ordered, capturable, no allocation, no synchronisation; B == 0 returns PHNN_OK with
+ * nothing launched; sizes are exact and inputs are never written.  PHNN_ERR_INVALID_ARG, nothing launched and no output
+ * touched: the refusals of phnn_ekf_step, and a gamma or wi that is not finite and positive, a wm0 or wc0 that is not
+ * finite; PHNN_ERR_UNSUPPORTED for n outside {2, 3, 4}. */
+#define PHNN_UKF_MAX_N 4 /* largest n with a k_ukf_sigma / k_ukf_moments */
+typedef struct {
+  uint32_t meas_mask;              /* bit i < n: state component i is measured */
+  double Qn[PHNN_UKF_MAX_N * PHNN_UKF_MAX_N]; /* additive process noise covariance, (n,n) row-major in the leading entries, finite */
+  double Rn[PHNN_UKF_MAX_N];       /* measurement noise variances, > 0 and finite where measured */
+  double gamma;                    /* sqrt(n + lambda): the spread of the sigma points, > 0 and finite */
+  double wm0;                      /* weight of sigma point 0 in the mean, finite */
+  double wc0;                      /* weight of sigma point 0 in the covariance, finite */
+  double wi;                       /* weight of every other sigma point, > 0 and finite */
+  int32_t reserved[4];             /* zero */
+} phnn_ukf_options;
+/* Bytes of the workspace of the step below: the sigma points (B,S,n), their control rows (B,S,1,m), K1's trajectory
+ * (B*S,2,n) and cost (B*S), xm (B,n) and the identity (B,n,n), each region 256-byte aligned.  0 for invalid arguments
+ * (B < 0, n outside {2, 3, 4}). */
+size_t phnn_ukf_workspace_bytes(const phnn_handle* h, int64_t B);
+/* k_ukf_sigma on its own: chi_dev (B,S,n) float32 and, when ctrl_dev is given, the control rows ctrl_dev (B,S,1,m) from
+ * u_dev[b * u_stride + k] (ctrl_dev == NULL: u_dev is not read and may be NULL).  Of opt, gamma is used. */
+int phnn_ukf_sigma(phnn_handle* h, const float* xhat_dev, const double* P_dev, const float* u_dev, int64_t u_stride,
+                   int64_t B, const phnn_ukf_options* opt, float* chi_dev, float* ctrl_dev, void* stream);
+/* k_ukf_moments on its own: image k of problem b is Y_dev[(b * S + k) * Y_stride + i], i < n (Y_stride = 2 n and
+ * Y_dev = traj + n read row 1 of a (B*S,2,n) trajectory in place).  xm_dev (B,n) float32, Pm_dev (B,n,n) float64,
+ * eye_dev (B,n,n) float32 or NULL.  Of opt, wm0, wc0 and wi are used. */
+int phnn_ukf_moments(phnn_handle* h, const float* Y_dev, int64_t Y_stride, int64_t B, const phnn_ukf_options* opt,
+                     float* xm_dev, double* Pm_dev, float* eye_dev, void* stream);
+/* One filter step through the learned model: xhat_dev (B,n) and P_dev (B,n,n) in/out; u, y, cost, integrator, dt, nis,
+ * innov, status and log as in phnn_ekf_step (cost is read for has_u_bounds / u_min / u_max only, NULL = no clamp).  Four
+ * launches in stream order and nothing else: k_ukf_sigma, K1 with H = 1 on the B * S sigma points on the path of the
+ * forward rollout above (its trajectory into the workspace), k_ukf_moments on row 1 of that trajectory (Pm into P_dev),
+ * k_ekf_update with the identity.  workspace_dev: the bytes of the size query above, required when B > 0. */
+int phnn_ukf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u_dev, int64_t u_stride, const float* y_dev,
+                  int64_t y_stride, int64_t B, const phnn_cost* cost, int32_t integrator, float dt,
+                  const phnn_ukf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                  const phnn_ekf_log* log, void* workspace_dev, void* stream);
+
 /* Introspection for tests: copies the packed weight image the kernels stage into LDS (phnn_kernels.hip.h layouts; a
  * device-resident private format) to image_host after the work queued on `stream`, and waits for the copy.
  * *image_floats (may be NULL) receives its size; image_host == NULL only queries the size. */

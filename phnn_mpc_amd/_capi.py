@@ -40,6 +40,7 @@ EXPORTED = [
     "phnn_gn_direction_box", "phnn_solve_gn_ex",
     "phnn_ekf_workspace_bytes", "phnn_ekf_update", "phnn_ekf_step",
     "phnn_dekf_workspace_bytes", "phnn_dekf_update", "phnn_dekf_step", "phnn_dist_compensate",
+    "phnn_ukf_workspace_bytes", "phnn_ukf_sigma", "phnn_ukf_moments", "phnn_ukf_step",
     "phnn_feedback_workspace_bytes", "phnn_feedback_plan", "phnn_feedback_control",
     "phnn_rollout_vjp_ref", "phnn_terminal_cost", "phnn_dare", "phnn_gn_direction_term", "phnn_solve_term",
     "phnn_solve_gn_term",
@@ -152,6 +153,17 @@ class DekfLog(C.Structure):
     """phnn_dekf_log: phnn_ekf_log's fields, then log_dhat (T+1,B,m) float32, row step + 1."""
     _fields_ = [("log_xhat_dev", C.c_void_p), ("log_nis_dev", C.c_void_p), ("step_dev", C.c_void_p), ("step_host", C.c_int32),
                 ("log_dhat_dev", C.c_void_p)]
+
+
+PHNN_UKF_MAX_N = 4  # largest n with a k_ukf_sigma / k_ukf_moments
+
+
+class UkfOptions(C.Structure):
+    """phnn_ukf_options: meas_mask, Qn and Rn as in EkfOptions (at most 4 state components); gamma = sqrt(n + lambda) the
+    spread of the sigma points, wm0 / wc0 the weights of sigma point 0 in the mean / the covariance, wi the weight of
+    every other one -- computed by the caller in float64 (estimation.UKF.options)."""
+    _fields_ = [("meas_mask", C.c_uint32), ("Qn", C.c_double * (PHNN_UKF_MAX_N * PHNN_UKF_MAX_N)), ("Rn", C.c_double * PHNN_UKF_MAX_N),
+                ("gamma", C.c_double), ("wm0", C.c_double), ("wc0", C.c_double), ("wi", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
 class EkfLog(C.Structure):
@@ -407,6 +419,16 @@ def load_library():
     lib.phnn_dekf_step.restype = C.c_int
     lib.phnn_dist_compensate.argtypes = [vp, f32p, i64, f32p, i64, C.POINTER(Cost), f32p, vp, vp]
     lib.phnn_dist_compensate.restype = C.c_int
+    uko = C.POINTER(UkfOptions)
+    lib.phnn_ukf_workspace_bytes.argtypes = [vp, i64]
+    lib.phnn_ukf_workspace_bytes.restype = C.c_size_t
+    lib.phnn_ukf_sigma.argtypes = [vp, f32p, vp, f32p, i64, i64, uko, f32p, f32p, vp]
+    lib.phnn_ukf_sigma.restype = C.c_int
+    lib.phnn_ukf_moments.argtypes = [vp, f32p, i64, i64, uko, f32p, vp, f32p, vp]
+    lib.phnn_ukf_moments.restype = C.c_int
+    lib.phnn_ukf_step.argtypes = [vp, f32p, vp, f32p, i64, f32p, i64, i64, C.POINTER(Cost), i32, C.c_float, uko, vp, vp, vp,
+                                  ekl, vp, vp]
+    lib.phnn_ukf_step.restype = C.c_int
     lib.phnn_feedback_workspace_bytes.argtypes = [vp, i64, i32]
     lib.phnn_feedback_workspace_bytes.restype = C.c_size_t
     lib.phnn_feedback_plan.argtypes = [vp, f32p, f32p, i64, i32, C.POINTER(Cost), i32, C.c_float, C.POINTER(TvlqrOptions), vp,

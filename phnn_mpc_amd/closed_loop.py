@@ -29,6 +29,8 @@
                          ekf_status (B,), the last step's.  An estimation.DisturbanceEKF also estimates an input
                          disturbance d (phnn_dekf_step): the result gains disturbances (T+1,B,m), and with
                          its compensate the plant is handed c(c(v) - dhat) (phnn_dist_compensate) instead of the command v.
+                         An estimation.UKF is the unscented filter on the same state (xhat, P) (phnn_ukf_step; DESIGN.md
+                         24): the same results, the step goes through the sigma points instead of a Jacobian.
   track                  (all three drivers, track=) a feedback.Tracking: the solve runs every solve_every-th control step
                          only, and every step applies row step % solve_every of the last plan plus the time-varying LQR
                          feedback on the deviation from its nominal trajectory (phnn_feedback_plan, phnn_feedback_control;
@@ -477,6 +479,9 @@ class DeviceClosedLoop:
         self.augmented = hasattr(est, "compensate")  # an estimation.DisturbanceEKF: the state of the filter is (x, d)
         if self.augmented and not hasattr(eng, "dekf_step"):
             raise NotImplementedError(f"{type(eng).__name__} has no batched disturbance filter step (RolloutEngine has)")
+        self.unscented = getattr(est, "unscented", False)  # an estimation.UKF: the same state (xhat, P), another step
+        if self.unscented and not hasattr(eng, "ukf_step"):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched unscented filter step (RolloutEngine has)")
         if self.augmented:
             xh0, dh0, P0 = est.initial(x0, eng.m)
             k["dhat"] = torch.tensor(dh0, device=dev)
@@ -522,9 +527,10 @@ class DeviceClosedLoop:
                                self.ekf_opt, nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"],
                                log=self.ekf_log, workspace=self.ekf_ws)
             return
-        self.eng.ekf_step(self.xhat32, self.P, u, stride, self.y32, self.ekf_cost, c.integrator, c.dt, self.ekf_opt,
-                          nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"], log=self.ekf_log,
-                          workspace=self.ekf_ws)
+        step = self.eng.ukf_step if self.unscented else self.eng.ekf_step  # the same arguments, another workspace
+        step(self.xhat32, self.P, u, stride, self.y32, self.ekf_cost, c.integrator, c.dt, self.ekf_opt,
+             nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"], log=self.ekf_log,
+             workspace=self.ekf_ws)
 
     def _scenario(self, sc, log):
         """Fills self.ex (phnn_plant_ex) from a PlantScenario."""

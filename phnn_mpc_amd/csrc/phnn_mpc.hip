@@ -21,6 +21,7 @@
 #include "phnn_gn.h"
 #include "phnn_ekf.h"
 #include "phnn_dekf.h"
+#include "phnn_ukf.h"
 #include "phnn_feedback.h"
 #include "phnn_terminal.h"
 #include "phnn_pack.h"
@@ -2353,6 +2354,101 @@ int phnn_dist_compensate(phnn_handle* h, const float* v_dev, int64_t v_stride, c
   DistCompensateParams p{v_dev, (long long)v_stride, dhat_dev, u_cmd_dev, status_dev, (long long)B, h->desc.m,
                          cost ? cost->has_u_bounds : 0, cost ? cost->u_min : 0.f, cost ? cost->u_max : 0.f};
   return checked(h, dist_compensate_launch(p, (hipStream_t)stream), "k_dist_compensate launch");
+}
+
+// ---- batched unscented Kalman filter: kernels in phnn_ukf.hip --------------------------------------------
+// The checks that the three entry points share; on success *e holds the options k_ekf_update takes.
+static int check_ukf(phnn_handle* h, int64_t B, const phnn_ukf_options* o, const phnn_ekf_log* log, phnn_ekf_options* e) {
+  if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
+  if (!o) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_options is NULL");
+  if (!ekf_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no unscented Kalman filter kernel for this n");
+  const int n = h->desc.n;
+  if (!(o->gamma > 0.0) || !std::isfinite(o->gamma) || !(o->wi > 0.0) || !std::isfinite(o->wi))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_options: gamma and wi must be positive and finite");
+  if (!std::isfinite(o->wm0) || !std::isfinite(o->wc0)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_options: wm0 / wc0 is not finite");
+  for (int r : o->reserved)
+    if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_options: reserved must be zero");
+  *e = phnn_ekf_options{};
+  e->meas_mask = o->meas_mask;
+  for (int i = 0; i < n * n; ++i) e->Qn[i] = o->Qn[i];
+  for (int i = 0; i < n; ++i) e->Rn[i] = o->Rn[i];
+  return check_ekf(h, B, e, log);
+}
+
+size_t phnn_ukf_workspace_bytes(const phnn_handle* h, int64_t B) {
+  if (!h || B < 0 || !ekf_supported(h)) return 0;
+  return std::max<size_t>(ukf_layout(B, h->desc.n, h->desc.m).total, 256);
+}
+
+int phnn_ukf_sigma(phnn_handle* h, const float* xhat_dev, const double* P_dev, const float* u_dev, int64_t u_stride,
+                   int64_t B, const phnn_ukf_options* opt, float* chi_dev, float* ctrl_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  phnn_ekf_options e;
+  if (int rc = check_ukf(h, B, opt, nullptr, &e)) return rc;
+  if (u_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_sigma: negative stride");
+  if (B == 0) return PHNN_OK;
+  if (!xhat_dev || !P_dev || !chi_dev || (ctrl_dev && !u_dev)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_sigma: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  const UkfSigmaParams p{xhat_dev, P_dev, u_dev, (long long)u_stride, chi_dev, ctrl_dev, (long long)B, h->desc.m, opt->gamma};
+  return checked(h, ukf_sigma_launch(h->desc.n, p, (hipStream_t)stream), "k_ukf_sigma launch");
+}
+
+int phnn_ukf_moments(phnn_handle* h, const float* Y_dev, int64_t Y_stride, int64_t B, const phnn_ukf_options* opt,
+                     float* xm_dev, double* Pm_dev, float* eye_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  phnn_ekf_options e;
+  if (int rc = check_ukf(h, B, opt, nullptr, &e)) return rc;
+  if (Y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_moments: negative stride");
+  if (B == 0) return PHNN_OK;
+  if (!Y_dev || !xm_dev || !Pm_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_moments: NULL tensor");
+  PHNN_ON_DEVICE(h);
+  const UkfMomentsParams p{Y_dev, (long long)Y_stride, xm_dev, Pm_dev, eye_dev, (long long)B, opt->wm0, opt->wc0, opt->wi};
+  return checked(h, ukf_moments_launch(h->desc.n, p, (hipStream_t)stream), "k_ukf_moments launch");
+}
+
+int phnn_ukf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u_dev, int64_t u_stride, const float* y_dev,
+                  int64_t y_stride, int64_t B, const phnn_cost* cost, int32_t integrator, float dt,
+                  const phnn_ukf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
+                  const phnn_ekf_log* log, void* workspace_dev, void* stream) {
+  if (!h) return PHNN_ERR_INVALID_ARG;
+  phnn_ekf_options e;
+  if (int rc = check_ukf(h, B, opt, log, &e)) return rc;
+  if (u_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_step: negative stride");
+  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
+  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
+  phnn_cost bounds = neutral_cost();  // what K1 takes from the cost: the clamp
+  if (cost) {
+    if (int rc = check_cost(h, cost)) return rc;
+    bounds.has_u_bounds = cost->has_u_bounds;
+    bounds.u_min = cost->u_min;
+    bounds.u_max = cost->u_max;
+  }
+  if (B == 0) return PHNN_OK;
+  if (!xhat_dev || !P_dev || !u_dev || !status_dev || !workspace_dev || (opt->meas_mask && !y_dev))
+    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_step: NULL tensor");
+  const int n = h->desc.n, m = h->desc.m;
+  const int64_t S = 2 * n + 1;
+  const UkfLayout l = ukf_layout(B, n, m);
+  char* ws = (char*)workspace_dev;
+  float* chi = (float*)(ws + l.chi);
+  float* ctrl = (float*)(ws + l.ctrl);
+  float* traj = (float*)(ws + l.traj);
+  float* xm = (float*)(ws + l.xm);
+  float* eye = (float*)(ws + l.eye);
+  {
+    PHNN_ON_DEVICE(h);
+    const UkfSigmaParams p{xhat_dev, P_dev, u_dev, (long long)u_stride, chi, ctrl, (long long)B, m, opt->gamma};
+    if (int rc = checked(h, ukf_sigma_launch(n, p, (hipStream_t)stream), "k_ukf_sigma launch")) return rc;
+  }
+  if (int rc = rollout_fwd(h, chi, ctrl, B * S, 1, &bounds, integrator, dt, (float*)(ws + l.cost), traj, nullptr, nullptr, stream))
+    return rc;
+  PHNN_ON_DEVICE(h);
+  // the covariance of the images goes where k_ekf_update reads and writes its P: k_ukf_sigma has read P by then
+  const UkfMomentsParams q{traj + n, 2 * n, xm, P_dev, eye, (long long)B, opt->wm0, opt->wc0, opt->wi};
+  if (int rc = checked(h, ukf_moments_launch(n, q, (hipStream_t)stream), "k_ukf_moments launch")) return rc;
+  const EkfUpdateParams p = ekf_update_params(h, xm, n, eye, y_dev, y_stride, B, &e, P_dev, xhat_dev, nis_dev, innov_dev,
+                                              status_dev, log);
+  return checked(h, ekf_update_launch(n, p, (hipStream_t)stream), "k_ekf_update launch");
 }
 
 // ---- tracking the plan between solves: kernel in phnn_feedback.hip -------------------------------------

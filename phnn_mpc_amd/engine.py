@@ -1207,6 +1207,70 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return u_cmd, status
 
+    # ------------------------------------------------------------------ unscented Kalman filter
+    def ukf_workspace_bytes(self, B):
+        return int(self.lib.phnn_ukf_workspace_bytes(self.h, int(B)))
+
+    def ukf_sigma(self, xhat, P, opt, u=None, u_stride=None, chi=None, ctrl=None):
+        """k_ukf_sigma on its own: the S = 2 n + 1 sigma points of (xhat (B,n) float32, P (B,n,n) float64, lower triangle
+        read) with the spread opt.gamma (_capi.UkfOptions) -> (chi (B,S,n) float32, ctrl).  With u (float32, problem b's
+        control at u.view(-1)[b * u_stride + k], default stride m) the control rows ctrl (B,S,1,m) are written too, else
+        ctrl is None.  A problem whose P is not positive definite or whose xhat is not finite has NaN sigma points."""
+        self._assert_device_f32(xhat, u, chi, ctrl)
+        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
+        B, S = xhat.shape[0], 2 * self.n + 1
+        assert xhat.numel() == B * self.n and P.numel() == B * self.n * self.n
+        if chi is None:
+            chi = torch.empty(B, S, self.n, dtype=torch.float32, device=self.device)
+        if ctrl is None and u is not None:
+            ctrl = torch.empty(B, S, 1, self.m, dtype=torch.float32, device=self.device)
+        assert chi.numel() == B * S * self.n and (ctrl is None or ctrl.numel() == B * S * self.m)
+        rc = self.lib.phnn_ukf_sigma(self.h, self._p(xhat), self._p(P), self._p(u), self.m if u_stride is None else int(u_stride),
+                                     B, C.byref(opt), self._p(chi), self._p(ctrl), self._stream())
+        _check(self.lib, self.h, rc)
+        return chi, ctrl
+
+    def ukf_moments(self, Y, B, opt, Y_stride=None, xm=None, Pm=None, eye=True):
+        """k_ukf_moments on its own: the weighted mean and covariance of the images of B problems' sigma points with the
+        weights opt.wm0, opt.wc0, opt.wi.  Y: float32, image k of problem b at Y.view(-1)[(b * S + k) * Y_stride + i]
+        (default stride n: a (B,S,n) tensor).  eye: True = allocate, False = skip, or a (B,n,n) float32 tensor.
+        -> dict(xm (B,n) float32, Pm (B,n,n) float64, eye (B,n,n) float32 identity or None)."""
+        self._assert_device_f32(Y, xm)
+        n = self.n
+        if xm is None:
+            xm = torch.empty(B, n, dtype=torch.float32, device=self.device)
+        if Pm is None:
+            Pm = torch.empty(B, n, n, dtype=torch.float64, device=self.device)
+        eye = torch.empty(B, n, n, dtype=torch.float32, device=self.device) if eye is True else (None if eye is False else eye)
+        self._assert_device_f32(eye)
+        assert Pm.dtype == torch.float64 and Pm.is_contiguous() and Pm.device == self.device
+        assert xm.numel() == B * n and Pm.numel() == B * n * n and (eye is None or eye.numel() == B * n * n)
+        rc = self.lib.phnn_ukf_moments(self.h, self._p(Y), n if Y_stride is None else int(Y_stride), int(B), C.byref(opt),
+                                       self._p(xm), self._p(Pm), self._p(eye), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(xm=xm, Pm=Pm, eye=eye)
+
+    def ukf_step(self, xhat, P, u, u_stride, y, cost, integrator, dt, opt, nis=True, innov=False, status=None, log=None,
+                 workspace=None, y_stride=None):
+        """phnn_ukf_step: one step of the unscented filter as ONE library call -- k_ukf_sigma, K1 with H = 1 on the
+        B * (2 n + 1) sigma points, k_ukf_moments, k_ekf_update with the identity -- IN PLACE on xhat (B,n) float32 and P
+        (B,n,n) float64.  The arguments are ekf_step's, opt a _capi.UkfOptions.  -> dict(xhat, P, nis, innov, status)."""
+        self._assert_device_f32(xhat, u, y)
+        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
+        B = xhat.shape[0]
+        ws = {} if workspace is None else workspace
+        if ws.get("ukf_key") != B:
+            ws["ukf_key"] = B
+            ws["ukf"] = torch.empty(max(self.ukf_workspace_bytes(B), 256), dtype=torch.uint8, device=self.device)
+        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
+        lg = self._ekf_log(log)
+        rc = self.lib.phnn_ukf_step(self.h, self._p(xhat), self._p(P), self._p(u), int(u_stride), self._p(y),
+                                    self.n if y_stride is None else int(y_stride), B, C.byref(cost) if cost is not None else None,
+                                    self._integ(integrator), float(dt), C.byref(opt), self._p(nis), self._p(innov),
+                                    self._p(status), None if lg is None else C.byref(lg), self._p(ws["ukf"]), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(xhat=xhat, P=P, nis=nis, innov=innov, status=status)
+
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,
                    step=0, step_dev=None, log_states=None, log_controls=None, ex=None, metrics=None):

@@ -15,6 +15,11 @@ phnn_ekf_step).
              lets the closed loops take dhat off the command (phnn_dist_compensate): offset-free control against a
              constant force bias.
 
+  UKF        the unscented filter on the same state (xhat, P): no Jacobian -- the 2 n + 1 sigma points of (xhat, P) go
+             through the real integrator step, clamp and activations included, as K1 rollouts, and the prediction is
+             their weighted mean and covariance (phnn_ukf_sigma, phnn_ukf_moments, phnn_ukf_step).
+  from_config  the estimator of a config's `estimator:` section, whatever its type.
+
 The closed-loop drivers (closed_loop.run_mpc_batch, DeviceClosedLoop, run_mpc_batch_device) take estimator=EKF(...): the
 controller then solves from the estimate instead of the raw measurement.
 """
@@ -195,3 +200,94 @@ class DisturbanceEKF(EKF):
         A, Bm, _ = engine.rollout_linearize(xhat, row, None, integrator, dt, traj=traj)
         return engine.dekf_update(traj[:, 1].contiguous(), A.reshape(B, n, n), Bm.reshape(B, n, m), y, Pz.clone(),
                                   dhat.clone().reshape(B, m), opt, log=log)
+
+
+class UKF(EKF):
+    """Unscented Kalman filter with additive process noise on the EKF's state (xhat (B,n) float32, P (B,n,n) float64),
+    n in {2, 3, 4}.  measured, Qn, Rn, P0, x0_hat, log: as in EKF.  alpha, beta, kappa: the scaled unscented transform,
+    lambda = alpha^2 (n + kappa) - n, gamma = sqrt(n + lambda), wm0 = lambda / (n + lambda), wc0 = wm0 + (1 - alpha^2 +
+    beta), wi = 1 / (2 (n + lambda)), computed here in float64; the library sees gamma and the weights only.
+
+    The defaults (1, 0, 1) are deliberate and not the textbook alpha = 1e-3: the sigma points and their images are
+    float32 (K1 is), and with a small alpha the spread gamma sqrt(P) sinks into the rounding of xhat.  Deviation of P
+    from the Kalman filter's P on a linear system (n = 4, positions measured, 60 steps of
+    tests/ekf_model.consistency_system, CPU model of the kernels):
+        (alpha, beta, kappa) = (1, 0, 1)      3.0e-7
+                               (0.1, 2, 0)    3.6e-6
+                               (1e-3, 2, 0)   4.2e-1
+    P must stay positive definite: a problem whose P has no Cholesky factor ends its step with status 2 and NaN."""
+
+    def __init__(self, measured=(0, 1), Qn=1e-6, Rn=1e-4, P0=1e-2, x0_hat=None, log=True, alpha=1.0, beta=0.0, kappa=1.0):
+        super().__init__(measured=measured, Qn=Qn, Rn=Rn, P0=P0, x0_hat=x0_hat, log=log)
+        self.alpha, self.beta, self.kappa = float(alpha), float(beta), float(kappa)
+        self.unscented = True  # what the closed-loop drivers tell this filter by
+
+    def weights(self, n):
+        """-> (gamma, wm0, wc0, wi) in float64 for n state components."""
+        a2 = self.alpha * self.alpha
+        lam = a2 * (n + self.kappa) - n
+        c = n + lam
+        if not (np.isfinite(c) and c > 0.0):
+            raise ValueError(f"alpha = {self.alpha}, kappa = {self.kappa}: n + lambda = {c} must be positive and finite")
+        wm0 = lam / c
+        return float(np.sqrt(c)), float(wm0), float(wm0 + (1.0 - a2 + self.beta)), float(1.0 / (2.0 * c))
+
+    def options(self, n):
+        """-> _capi.UkfOptions (phnn_ukf_options) for an n-state model."""
+        if n > _capi.PHNN_UKF_MAX_N:
+            raise ValueError(f"n = {n}: the unscented filter holds at most {_capi.PHNN_UKF_MAX_N} state components")
+        e = super().options(n)
+        o = _capi.UkfOptions()
+        o.meas_mask = e.meas_mask
+        for i in range(n * n):
+            o.Qn[i] = e.Qn[i]
+        for i in range(n):
+            o.Rn[i] = e.Rn[i]
+        o.gamma, o.wm0, o.wc0, o.wi = self.weights(n)
+        return o
+
+    def initial(self, x0, n=None):
+        """EKF.initial; a P0 that is not positive definite is refused (the filter factors P at every step)."""
+        xh, P = super().initial(x0, n)
+        if P.shape[0]:
+            try:
+                np.linalg.cholesky(P[0])
+            except np.linalg.LinAlgError:
+                raise ValueError("P0 must be positive definite") from None
+        return xh, P
+
+    def step(self, engine, xhat, P, u, y, cost, integrator, dt, opt=None, log=None):
+        """One filter step, the statement of phnn_ukf_step over the engine's methods (ukf_sigma, rollout_cost,
+        ukf_moments, ekf_update); arguments and result as in EKF.step."""
+        import torch
+        B, n, m = xhat.shape[0], engine.n, engine.m
+        S = 2 * n + 1
+        opt = self.options(n) if opt is None else opt
+        row = torch.as_tensor(u, dtype=torch.float32).to(engine.device).reshape(B, m).contiguous()
+        bounds = _capi.Cost()  # what the prediction takes from the cost: the clamp
+        if cost is not None:
+            bounds.has_u_bounds, bounds.u_min, bounds.u_max = cost.has_u_bounds, cost.u_min, cost.u_max
+        chi, ctrl = engine.ukf_sigma(xhat, P, opt, u=row)
+        _, traj = engine.rollout_cost(chi.reshape(B * S, n), ctrl.reshape(B * S, 1, m), bounds, integrator, dt, want_traj=True)
+        mo = engine.ukf_moments(traj[:, 1].contiguous(), B, opt)
+        e = _capi.EkfOptions()  # the update's share of the options
+        e.meas_mask = opt.meas_mask
+        for i in range(n * n):
+            e.Qn[i] = opt.Qn[i]
+        for i in range(n):
+            e.Rn[i] = opt.Rn[i]
+        return engine.ekf_update(mo["xm"], mo["eye"], y, mo["Pm"], e, log=log)
+
+
+def from_config(config):
+    """The estimator of the optional `estimator:` section of a config dict, or None without one: a UKF for type "ukf"
+    (keys: the EKF's plus alpha, beta, kappa), every other section is EKF.from_config's."""
+    sec = config.get("estimator")
+    if sec is None or str(dict(sec).get("type", "ekf")).lower() != "ukf":
+        return EKF.from_config(config)
+    sec = dict(sec)
+    sec.pop("type")
+    unknown = set(sec) - {"measured", "Qn", "Rn", "P0", "x0_hat", "log", "alpha", "beta", "kappa"}
+    if unknown:
+        raise ValueError(f"estimator: unknown key(s) {sorted(unknown)}")
+    return UKF(**sec)
