@@ -248,16 +248,11 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
     if estimator is not None:
         import torch
         eng = controller.engine
-        augmented = hasattr(estimator, "compensate")  # an estimation.DisturbanceEKF: the state of the filter is (x, d)
-        if augmented:
-            xh0, dh0, P0 = estimator.initial(x, eng.m)
-            dhat, disturbances = torch.tensor(dh0, device=eng.device), [dh0]
-            ekf_opt, ekf_cost = estimator.options(eng.n, eng.m), controller._cost()  # the bounds of the command's clamps
-        else:
-            xh0, P0 = estimator.initial(x)
-            ekf_opt, ekf_cost = estimator.options(eng.n), (None if canonical else controller._cost())
-        xhat, P = torch.tensor(xh0, device=eng.device), torch.tensor(P0, device=eng.device)
-        estimates, nis, ekf_status = [xh0], [], None
+        start = estimator.start(x, eng.n, eng.m)
+        filt = {name: torch.tensor(v, device=eng.device) for name, v in start.items()}  # the state of the running filter
+        ekf_opt, ekf_cost = estimator.bind(eng.n, eng.m), estimator.filter_cost(controller._cost(), canonical)
+        estimates, nis, ekf_status = [start["xhat"]], [], None
+        extra = {name: [start[name]] for name in estimator.log_rows}
     if track is not None:
         import torch
         eng = controller.engine
@@ -268,7 +263,7 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
         if x_ref is not None:
             rkw.update(x_ref=x_ref, ref_offset=step)
         if estimator is not None:
-            x32 = xhat.cpu().numpy()
+            x32 = filt["xhat"].cpu().numpy()
         else:
             x32 = simulator.measurement() if measured else x.astype(np.float32)
         if track is not None:
@@ -285,9 +280,9 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
             u, u_prev, _ = controller.control_batch(x32, u_prev, **rkw)
         else:
             u = controller.compute_control_batch(x32, **rkw)
-        if estimator is not None and augmented and estimator.compensate:  # the plant is handed c(c(v) - dhat)
+        if estimator is not None and estimator.compensate:  # the plant is handed c(c(v) - dhat)
             v = torch.as_tensor(np.ascontiguousarray(np.asarray(u, dtype=np.float32).reshape(B, -1))).to(eng.device)
-            u = eng.dist_compensate(v, eng.m, dhat, ekf_cost)[0].cpu().numpy()
+            u = eng.dist_compensate(v, eng.m, filt["dhat"], ekf_cost)[0].cpu().numpy()
         x, done = simulator.step(u)
         newly = done & (done_step < 0)
         done_step[newly] = step
@@ -297,15 +292,13 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
             dist.append(simulator.disturbance.copy())
         if estimator is not None:  # the filter advances with the control the plant applied and the new measurement
             y32 = simulator.measurement() if measured else x.astype(np.float32)
-            state = (xhat, dhat, P) if augmented else (xhat, P)
-            r = estimator.step(eng, *state, torch.as_tensor(np.asarray(u, dtype=np.float32).reshape(B, -1)),
+            r = estimator.step(eng, *filt.values(), torch.as_tensor(np.asarray(u, dtype=np.float32).reshape(B, -1)),
                                torch.tensor(np.ascontiguousarray(y32, dtype=np.float32), device=eng.device), ekf_cost,
                                controller.integrator, controller.dt, opt=ekf_opt)
-            xhat, P, ekf_status = r["xhat"], r["P"], r["status"]
-            if augmented:
-                dhat = r["dhat"]
-                disturbances.append(dhat.cpu().numpy())
-            estimates.append(xhat.cpu().numpy())
+            filt, ekf_status = {name: r[name] for name in filt}, r["status"]
+            for name, rows in extra.items():
+                rows.append(filt[name].cpu().numpy())
+            estimates.append(filt["xhat"].cpu().numpy())
             nis.append(r["nis"].cpu().numpy())
     out = {"states": np.stack(states), "controls": np.stack(controls), "done_step": done_step}
     if dist:
@@ -313,8 +306,7 @@ def run_mpc_batch(simulator, controller, initial_states, num_steps, x_ref=None, 
     if estimator is not None:
         out.update(estimates=np.stack(estimates), nis=np.stack(nis) if nis else np.zeros((0, B)),
                    ekf_status=None if ekf_status is None else ekf_status.cpu().numpy().astype(np.int64))
-        if augmented:
-            out["disturbances"] = np.stack(disturbances)
+        out.update({key: np.stack(extra[name]) for name, key in estimator.log_rows.items()})
     if track is not None:
         kept = track.log
         out.update(track_status=(np.stack(track_status) if track_status else np.zeros((0, B), np.int64)) if kept else None,
@@ -439,6 +431,7 @@ class DeviceClosedLoop:
         if metrics:
             self._metrics(STABILITY_DEFAULTS if metrics is True else metrics, x)
         self.ekf = estimator
+        self.comp = None  # the command the plant takes when a filter's dhat is taken off it
         if estimator is not None:
             self._estimator(estimator, x)
         self.track = track
@@ -473,31 +466,18 @@ class DeviceClosedLoop:
         if self.plant.dt != float(self.ctl.dt):  # the filter predicts over the controller's dt, as the solve does
             raise ValueError(f"estimator: the plant's dt ({self.plant.dt}) differs from the controller's ({self.ctl.dt}); "
                              "the filter's one-step prediction would cover another interval than the plant stepped")
-        if not hasattr(eng, "ekf_step"):
-            raise NotImplementedError(f"{type(eng).__name__} has no batched filter step (RolloutEngine has)")
+        if not hasattr(eng, est.engine_step):
+            raise NotImplementedError(f"{type(eng).__name__} has no batched filter step {est.engine_step} (RolloutEngine has)")
         dev = eng.device
-        self.augmented = hasattr(est, "compensate")  # an estimation.DisturbanceEKF: the state of the filter is (x, d)
-        if self.augmented and not hasattr(eng, "dekf_step"):
-            raise NotImplementedError(f"{type(eng).__name__} has no batched disturbance filter step (RolloutEngine has)")
-        self.unscented = getattr(est, "unscented", False)  # an estimation.UKF: the same state (xhat, P), another step
-        if self.unscented and not hasattr(eng, "ukf_step"):
-            raise NotImplementedError(f"{type(eng).__name__} has no batched unscented filter step (RolloutEngine has)")
-        if self.augmented:
-            xh0, dh0, P0 = est.initial(x0, eng.m)
-            k["dhat"] = torch.tensor(dh0, device=dev)
-            self.comp = None  # the command the plant takes when dhat is taken off it
-            if est.compensate:
-                k["u_cmd"] = torch.zeros(B, eng.m, dtype=torch.float32, device=dev)
-                self.comp = k["u_cmd"]
-        else:
-            xh0, P0 = est.initial(x0)
+        # the state of the running filter by est.state_names, updated in place by the engine's step
+        self.filt = {name: torch.tensor(v, device=dev) for name, v in est.start(x0, eng.n, eng.m).items()}
+        if est.compensate:
+            k["u_cmd"] = torch.zeros(B, eng.m, dtype=torch.float32, device=dev)
+            self.comp = k["u_cmd"]
         self.y32 = self.x32  # the plant keeps writing its measurement here
-        self.x32 = self.xhat32 = torch.tensor(xh0, device=dev)  # what every solve reads: the estimate
-        self.P = torch.tensor(P0, device=dev)
-        self.ekf_opt = est.options(eng.n, eng.m) if self.augmented else est.options(eng.n)
-        self.ekf_cost = None if self.canonical else self.cost  # the plant's clamp: the canonical sequence is clamped already
-        if self.augmented:
-            self.ekf_cost = self.cost  # the bounds of the command's clamps, in the compensation and in the filter
+        self.x32 = self.xhat32 = self.filt["xhat"]  # what every solve reads: the estimate
+        self.ekf_opt = est.bind(eng.n, eng.m)
+        self.ekf_cost = est.filter_cost(self.cost, self.canonical)
         k["ekf_status"] = torch.zeros(B, dtype=torch.int32, device=dev)
         k["ekf_nis"] = torch.empty(B, dtype=torch.float64, device=dev)
         self.ekf_ws = {}  # the device buffer of the filter step, kept across steps
@@ -507,30 +487,24 @@ class DeviceClosedLoop:
             k["estimates"][0].copy_(self.xhat32)
             k["nis"] = torch.empty(self.T, B, dtype=torch.float64, device=dev)
             self.ekf_log = dict(log_xhat=k["estimates"], log_nis=k["nis"], step_dev=self.step_dev)
-            if self.augmented:
-                k["disturbances"] = torch.empty(self.T + 1, B, eng.m, dtype=torch.float32, device=dev)
-                k["disturbances"][0].copy_(k["dhat"])
-                self.ekf_log["log_dhat"] = k["disturbances"]
+            for name, key in est.log_rows.items():
+                k[key] = torch.empty(self.T + 1, *self.filt[name].shape, dtype=self.filt[name].dtype, device=dev)
+                k[key][0].copy_(self.filt[name])
+                self.ekf_log["log_" + name] = k[key]
 
     def _applied(self, v, stride):
         """The control the plant takes and its stride: the command v itself, or with a compensating DisturbanceEKF
         c(c(v) - dhat), written by engine.dist_compensate into a (B,m) buffer."""
-        if self.ekf is None or not self.augmented or self.comp is None:
+        if self.comp is None:
             return v, stride
-        self.eng.dist_compensate(v, stride, self._keep["dhat"], self.ekf_cost, u_cmd=self.comp)
+        self.eng.dist_compensate(v, stride, self.filt["dhat"], self.ekf_cost, u_cmd=self.comp)
         return self.comp, self.eng.m
 
     def _ekf_step(self, u, stride):
         c = self.ctl
-        if self.augmented:
-            self.eng.dekf_step(self.xhat32, self._keep["dhat"], self.P, u, stride, self.y32, self.ekf_cost, c.integrator, c.dt,
-                               self.ekf_opt, nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"],
-                               log=self.ekf_log, workspace=self.ekf_ws)
-            return
-        step = self.eng.ukf_step if self.unscented else self.eng.ekf_step  # the same arguments, another workspace
-        step(self.xhat32, self.P, u, stride, self.y32, self.ekf_cost, c.integrator, c.dt, self.ekf_opt,
-             nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"], log=self.ekf_log,
-             workspace=self.ekf_ws)
+        getattr(self.eng, self.ekf.engine_step)(
+            *self.filt.values(), u, stride, self.y32, self.ekf_cost, c.integrator, c.dt, self.ekf_opt,
+            nis=self._keep["ekf_nis"], innov=False, status=self._keep["ekf_status"], log=self.ekf_log, workspace=self.ekf_ws)
 
     def _scenario(self, sc, log):
         """Fills self.ex (phnn_plant_ex) from a PlantScenario."""
@@ -711,8 +685,7 @@ class DeviceClosedLoop:
             out.update(estimates=self._keep["estimates"].cpu().numpy() if kept else None,
                        nis=self._keep["nis"].cpu().numpy() if kept else None,
                        ekf_status=self._keep["ekf_status"].cpu().numpy().astype(np.int64))
-            if self.augmented:
-                out["disturbances"] = self._keep["disturbances"].cpu().numpy() if kept else None
+            out.update({key: self._keep[key].cpu().numpy() if kept else None for key in self.ekf.log_rows.values()})
         if self.track is not None:
             kept = self.track.log
             out.update(track_status=self._keep["track_status_log"].cpu().numpy().astype(np.int64) if kept else None,

@@ -55,12 +55,6 @@ struct DistCompensateParams {
   float u_min, u_max;
 };
 
-// Byte offsets of the caller-owned workspace of phnn_dekf_step, every region 256-byte aligned.
-struct DekfLayout {
-  size_t ctrl, traj, cost, A, Bm, total;
-};
-DekfLayout dekf_layout(long long B, int n, int m);
-
 // is there a k_dekf_update<n, m>?
 bool dekf_has_kernel(int n, int m);
 // hipErrorInvalidValue: no kernel for (n, m)

@@ -13,8 +13,6 @@ namespace {
 constexpr int kUpdThreads = 64;
 constexpr int kFlat = 256;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __device__ __forceinline__ bool finite32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // the library's clamp: a NaN stays NaN, as in torch.clamp (fminf / fmaxf alone would turn it into lo)
@@ -274,24 +272,6 @@ hipError_t update_launch(const DekfUpdateParams& p, hipStream_t st) {
 }
 
 }  // namespace
-
-DekfLayout dekf_layout(long long B, int n, int m) {
-  DekfLayout l{};
-  const size_t b = (size_t)B, f = sizeof(float);
-  size_t off = 0;
-  const auto region = [&off](size_t bytes) {
-    const size_t at = off;
-    off = align256(off + bytes);
-    return at;
-  };
-  l.ctrl = region(b * m * f);
-  l.traj = region(b * 2 * n * f);
-  l.cost = region(b * f);
-  l.A = region(b * n * n * f);
-  l.Bm = region(b * n * m * f);
-  l.total = off;
-  return l;
-}
 
 bool dekf_has_kernel(int n, int m) { return (m == 1 && n >= 2 && n <= 4) || (m == 2 && n == 4); }
 

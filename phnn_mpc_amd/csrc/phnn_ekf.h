@@ -37,12 +37,6 @@ struct EkfControlsParams {
   int m;
 };
 
-// Byte offsets of the caller-owned workspace of phnn_ekf_step, every region 256-byte aligned.
-struct EkfLayout {
-  size_t ctrl, traj, cost, A, Bm, total;
-};
-EkfLayout ekf_layout(long long B, int n, int m);
-
 // hipErrorInvalidValue: no kernel for n
 hipError_t ekf_update_launch(int n, const EkfUpdateParams& p, hipStream_t st);
 hipError_t ekf_controls_launch(const EkfControlsParams& p, hipStream_t st);

@@ -11,8 +11,6 @@ namespace {
 constexpr int kUpdThreads = 64;
 constexpr int kFlat = 256;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __device__ __forceinline__ bool finite32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // ------------------------------------------------------------------------------------------------ k_ekf_update
@@ -229,24 +227,6 @@ hipError_t update_launch(const EkfUpdateParams& p, hipStream_t st) {
 }
 
 }  // namespace
-
-EkfLayout ekf_layout(long long B, int n, int m) {
-  EkfLayout l{};
-  const size_t b = (size_t)B, f = sizeof(float);
-  size_t off = 0;
-  const auto region = [&off](size_t bytes) {
-    const size_t at = off;
-    off = align256(off + bytes);
-    return at;
-  };
-  l.ctrl = region(b * m * f);
-  l.traj = region(b * 2 * n * f);
-  l.cost = region(b * f);
-  l.A = region(b * n * n * f);
-  l.Bm = region(b * n * m * f);
-  l.total = off;
-  return l;
-}
 
 hipError_t ekf_update_launch(int n, const EkfUpdateParams& p, hipStream_t st) {
   switch (n) {

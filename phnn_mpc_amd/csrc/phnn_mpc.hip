@@ -22,6 +22,7 @@
 #include "phnn_ekf.h"
 #include "phnn_dekf.h"
 #include "phnn_ukf.h"
+#include "phnn_filter_layout.h"
 #include "phnn_feedback.h"
 #include "phnn_terminal.h"
 #include "phnn_pack.h"
@@ -2120,75 +2121,162 @@ int phnn_solve_gn_term(phnn_handle* h, const float* x0_dev, float* u_dev, int64_
                   accepts_dev, alpha_hist_dev, box, nclamp_hist_dev, stream, term);
 }
 
-// ---- batched extended Kalman filter (DESIGN.md 20): kernels in phnn_ekf.hip --------------------------------------
+// ---- the filters' shared host side: one view of the options and the log, one check, one step prologue,
+// one prediction; the workspaces are laid out in phnn_filter_layout.h ------------------------------------------------
 static bool ekf_supported(const phnn_handle* h) { return h->desc.n >= 2 && h->desc.n <= 4; }
 
-// The checks of the options and the log that phnn_ekf_update and phnn_ekf_step share.
-static int check_ekf(phnn_handle* h, int64_t B, const phnn_ekf_options* o, const phnn_ekf_log* log) {
+// What phnn_ekf_options, phnn_dekf_options, phnn_ukf_options and the two logs have in common, as the checks and the
+// parameters of the update kernels read it.
+struct FilterCommon {
+  const char* who;          // the struct a NULL options pointer is reported as
+  bool given;               // the options pointer is not NULL
+  bool supported;           // there is a kernel for this handle
+  const char* unsupported;  // what is said when there is none
+  const char* opts;         // how the checks of mask, noise and reserved name the struct
+  const char* log_name;     // how the check of the log names it
+  const char* q_name;       // "Qn" / "Qz"
+  int q_count;              // entries of the process noise matrix that are read
+  uint32_t meas_mask = 0;
+  const double* Q = nullptr;
+  const double* Rn = nullptr;
+  const int32_t* reserved = nullptr;  // four entries, or NULL: the caller has checked its own
+  phnn_dekf_log log{};  // the rows and the step source; no log: no rows
+};
+
+// a phnn_ekf_log as the phnn_dekf_log without a dhat row that it is
+static phnn_dekf_log filter_log(const phnn_ekf_log* log) {
+  return log ? phnn_dekf_log{log->log_xhat_dev, log->log_nis_dev, log->step_dev, log->step_host, nullptr} : phnn_dekf_log{};
+}
+
+static FilterCommon ekf_common(const phnn_handle* h, const phnn_ekf_options* o, const phnn_ekf_log* log) {
+  FilterCommon c{"phnn_ekf_options", o != nullptr, ekf_supported(h), "no extended Kalman filter kernel for this n",
+                 "phnn_ekf_options", "phnn_ekf_log", "Qn", h->desc.n * h->desc.n};
+  if (o) c.meas_mask = o->meas_mask, c.Q = o->Qn, c.Rn = o->Rn, c.reserved = o->reserved;
+  c.log = filter_log(log);
+  return c;
+}
+
+static FilterCommon dekf_common(const phnn_handle* h, const phnn_dekf_options* o, const phnn_dekf_log* log) {
+  const int nz = h->desc.n + h->desc.m;
+  FilterCommon c{"phnn_dekf_options", o != nullptr, dekf_has_kernel(h->desc.n, h->desc.m),
+                 "no disturbance filter kernel for this (n, m)", "phnn_dekf_options", "phnn_dekf_log", "Qz", nz * nz};
+  if (o) c.meas_mask = o->meas_mask, c.Q = o->Qz, c.Rn = o->Rn, c.reserved = o->reserved;
+  if (log) c.log = *log;
+  return c;
+}
+
+// the first three checks of every filter entry point
+static int check_filter_head(phnn_handle* h, const FilterCommon& c, int64_t B) {
   if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
-  if (!o) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options is NULL");
-  if (!ekf_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no extended Kalman filter kernel for this n");
-  const int n = h->desc.n;
-  if (o->meas_mask >> n) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options: meas_mask has bits at or above n");
-  for (int i = 0; i < n * n; ++i)
-    if (!std::isfinite(o->Qn[i])) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options: Qn is not finite");
-  for (int i = 0; i < n; ++i)
-    if (((o->meas_mask >> i) & 1u) && (!(o->Rn[i] > 0.0) || !std::isfinite(o->Rn[i])))
-      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options: Rn of a measured component is not positive and finite");
-  for (int r : o->reserved)
-    if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_options: reserved must be zero");
-  if (log && (log->log_xhat_dev || log->log_nis_dev) && !log->step_dev && log->step_host < 0)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_log: a log without a step source");
+  if (!c.given) return fail(h, PHNN_ERR_INVALID_ARG, std::string(c.who) + " is NULL");
+  if (!c.supported) return fail(h, PHNN_ERR_UNSUPPORTED, c.unsupported);
   return PHNN_OK;
 }
 
-static EkfUpdateParams ekf_update_params(const phnn_handle* h, const float* xpred_dev, int64_t xpred_stride, const float* A_dev,
-                                         const float* y_dev, int64_t y_stride, int64_t B, const phnn_ekf_options* o,
-                                         double* P_dev, float* xhat_dev, double* nis_dev, double* innov_dev,
-                                         int32_t* status_dev, const phnn_ekf_log* log) {
+// The checks of the options and the log that every update and step entry point makes.
+static int check_filter(phnn_handle* h, const FilterCommon& c, int64_t B) {
+  if (int rc = check_filter_head(h, c, B)) return rc;
   const int n = h->desc.n;
-  EkfUpdateParams p{};
+  const auto bad = [&](const std::string& what) { return fail(h, PHNN_ERR_INVALID_ARG, std::string(c.opts) + ": " + what); };
+  if (c.meas_mask >> n) return bad("meas_mask has bits at or above n");
+  for (int i = 0; i < c.q_count; ++i)
+    if (!std::isfinite(c.Q[i])) return bad(std::string(c.q_name) + " is not finite");
+  for (int i = 0; i < n; ++i)
+    if (((c.meas_mask >> i) & 1u) && (!(c.Rn[i] > 0.0) || !std::isfinite(c.Rn[i])))
+      return bad("Rn of a measured component is not positive and finite");
+  for (int i = 0; c.reserved && i < 4; ++i)
+    if (c.reserved[i] != 0) return bad("reserved must be zero");
+  if ((c.log.log_xhat_dev || c.log.log_dhat_dev || c.log.log_nis_dev) && !c.log.step_dev && c.log.step_host < 0)
+    return fail(h, PHNN_ERR_INVALID_ARG, std::string(c.log_name) + ": a log without a step source");
+  return PHNN_OK;
+}
+
+// The checks every *_step makes between its options and its tensors: strides, integrator, dt, cost, the empty batch.
+// *bounds is what K1 takes from the cost, the clamp; *empty says that B == 0 and nothing is to be launched.
+static int check_filter_step(phnn_handle* h, const char* who, int64_t u_stride, int64_t y_stride, int32_t integrator, float dt,
+                             const phnn_cost* cost, int64_t B, phnn_cost* bounds, bool* empty) {
+  if (u_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, std::string(who) + ": negative stride");
+  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
+  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
+  *bounds = neutral_cost();
+  if (cost) {
+    if (int rc = check_cost(h, cost)) return rc;
+    bounds->has_u_bounds = cost->has_u_bounds;
+    bounds->u_min = cost->u_min;
+    bounds->u_max = cost->u_max;
+  }
+  *empty = B == 0;
+  return PHNN_OK;
+}
+
+extern "C++" {  // a template over the parameter struct
+// The fields EkfUpdateParams and DekfUpdateParams share, by name; the caller adds its covariance and process noise.
+template <class P>
+static P filter_update_params(const phnn_handle* h, const FilterCommon& c, const float* xpred_dev, int64_t xpred_stride,
+                              const float* A_dev, const float* y_dev, int64_t y_stride, int64_t B, float* xhat_dev,
+                              double* nis_dev, double* innov_dev, int32_t* status_dev) {
+  P p{};
   p.xpred = xpred_dev;
   p.xpred_stride = xpred_stride;
   p.A = A_dev;
   p.y = y_dev;
   p.y_stride = y_stride;
-  p.P = P_dev;
   p.xhat = xhat_dev;
   p.nis = nis_dev;
   p.innov = innov_dev;
   p.status = status_dev;
-  if (log) {
-    p.log_xhat = log->log_xhat_dev;
-    p.log_nis = log->log_nis_dev;
-    p.step_dev = log->step_dev;
-    p.step_host = log->step_host;
-  }
+  p.log_xhat = c.log.log_xhat_dev;
+  p.log_nis = c.log.log_nis_dev;
+  p.step_dev = c.log.step_dev;
+  p.step_host = c.log.step_host;
   p.B = (long long)B;
-  p.mask = o->meas_mask;
-  for (int i = 0; i < n * n; ++i) p.Qn[i] = o->Qn[i];
-  for (int i = 0; i < n; ++i) p.Rn[i] = o->Rn[i];
+  p.mask = c.meas_mask;
+  for (int i = 0; i < h->desc.n; ++i) p.Rn[i] = c.Rn[i];
   return p;
+}
+}  // extern "C++"
+
+// The prediction of every filter step: K1 with H = 1 on `rows` rollouts from x with the control rows ctrl, under
+// k1_cost, and with A_dev given the Jacobians of that step under lin_cost.
+static int filter_predict(phnn_handle* h, const float* x_dev, const float* ctrl, int64_t rows, const phnn_cost* k1_cost,
+                          const phnn_cost* lin_cost, int32_t integrator, float dt, float* cost_out, float* traj, float* A_dev,
+                          float* Bm_dev, void* stream) {
+  if (int rc = rollout_fwd(h, x_dev, ctrl, rows, 1, k1_cost, integrator, dt, cost_out, traj, nullptr, nullptr, stream)) return rc;
+  if (!A_dev) return PHNN_OK;
+  return phnn_rollout_linearize(h, ctrl, rows, 1, lin_cost, integrator, dt, traj, A_dev, Bm_dev, stream);
+}
+
+// ---- batched extended Kalman filter (DESIGN.md 20): kernels in phnn_ekf.hip --------------------------------------
+// k_ekf_update from (x-, A) on P, on the current device: the EKF's, and with the identity as A the last launch of the
+// unscented step.
+static int ekf_update(phnn_handle* h, const FilterCommon& c, const float* xpred_dev, int64_t xpred_stride, const float* A_dev,
+                      const float* y_dev, int64_t y_stride, int64_t B, double* P_dev, float* xhat_dev, double* nis_dev,
+                      double* innov_dev, int32_t* status_dev, void* stream) {
+  EkfUpdateParams p = filter_update_params<EkfUpdateParams>(h, c, xpred_dev, xpred_stride, A_dev, y_dev, y_stride, B, xhat_dev,
+                                                            nis_dev, innov_dev, status_dev);
+  p.P = P_dev;
+  for (int i = 0; i < c.q_count; ++i) p.Qn[i] = c.Q[i];
+  return checked(h, ekf_update_launch(h->desc.n, p, (hipStream_t)stream), "k_ekf_update launch");
 }
 
 size_t phnn_ekf_workspace_bytes(const phnn_handle* h, int64_t B) {
   if (!h || B < 0 || !ekf_supported(h)) return 0;
-  return std::max<size_t>(ekf_layout(B, h->desc.n, h->desc.m).total, 256);
+  return std::max<size_t>(filter_step_layout(B, h->desc.n, h->desc.m).total, 256);
 }
 
 int phnn_ekf_update(phnn_handle* h, const float* xpred_dev, int64_t xpred_stride, const float* A_dev, const float* y_dev,
                     int64_t y_stride, int64_t B, const phnn_ekf_options* opt, double* P_dev, float* xhat_dev, double* nis_dev,
                     double* innov_dev, int32_t* status_dev, const phnn_ekf_log* log, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_ekf(h, B, opt, log)) return rc;
+  const FilterCommon c = ekf_common(h, opt, log);
+  if (int rc = check_filter(h, c, B)) return rc;
   if (xpred_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_update: negative stride");
   if (B == 0) return PHNN_OK;
   if (!xpred_dev || !A_dev || !P_dev || !xhat_dev || !status_dev || (opt->meas_mask && !y_dev))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_update: NULL tensor");
   PHNN_ON_DEVICE(h);
-  const EkfUpdateParams p = ekf_update_params(h, xpred_dev, xpred_stride, A_dev, y_dev, y_stride, B, opt, P_dev, xhat_dev,
-                                              nis_dev, innov_dev, status_dev, log);
-  return checked(h, ekf_update_launch(h->desc.n, p, (hipStream_t)stream), "k_ekf_update launch");
+  return ekf_update(h, c, xpred_dev, xpred_stride, A_dev, y_dev, y_stride, B, P_dev, xhat_dev, nis_dev, innov_dev, status_dev,
+                    stream);
 }
 
 int phnn_ekf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u_dev, int64_t u_stride, const float* y_dev,
@@ -2196,96 +2284,49 @@ int phnn_ekf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u
                   const phnn_ekf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
                   const phnn_ekf_log* log, void* workspace_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_ekf(h, B, opt, log)) return rc;
-  if (u_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_step: negative stride");
-  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
-  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
-  phnn_cost bounds = neutral_cost();  // what K1 and the linearisation take from the cost: the clamp
-  if (cost) {
-    if (int rc = check_cost(h, cost)) return rc;
-    bounds.has_u_bounds = cost->has_u_bounds;
-    bounds.u_min = cost->u_min;
-    bounds.u_max = cost->u_max;
-  }
-  if (B == 0) return PHNN_OK;
+  const FilterCommon c = ekf_common(h, opt, log);
+  if (int rc = check_filter(h, c, B)) return rc;
+  phnn_cost bounds;  // what K1 and the linearisation take from the cost: the clamp
+  bool empty;
+  if (int rc = check_filter_step(h, "phnn_ekf_step", u_stride, y_stride, integrator, dt, cost, B, &bounds, &empty); rc || empty)
+    return rc;
   if (!xhat_dev || !P_dev || !u_dev || !status_dev || !workspace_dev || (opt->meas_mask && !y_dev))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ekf_step: NULL tensor");
   const int n = h->desc.n, m = h->desc.m;
-  const EkfLayout l = ekf_layout(B, n, m);
+  const FilterStepLayout l = filter_step_layout(B, n, m);
   char* ws = (char*)workspace_dev;
   float* ctrl = (float*)(ws + l.ctrl);
   float* traj = (float*)(ws + l.traj);
+  float* A = (float*)(ws + l.A);
   {
     PHNN_ON_DEVICE(h);
-    EkfControlsParams c{u_dev, (long long)u_stride, ctrl, (long long)B, m};
-    if (int rc = checked(h, ekf_controls_launch(c, (hipStream_t)stream), "k_ekf_controls launch")) return rc;
+    EkfControlsParams p{u_dev, (long long)u_stride, ctrl, (long long)B, m};
+    if (int rc = checked(h, ekf_controls_launch(p, (hipStream_t)stream), "k_ekf_controls launch")) return rc;
   }
-  if (int rc = rollout_fwd(h, xhat_dev, ctrl, B, 1, &bounds, integrator, dt, (float*)(ws + l.cost), traj, nullptr, nullptr, stream))
-    return rc;
-  if (int rc = phnn_rollout_linearize(h, ctrl, B, 1, &bounds, integrator, dt, traj, (float*)(ws + l.A), (float*)(ws + l.Bm), stream))
+  if (int rc = filter_predict(h, xhat_dev, ctrl, B, &bounds, &bounds, integrator, dt, (float*)(ws + l.cost), traj, A,
+                              (float*)(ws + l.Bm), stream))
     return rc;
   PHNN_ON_DEVICE(h);
-  const EkfUpdateParams p = ekf_update_params(h, traj + n, 2 * n, (float*)(ws + l.A), y_dev, y_stride, B, opt, P_dev, xhat_dev,
-                                              nis_dev, innov_dev, status_dev, log);
-  return checked(h, ekf_update_launch(n, p, (hipStream_t)stream), "k_ekf_update launch");
+  return ekf_update(h, c, traj + n, 2 * n, A, y_dev, y_stride, B, P_dev, xhat_dev, nis_dev, innov_dev, status_dev, stream);
 }
 
 // ---- input-disturbance estimation and offset-free control: kernels in phnn_dekf.hip ------------------
-// The checks of the options and the log that phnn_dekf_update and phnn_dekf_step share.
-static int check_dekf(phnn_handle* h, int64_t B, const phnn_dekf_options* o, const phnn_dekf_log* log) {
-  if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
-  if (!o) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options is NULL");
-  const int n = h->desc.n, nz = h->desc.n + h->desc.m;
-  if (!dekf_has_kernel(n, h->desc.m)) return fail(h, PHNN_ERR_UNSUPPORTED, "no disturbance filter kernel for this (n, m)");
-  if (o->meas_mask >> n) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options: meas_mask has bits at or above n");
-  for (int i = 0; i < nz * nz; ++i)
-    if (!std::isfinite(o->Qz[i])) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options: Qz is not finite");
-  for (int i = 0; i < n; ++i)
-    if (((o->meas_mask >> i) & 1u) && (!(o->Rn[i] > 0.0) || !std::isfinite(o->Rn[i])))
-      return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options: Rn of a measured component is not positive and finite");
-  for (int r : o->reserved)
-    if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_options: reserved must be zero");
-  if (log && (log->log_xhat_dev || log->log_dhat_dev || log->log_nis_dev) && !log->step_dev && log->step_host < 0)
-    return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_log: a log without a step source");
-  return PHNN_OK;
-}
-
-static DekfUpdateParams dekf_update_params(const phnn_handle* h, const float* xpred_dev, int64_t xpred_stride,
-                                           const float* A_dev, const float* Bm_dev, const float* y_dev, int64_t y_stride,
-                                           int64_t B, const phnn_dekf_options* o, double* Pz_dev, float* xhat_dev,
-                                           float* dhat_dev, double* nis_dev, double* innov_dev, int32_t* status_dev,
-                                           const phnn_dekf_log* log) {
-  const int n = h->desc.n, nz = h->desc.n + h->desc.m;
-  DekfUpdateParams p{};
-  p.xpred = xpred_dev;
-  p.xpred_stride = xpred_stride;
-  p.A = A_dev;
+static int dekf_update(phnn_handle* h, const FilterCommon& c, const float* xpred_dev, int64_t xpred_stride, const float* A_dev,
+                       const float* Bm_dev, const float* y_dev, int64_t y_stride, int64_t B, double* Pz_dev, float* xhat_dev,
+                       float* dhat_dev, double* nis_dev, double* innov_dev, int32_t* status_dev, void* stream) {
+  DekfUpdateParams p = filter_update_params<DekfUpdateParams>(h, c, xpred_dev, xpred_stride, A_dev, y_dev, y_stride, B, xhat_dev,
+                                                              nis_dev, innov_dev, status_dev);
   p.Bm = Bm_dev;
-  p.y = y_dev;
-  p.y_stride = y_stride;
   p.Pz = Pz_dev;
-  p.xhat = xhat_dev;
   p.dhat = dhat_dev;
-  p.nis = nis_dev;
-  p.innov = innov_dev;
-  p.status = status_dev;
-  if (log) {
-    p.log_xhat = log->log_xhat_dev;
-    p.log_dhat = log->log_dhat_dev;
-    p.log_nis = log->log_nis_dev;
-    p.step_dev = log->step_dev;
-    p.step_host = log->step_host;
-  }
-  p.B = (long long)B;
-  p.mask = o->meas_mask;
-  for (int i = 0; i < nz * nz; ++i) p.Qz[i] = o->Qz[i];
-  for (int i = 0; i < n; ++i) p.Rn[i] = o->Rn[i];
-  return p;
+  p.log_dhat = c.log.log_dhat_dev;
+  for (int i = 0; i < c.q_count; ++i) p.Qz[i] = c.Q[i];
+  return checked(h, dekf_update_launch(h->desc.n, h->desc.m, p, (hipStream_t)stream), "k_dekf_update launch");
 }
 
 size_t phnn_dekf_workspace_bytes(const phnn_handle* h, int64_t B) {
   if (!h || B < 0 || !dekf_has_kernel(h->desc.n, h->desc.m)) return 0;
-  return std::max<size_t>(dekf_layout(B, h->desc.n, h->desc.m).total, 256);
+  return std::max<size_t>(filter_step_layout(B, h->desc.n, h->desc.m).total, 256);
 }
 
 int phnn_dekf_update(phnn_handle* h, const float* xpred_dev, int64_t xpred_stride, const float* A_dev, const float* Bm_dev,
@@ -2293,15 +2334,15 @@ int phnn_dekf_update(phnn_handle* h, const float* xpred_dev, int64_t xpred_strid
                      float* xhat_dev, float* dhat_dev, double* nis_dev, double* innov_dev, int32_t* status_dev,
                      const phnn_dekf_log* log, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_dekf(h, B, opt, log)) return rc;
+  const FilterCommon c = dekf_common(h, opt, log);
+  if (int rc = check_filter(h, c, B)) return rc;
   if (xpred_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_update: negative stride");
   if (B == 0) return PHNN_OK;
   if (!xpred_dev || !A_dev || !Bm_dev || !Pz_dev || !xhat_dev || !dhat_dev || !status_dev || (opt->meas_mask && !y_dev))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_update: NULL tensor");
   PHNN_ON_DEVICE(h);
-  const DekfUpdateParams p = dekf_update_params(h, xpred_dev, xpred_stride, A_dev, Bm_dev, y_dev, y_stride, B, opt, Pz_dev,
-                                                xhat_dev, dhat_dev, nis_dev, innov_dev, status_dev, log);
-  return checked(h, dekf_update_launch(h->desc.n, h->desc.m, p, (hipStream_t)stream), "k_dekf_update launch");
+  return dekf_update(h, c, xpred_dev, xpred_stride, A_dev, Bm_dev, y_dev, y_stride, B, Pz_dev, xhat_dev, dhat_dev, nis_dev,
+                     innov_dev, status_dev, stream);
 }
 
 int phnn_dekf_step(phnn_handle* h, float* xhat_dev, float* dhat_dev, double* Pz_dev, const float* u_dev, int64_t u_stride,
@@ -2309,36 +2350,34 @@ int phnn_dekf_step(phnn_handle* h, float* xhat_dev, float* dhat_dev, double* Pz_
                    const phnn_dekf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
                    const phnn_dekf_log* log, void* workspace_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  if (int rc = check_dekf(h, B, opt, log)) return rc;
-  if (u_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_step: negative stride");
-  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
-  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
-  if (cost)
-    if (int rc = check_cost(h, cost)) return rc;
-  if (B == 0) return PHNN_OK;
+  const FilterCommon c = dekf_common(h, opt, log);
+  if (int rc = check_filter(h, c, B)) return rc;
+  phnn_cost bounds;  // the clamp of the command, k_dekf_controls' alone
+  bool empty;
+  if (int rc = check_filter_step(h, "phnn_dekf_step", u_stride, y_stride, integrator, dt, cost, B, &bounds, &empty); rc || empty)
+    return rc;
   if (!xhat_dev || !dhat_dev || !Pz_dev || !u_dev || !status_dev || !workspace_dev || (opt->meas_mask && !y_dev))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_dekf_step: NULL tensor");
   const int n = h->desc.n, m = h->desc.m;
-  const DekfLayout l = dekf_layout(B, n, m);
+  const FilterStepLayout l = filter_step_layout(B, n, m);
   char* ws = (char*)workspace_dev;
   float* ctrl = (float*)(ws + l.ctrl);
   float* traj = (float*)(ws + l.traj);
+  float* A = (float*)(ws + l.A);
+  float* Bm = (float*)(ws + l.Bm);
   {
     PHNN_ON_DEVICE(h);
-    DekfControlsParams c{u_dev, (long long)u_stride, dhat_dev, ctrl, (long long)B, m, cost ? cost->has_u_bounds : 0,
-                         cost ? cost->u_min : 0.f, cost ? cost->u_max : 0.f};
-    if (int rc = checked(h, dekf_controls_launch(c, (hipStream_t)stream), "k_dekf_controls launch")) return rc;
+    DekfControlsParams p{u_dev, (long long)u_stride, dhat_dev, ctrl, (long long)B, m, bounds.has_u_bounds, bounds.u_min,
+                         bounds.u_max};
+    if (int rc = checked(h, dekf_controls_launch(p, (hipStream_t)stream), "k_dekf_controls launch")) return rc;
   }
   // the disturbed control c(u) + dhat enters the model as it is: a zero cost and no bounds for K1, none for the Jacobians
   const phnn_cost none = neutral_cost();
-  if (int rc = rollout_fwd(h, xhat_dev, ctrl, B, 1, &none, integrator, dt, (float*)(ws + l.cost), traj, nullptr, nullptr, stream))
-    return rc;
-  if (int rc = phnn_rollout_linearize(h, ctrl, B, 1, nullptr, integrator, dt, traj, (float*)(ws + l.A), (float*)(ws + l.Bm), stream))
+  if (int rc = filter_predict(h, xhat_dev, ctrl, B, &none, nullptr, integrator, dt, (float*)(ws + l.cost), traj, A, Bm, stream))
     return rc;
   PHNN_ON_DEVICE(h);
-  const DekfUpdateParams p = dekf_update_params(h, traj + n, 2 * n, (float*)(ws + l.A), (float*)(ws + l.Bm), y_dev, y_stride, B,
-                                                opt, Pz_dev, xhat_dev, dhat_dev, nis_dev, innov_dev, status_dev, log);
-  return checked(h, dekf_update_launch(n, m, p, (hipStream_t)stream), "k_dekf_update launch");
+  return dekf_update(h, c, traj + n, 2 * n, A, Bm, y_dev, y_stride, B, Pz_dev, xhat_dev, dhat_dev, nis_dev, innov_dev, status_dev,
+                     stream);
 }
 
 int phnn_dist_compensate(phnn_handle* h, const float* v_dev, int64_t v_stride, const float* dhat_dev, int64_t B,
@@ -2357,22 +2396,20 @@ int phnn_dist_compensate(phnn_handle* h, const float* v_dev, int64_t v_stride, c
 }
 
 // ---- batched unscented Kalman filter: kernels in phnn_ukf.hip --------------------------------------------
-// The checks that the three entry points share; on success *e holds the options k_ekf_update takes.
-static int check_ukf(phnn_handle* h, int64_t B, const phnn_ukf_options* o, const phnn_ekf_log* log, phnn_ekf_options* e) {
-  if (B < 0) return fail(h, PHNN_ERR_INVALID_ARG, "negative batch");
-  if (!o) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_options is NULL");
-  if (!ekf_supported(h)) return fail(h, PHNN_ERR_UNSUPPORTED, "no unscented Kalman filter kernel for this n");
-  const int n = h->desc.n;
+// The checks that the three entry points share: the filter's head, the four weights and reserved here, the rest with the
+// view *c -- which k_ekf_update then takes its options from, so mask, Qn, Rn and the log are reported as the EKF's.
+static int check_ukf(phnn_handle* h, int64_t B, const phnn_ukf_options* o, const phnn_ekf_log* log, FilterCommon* c) {
+  *c = FilterCommon{"phnn_ukf_options", o != nullptr, ekf_supported(h), "no unscented Kalman filter kernel for this n",
+                    "phnn_ekf_options", "phnn_ekf_log", "Qn", h->desc.n * h->desc.n};
+  if (int rc = check_filter_head(h, *c, B)) return rc;
   if (!(o->gamma > 0.0) || !std::isfinite(o->gamma) || !(o->wi > 0.0) || !std::isfinite(o->wi))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_options: gamma and wi must be positive and finite");
   if (!std::isfinite(o->wm0) || !std::isfinite(o->wc0)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_options: wm0 / wc0 is not finite");
   for (int r : o->reserved)
     if (r != 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_options: reserved must be zero");
-  *e = phnn_ekf_options{};
-  e->meas_mask = o->meas_mask;
-  for (int i = 0; i < n * n; ++i) e->Qn[i] = o->Qn[i];
-  for (int i = 0; i < n; ++i) e->Rn[i] = o->Rn[i];
-  return check_ekf(h, B, e, log);
+  c->meas_mask = o->meas_mask, c->Q = o->Qn, c->Rn = o->Rn;
+  c->log = filter_log(log);
+  return check_filter(h, *c, B);
 }
 
 size_t phnn_ukf_workspace_bytes(const phnn_handle* h, int64_t B) {
@@ -2383,8 +2420,8 @@ size_t phnn_ukf_workspace_bytes(const phnn_handle* h, int64_t B) {
 int phnn_ukf_sigma(phnn_handle* h, const float* xhat_dev, const double* P_dev, const float* u_dev, int64_t u_stride,
                    int64_t B, const phnn_ukf_options* opt, float* chi_dev, float* ctrl_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  phnn_ekf_options e;
-  if (int rc = check_ukf(h, B, opt, nullptr, &e)) return rc;
+  FilterCommon c;
+  if (int rc = check_ukf(h, B, opt, nullptr, &c)) return rc;
   if (u_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_sigma: negative stride");
   if (B == 0) return PHNN_OK;
   if (!xhat_dev || !P_dev || !chi_dev || (ctrl_dev && !u_dev)) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_sigma: NULL tensor");
@@ -2396,8 +2433,8 @@ int phnn_ukf_sigma(phnn_handle* h, const float* xhat_dev, const double* P_dev, c
 int phnn_ukf_moments(phnn_handle* h, const float* Y_dev, int64_t Y_stride, int64_t B, const phnn_ukf_options* opt,
                      float* xm_dev, double* Pm_dev, float* eye_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  phnn_ekf_options e;
-  if (int rc = check_ukf(h, B, opt, nullptr, &e)) return rc;
+  FilterCommon c;
+  if (int rc = check_ukf(h, B, opt, nullptr, &c)) return rc;
   if (Y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_moments: negative stride");
   if (B == 0) return PHNN_OK;
   if (!Y_dev || !xm_dev || !Pm_dev) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_moments: NULL tensor");
@@ -2411,19 +2448,12 @@ int phnn_ukf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u
                   const phnn_ukf_options* opt, double* nis_dev, double* innov_dev, int32_t* status_dev,
                   const phnn_ekf_log* log, void* workspace_dev, void* stream) {
   if (!h) return PHNN_ERR_INVALID_ARG;
-  phnn_ekf_options e;
-  if (int rc = check_ukf(h, B, opt, log, &e)) return rc;
-  if (u_stride < 0 || y_stride < 0) return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_step: negative stride");
-  if (integrator != PHNN_INTEG_EULER && integrator != PHNN_INTEG_RK4) return fail(h, PHNN_ERR_INVALID_ARG, "Unknown integrator");
-  if (!std::isfinite(dt)) return fail(h, PHNN_ERR_INVALID_ARG, "dt is not finite");
-  phnn_cost bounds = neutral_cost();  // what K1 takes from the cost: the clamp
-  if (cost) {
-    if (int rc = check_cost(h, cost)) return rc;
-    bounds.has_u_bounds = cost->has_u_bounds;
-    bounds.u_min = cost->u_min;
-    bounds.u_max = cost->u_max;
-  }
-  if (B == 0) return PHNN_OK;
+  FilterCommon c;
+  if (int rc = check_ukf(h, B, opt, log, &c)) return rc;
+  phnn_cost bounds;  // what K1 takes from the cost: the clamp
+  bool empty;
+  if (int rc = check_filter_step(h, "phnn_ukf_step", u_stride, y_stride, integrator, dt, cost, B, &bounds, &empty); rc || empty)
+    return rc;
   if (!xhat_dev || !P_dev || !u_dev || !status_dev || !workspace_dev || (opt->meas_mask && !y_dev))
     return fail(h, PHNN_ERR_INVALID_ARG, "phnn_ukf_step: NULL tensor");
   const int n = h->desc.n, m = h->desc.m;
@@ -2440,15 +2470,14 @@ int phnn_ukf_step(phnn_handle* h, float* xhat_dev, double* P_dev, const float* u
     const UkfSigmaParams p{xhat_dev, P_dev, u_dev, (long long)u_stride, chi, ctrl, (long long)B, m, opt->gamma};
     if (int rc = checked(h, ukf_sigma_launch(n, p, (hipStream_t)stream), "k_ukf_sigma launch")) return rc;
   }
-  if (int rc = rollout_fwd(h, chi, ctrl, B * S, 1, &bounds, integrator, dt, (float*)(ws + l.cost), traj, nullptr, nullptr, stream))
+  if (int rc = filter_predict(h, chi, ctrl, B * S, &bounds, nullptr, integrator, dt, (float*)(ws + l.cost), traj, nullptr, nullptr,
+                              stream))
     return rc;
   PHNN_ON_DEVICE(h);
   // the covariance of the images goes where k_ekf_update reads and writes its P: k_ukf_sigma has read P by then
   const UkfMomentsParams q{traj + n, 2 * n, xm, P_dev, eye, (long long)B, opt->wm0, opt->wc0, opt->wi};
   if (int rc = checked(h, ukf_moments_launch(n, q, (hipStream_t)stream), "k_ukf_moments launch")) return rc;
-  const EkfUpdateParams p = ekf_update_params(h, xm, n, eye, y_dev, y_stride, B, &e, P_dev, xhat_dev, nis_dev, innov_dev,
-                                              status_dev, log);
-  return checked(h, ekf_update_launch(n, p, (hipStream_t)stream), "k_ekf_update launch");
+  return ekf_update(h, c, xm, n, eye, y_dev, y_stride, B, P_dev, xhat_dev, nis_dev, innov_dev, status_dev, stream);
 }
 
 // ---- tracking the plan between solves: kernel in phnn_feedback.hip -------------------------------------

@@ -31,12 +31,6 @@ struct UkfMomentsParams {
   double wm0, wc0, wi;
 };
 
-// Byte offsets of the caller-owned workspace of phnn_ukf_step, every region 256-byte aligned.
-struct UkfLayout {
-  size_t chi, ctrl, traj, cost, xm, eye, total;
-};
-UkfLayout ukf_layout(long long B, int n, int m);
-
 // hipErrorInvalidValue: no kernel for n
 hipError_t ukf_sigma_launch(int n, const UkfSigmaParams& p, hipStream_t st);
 hipError_t ukf_moments_launch(int n, const UkfMomentsParams& p, hipStream_t st);

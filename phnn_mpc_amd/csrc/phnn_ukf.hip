@@ -11,8 +11,6 @@ namespace {
 
 constexpr int kThreads = 64;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __device__ __forceinline__ bool finite32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // A float that goes in or out of a kernel here, kept a scalar value of its own: without the empty asm the compiler
@@ -153,25 +151,6 @@ hipError_t moments_launch(const UkfMomentsParams& p, hipStream_t st) {
 }
 
 }  // namespace
-
-UkfLayout ukf_layout(long long B, int n, int m) {
-  UkfLayout l{};
-  const size_t b = (size_t)B, s = (size_t)(2 * n + 1), f = sizeof(float);
-  size_t off = 0;
-  const auto region = [&off](size_t bytes) {
-    const size_t at = off;
-    off = align256(off + bytes);
-    return at;
-  };
-  l.chi = region(b * s * n * f);
-  l.ctrl = region(b * s * m * f);
-  l.traj = region(b * s * 2 * n * f);
-  l.cost = region(b * s * f);
-  l.xm = region(b * n * f);
-  l.eye = region(b * n * n * f);
-  l.total = off;
-  return l;
-}
 
 hipError_t ukf_sigma_launch(int n, const UkfSigmaParams& p, hipStream_t st) {
   switch (n) {

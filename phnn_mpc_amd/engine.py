@@ -999,19 +999,17 @@ class RolloutEngine:
         _check(self.lib, self.h, rc)
         return out
 
-    # ------------------------------------------------------------------ extended Kalman filter
-    def ekf_workspace_bytes(self, B):
-        return int(self.lib.phnn_ekf_workspace_bytes(self.h, int(B)))
-
-    def _ekf_log(self, log):
-        """log: None or dict(log_xhat (T+1,B,n) float32, log_nis (T,B) float64, step_dev int32 tensor or step int)."""
+    # ------------------------------------------------------------------ what the three filters share
+    def _filter_log(self, struct_cls, log):
+        """log: None or dict(log_xhat (T+1,B,n) float32, log_dhat (T+1,B,m) float32 -- a _capi.DekfLog's only --, log_nis
+        (T,B) float64, step_dev int32 tensor or step int) -> a struct_cls (_capi.EkfLog / _capi.DekfLog) or None."""
         if log is None:
             return None
-        lg = _capi.EkfLog()
-        lg.log_xhat_dev = log["log_xhat"].data_ptr() if log.get("log_xhat") is not None else None
-        lg.log_nis_dev = log["log_nis"].data_ptr() if log.get("log_nis") is not None else None
-        if log.get("step_dev") is not None:
-            lg.step_dev = log["step_dev"].data_ptr()
+        lg = struct_cls()
+        for key, field in (("log_xhat", "log_xhat_dev"), ("log_dhat", "log_dhat_dev"), ("log_nis", "log_nis_dev"),
+                           ("step_dev", "step_dev")):
+            if log.get(key) is not None and hasattr(lg, field):
+                setattr(lg, field, log[key].data_ptr())
         lg.step_host = int(log.get("step", -1))
         return lg
 
@@ -1022,6 +1020,53 @@ class RolloutEngine:
         status = torch.empty(B, dtype=torch.int32, device=self.device) if status is None else status
         return nis, innov, status
 
+    def _filter_update(self, symbol, log_cls, xpred, jac, y, P, nz, extra, opt, xhat, nis, innov, status, log, xpred_stride,
+                       y_stride):
+        """The body of ekf_update and dekf_update.  jac: the Jacobians the library takes after xpred, (A,) or (A, Bm); P
+        (B,nz,nz) float64; extra: the float32 state it takes after xhat, () or (dhat,).  -> (xhat, nis, innov, status)."""
+        self._assert_device_f32(xpred, *jac, y, *extra)
+        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
+        B = P.shape[0]
+        assert P.numel() == B * nz * nz and jac[0].numel() == B * self.n * self.n
+        if xhat is None:
+            xhat = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
+        self._assert_device_f32(xhat)
+        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
+        lg = self._filter_log(log_cls, log)
+        rc = getattr(self.lib, symbol)(self.h, self._p(xpred), self.n if xpred_stride is None else int(xpred_stride),
+                                       *map(self._p, jac), self._p(y), self.n if y_stride is None else int(y_stride), B,
+                                       C.byref(opt), self._p(P), self._p(xhat), *map(self._p, extra), self._p(nis),
+                                       self._p(innov), self._p(status), None if lg is None else C.byref(lg), self._stream())
+        _check(self.lib, self.h, rc)
+        return xhat, nis, innov, status
+
+    def _filter_step(self, symbol, ws_name, ws_bytes, log_cls, state, u, u_stride, y, cost, integrator, dt, opt, nis, innov,
+                     status, log, workspace, y_stride):
+        """The body of ekf_step, dekf_step and ukf_step.  state: the filter's tensors by the names of the result, in the
+        order the library takes them -- float32 (B,.) ones, then the float64 covariance; ws_name: the key of the device
+        buffer of ws_bytes(B) bytes in the workspace dict.  -> dict(**state, nis, innov, status)."""
+        *x, P = state.values()
+        self._assert_device_f32(*x, u, y)
+        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
+        B = x[0].shape[0]
+        ws = {} if workspace is None else workspace
+        if ws.get(ws_name + "_key") != B:
+            ws[ws_name + "_key"] = B
+            ws[ws_name] = torch.empty(max(ws_bytes(B), 256), dtype=torch.uint8, device=self.device)
+        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
+        lg = self._filter_log(log_cls, log)
+        rc = getattr(self.lib, symbol)(self.h, *map(self._p, x), self._p(P), self._p(u), int(u_stride), self._p(y),
+                                       self.n if y_stride is None else int(y_stride), B,
+                                       C.byref(cost) if cost is not None else None, self._integ(integrator), float(dt),
+                                       C.byref(opt), self._p(nis), self._p(innov), self._p(status),
+                                       None if lg is None else C.byref(lg), self._p(ws[ws_name]), self._stream())
+        _check(self.lib, self.h, rc)
+        return dict(state, nis=nis, innov=innov, status=status)
+
+    # ------------------------------------------------------------------ extended Kalman filter (DESIGN.md 20)
+    def ekf_workspace_bytes(self, B):
+        return int(self.lib.phnn_ekf_workspace_bytes(self.h, int(B)))
+
     def ekf_update(self, xpred, A, y, P, opt, xhat=None, nis=True, innov=True, status=None, log=None, xpred_stride=None,
                    y_stride=None):
         """k_ekf_update on its own: the covariance propagation through A and the measurement update of the components
@@ -1030,20 +1075,8 @@ class RolloutEngine:
         read); P (B,n,n) float64, updated IN PLACE.  nis / innov: True = allocate, False = skip, or a float64 tensor (B) /
         (B,n) to write.  -> dict(xhat (B,n) float32, P, nis, innov, status (B) int32: 0 updated or nothing measured, 1
         dropped measurement, 2 failure with NaN outputs)."""
-        self._assert_device_f32(xpred, A, y)
-        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
-        B = P.shape[0]
-        assert P.numel() == B * self.n * self.n and A.numel() == B * self.n * self.n
-        if xhat is None:
-            xhat = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
-        self._assert_device_f32(xhat)
-        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
-        lg = self._ekf_log(log)
-        rc = self.lib.phnn_ekf_update(self.h, self._p(xpred), self.n if xpred_stride is None else int(xpred_stride), self._p(A),
-                                      self._p(y), self.n if y_stride is None else int(y_stride), B, C.byref(opt), self._p(P),
-                                      self._p(xhat), self._p(nis), self._p(innov), self._p(status),
-                                      None if lg is None else C.byref(lg), self._stream())
-        _check(self.lib, self.h, rc)
+        xhat, nis, innov, status = self._filter_update("phnn_ekf_update", _capi.EkfLog, xpred, (A,), y, P, self.n, (), opt,
+                                                       xhat, nis, innov, status, log, xpred_stride, y_stride)
         return dict(xhat=xhat, P=P, nis=nis, innov=innov, status=status)
 
     def ekf_step(self, xhat, P, u, u_stride, y, cost, integrator, dt, opt, nis=True, innov=False, status=None, log=None,
@@ -1053,21 +1086,8 @@ class RolloutEngine:
         u: float32, problem b's applied control at u.view(-1)[b * u_stride + k]; cost: its bounds clamp the control as
         K1 and the plant do (None: no clamp); y, opt, nis, innov, status, log: as in ekf_update.  workspace: a dict
         reused across calls (keeps the device buffer of ekf_workspace_bytes).  -> dict(xhat, P, nis, innov, status)."""
-        self._assert_device_f32(xhat, u, y)
-        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
-        B = xhat.shape[0]
-        ws = {} if workspace is None else workspace
-        if ws.get("ekf_key") != B:
-            ws["ekf_key"] = B
-            ws["ekf"] = torch.empty(max(self.ekf_workspace_bytes(B), 256), dtype=torch.uint8, device=self.device)
-        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
-        lg = self._ekf_log(log)
-        rc = self.lib.phnn_ekf_step(self.h, self._p(xhat), self._p(P), self._p(u), int(u_stride), self._p(y),
-                                    self.n if y_stride is None else int(y_stride), B, C.byref(cost) if cost is not None else None,
-                                    self._integ(integrator), float(dt), C.byref(opt), self._p(nis), self._p(innov),
-                                    self._p(status), None if lg is None else C.byref(lg), self._p(ws["ekf"]), self._stream())
-        _check(self.lib, self.h, rc)
-        return dict(xhat=xhat, P=P, nis=nis, innov=innov, status=status)
+        return self._filter_step("phnn_ekf_step", "ekf", self.ekf_workspace_bytes, _capi.EkfLog, dict(xhat=xhat, P=P), u,
+                                 u_stride, y, cost, integrator, dt, opt, nis, innov, status, log, workspace, y_stride)
 
     # ------------------------------------------------------------------ tracking the plan between solves (DESIGN.md 21)
     def feedback_workspace_bytes(self, B, H):
@@ -1129,42 +1149,17 @@ class RolloutEngine:
     def dekf_workspace_bytes(self, B):
         return int(self.lib.phnn_dekf_workspace_bytes(self.h, int(B)))
 
-    def _dekf_log(self, log):
-        """log: None or dict(log_xhat (T+1,B,n) float32, log_dhat (T+1,B,m) float32, log_nis (T,B) float64, step_dev int32
-        tensor or step int)."""
-        if log is None:
-            return None
-        lg = _capi.DekfLog()
-        lg.log_xhat_dev = log["log_xhat"].data_ptr() if log.get("log_xhat") is not None else None
-        lg.log_dhat_dev = log["log_dhat"].data_ptr() if log.get("log_dhat") is not None else None
-        lg.log_nis_dev = log["log_nis"].data_ptr() if log.get("log_nis") is not None else None
-        if log.get("step_dev") is not None:
-            lg.step_dev = log["step_dev"].data_ptr()
-        lg.step_host = int(log.get("step", -1))
-        return lg
-
     def dekf_update(self, xpred, A, Bm, y, Pz, dhat, opt, xhat=None, nis=True, innov=True, status=None, log=None,
                     xpred_stride=None, y_stride=None):
         """k_dekf_update on its own: ekf_update on the augmented state z = (x, d) with the Jacobian [[A, Bm], [0, I]] and
         the options of _capi.DekfOptions.  xpred, y, strides, nis, innov, status: as in ekf_update; A (B,n,n) and Bm
         (B,n,m) float32; Pz (B,n+m,n+m) float64 and dhat (B,m) float32 are updated IN PLACE.  -> dict(xhat (B,n) float32,
         dhat, P (= Pz), nis, innov (B,n), status (B) int32)."""
-        self._assert_device_f32(xpred, A, Bm, y, dhat)
-        nz = self.n + self.m
-        assert Pz.dtype == torch.float64 and Pz.is_contiguous() and Pz.device == self.device
         B = Pz.shape[0]
-        assert Pz.numel() == B * nz * nz and A.numel() == B * self.n * self.n and Bm.numel() == B * self.n * self.m
-        assert dhat.numel() == B * self.m
-        if xhat is None:
-            xhat = torch.empty(B, self.n, dtype=torch.float32, device=self.device)
-        self._assert_device_f32(xhat)
-        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
-        lg = self._dekf_log(log)
-        rc = self.lib.phnn_dekf_update(self.h, self._p(xpred), self.n if xpred_stride is None else int(xpred_stride), self._p(A),
-                                       self._p(Bm), self._p(y), self.n if y_stride is None else int(y_stride), B, C.byref(opt),
-                                       self._p(Pz), self._p(xhat), self._p(dhat), self._p(nis), self._p(innov), self._p(status),
-                                       None if lg is None else C.byref(lg), self._stream())
-        _check(self.lib, self.h, rc)
+        assert Bm.numel() == B * self.n * self.m and dhat.numel() == B * self.m
+        xhat, nis, innov, status = self._filter_update("phnn_dekf_update", _capi.DekfLog, xpred, (A, Bm), y, Pz,
+                                                       self.n + self.m, (dhat,), opt, xhat, nis, innov, status, log,
+                                                       xpred_stride, y_stride)
         return dict(xhat=xhat, dhat=dhat, P=Pz, nis=nis, innov=innov, status=status)
 
     def dekf_step(self, xhat, dhat, Pz, u, u_stride, y, cost, integrator, dt, opt, nis=True, innov=False, status=None, log=None,
@@ -1174,21 +1169,9 @@ class RolloutEngine:
         k_dekf_update -- IN PLACE on xhat (B,n) float32, dhat (B,m) float32 and Pz (B,n+m,n+m) float64.  u: float32,
         problem b's applied command at u.view(-1)[b * u_stride + k]; cost: its bounds clamp the command (None: no clamp);
         the rest as in ekf_step.  -> dict(xhat, dhat, P, nis, innov, status)."""
-        self._assert_device_f32(xhat, dhat, u, y)
-        assert Pz.dtype == torch.float64 and Pz.is_contiguous() and Pz.device == self.device
-        B = xhat.shape[0]
-        ws = {} if workspace is None else workspace
-        if ws.get("dekf_key") != B:
-            ws["dekf_key"] = B
-            ws["dekf"] = torch.empty(max(self.dekf_workspace_bytes(B), 256), dtype=torch.uint8, device=self.device)
-        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
-        lg = self._dekf_log(log)
-        rc = self.lib.phnn_dekf_step(self.h, self._p(xhat), self._p(dhat), self._p(Pz), self._p(u), int(u_stride), self._p(y),
-                                     self.n if y_stride is None else int(y_stride), B, C.byref(cost) if cost is not None else None,
-                                     self._integ(integrator), float(dt), C.byref(opt), self._p(nis), self._p(innov),
-                                     self._p(status), None if lg is None else C.byref(lg), self._p(ws["dekf"]), self._stream())
-        _check(self.lib, self.h, rc)
-        return dict(xhat=xhat, dhat=dhat, P=Pz, nis=nis, innov=innov, status=status)
+        return self._filter_step("phnn_dekf_step", "dekf", self.dekf_workspace_bytes, _capi.DekfLog,
+                                 dict(xhat=xhat, dhat=dhat, P=Pz), u, u_stride, y, cost, integrator, dt, opt, nis, innov, status,
+                                 log, workspace, y_stride)
 
     def dist_compensate(self, v, v_stride, dhat, cost, u_cmd=None, status=None):
         """phnn_dist_compensate: u_cmd (B,m) = c(c(v) - dhat), c the clamp to the cost's bounds (None: none); v: float32,
@@ -1255,21 +1238,8 @@ class RolloutEngine:
         """phnn_ukf_step: one step of the unscented filter as ONE library call -- k_ukf_sigma, K1 with H = 1 on the
         B * (2 n + 1) sigma points, k_ukf_moments, k_ekf_update with the identity -- IN PLACE on xhat (B,n) float32 and P
         (B,n,n) float64.  The arguments are ekf_step's, opt a _capi.UkfOptions.  -> dict(xhat, P, nis, innov, status)."""
-        self._assert_device_f32(xhat, u, y)
-        assert P.dtype == torch.float64 and P.is_contiguous() and P.device == self.device
-        B = xhat.shape[0]
-        ws = {} if workspace is None else workspace
-        if ws.get("ukf_key") != B:
-            ws["ukf_key"] = B
-            ws["ukf"] = torch.empty(max(self.ukf_workspace_bytes(B), 256), dtype=torch.uint8, device=self.device)
-        nis, innov, status = self._ekf_outputs(B, nis, innov, status)
-        lg = self._ekf_log(log)
-        rc = self.lib.phnn_ukf_step(self.h, self._p(xhat), self._p(P), self._p(u), int(u_stride), self._p(y),
-                                    self.n if y_stride is None else int(y_stride), B, C.byref(cost) if cost is not None else None,
-                                    self._integ(integrator), float(dt), C.byref(opt), self._p(nis), self._p(innov),
-                                    self._p(status), None if lg is None else C.byref(lg), self._p(ws["ukf"]), self._stream())
-        _check(self.lib, self.h, rc)
-        return dict(xhat=xhat, P=P, nis=nis, innov=innov, status=status)
+        return self._filter_step("phnn_ukf_step", "ukf", self.ukf_workspace_bytes, _capi.EkfLog, dict(xhat=xhat, P=P), u,
+                                 u_stride, y, cost, integrator, dt, opt, nis, innov, status, log, workspace, y_stride)
 
     # ------------------------------------------------------------------ the plant, on the device (SURVEY 8 f3)
     def plant_step(self, plant, state, action, action_stride, u_min=None, u_max=None, state_f32=None, done_step=None,

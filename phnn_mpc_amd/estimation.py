@@ -42,13 +42,46 @@ def _square(v, n, what):
     return np.ascontiguousarray(a)
 
 
+def _bounds(cost):
+    """What a prediction takes from a cost, the clamp: a zero _capi.Cost with the cost's bounds (None: without bounds)."""
+    bounds = _capi.Cost()
+    if cost is not None:
+        bounds.has_u_bounds, bounds.u_min, bounds.u_max = cost.has_u_bounds, cost.u_min, cost.u_max
+    return bounds
+
+
+def _copy_noise(dst, src, n):
+    """meas_mask, Qn and Rn of an n-state model from one options struct to another -> dst."""
+    dst.meas_mask = src.meas_mask
+    for i in range(n * n):
+        dst.Qn[i] = src.Qn[i]
+    for i in range(n):
+        dst.Rn[i] = src.Rn[i]
+    return dst
+
+
 class EKF:
     """measured: indices of the measured state components (no duplicates; () = predict only).  Qn: process noise
     covariance added at every step -- a scalar (times I), a diagonal or a full (n,n) matrix.  Rn: measurement noise
     VARIANCES -- a scalar, or one value per state component (n,) or per measured component (len(measured),); positive
     and finite where measured.  P0: the initial covariance, like Qn.  x0_hat: the initial estimate, broadcastable to
     (B,n); None = float32 of the true initial state.  log: the closed-loop drivers record the estimates and the nis of
-    every step."""
+    every step.
+
+    What the closed-loop drivers use of a filter, and all they know of it:
+      state_names   the tensors of a running filter, in the order step and the engine's device step take them
+      start(x0, n, m)  -> their initial values, a dict of numpy arrays by those names
+      bind(n, m)    -> the options struct of an n-state, m-input model
+      filter_cost(cost, canonical)  -> the cost whose bounds the filter clamps with, or None
+      engine_step   the name of the engine's device step
+      log_rows      the extra per-step logs, {state name: key of the drivers' result}
+      compensate    the drivers hand the plant engine.dist_compensate(u, dhat) instead of u
+      step, log     below"""
+
+    state_names = ("xhat", "P")
+    engine_step = "ekf_step"
+    log_rows = {}
+    compensate = False
 
     def __init__(self, measured=(0, 1), Qn=1e-6, Rn=1e-4, P0=1e-2, x0_hat=None, log=True):
         self.measured = tuple(int(i) for i in measured)
@@ -61,21 +94,9 @@ class EKF:
     @classmethod
     def from_config(cls, config):
         """An EKF from the optional `estimator:` section of a config dict (keys: measured, Qn, Rn, P0, x0_hat, log; type:
-        "ekf" may be given), or None when there is no such section."""
-        sec = config.get("estimator")
-        if sec is None:
-            return None
-        sec = dict(sec)
-        kind = str(sec.pop("type", "ekf")).lower()
-        if kind not in ("ekf", "ekf_disturbance"):
-            raise ValueError(f"Unknown estimator type: {kind}")
-        keys = {"measured", "Qn", "Rn", "P0", "x0_hat", "log"}
-        if kind == "ekf_disturbance":  # the filter with an input disturbance in its state (DisturbanceEKF below)
-            cls, keys = DisturbanceEKF, keys | {"Qd", "Pd0", "Qz", "d0_hat", "compensate"}
-        unknown = set(sec) - keys
-        if unknown:
-            raise ValueError(f"estimator: unknown key(s) {sorted(unknown)}")
-        return cls(**sec)
+        "ekf" may be given), a DisturbanceEKF for type "ekf_disturbance", or None when there is no such section: the
+        module's from_config with these two types."""
+        return from_config(config, types=("ekf", "ekf_disturbance"))
 
     @property
     def mask(self):
@@ -98,11 +119,10 @@ class EKF:
             raise ValueError("Rn must be positive and finite at the measured components")
         return out
 
-    def options(self, n):
-        """-> _capi.EkfOptions (phnn_ekf_options) for an n-state model."""
+    def _fill(self, o, n):
+        """meas_mask, Qn and Rn of an n-state model into an options struct that has them -> o."""
         if any(i >= n for i in self.measured):
             raise ValueError(f"measured {self.measured}: the model has {n} state components")
-        o = _capi.EkfOptions()
         o.meas_mask = self.mask
         Qn, Rn = _square(self.Qn, n, "Qn"), self.rn_vector(n)
         for i in range(n):
@@ -110,6 +130,20 @@ class EKF:
                 o.Qn[i * n + j] = Qn[i, j]
             o.Rn[i] = Rn[i]
         return o
+
+    def options(self, n):
+        """-> _capi.EkfOptions (phnn_ekf_options) for an n-state model."""
+        return self._fill(_capi.EkfOptions(), n)
+
+    def bind(self, n, m):
+        return self.options(n)
+
+    def start(self, x0, n, m):
+        return dict(zip(self.state_names, self.initial(x0, n)))
+
+    def filter_cost(self, cost, canonical):
+        """The plant's clamp; a canonical controller's sequence is clamped already."""
+        return None if canonical else cost
 
     def initial(self, x0, n=None):
         """x0 (B,n) true initial states -> (xhat0 (B,n) float32, P0 (B,n,n) float64), numpy."""
@@ -128,9 +162,7 @@ class EKF:
         B = xhat.shape[0]
         opt = self.options(engine.n) if opt is None else opt
         row = torch.as_tensor(u, dtype=torch.float32).to(engine.device).reshape(B, 1, engine.m).contiguous()
-        bounds = _capi.Cost()  # what the prediction takes from the cost: the clamp
-        if cost is not None:
-            bounds.has_u_bounds, bounds.u_min, bounds.u_max = cost.has_u_bounds, cost.u_min, cost.u_max
+        bounds = _bounds(cost)
         _, traj = engine.rollout_cost(xhat, row, bounds, integrator, dt, want_traj=True)
         A, _, _ = engine.rollout_linearize(xhat, row, bounds, integrator, dt, traj=traj)
         return engine.ekf_update(traj[:, 1].contiguous(), A.reshape(B, engine.n, engine.n), y, P.clone(), opt, log=log)
@@ -144,6 +176,10 @@ class DisturbanceEKF(EKF):
     disturbance estimate, broadcastable to (B,m).  compensate: the closed-loop drivers hand the plant
     c(c(v) - dhat) instead of the controller's command v (engine.dist_compensate); False: the plain loop's control, the
     disturbance is estimated only."""
+
+    state_names = ("xhat", "dhat", "P")
+    engine_step = "dekf_step"
+    log_rows = {"dhat": "disturbances"}
 
     def __init__(self, measured=(0, 1), Qn=1e-6, Rn=1e-4, P0=1e-2, Qd=0.0, Pd0=1.0, Qz=None, x0_hat=None, d0_hat=0.0,
                  compensate=True, log=True):
@@ -173,6 +209,16 @@ class DisturbanceEKF(EKF):
             o.Rn[i] = Rn[i]
         return o
 
+    def bind(self, n, m):
+        return self.options(n, m)
+
+    def start(self, x0, n, m):
+        return dict(zip(self.state_names, self.initial(x0, m, n)))
+
+    def filter_cost(self, cost, canonical):
+        """The bounds of the command's clamps, in the compensation and in the filter."""
+        return cost
+
     def initial(self, x0, m, n=None):
         """x0 (B,n) true initial states -> (xhat0 (B,n) float32, dhat0 (B,m) float32, Pz0 (B,n+m,n+m) float64 =
         blockdiag(P0, Pd0)), numpy."""
@@ -196,7 +242,7 @@ class DisturbanceEKF(EKF):
                 raise ValueError("u_min > u_max")
             cu = torch.clamp(cu, float(cost.u_min), float(cost.u_max))  # a NaN stays NaN
         row = (cu + dhat.reshape(B, m)).reshape(B, 1, m).contiguous()
-        _, traj = engine.rollout_cost(xhat, row, _capi.Cost(), integrator, dt, want_traj=True)  # a zero cost, no bounds
+        _, traj = engine.rollout_cost(xhat, row, _bounds(None), integrator, dt, want_traj=True)  # a zero cost, no bounds
         A, Bm, _ = engine.rollout_linearize(xhat, row, None, integrator, dt, traj=traj)
         return engine.dekf_update(traj[:, 1].contiguous(), A.reshape(B, n, n), Bm.reshape(B, n, m), y, Pz.clone(),
                                   dhat.clone().reshape(B, m), opt, log=log)
@@ -217,10 +263,11 @@ class UKF(EKF):
                                (1e-3, 2, 0)   4.2e-1
     P must stay positive definite: a problem whose P has no Cholesky factor ends its step with status 2 and NaN."""
 
+    engine_step = "ukf_step"
+
     def __init__(self, measured=(0, 1), Qn=1e-6, Rn=1e-4, P0=1e-2, x0_hat=None, log=True, alpha=1.0, beta=0.0, kappa=1.0):
         super().__init__(measured=measured, Qn=Qn, Rn=Rn, P0=P0, x0_hat=x0_hat, log=log)
         self.alpha, self.beta, self.kappa = float(alpha), float(beta), float(kappa)
-        self.unscented = True  # what the closed-loop drivers tell this filter by
 
     def weights(self, n):
         """-> (gamma, wm0, wc0, wi) in float64 for n state components."""
@@ -236,13 +283,7 @@ class UKF(EKF):
         """-> _capi.UkfOptions (phnn_ukf_options) for an n-state model."""
         if n > _capi.PHNN_UKF_MAX_N:
             raise ValueError(f"n = {n}: the unscented filter holds at most {_capi.PHNN_UKF_MAX_N} state components")
-        e = super().options(n)
-        o = _capi.UkfOptions()
-        o.meas_mask = e.meas_mask
-        for i in range(n * n):
-            o.Qn[i] = e.Qn[i]
-        for i in range(n):
-            o.Rn[i] = e.Rn[i]
+        o = self._fill(_capi.UkfOptions(), n)
         o.gamma, o.wm0, o.wc0, o.wi = self.weights(n)
         return o
 
@@ -264,30 +305,32 @@ class UKF(EKF):
         S = 2 * n + 1
         opt = self.options(n) if opt is None else opt
         row = torch.as_tensor(u, dtype=torch.float32).to(engine.device).reshape(B, m).contiguous()
-        bounds = _capi.Cost()  # what the prediction takes from the cost: the clamp
-        if cost is not None:
-            bounds.has_u_bounds, bounds.u_min, bounds.u_max = cost.has_u_bounds, cost.u_min, cost.u_max
+        bounds = _bounds(cost)
         chi, ctrl = engine.ukf_sigma(xhat, P, opt, u=row)
         _, traj = engine.rollout_cost(chi.reshape(B * S, n), ctrl.reshape(B * S, 1, m), bounds, integrator, dt, want_traj=True)
         mo = engine.ukf_moments(traj[:, 1].contiguous(), B, opt)
-        e = _capi.EkfOptions()  # the update's share of the options
-        e.meas_mask = opt.meas_mask
-        for i in range(n * n):
-            e.Qn[i] = opt.Qn[i]
-        for i in range(n):
-            e.Rn[i] = opt.Rn[i]
+        e = _copy_noise(_capi.EkfOptions(), opt, n)  # the update's share of the options
         return engine.ekf_update(mo["xm"], mo["eye"], y, mo["Pm"], e, log=log)
 
 
-def from_config(config):
-    """The estimator of the optional `estimator:` section of a config dict, or None without one: a UKF for type "ukf"
-    (keys: the EKF's plus alpha, beta, kappa), every other section is EKF.from_config's."""
+_KEYS = {"measured", "Qn", "Rn", "P0", "x0_hat", "log"}  # of every estimator
+_TYPES = {"ekf": (EKF, set()),
+          "ekf_disturbance": (DisturbanceEKF, {"Qd", "Pd0", "Qz", "d0_hat", "compensate"}),
+          "ukf": (UKF, {"alpha", "beta", "kappa"})}  # type -> (class, the keys it adds)
+
+
+def from_config(config, types=tuple(_TYPES)):
+    """The estimator of the optional `estimator:` section of a config dict, or None without one: the class of its
+    `type` (default "ekf") in the table above, built from the section's other keys.  types: the types accepted."""
     sec = config.get("estimator")
-    if sec is None or str(dict(sec).get("type", "ekf")).lower() != "ukf":
-        return EKF.from_config(config)
+    if sec is None:
+        return None
     sec = dict(sec)
-    sec.pop("type")
-    unknown = set(sec) - {"measured", "Qn", "Rn", "P0", "x0_hat", "log", "alpha", "beta", "kappa"}
+    kind = str(sec.pop("type", "ekf")).lower()
+    if kind not in types:
+        raise ValueError(f"Unknown estimator type: {kind}")
+    cls, extra = _TYPES[kind]
+    unknown = set(sec) - _KEYS - extra
     if unknown:
         raise ValueError(f"estimator: unknown key(s) {sorted(unknown)}")
-    return UKF(**sec)
+    return cls(**sec)

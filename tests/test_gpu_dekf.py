@@ -420,6 +420,9 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch):
             edit(o)
             yield what, o
 
+    # the complete text each edit leaves in phnn_last_error, for the update and for the step alike
+    text = {"mask": "meas_mask has bits at or above n", "Qz": "Qz is not finite",
+            "Rn": "Rn of a measured component is not positive and finite", "reserved": "reserved must be zero"}
     good = dm.dekf_options(p)
     good.Rn[3] = float("nan")  # not measured: not looked at
     good.Qz[25] = float("nan")  # past the (5,5) entries: not looked at
@@ -429,11 +432,12 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch):
     nolog = dict(log_dhat=torch.zeros(2, B, m, device="cuda:0"), step=-1)
     for what, opt in bad_options():
         o = fresh()
-        with pytest.raises(PhnnError, match="error -"):
+        with pytest.raises(PhnnError, match="error -") as upd:
             update(o, opt)
-        with pytest.raises(PhnnError, match="error -"):
+        with pytest.raises(PhnnError, match="error -") as stp:
             step(o, opt)
         untouched(o)
+        assert str(upd.value) == str(stp.value) == "phnn_mpc error -1: phnn_dekf_options: " + text[what.split()[0]], what
     o = fresh()
     with pytest.raises(PhnnError, match="step source"):
         update(o, good, log=nolog)

@@ -317,6 +317,9 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch):
             edit(o)
             yield what, o
 
+    # the complete text each edit leaves in phnn_last_error, for the update and for the step alike
+    text = {"mask": "meas_mask has bits at or above n", "Qn": "Qn is not finite",
+            "Rn": "Rn of a measured component is not positive and finite", "reserved": "reserved must be zero"}
     good = options(p, n)
     good.Rn[3] = float("nan")  # not measured: not looked at
     o = fresh()
@@ -325,11 +328,12 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch):
     nolog = dict(log_xhat=torch.zeros(2, B, n, device="cuda:0"), step=-1)
     for what, opt in bad_options():
         o = fresh()
-        with pytest.raises(PhnnError, match="error -"):
+        with pytest.raises(PhnnError, match="error -") as upd:
             eng.ekf_update(t["xpred"], t["A"], t["y"], o["P"], opt, xhat=o["xhat"], nis=o["nis"], status=o["status"])
-        with pytest.raises(PhnnError, match="error -"):
+        with pytest.raises(PhnnError, match="error -") as stp:
             eng.ekf_step(o["xhat"], o["P"], t["xpred"], n, t["y"], cost, "euler", 0.02, opt, nis=o["nis"], status=o["status"])
         untouched(o)
+        assert str(upd.value) == str(stp.value) == "phnn_mpc error -1: phnn_ekf_options: " + text[what.split()[0]], what
     o = fresh()
     with pytest.raises(PhnnError, match="step source"):
         eng.ekf_update(t["xpred"], t["A"], t["y"], o["P"], good, xhat=o["xhat"], nis=o["nis"], status=o["status"], log=nolog)

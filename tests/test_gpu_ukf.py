@@ -368,6 +368,12 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch):
             edit(o)
             yield what, o
 
+    # The complete text each edit leaves in phnn_last_error, for the step, the sigma points and the moments alike: the
+    # mask, Qn and Rn are reported under the EKF's struct name (k_ekf_update takes them), the rest under the UKF's.
+    ekf_text = {"mask": "meas_mask has bits at or above n", "Qn": "Qn is not finite",
+                "Rn": "Rn of a measured component is not positive and finite"}
+    ukf_text = {"reserved": "reserved must be zero", "gamma": "gamma and wi must be positive and finite",
+                "wi": "gamma and wi must be positive and finite", "wm0": "wm0 / wc0 is not finite", "wc0": "wm0 / wc0 is not finite"}
     good = opts()
     good.wm0, good.wc0 = -3.0, -0.5  # negative weights of sigma point 0 are the textbook's small alpha: allowed
     good.Rn[3] = float("nan")  # not measured: not looked at
@@ -377,13 +383,16 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch):
     nolog = dict(log_xhat=torch.zeros(2, B, n, device="cuda:0"), step=-1)
     for what, opt in bad_options():
         o = fresh()
-        with pytest.raises(PhnnError, match="error -"):
+        with pytest.raises(PhnnError, match="error -") as stp:
             eng.ukf_step(o["xhat"], o["P"], u, 1, y, cost, "euler", 0.02, opt, nis=o["nis"], status=o["status"])
-        with pytest.raises(PhnnError, match="error -"):
+        with pytest.raises(PhnnError, match="error -") as sig:
             eng.ukf_sigma(o["xhat"], o["P"], opt, u=u, chi=o["chi"], ctrl=o["ctrl"])
-        with pytest.raises(PhnnError, match="error -"):
+        with pytest.raises(PhnnError, match="error -") as mom:
             eng.ukf_moments(Y, B, opt, xm=o["xm"], Pm=o["Pm"], eye=o["eye"])
         untouched(o)
+        key = what.split()[0]
+        full = "phnn_ekf_options: " + ekf_text[key] if key in ekf_text else "phnn_ukf_options: " + ukf_text[key]
+        assert str(stp.value) == str(sig.value) == str(mom.value) == "phnn_mpc error -1: " + full, what
     o, good = fresh(), opts()
     with pytest.raises(PhnnError, match="step source"):
         eng.ukf_step(o["xhat"], o["P"], u, 1, y, cost, "euler", 0.02, good, nis=o["nis"], status=o["status"], log=nolog)
